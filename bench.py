@@ -3,7 +3,13 @@
 config 2: batch 32, 8 prongs/event, 3x400x280 maps) on N MI355X GPUs, one process per GPU, RCCL gradient all-reduce
 overlapped with backward.  Prints ONE JSON line (rank 0).
 
+A plain run sets up, warms up, times --steps steps, writes the last step's outputs if --dump-outputs is given, and prints the line.
+--full adds everything else the line can carry: the serialised per-kernel survey step and the dominant kernel's roofline, the
+with-optimizer leg, the fp32 parity mode, batch 8 / 64, the --sdxl configuration and the CPU baseline.
+
     python bench.py [--gpus 1 --steps 5 --warmup 2 --precision bf16]
+    python bench.py --full                  # the headline line plus every extra figure above
+    python bench.py --dump-outputs DIR      # DIR/loss.npy, DIR/gradients.npy (float32) of the last timed step
     python bench.py --gpus N ...            # starts its N ranks itself (one child process per GPU, before any GPU call)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
     python bench.py --gpus 8 --global-batch 64      # strong scaling: the global batch is split over the ranks
@@ -256,6 +262,25 @@ def sdxl_mode_ms(opt_path, args, dev):
     return 1000 * (time.perf_counter() - t0) / 2
 
 
+DUMP_LIMIT_BYTES = 64 * 10**6
+
+
+def dump_outputs(path, arrays):
+    """Write what the timed path computed in its last step as path/<name>.npy, float32, at most DUMP_LIMIT_BYTES in all: when the
+    arrays are larger, each is replaced by the same fixed, seeded sample of a share of its elements in every run."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    budget = (DUMP_LIMIT_BYTES - 4096 * len(arrays)) // 4            # elements (float32), less the .npy headers
+    total = sum(t.numel() for t in arrays.values())
+    for name, t in arrays.items():
+        a = t.detach().float().cpu()
+        if total > budget:
+            keep = max(1, a.numel() * budget // total)
+            idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a.numpy())
+
+
 def pmc_traffic(label):
     """HBM bytes per launch of `label` from the committed rocprofv3 PMC passes of this command (tools/pmc_traffic.py): the
     newest round's file that has the kernel, or None."""
@@ -294,8 +319,15 @@ def main():
     ap.add_argument("--bwd-overlap", action="store_true", help="A/B: 3x3 weight gradients on the plan's side stream (tcvn_backward_overlap(1), the default of rounds 2-3)")
     ap.add_argument("--no-fp32", action="store_true", help="skip the fp32 parity-mode timing (fp32_ms_per_step)")
     ap.add_argument("--no-optimizer-leg", action="store_true", help="skip the with_optimizer_ms_per_step leg (5 extra steps): counter passes that are divided by the steps in the run")
-    ap.add_argument("--dump-records", default="", help="write every profiled launch (name, ms, flops) to this JSON file")
+    ap.add_argument("--dump-records", default="", help="write every profiled launch (name, ms, flops) to this JSON file (with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the survey step + roofline, the with-optimizer leg, fp32 parity mode, batch 8 / 64, --sdxl and the CPU baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's outputs to DIR/<name>.npy (float32): loss and the parameter gradients in "
+                         "named_parameters() order, or event and prong logits with --ragged-inference")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:          # no launcher around us: start the ranks (no GPU call so far)
         sys.exit(launch_ranks(args.gpus))
     rank = int(os.environ.get("RANK", 0))
@@ -351,10 +383,13 @@ def main():
         model.eval()
     reducer = model.enable_data_parallel() if world > 1 else None    # state broadcast from rank 0 + overlapped arena all-reduce hooks
 
+    last = {}
+
     def step():
         if args.ragged_inference:                 # inference only: no loss, no backward, no exchange (embarrassingly parallel)
             with torch.no_grad():
-                return model.shared_step(batch)[2].sum()
+                last["logits"] = model.shared_step(batch)[2:4]
+                return last["logits"][0].sum()
         if reducer:
             broadcast_buffers(rt.flat_buf)
         rt.zero_grad()
@@ -373,8 +408,9 @@ def main():
     # one stream so that the per-kernel times are not smeared by the overlap.  It names the dominant kernel.  Every rank runs
     # the same two extra steps (they contain collectives); only rank 0 records.
     agg, kernels, top, biggest = {}, None, None, {}
-    profiled = rank == 0 and not args.no_profile
-    if not args.no_profile:
+    survey = args.full and not args.no_profile
+    profiled = rank == 0 and survey
+    if survey:
         rt.overlap_embedders = False
         _lib.lib.tcvn_backward_overlap(0)          # serial per-kernel timings for the survey
         if profiled:
@@ -430,6 +466,13 @@ def main():
     lossv = float(loss.detach())
 
     note(f"timed {args.steps} steps in {elapsed:.3f}s")
+    if args.dump_outputs and rank == 0:           # before anything else runs a step: these are the last timed step's results
+        if args.ragged_inference:
+            outputs = {"event_logits": last["logits"][0], "prong_logits": last["logits"][1]}
+        else:
+            outputs = {"loss": loss.detach().reshape(1), "gradients": rt.flat_grad}
+        dump_outputs(args.dump_outputs, outputs)
+        note(f"outputs of the last timed step written to {args.dump_outputs}")
     roof = None
     if profiled:
         _lib.lib.tcvn_profile_enable(0)
@@ -503,7 +546,7 @@ def main():
         if roof:
             out["roofline"] = roof
             out["kernels"] = kernels[:8]
-        if not args.ragged_inference and world == 1 and not args.no_optimizer_leg:
+        if args.full and not args.ragged_inference and world == 1 and not args.no_optimizer_leg:
             # beside the fwd+bwd figure BASELINE.json's metric names: the same step followed by the optimizer update the reference's
             # train.py performs (AdamW over two groups + gradient clipping; here one fused launch over the flat arenas)
             try:
@@ -519,14 +562,14 @@ def main():
                 out["with_optimizer_note"] = f"fwd+loss+bwd + {type(optimizer).__name__}.step(), 3 steps"
             except Exception as ex:                # a reported extra, never a reason to lose the line
                 note(f"optimizer-step timing skipped: {ex}")
-        if args.precision == "bf16" and world == 1 and not args.no_fp32 and not args.sdxl and not args.ragged_inference:
+        if args.full and args.precision == "bf16" and world == 1 and not args.no_fp32 and not args.sdxl and not args.ragged_inference:
             note("fp32 parity mode (1 warm-up + 2 steps) ...")
             del model, rt
             torch.cuda.empty_cache()
             out["fp32_ms_per_step"] = round(fp32_parity_mode_ms(opt_path, args, dev, batch), 2)
             out["fp32_events_per_s"] = round(args.batch / out["fp32_ms_per_step"] * 1000, 1)
-        if (args.precision == "bf16" and world == 1 and not args.no_batch8 and not args.sdxl and not args.ragged_inference and not strong
-                and args.batch == 32):
+        if (args.full and args.precision == "bf16" and world == 1 and not args.no_batch8 and not args.sdxl and not args.ragged_inference
+                and not strong and args.batch == 32):
             # the strong-scaling regime of the north star (batch 64 over 8 GPUs = 8 events per rank) as this one GPU sees it: the per-rank
             # share and the whole batch, so that the 8-way ceiling (batch-64 time / batch-8 time, before any exchange cost) is on the record
             note("batch 8 and batch 64 per GPU (2 warm-up + 5 / 3 steps) ...")
@@ -540,7 +583,7 @@ def main():
             out["batch8_note"] = ("same bf16 fwd+loss+bwd step at 8 events/GPU (one rank's share of batch 64 over 8 GPUs) and at 64 events on "
                                   "this one GPU; ceiling = their ratio, no exchange cost in it")
             torch.cuda.empty_cache()
-        if args.precision == "bf16" and world == 1 and not args.no_sdxl and not args.sdxl and not args.ragged_inference and not strong:
+        if args.full and args.precision == "bf16" and world == 1 and not args.no_sdxl and not args.sdxl and not args.ragged_inference and not strong:
             note("--sdxl embedder, config 4 (1 warm-up + 2 steps) ...")
             model = rt = None
             torch.cuda.empty_cache()
@@ -548,7 +591,7 @@ def main():
             out["sdxl_events_per_s"] = round(16 / out["sdxl_ms_per_step"] * 1000, 1)
             out["sdxl_note"] = "BASELINE config 4: batch 16 x 8 prongs, bf16, fwd+loss+bwd; parity of this embedder is unpinned (diffusers absent)"
             torch.cuda.empty_cache()
-        if not args.no_cpu_baseline and world == 1 and not args.sdxl and not args.ragged_inference:       # rank 0 at N=1 only (DenseNet workload)
+        if args.full and not args.no_cpu_baseline and world == 1 and not args.sdxl and not args.ragged_inference:   # rank 0 at N=1 only (DenseNet workload)
             note("cpu baseline (oracle on host cores) ...")
             out["cpu_baseline"] = cpu_baseline(host_threads(), args.prongs)
         print(json.dumps(out))

@@ -230,10 +230,60 @@ def run_case(name, cfg_over, prongs, batch_seed, weight_seed, with_train=True, m
         out["train_event_logits"], out["train_prong_logits"] = ev2.numpy(), pr2.numpy()
         out["train_event_loss"], out["train_prong_loss"] = np.array(el.item()), np.array(pl.item())
         print(f"[{name}] train loss {loss.item():.6f} event {el.item():.6f} prong {pl.item():.6f}")
+    save_case(name, out)
+
+
+PART_BYTES = 900 * 1024      # committed files stay under 1 MiB: a larger case is split over name.npz, name.1.npz, ...
+
+
+def save_case(name, out):
+    """First-fit packing of the arrays (by compressed size) into parts of at most PART_BYTES; golden_utils.load_case merges them."""
+    import zlib
+    parts, sizes = [], []
+    for k, v in out.items():
+        n = len(zlib.compress(np.ascontiguousarray(v).tobytes(), 6)) + 256
+        for i in range(len(parts)):
+            if sizes[i] + n <= PART_BYTES:
+                parts[i][k] = v
+                sizes[i] += n
+                break
+        else:
+            parts.append({k: v})
+            sizes.append(n)
     os.makedirs(GOLD, exist_ok=True)
-    path = os.path.join(GOLD, name + ".npz")
-    np.savez_compressed(path, **out)
-    print(f"[{name}] wrote {path} ({os.path.getsize(path) / 1024:.0f} KiB)")
+    for i, part in enumerate(parts):
+        path = os.path.join(GOLD, name + (f".{i}" if i else "") + ".npz")
+        np.savez_compressed(path, **part)
+        print(f"[{name}] wrote {path} ({os.path.getsize(path) / 1024:.0f} KiB)")
+
+
+def fresh_case():
+    """The reference's results on a seeded case that is not among the other goldens (tests/test_oracle_vs_reference.py): eval logits,
+    the training-step loss and three gradients."""
+    over = dict(densenet_structure=[2, 1], densenet_growth_rate=8, initial_pixel_dim=16, num_encoder_layers=2,
+                pixel_embedding_dim=64, hidden_dim=64, num_prong_decoder_layers=3, dropout=0.0, pixel_noise_std=0.0)
+    prongs, batch_seed, weight_seed = [3, 1, 2], 4242, 77
+    cfg = O.tutorial_config(**over)
+    batch = O.synthetic_batch(prongs, batch_seed, cfg)
+    sd = O.fill_state(cfg, weight_seed)
+    torch.manual_seed(0)
+    ref = build_reference(cfg)
+    res = ref.load_state_dict(sd, strict=True)
+    assert not res.missing_keys and not res.unexpected_keys
+    ref.eval()
+    with torch.no_grad():
+        _, _, ev, pr = ref.shared_step(batch)
+    ref.train()
+    loss = ref.training_step(batch, 0)
+    loss.backward()
+    out = {"cfg_keys": np.array(list(over.keys())), "cfg_vals": np.array([repr(v) for v in over.values()]),
+           "prongs": np.array(prongs), "batch_seed": batch_seed, "weight_seed": weight_seed,
+           "eval_event_logits": ev.numpy(), "eval_prong_logits": pr.numpy(), "train_total_loss": np.array(loss.item())}
+    named = dict(ref.named_parameters())
+    for k in ("network.encoder.encoder.layers.0.self_attn.in_proj_weight", "network.prong_decoder.output_layer.weight",
+              "network.prong_embedding.prong_pixel_embedding.features.dense1.layers.0.output_block.conv2.weight"):
+        out["grad:" + k] = named[k].grad.numpy().copy()
+    save_case("fresh_case", out)
 
 
 def main():
@@ -260,6 +310,8 @@ def main():
                               num_encoder_layers=2, pixel_embedding_dim=64, hidden_dim=64,
                               num_prong_decoder_layers=3),
              [2, 3, 1], batch_seed=13, weight_seed=3)
+    if not only or "fresh_case" in only:
+        fresh_case()
 
 
 if __name__ == "__main__":

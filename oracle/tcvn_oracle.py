@@ -14,8 +14,8 @@ Parity pinning: ``oracle/make_golden.py`` imports the real reference (read-only,
 stub modules for absent third-party packages) in the build container, runs it on
 seeded inputs/weights and commits the results under ``tests/golden``;
 ``tests/test_oracle_golden.py`` checks this restatement against those vectors, and
-``tests/test_oracle_vs_reference.py`` checks it against the live reference whenever
-``/root/reference`` exists.
+``tests/test_oracle_vs_reference.py`` checks it against the reference's results on one
+more seeded case (``tests/golden/fresh_case.npz``).
 
 Every function cites the reference file:line it follows (paths relative to
 ``/root/reference``).

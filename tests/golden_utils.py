@@ -10,8 +10,19 @@ from oracle import tcvn_oracle as O
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
+def load_arrays(name):
+    """All arrays of a case: name.npz and, for a case split to keep each file under 1 MiB, name.1.npz, name.2.npz, ..."""
+    g, part = {}, 0
+    while True:
+        path = os.path.join(GOLD, name + (f".{part}" if part else "") + ".npz")
+        if part and not os.path.exists(path):
+            return g
+        g.update(np.load(path, allow_pickle=False))
+        part += 1
+
+
 def load_case(name):
-    g = dict(np.load(os.path.join(GOLD, name + ".npz"), allow_pickle=False))
+    g = load_arrays(name)
     over = {str(k): ast.literal_eval(str(v)) for k, v in zip(g["cfg_keys"], g["cfg_vals"])}
     cfg = O.tutorial_config(**over)
     batch = (

@@ -21,8 +21,8 @@ def _run(extra):
     env = dict(os.environ, TCVN_BENCH_REHEARSAL="1", HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):      # no launcher around us: bench.py starts its ranks itself
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-fp32",
-           "--no-sdxl", "--no-batch8"] + extra
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
+           "--no-fp32", "--no-sdxl", "--no-batch8"] + extra
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     print(p.stdout[-3000:], p.stderr[-3000:])
     assert p.returncode == 0

@@ -7,10 +7,13 @@ set -e
 cd "$(dirname "$0")/../dune-transformercvn_amd/csrc"
 ARCH=${1:-gfx950}; shift || true
 FLAGS=${@:--mllvm -amdgpu-mfma-vgpr-form}
-hipcc --offload-arch=$ARCH -O3 -std=c++17 -fPIC $FLAGS -S --cuda-device-only bwd1x1_wide.hip -o /tmp/tcvn_wide.s 2>/dev/null
-python3 - <<'PY'
-import re, sys
-text = open('/tmp/tcvn_wide.s').read().split('\n')
+# a private temporary file: a fixed name in a shared temporary directory may belong to another user (or another build running at once)
+ASM=$(mktemp "${TMPDIR:-/tmp}/tcvn_wide.XXXXXX.s")
+trap 'rm -f "$ASM"' EXIT
+hipcc --offload-arch=$ARCH -O3 -std=c++17 -fPIC $FLAGS -S --cuda-device-only bwd1x1_wide.hip -o "$ASM" 2>/dev/null
+ASM="$ASM" python3 - <<'PY'
+import os, re, sys
+text = open(os.environ['ASM']).read().split('\n')
 def regs(tok):
     out = []
     for m in re.finditer(r'\b([va])\[(\d+):(\d+)\]|\b([va])(\d+)\b', tok):

@@ -8,7 +8,7 @@ Needs a library whose conv3x3_f32.hip was compiled with -DTCVN_PHASE_PROF (adds 
 Runs bench.py --precision fp32 for 3 steps, then prints the counters."""
 import ctypes, os, subprocess, sys, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.argv = ["bench.py", "--precision", "fp32", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-profile"]
+sys.argv = ["bench.py", "--precision", "fp32", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-profile", "--full"]
 import runpy
 try:
     runpy.run_path(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py"), run_name="__main__")
