@@ -12,8 +12,9 @@
 // the activated input exists in HBM for these kernels: per pixel and layer the backward of the 1x1 moves 512 + 6*cin bytes instead of
 // 1792 + 8*cin (EY written once and read twice, the activated copy read once, x and G as here).
 // The weight-gradient tile (128 x 128 fp32 = 64 accumulator registers per lane) stays in registers for the whole launch and leaves as one
-// slab per workgroup (k_slab_reduce: the slabs of one y-slice are summed in a fixed order; launches with more than 32 slabs split them over
-// up to 16 y-slices whose partial sums meet in fp32 atomics, i.e. the last bits of a weight gradient can differ from run to run).
+// slab per workgroup (k_slab_reduce: one y-slice takes up to 512 slabs and sums them in a fixed order, so the weight gradient is the same
+// from run to run; only jobs with more than 512 slabs, and the scalar bias column-sum jobs (64 slabs per y-slice), split over y-slices whose
+// partial sums meet in fp32 atomics, i.e. the last bits of a bias gradient can differ from run to run).
 #include "tcvn_ops.h"
 #include "prof.h"
 
@@ -373,7 +374,6 @@ bool bwd1x1_fused_ok(const Bwd1x1Args& a) {
 }
 
 int bwd1x1_fused_nblk(const Bwd1x1Args& a) {
-    if (bwd1x1_wide_ok(a)) return bwd1x1_wide_nblk(a);       // 128 < cin <= 512: one workgroup per tile walks the column slices (bwd1x1_wide.hip)
     const int nn = cdiv(a.cin, 128);
     int cap = 512 / nn;                    // two resident workgroups per CU, shared by the nn column slices
     if (cap < 64) cap = 64;
@@ -385,7 +385,6 @@ int bwd1x1_fused_launch(const Bwd1x1Args& a, hipStream_t st) {
     if (a.M <= 0) return 0;
     if (!bwd1x1_fused_ok(a)) return -2;
     if (a.nblk != bwd1x1_fused_nblk(a)) { fprintf(stderr, "tcvn: bwd1x1_fused nblk mismatch\n"); return -3; }
-    if (bwd1x1_wide_ok(a)) return bwd1x1_wide_launch(a, st);
     static bool attr = false;
     if (!attr) {
         TCVN_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bwd1x1_fused_bf16), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));

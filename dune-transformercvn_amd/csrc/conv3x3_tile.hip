@@ -127,7 +127,7 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_fwd_bf16(const ConvFwdArgs g
     int cur = 0, ts = 0;                                         // image buffer / table slot of the current tile
     for (int t = lb; t < ntiles; t += nb, cur ^= 1, ts = ts == 2 ? 0 : ts + 1) {
         const int tn = ts == 2 ? 0 : ts + 1, tnn = tn == 2 ? 0 : tn + 1;
-        if (t + nb < ntiles && !TCVN_DBG_BIT(g.dbg, 1))                     // prefetch the next tile's image under this tile's MFMAs
+        if (t + nb < ntiles)                     // prefetch the next tile's image under this tile's MFMAs
             dma_image(smem, (cur ^ 1) * img_bytes, YA, zeros, tbl + tn * nrows4, nrows4, wave, lane);
         f32x16 acc;
 #pragma unroll
@@ -143,7 +143,6 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_fwd_bf16(const ConvFwdArgs g
             for (int ks = 0; ks < 8; ++ks)
                 af[0][ks] = *reinterpret_cast<const bf16x8_t*>(smem + image + lr * 256 + (((2 * ks + h) ^ (lr & 15)) << 4));
         }
-        if (!TCVN_DBG_BIT(g.dbg, 2))
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
             if (tap + 1 < 9) {
@@ -175,7 +174,7 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_fwd_bf16(const ConvFwdArgs g
         for (int e = 0; e < 16; ++e) {
             const int lp = wave * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
             const int m = px[lp];
-            if (m >= 0 && nok && !TCVN_DBG_BIT(g.dbg, 4)) {
+            if (m >= 0 && nok) {
                 float v = acc[e] + bias;
                 if (drop) {
                     if ((m >> 1) != cur_grp) { cur_grp = m >> 1; bits = drop_bits(dkey, m, r, g.N); }
@@ -261,7 +260,7 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_fwd_ring_bf16(const ConvFwdA
     __syncthreads();
     for (int t = t0; t < t1; ++t) {
         const int k128 = (t - t0) * TP;                          // row of this tile's first image row
-        if (t + 1 < t1 && !TCVN_DBG_BIT(g.dbg, 1)) dma_rows(nrows4 + k128, TP);     // the next tile's 128 new rows, under this tile's MFMAs
+        if (t + 1 < t1) dma_rows(nrows4 + k128, TP);     // the next tile's 128 new rows, under this tile's MFMAs
         // two accumulator chains (even / odd k-steps): a dependent MFMA chain issues one MFMA per ~54 cycles, two independent
         // chains keep the matrix pipe at its 32-cycle cadence
         f32x16 acc, acc2;
@@ -276,7 +275,6 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_fwd_ring_bf16(const ConvFwdA
             for (int ks = 0; ks < 8; ++ks)
                 af[0][ks] = *reinterpret_cast<const bf16x8_t*>(smem + lr * 256 + (((2 * ks + h) ^ (lr & 15)) << 4));
         }
-        if (!TCVN_DBG_BIT(g.dbg, 2))
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
             if (tap + 1 < 9) {
@@ -306,7 +304,7 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_fwd_ring_bf16(const ConvFwdA
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             const int m = mrow[e];
-            if (m >= 0 && nok && !TCVN_DBG_BIT(g.dbg, 4)) {
+            if (m >= 0 && nok) {
                 float v = acc[e] + acc2[e] + bias;
                 if (drop) {
                     if ((m >> 1) != cur_grp) { cur_grp = m >> 1; bits = drop_bits(dkey, m, r, g.N); }
@@ -339,7 +337,7 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_fwd_ring_bf16(const ConvFwdA
 }
 size_t fwd_ring_smem() { return RING * 256 + RING * 4 + 4 * 32 * 16; }
 
-// Pair variant of the ring kernel: 512 threads = two waves per SIMD.  The ablation of the ring kernel (tools/ablate_conv3x3.py: block 1,
+// Pair variant of the ring kernel: 512 threads = two waves per SIMD.  The timing ablation of the ring kernel (round 4, since removed: block 1,
 // 277 us = 76 fixed + 47 DMA issue + 86 MFMA + 68 epilogue, nothing overlapping) says a single wave per SIMD serialises its phases; here the
 // two waves of a SIMD split the NINE TAPS of the same 32 positions -- wave w (role A) owns taps 0-4 (40 weight fragments = 160 registers),
 // wave w+4 (role B) taps 5-8 (32 fragments) -- which is what fits the 256 registers a wave has at two waves per SIMD, and they run
@@ -475,7 +473,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_fwd_pair_bf16(const ConvFwdA
         const float* xc = xchg + (((te - t0) & 1) * 4 + pw) * 16 * 64 + lane;
         float part[16];
 #pragma unroll
-        for (int e = 0; e < 16; ++e) part[e] = TCVN_DBG_BIT(g.dbg, 512) ? 0.f : xc[e * 64];
+        for (int e = 0; e < 16; ++e) part[e] = xc[e * 64];
         int mrow[16];
 #pragma unroll
         for (int e = 0; e < 16; ++e) mrow[e] = tbl[((te - t0) * TP + q.halo + pw * 32 + (e & 3) + 8 * (e >> 2) + 4 * h) & (PAIR_TBL - 1)];
@@ -498,7 +496,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_fwd_pair_bf16(const ConvFwdA
             const bf16 o = ok ? f2bf(v) : (bf16)0;
             const float x = bf2f(o);                                                  // 0 for padding positions / absent channels
             f1 += x; f2 = fmaf(x, x, f2);
-            if (VEC) { if (!TCVN_DBG_BIT(g.dbg, 256)) ct[((e & 3) + 8 * (e >> 2) + 4 * h) * 32 + r] = o; }
+            if (VEC) ct[((e & 3) + 8 * (e >> 2) + 4 * h) * 32 + r] = o;
             else if (ok) Out[(long)m * g.ldo + g.n_off + r] = o;
         }
         s1 += (double)f1; s2 += (double)f2;
@@ -513,7 +511,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_fwd_pair_bf16(const ConvFwdA
                 const int c = lane + 64 * i, pos = c >> 2, chunk = c & 3;
                 const int m = tbl[((te - t0) * TP + q.halo + pw * 32 + pos) & (PAIR_TBL - 1)];
                 const u16x8 v8 = *reinterpret_cast<const u16x8*>(ct + pos * 32 + chunk * 8);
-                if (m >= 0 && !TCVN_DBG_BIT(g.dbg, 128)) *reinterpret_cast<u16x8*>(Out + (long)m * g.ldo + g.n_off + chunk * 8) = v8;
+                if (m >= 0) *reinterpret_cast<u16x8*>(Out + (long)m * g.ldo + g.n_off + chunk * 8) = v8;
             }
         }
     };
@@ -599,7 +597,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_fwd_pair_bf16(const ConvFwdA
         bf16x8_t bw[32];
 #pragma unroll
         for (int i = 0; i < 32; ++i) bw[i] = *reinterpret_cast<const bf16x8_t*>(Wf + (40 + i) * 512);
-        if (!TCVN_DBG_BIT(g.dbg, 1024)) __builtin_amdgcn_s_setprio(1);     // the second-dispatched half loses every issue arbitration otherwise
+        __builtin_amdgcn_s_setprio(1);     // the second-dispatched half loses every issue arbitration otherwise
         PAIR_T0();
         int slot_dma = 0;
         for (int t = t0; t < t1; ++t) {
@@ -1263,7 +1261,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_dgrad_bf16(const ConvDgradAr
 // __syncthreads() would drain the DMA and the prefetched loads (its fence waits for vmcnt(0)).
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-__global__ __launch_bounds__(256, 2) void k_conv3x3_dgrad2_bf16(const ConvDgradArgs g, int n_img, int ntiles, int swz, int dbg) {
+__global__ __launch_bounds__(256, 2) void k_conv3x3_dgrad2_bf16(const ConvDgradArgs g, int n_img, int ntiles, int swz) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const EffSrc& e = g.e;
     const PadGeom q(n_img, g.H, g.W);
@@ -1359,7 +1357,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_dgrad2_bf16(const ConvDgradA
         for (int rr = er0; rr < nr; rr += 64) {
             const int m = tbl[cur * nr + rr];
             u16x8 o = {0, 0, 0, 0, 0, 0, 0, 0};
-            if (m >= 0 && !TCVN_DBG_BIT(dbg, 8)) {
+            if (m >= 0) {
                 const u16x8 gv = *reinterpret_cast<const u16x8*>(smem + o_rg + rr * 64 + ec * 16);
                 const u16x8 xv = *reinterpret_cast<const u16x8*>(smem + o_rd + rr * 64 + ec * 16);
                 const uint32_t kb = KM != nullptr ? *reinterpret_cast<const uint32_t*>(smem + o_km + rr * 4) >> (ec * 8) : 0u;
@@ -1385,7 +1383,6 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_dgrad2_bf16(const ConvDgradA
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int k = 0; k < 16; ++k) acc[i][k] = 0.f;
-        if (!TCVN_DBG_BIT(dbg, 2))
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
             const int base = q.halo - ((tap / 3 - 1) * q.Wp + (tap % 3 - 1)) + r + half * 64;      // source position = p - shift(tap)
@@ -1424,7 +1421,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_dgrad2_bf16(const ConvDgradA
             for (int i = 0; i < 2; ++i) {
                 const int rr = e_r0 + 16 * i;
                 const int m = tbl[cur * nr + q.halo + pass * 32 + rr];
-                if (m >= 0 && !TCVN_DBG_BIT(dbg, 4)) {
+                if (m >= 0) {
                     const float4 ca = *reinterpret_cast<const float4*>(Cs + rr * CLD3 + e_c8 * 8);
                     const float4 cc = *reinterpret_cast<const float4*>(Cs + rr * CLD3 + e_c8 * 8 + 4);
                     const float cv[8] = {ca.x, ca.y, ca.z, ca.w, cc.x, cc.y, cc.z, cc.w};
@@ -1677,13 +1674,13 @@ __global__ __launch_bounds__(512, 1) void k_conv3x3_dgrad3_bf16(const ConvDgradA
 static long cu_tiles() { return 256; }      // workgroups of a full persistent grid (one per CU)
 size_t dgrad3_smem() { return size_t(DG_RING) * 64 + DG_TBL * 4 + 448 * 4 + 8 * 32 * DG_CP * 4 + 4 * 18 * 1024; }
 bool dgrad3_ok(const ConvDgradArgs& a, const PadGeom& q) {
-    [[maybe_unused]] static const int dbg = TCVN_KNOB_INT("TCVN_DBG");
+    static const bool any_size = TCVN_KNOB_SET("TCVN_DGRAD3_ANY_SIZE");      // validation build: at any size
     // from 8 tiles per workgroup on: below that its prologue (72 KB of weights into LDS, the whole first eff image) costs more than the
     // ring saves (block 3, 816 tiles: 37 us against 32 us for the two-workgroup kernel; block 2, 3 600 tiles: 94 against 102)
-    return a.zeros != nullptr && a.e.N == 32 && (a.e.c_off & 7) == 0 && q.rows() + TP + 8 <= DG_RING && !TCVN_DBG_BIT(dbg, 4096) &&
-           (q.tiles() >= 8 * cu_tiles() || TCVN_DBG_BIT(dbg, 8192)) &&                 // TCVN_DBG=8192 (validation build): at any size
+    return a.zeros != nullptr && a.e.N == 32 && (a.e.c_off & 7) == 0 && q.rows() + TP + 8 <= DG_RING &&
+           (q.tiles() >= 8 * cu_tiles() || any_size) &&
            (reinterpret_cast<uintptr_t>(a.e.G) & 15) == 0 && (reinterpret_cast<uintptr_t>(a.e.X) & 15) == 0 &&
-           (reinterpret_cast<uintptr_t>(a.Xin) & 15) == 0 && (reinterpret_cast<uintptr_t>(a.Gout) & 15) == 0;      // TCVN_DBG=4096: the two-workgroup kernel
+           (reinterpret_cast<uintptr_t>(a.Xin) & 15) == 0 && (reinterpret_cast<uintptr_t>(a.Gout) & 15) == 0;
 }
 
 size_t dgrad2_smem(const PadGeom& q) { const size_t nr = (q.rows() + 15) & ~15; return 3 * nr * 64 + 2 * nr * 4 + 32 * 132 * 4 + 448 * 4 + ((nr + 63) & ~size_t(63)) * 4; }
@@ -1698,8 +1695,6 @@ int tile_grid2(long ntiles) {           // two workgroups per CU
 size_t wgrad_smem(const PadGeom& q) { const size_t r4 = (q.rows() + 3) & ~3; return r4 + TP + 8 <= 512 ? size_t(WG_RING_BYTES) + 2 * TP * 64 + 1024 * 4 + 3 * 128 * 4 : size_t(1) << 30; }
 
 int tile_grid(long ntiles) {            // one persistent workgroup per CU
-    [[maybe_unused]] static const int dbg = TCVN_KNOB_INT("TCVN_DBG");
-    if (TCVN_DBG_BIT(dbg, 16)) return (int)ntiles;                 // debug: one tile per workgroup
     if (ntiles >= 256) return 256;
     if (ntiles >= 8) return (int)(ntiles / 8 * 8);
     return (int)ntiles;
@@ -1728,27 +1723,28 @@ int conv3x3_tile_nblk(const ConvFwdArgs& a) {
     const PadGeom q(a.M / (a.H * a.W), a.H, a.W);
     return tile_grid(q.tiles());
 }
-static bool fwd_pair_ok(const ConvFwdArgs& a, const PadGeom& q, int dbg) {
-    return fwd_pair_smem(q) <= 160 * 1024 && 4 * TP + q.halo + q.Wp + 1 < PAIR_TBL && (long)a.M * a.N < (1L << 32) && !TCVN_DBG_BIT(dbg, 32) &&
-           !TCVN_DBG_BIT(dbg, 64);
+// validation build: TCVN_FWD_STRIP runs the strip kernel (k_conv3x3_fwd_bf16) where the pair or ring kernel would
+static bool fwd_strip_forced() {
+    static const bool on = TCVN_KNOB_SET("TCVN_FWD_STRIP");
+    return on;
+}
+static bool fwd_pair_ok(const ConvFwdArgs& a, const PadGeom& q) {
+    return fwd_pair_smem(q) <= 160 * 1024 && 4 * TP + q.halo + q.Wp + 1 < PAIR_TBL && (long)a.M * a.N < (1L << 32) && !fwd_strip_forced();
 }
 bool conv3x3_act_fusable(const ConvFwdArgs& a) {
     if (!conv3x3_tile_ok(a) || a.sc == nullptr || a.sh == nullptr || a.sl == nullptr) return false;
-    [[maybe_unused]] static const int dbg = TCVN_KNOB_INT("TCVN_DBG");
     static const bool off = TCVN_KNOB_SET("TCVN_NO_ACT_FUSE");      // validation build: keep the materialised activation (A/B and variant tests)
     const PadGeom q(a.M / (a.H * a.W), a.H, a.W);
     // forward: only the pair kernel activates in LDS; backward: the weight-gradient tile kernel (same geometry conditions as conv3x3_wgrad_tile_ok)
-    return !off && fwd_pair_ok(a, q, dbg) && wgrad_smem(q) <= 160 * 1024;
+    return !off && fwd_pair_ok(a, q) && wgrad_smem(q) <= 160 * 1024;
 }
 bool conv3x3_fwd_pair(const ConvFwdArgs& a) {          // conv_fwd(a) runs k_conv3x3_fwd_pair_bf16 (the kernel that honours lf / isum_out)
     if (!conv3x3_tile_ok(a)) return false;
-    [[maybe_unused]] static const int dbg = TCVN_KNOB_INT("TCVN_DBG");
-    return fwd_pair_ok(a, PadGeom(a.M / (a.H * a.W), a.H, a.W), dbg);
+    return fwd_pair_ok(a, PadGeom(a.M / (a.H * a.W), a.H, a.W));
 }
 bool conv3x3_fwd_writes_keep(const ConvFwdArgs& a) {
     if (a.keep_out == nullptr || a.drop_p <= 0.f || !conv3x3_tile_ok(a)) return false;
-    [[maybe_unused]] static const int dbg = TCVN_KNOB_INT("TCVN_DBG");
-    return fwd_pair_ok(a, PadGeom(a.M / (a.H * a.W), a.H, a.W), dbg);
+    return fwd_pair_ok(a, PadGeom(a.M / (a.H * a.W), a.H, a.W));
 }
 int conv3x3_fwd_tile(const ConvFwdArgs& a, hipStream_t st) {
     const int n_img = a.M / (a.H * a.W);
@@ -1763,34 +1759,31 @@ int conv3x3_fwd_tile(const ConvFwdArgs& a, hipStream_t st) {
         attr = true;
     }
     ProfScope ps("k_conv3x3_fwd_bf16", 2.0 * a.M * (double)a.N * a.K, (double)a.M * 2.0 * (a.C + a.N), st);   // read 128 ch, write N ch
-    ConvFwdArgs b = a;
-    static const int dbg = TCVN_KNOB_INT("TCVN_DBG");
-    b.dbg = dbg;
-    if (fwd_pair_ok(a, q, dbg)) {   // two waves per SIMD, taps split (TCVN_DBG=64: one-wave ring kernel)
+    if (fwd_pair_ok(a, q)) {   // two waves per SIMD, taps split
         static bool attr3 = false;
         if (!attr3) {
             TCVN_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv3x3_fwd_pair_bf16), hipFuncAttributeMaxDynamicSharedMemorySize,
                                            160 * 1024));
             attr3 = true;
         }
-        hipLaunchKernelGGL(k_conv3x3_fwd_pair_bf16, dim3(nb), dim3(512), fwd_pair_smem(q), st, b, n_img, ntiles, fwd_pair_ring(q));
+        hipLaunchKernelGGL(k_conv3x3_fwd_pair_bf16, dim3(nb), dim3(512), fwd_pair_smem(q), st, a, n_img, ntiles, fwd_pair_ring(q));
         TCVN_LAUNCH_CHECK();
         return 0;
     }
     if (a.lf.isum != nullptr || a.isum_out != nullptr) return -2;            // only the pair kernel derives / adds link-free statistics (conv3x3_fwd_pair)
-    if (!a.act_fused && ((q.rows() + 3) & ~3) + TP <= RING && !TCVN_DBG_BIT(dbg, 32)) {       // consecutive tiles per workgroup, ring image (TCVN_DBG=32: strips)
+    if (!a.act_fused && ((q.rows() + 3) & ~3) + TP <= RING && !fwd_strip_forced()) {       // consecutive tiles per workgroup, ring image
         static bool attr2 = false;
         if (!attr2) {
             TCVN_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv3x3_fwd_ring_bf16), hipFuncAttributeMaxDynamicSharedMemorySize,
                                            160 * 1024));
             attr2 = true;
         }
-        hipLaunchKernelGGL(k_conv3x3_fwd_ring_bf16, dim3(nb), dim3(256), fwd_ring_smem(), st, b, n_img, ntiles);
+        hipLaunchKernelGGL(k_conv3x3_fwd_ring_bf16, dim3(nb), dim3(256), fwd_ring_smem(), st, a, n_img, ntiles);
         TCVN_LAUNCH_CHECK();
         return 0;
     }
     if (a.act_fused) return -2;                                               // only the pair kernel activates in LDS (conv3x3_act_fusable)
-    hipLaunchKernelGGL(k_conv3x3_fwd_bf16, dim3(nb), dim3(256), smem, st, b, n_img, ntiles, (nb >= 8 && nb % 8 == 0 && !TCVN_DBG_BIT(dbg, 8)) ? 1 : 0);
+    hipLaunchKernelGGL(k_conv3x3_fwd_bf16, dim3(nb), dim3(256), smem, st, a, n_img, ntiles, (nb >= 8 && nb % 8 == 0) ? 1 : 0);
     TCVN_LAUNCH_CHECK();
     return 0;
 }
@@ -1877,8 +1870,7 @@ int conv3x3_dgrad_tile(const ConvDgradArgs& a, hipStream_t st) {
             TCVN_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv3x3_dgrad2_bf16), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
             attr = true;
         }
-        static const int dbgd = TCVN_KNOB_INT("TCVN_DBG");
-        hipLaunchKernelGGL(k_conv3x3_dgrad2_bf16, dim3(nb), dim3(256), dgrad2_smem(q), st, a, n_img, ntiles, (nb >= 8 && nb % 8 == 0) ? 1 : 0, dbgd);
+        hipLaunchKernelGGL(k_conv3x3_dgrad2_bf16, dim3(nb), dim3(256), dgrad2_smem(q), st, a, n_img, ntiles, (nb >= 8 && nb % 8 == 0) ? 1 : 0);
         TCVN_LAUNCH_CHECK();
         return 0;
     }

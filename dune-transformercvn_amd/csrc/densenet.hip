@@ -165,9 +165,7 @@ void DenseNetPlan::layout(int n, bool bwd, Layout& L) const {
         std::vector<long> xas;
         for (int l = 0; l < bg.L; ++l) {
             const int cin = bg.C0 + l * cfg.growth;
-            // >= 0 marks the bf16 GEMM path; the activated copy itself is skipped with TCVN_XA_ONTHEFLY (then the GEMMs
-            // transform the raw concat buffer in LDS)
-            xas.push_back(fast1_ok(cin) ? b.take(xa_materialize() ? M * round_up(cin, 8) * esz : 0) : -1);
+            xas.push_back(fast1_ok(cin) ? b.take(M * round_up(cin, 8) * esz) : -1);     // >= 0 marks the bf16 GEMM path
         }
         L.XA.push_back(xas);
         const bool tfast = bg.has_trans && fastt_ok(bg.Ctot);
@@ -236,12 +234,6 @@ bool DenseNetPlan::fast1_ok(int cin) const {
 }
 bool DenseNetPlan::sparse_stem_possible() const {
     return cfg.mode == MODE_BF16 && cfg.in_ch >= 1 && cfg.in_ch <= 3 && cfg.init_ch == 64 && !blocks.empty() && (blocks[0].ld & 7) == 0;
-}
-bool tcvn::xa_materialize() {
-    static const bool on = !TCVN_KNOB_SET("TCVN_XA_ONTHEFLY");   // default: write prelu(bn1(x)) to HBM once per layer.  A/B on
-    // MI355X (B=32 x 8 prongs): transforming the raw tile in LDS inside the two GEMMs instead saves the copy (2.4 GB, 1.5 ms of
-    // k_act_bf16) but costs more than it saves at one or two waves per SIMD: fwd1x1 2.2 -> 4.8 ms, dW1 2.0 -> 3.0 ms, step 29.3 -> 30.7 ms
-    return on;
 }
 bool DenseNetPlan::fastt_ok(int Ctot) const {
     return cfg.mode == MODE_BF16 && conv3x3_tile_enabled() && round_up(Ctot, 32) <= 640 && Ctot / 2 <= 512;
@@ -504,7 +496,7 @@ int DenseNetPlan::forward(int n, const int32_t* coords, const float* values, lon
             // applies norm2 + PReLU and writes the activated map the 3x3 tile kernel stages -- the raw bottleneck output Y and the
             // k_act_bf16 pass over it (512 B per pixel and layer, one launch) do not exist.  Train mode needs Y for the statistics.
             bool fuse_ya = false;
-            if (mode == MODE_BF16 && !train && fast1 && xa_materialize()) {
+            if (mode == MODE_BF16 && !train && fast1) {
                 ConvFwdArgs c3{};
                 c3.mode = mode; c3.amode = A_3X3; c3.A = ws + L.Y[bi][l]; c3.lda = mid; c3.M = (int)M; c3.N = g; c3.K = 9 * mid;
                 c3.Kp = wk_find(ls.w2, 0).Kp; c3.C = mid; c3.H = bg.H; c3.W = bg.W; c3.Wk = ws + L.wk + wk_find(ls.w2, 0).off;
@@ -518,14 +510,13 @@ int DenseNetPlan::forward(int n, const int32_t* coords, const float* values, lon
             // Train mode (round 4): the 1x1 runs on the RAW concat buffer, norm1 + PReLU1 applied to the landed LDS tiles (fwd1x1_fused.hip);
             // the fused 1x1 backward kernel rebuilds that activation from x, so the activated copy XA is neither written nor read.
             static const bool no_fuse1 = TCVN_KNOB_SET("TCVN_NO_FWD1_FUSE") || TCVN_KNOB_SET("TCVN_NO_BWD1_FUSE");
-            static const bool no_wide1 = TCVN_KNOB_SET("TCVN_NO_FWD1_WIDE");         // validation build: wide layers on k_act_bf16 + the 128-row GEMM
             bool lf2 = false;                  // the 3x3 pair kernel derives norm2's table itself (no link launch in front of it)
             bool n1_linked = false;
             auto link_n1 = [&]() -> int {      // norm1's table by the link kernel (window sums from the partial rows or from isumD)
                 n1_linked = true;
                 return link(ls.n1, part, new_nblk, new_ld, new_c0, new_n, bstatD, M, new_isum ? isumD + 2 * new_c0 : nullptr, 2L * bg.ld);
             };
-            if ((train || fuse_ya) && fast1 && !no_fuse1 && mid == 128 && mode == MODE_BF16 && !(no_wide1 && wk_find(ls.w1, 0, 1).Kp > 256)) {
+            if ((train || fuse_ya) && fast1 && !no_fuse1 && mid == 128 && mode == MODE_BF16) {
                 const WkEntry& e = wk_find(ls.w1, 0, 1);
                 Tab t1 = tab(ls.n1);
                 Fwd1x1Args fa{};
@@ -542,8 +533,7 @@ int DenseNetPlan::forward(int n, const int32_t* coords, const float* values, lon
                     long long* isumY = lf_on ? reinterpret_cast<long long*>(ws + L.isumY[bi][l]) : nullptr;
                     // link-free consumer of norm1: the fresh window was added to isumD by the previous layer's 3x3 kernel (the block's first
                     // layer follows a transition / the stem, whose statistics still leave as partial rows: link kernel)
-                    static const bool lf_no1 = TCVN_KNOB_SET("TCVN_LF_NO1"), lf_no2 = TCVN_KNOB_SET("TCVN_LF_NO2");      // validation build: the link kernel
-                    if (lf_on && new_isum && !lf_no1) fa.lf = lf_of(ls.n1, isumD + 2 * new_c0, 2L * bg.ld, new_c0, new_n, bstatD, M);
+                    if (lf_on && new_isum) fa.lf = lf_of(ls.n1, isumD + 2 * new_c0, 2L * bg.ld, new_c0, new_n, bstatD, M);
                     else if ((rc = link_n1())) return rc;
                     fa.isum_out = isumY; fa.isum_stride = 2L * mid;       // link-free producer of norm2's statistics
                     if ((rc = fwd1x1_fused(fa, st))) return rc;
@@ -555,7 +545,7 @@ int DenseNetPlan::forward(int n, const int32_t* coords, const float* values, lon
                         c3.Wfrag = wk_frag(ws, L, ls.w2, 0); c3.Aact = ws + L.Y[bi][l]; c3.zeros = ws + L.zeros;
                         Tab t2 = tab(ls.n2);
                         c3.sc = t2.sc; c3.sh = t2.sh; c3.sl = data[ls.a2];
-                        lf2 = conv3x3_act_fusable(c3) && conv3x3_fwd_pair(c3) && !lf_no2;
+                        lf2 = conv3x3_act_fusable(c3) && conv3x3_fwd_pair(c3);
                     }
                     if (!lf2 && (rc = link(ls.n2, part, fa.nblk, mid, 0, mid, reinterpret_cast<double*>(ws + L.bstatY[bi][l]), M, isumY, 2L * mid))) return rc;
                     xa_skipped[bi][l] = 1;
@@ -563,7 +553,7 @@ int DenseNetPlan::forward(int n, const int32_t* coords, const float* values, lon
                 }
             }
             if (!n1_linked && (rc = link_n1())) return rc;
-            if (fast1 && xa_materialize()) {     // activated copy of the 1x1 input: operand of the bf16 GEMMs (forward, weight gradient)
+            if (fast1) {     // activated copy of the 1x1 input: operand of the bf16 GEMMs (forward, weight gradient)
                 Tab t1 = tab(ls.n1);
                 ActArgs act{D, bg.ld, M, ls.cin, t1.sc, t1.sh, data[ls.a1], ws + L.XA[bi][l], cin8};
                 if ((rc = act_bf16(act, st))) return rc;
@@ -572,10 +562,6 @@ int DenseNetPlan::forward(int n, const int32_t* coords, const float* values, lon
                 const WkEntry& e = wk_find(ls.w1, 0, 1);
                 GemmNtArgs a{};
                 a.epi = EPI_FWD; a.A = ws + L.XA[bi][l]; a.lda = cin8; a.K = cin8; a.M = M; a.N = mid;
-                if (!xa_materialize()) {      // raw concat buffer in, BatchNorm + PReLU applied to every landed LDS tile
-                    Tab t1 = tab(ls.n1);
-                    a.A = D; a.lda = bg.ld; a.asc = t1.sc; a.ash = t1.sh; a.asl = data[ls.a1]; a.Kreal = ls.cin;
-                }
                 a.Wfrag = ws + L.wk + e.off; a.Kp = e.Kp; a.zeros = ws + L.zeros; a.bias = data[ls.b1];
                 a.Out = ws + L.Y[bi][l]; a.ldo = mid; a.n_off = 0; a.part = train ? part : nullptr; a.nblk = gemm_nt_nblk(a);
                 if (fuse_ya) {                 // eval: norm2 + PReLU in the GEMM epilogue, the activated map is the only output
@@ -740,7 +726,7 @@ int DenseNetPlan::tap(int n, const char* name, long* off, int* tn, int* th, int*
         b -= 1;
         if (b < 0 || b >= (int)blocks.size() || l < 0 || l >= blocks[b].L) return -1;
         const bool xa = s[0] == 'x';
-        if ((xa && (!xa_materialize() || L.XA[b].empty() || L.XA[b][l] < 0)) || (!xa && L.YA[b].empty())) return -1;
+        if ((xa && (L.XA[b].empty() || L.XA[b][l] < 0)) || (!xa && L.YA[b].empty())) return -1;
         if (xa && n == last_n && b < (int)xa_skipped.size() && l < (int)xa_skipped[b].size() && xa_skipped[b][l]) return -1;                 // 1x1 ran on the raw buffer
         if (!xa && n == last_n && b < (int)act_fused.size() && l < (int)act_fused[b].size() && act_fused[b][l]) return -1;   // activated in LDS only
         *off = xa ? L.XA[b][l] : L.YA[b][l]; *th = blocks[b].H; *tw = blocks[b].W;

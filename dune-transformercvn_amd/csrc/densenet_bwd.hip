@@ -22,7 +22,7 @@ void tcvn::set_backward_overlap(int on) { g_backward_overlap = on; }
 namespace {
 constexpr float kEps = 1e-5f;
 constexpr long kSlabBytes = 48L << 20;      // per-workgroup partial weight gradients (<= 256 x 147 KB) and column sums
-constexpr long kSlab1GemmBytes = 64L << 20; // fused 1x1 backward: 256 workgroups x [128][512] fp32 (bwd1x1_wide.hip), bias column sums behind them
+constexpr long kSlab1GemmBytes = 64L << 20; // fused 1x1 backward: per-workgroup [128][ldc] fp32 weight-gradient tiles, bias column sums behind them
 constexpr long kSlab1Bytes = 68L << 20;
 constexpr long kSlabGemmBytes = 44L << 20;  // GEMM slabs; the tail [44 MB, 48 MB) holds the bias column-sum partials (<= 1024 x 512 floats)
 struct Bump {
@@ -114,15 +114,13 @@ int DenseNetPlan::backward(int n, const float* d_out, long d_out_ld, char* ws, l
     const uint64_t seed = last_seed;
     // Weight gradients (3x3 and 1x1, with their slab reductions) do not feed the data-gradient chain: in bf16 mode they run on a
     // side stream beside it.  Shared state: the slab (side stream only between drains), EY (double buffered, released by
-    // ev_done), the bias column-sum partials (two halves of the slab tail).  TCVN_BWD_SERIAL=1 keeps everything on `st`.
-    static const bool serial_env = TCVN_KNOB_SET("TCVN_BWD_SERIAL");
+    // ev_done), the bias column-sum partials (two halves of the slab tail).  tcvn_backward_overlap(0), the default, keeps everything on `st`.
     static const bool no_fuse1 = TCVN_KNOB_SET("TCVN_NO_BWD1_FUSE");      // validation build: the three-kernel 1x1 backward (eff copy, TN GEMM, NT GEMM)
     // Every width takes the fused kernel.  A/B on MI355X (B = 32 x 8 prongs, validation build): fused for cin <= 256 only 19.76 ms/step, <= 384
     // 19.39, all layers 19.16 -- although a launch with three or four 128-column slices (block 3: every slice re-reads DU / Y and rebuilds EY)
     // takes longer than k_eff_mat + k_gemm_nt did (105 against ~58 us at four slices), the step is shorter without the two extra launches
-    // per layer on the main stream and the TN GEMM competing on the side stream.  TCVN_BWD1_MAXCIN (validation build) restores a limit.
-    static const int fuse1_maxcin = TCVN_KNOB_INT("TCVN_BWD1_MAXCIN") > 0 ? TCVN_KNOB_INT("TCVN_BWD1_MAXCIN") : (1 << 30);
-    const bool side_on = fast3x3 && !serial_env && backward_overlap_enabled();
+    // per layer on the main stream and the TN GEMM competing on the side stream.
+    const bool side_on = fast3x3 && backward_overlap_enabled();
     if (side_on && (rc = ensure_side())) return rc;
     int seq = 0;                                   // parity of the EY buffer / tail half; reset by drain()
     bool side_busy = false;
@@ -306,9 +304,8 @@ int DenseNetPlan::backward(int n, const float* d_out, long d_out_ld, char* ws, l
             // Fused 1x1 backward (round 4, bwd1x1_fused.hip): effective gradient formed in LDS, bias / data / weight gradient and the norm1
             // backward epilogue in one pass -- no EY in HBM, no read of the activated copy XA, one launch instead of three.  It writes G, so it
             // runs on `st`; its slabs are its own (L.slab belongs to the 3x3 weight gradient, which may be on the side stream).
-            const bool xa_absent = bi < (int)xa_skipped.size() && l < (int)xa_skipped[bi].size() && xa_skipped[bi][l];
             Bwd1x1Args fa{};
-            bool fuse1 = L.XA[bi][l] >= 0 && !no_fuse1 && mid == 128 && L.slab1 >= 0 && (ls.cin <= fuse1_maxcin || xa_absent);
+            bool fuse1 = L.XA[bi][l] >= 0 && !no_fuse1 && mid == 128 && L.slab1 >= 0;
             if (fuse1) fuse1 = bwd1x1_fill(bi, l, M, ws, L, fa);       // (the same function the forward asked before it dropped the activated copy)
             SlabJob w3jobs[2] = {};        // the 3x3 weight gradient's slab reductions, folded into the fused kernel's reduction launch (same stream only)
             bool w3_deferred = false;
@@ -340,16 +337,10 @@ int DenseNetPlan::backward(int n, const float* d_out, long d_out_ld, char* ws, l
                 // one launch reduces this kernel's slabs and the 3x3 weight gradient's.
                 if ((rc = bwd1x1_fused_launch(fa, st))) return rc;
                 // Round 5: the norm1 link rides in the reduction launch (an extra z-plane of k_slab_reduce_link): both are ~5 us latency-floor
-                // launches on the critical chain and independent of each other -- 60 launches fewer per step (TCVN_SPLIT_LINK: two launches)
-                static const bool split_link = TCVN_KNOB_SET("TCVN_SPLIT_LINK");
-                if (split_link) {
-                    if ((rc = bwd1x1_fused_reduce(fa, gw_of(ls.w1), grad[ls.b1], w3_deferred ? w3jobs : nullptr, st))) return rc;
-                    if ((rc = bwd_link(ls.n1, fa.nblk, bstatD, M, P, Q, 1, ls.a1))) return rc;
-                } else {
-                    const BnSlots& s1 = ls.n1;
-                    BnBwdLinkArgs la{part, fa.nblk, s1.C, bstatD, M, kEps, data[s1.w], grad[s1.w], grad[s1.b], grad[ls.a1], P, Q, 1};
-                    if ((rc = bwd1x1_fused_reduce(fa, gw_of(ls.w1), grad[ls.b1], w3_deferred ? w3jobs : nullptr, st, &la))) return rc;
-                }
+                // launches on the critical chain and independent of each other -- 60 launches fewer per step
+                const BnSlots& s1 = ls.n1;
+                BnBwdLinkArgs la{part, fa.nblk, s1.C, bstatD, M, kEps, data[s1.w], grad[s1.w], grad[s1.b], grad[ls.a1], P, Q, 1};
+                if ((rc = bwd1x1_fused_reduce(fa, gw_of(ls.w1), grad[ls.b1], w3_deferred ? w3jobs : nullptr, st, &la))) return rc;
                 continue;
             }
             if (bi < (int)xa_skipped.size() && l < (int)xa_skipped[bi].size() && xa_skipped[bi][l]) {
@@ -380,9 +371,6 @@ int DenseNetPlan::backward(int n, const float* d_out, long d_out_ld, char* ws, l
                     const int cin8 = (int)round_up(ls.cin, 8);
                     GemmTnArgs ga{EY, mid, mid, ws + L.XA[bi][l], cin8, cin8, M, gw_of(ls.w1), ef.Kp, ws + L.zeros,
                                   reinterpret_cast<float*>(ws + L.slab), kSlabGemmBytes, mid, bias_job};
-                    if (!xa_materialize()) {      // raw concat buffer as the R operand, transformed tile by tile in LDS
-                        ga.R = D; ga.ldr = bg.ld; ga.rsc = sc_of(ls.n1); ga.rsh = sh_of(ls.n1); ga.rsl = data[ls.a1]; ga.Rreal = ls.cin;
-                    }
                     if ((rc = gemm_tn_bf16(ga, "k_gemm_tn_bf16<conv1>", par ? side_st : st))) return rc;
                     if (par) TCVN_CHECK(hipEventRecord(ev_done[seq & 1], side_st));
                 } else if ((rc = conv_wgrad(w, st))) return rc;

@@ -198,7 +198,7 @@ __device__ __forceinline__ void slab_reduce_body(const SlabJob& j, float (*red)[
         // 16 B per lane: a block covers 128 columns with eight slab lanes, eight loads in flight per thread.  (Round 4: the scalar version
         // moved the 37.7 MB slabs of a 3x3 weight gradient at 0.7 TB/s.  Round 5: with the slabs split over up to 16 y-slices the launch
         // spent its time in the fp32 atomics that merge the slices -- 557 K of them per dense layer; one y-slice per job (every launch of
-        // the DenseNet plan: <= 512 slabs) adds into dst directly, in a fixed order: 19.40 -> 19.17 ms per step, tools/r05_ab2.sh.)
+        // the DenseNet plan: <= 512 slabs) adds into dst directly, in a fixed order: 19.40 -> 19.17 ms per step; the A/B script, tools/r05_ab2.sh, is removed, see git history.)
         const int cl = threadIdx.x & 31, sl = threadIdx.x >> 5;
         const long i = ((long)blockIdx.x * 32 + cl) * 4;
         if ((long)blockIdx.x * 128 >= j.count) return;
@@ -325,8 +325,7 @@ SlabJob slab_job(const float* slab, int nslab, long count, float* dst, long stri
     SlabJob j{slab, dst, nslab, count, stride > 0 ? stride : count, 1, 1, 0};
     if (count <= 0 || nslab <= 0) { j.count = 0; return j; }
     j.v4 = (count % 4 == 0 && j.stride % 4 == 0 && (reinterpret_cast<uintptr_t>(slab) & 15) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0 && count >= 1024) ? 1 : 0;
-    static const int per_knob = TCVN_KNOB_INT("TCVN_SLAB_PER");     // validation build: slabs per y-slice of the 16-B path (A/B)
-    int ny = cdiv(nslab, j.v4 ? (per_knob > 0 ? per_knob : 512) : 64);           // 16-B path: one y-slice up to 512 slabs (no atomics; see slab_reduce_body)
+    int ny = cdiv(nslab, j.v4 ? 512 : 64);           // 16-B path: one y-slice up to 512 slabs (no atomics; see slab_reduce_body)
     if (ny > 16) ny = 16;
     j.ny = ny; j.per_y = cdiv(nslab, ny);
     return j;

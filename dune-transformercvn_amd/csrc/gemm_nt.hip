@@ -36,19 +36,16 @@ __device__ __forceinline__ void dma_a(char* smem_base, int buf_off, const bf16* 
     }
 }
 
-// XF = 1 (forward only): A is the RAW BatchNorm input; every landed A tile is transformed in LDS to prelu(sc*x + sh) before the
-// MFMAs read it (tables in LDS, 4-8 16-B chunks per thread), so the activated copy of the concat buffer is never written to HBM
-// XF = 2 (forward, eval mode): the epilogue applies the NEXT BatchNorm (running statistics: no batch reduction to wait for) and
+// OUT = OUT_ACT (forward, eval mode): the epilogue applies the NEXT BatchNorm (running statistics: no batch reduction to wait for) and
 // PReLU to the fp32 result before the one rounding to bf16 -- the raw 1x1 output and the pass that activated it disappear;
 // no statistics in this instance
-template <int EPI, int MAXKS, int ROWS, int XF = 0>
+enum { OUT_RAW = 0, OUT_ACT = 2 };
+template <int EPI, int MAXKS, int ROWS, int OUT = OUT_RAW>
 __global__ __launch_bounds__(256, ROWS == 64 ? 2 : 1) void k_gemm_nt_bf16(const GemmNtArgs g) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int TILE = ROWS * 256;
     float* Cs = reinterpret_cast<float*>(smem + 2 * TILE);                 // [ROWS][CLD]
     double* red = reinterpret_cast<double*>(smem + 2 * TILE);              // [4][128][3] aliases Cs after the last tile
-    float* atab = reinterpret_cast<float*>(smem + 2 * TILE + ROWS * CLD * 4);   // XF: [3][Kt] scale, shift, slope of the A transform
-    const int Kt = (g.K + 7) & ~7;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, h = lane >> 5;
@@ -78,7 +75,7 @@ __global__ __launch_bounds__(256, ROWS == 64 ? 2 : 1) void k_gemm_nt_bf16(const 
     for (int j = 0; j < 8; ++j) {
         const bool ok = ncol + j < g.N;
         cb[j] = (EPI == EPI_FWD && ok) ? g.bias[ncol + j] : 0.f;
-        if (XF == 2) {
+        if (OUT == OUT_ACT) {
             csc[j] = ok ? g.osc[ncol + j] : 0.f; csh[j] = ok ? g.osh[ncol + j] : 0.f; csl[j] = ok ? g.osl[ncol + j] : 0.f;
         } else {
             csc[j] = (EPI != EPI_FWD && ok) ? g.sc[ncol + j] : 0.f;
@@ -93,34 +90,6 @@ __global__ __launch_bounds__(256, ROWS == 64 ? 2 : 1) void k_gemm_nt_bf16(const 
 #pragma unroll
     for (int j = 0; j < 8; ++j) { st1[j] = 0; st2[j] = 0; st3[j] = 0; }
 
-    if (XF == 1) {
-        for (int i = threadIdx.x; i < Kt; i += 256) {
-            const bool ok = i < g.Kreal;
-            atab[i] = ok ? g.asc[i] : 0.f; atab[Kt + i] = ok ? g.ash[i] : 0.f; atab[2 * Kt + i] = ok ? g.asl[i] : 0.f;
-        }
-    }
-    // in-LDS transform of the k-chunk kc held in buffer `buf`: slot s of row r holds source chunk s ^ (r & 15)
-    auto xform = [&](int buf, int kc) {
-#pragma unroll
-        for (int it = 0; it < ROWS * 16 / 256; ++it) {
-            const int idx = tid + 256 * it, row = idx >> 4, slot = idx & 15;
-            const int col = kc * 128 + ((slot ^ (row & 15)) << 3);
-            if (col < Kt) {
-                u16x8* p = reinterpret_cast<u16x8*>(smem + buf + row * 256 + (slot << 4));
-                const u16x8 v = *p;
-                const float4 s0 = *reinterpret_cast<const float4*>(atab + col), s1 = *reinterpret_cast<const float4*>(atab + col + 4);
-                const float4 h0 = *reinterpret_cast<const float4*>(atab + Kt + col), h1 = *reinterpret_cast<const float4*>(atab + Kt + col + 4);
-                const float4 l0 = *reinterpret_cast<const float4*>(atab + 2 * Kt + col), l1 = *reinterpret_cast<const float4*>(atab + 2 * Kt + col + 4);
-                const float sc[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
-                const float sh[8] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
-                const float sl[8] = {l0.x, l0.y, l0.z, l0.w, l1.x, l1.y, l1.z, l1.w};
-                u16x8 o;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) o[j] = col + j < g.Kreal ? f2bf(prelu(fmaf(bf2f(v[j]), sc[j], sh[j]), sl[j])) : (bf16)0;
-                *p = o;
-            }
-        }
-    };
     long mt = blockIdx.x;
     if (mt < mtiles) dma_a<ROWS>(smem, 0, A, g.lda, g.K, 0, mt * ROWS, g.M, zeros, wave, lane);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -154,10 +123,6 @@ __global__ __launch_bounds__(256, ROWS == 64 ? 2 : 1) void k_gemm_nt_bf16(const 
                 if (kc + 1 < nkc) dma_a<ROWS>(smem, (cur ^ 1) * TILE, A, g.lda, g.K, (kc + 1) * 128, mt * ROWS, g.M, zeros, wave, lane);
                 else if (mt + gridDim.x < mtiles) dma_a<ROWS>(smem, (cur ^ 1) * TILE, A, g.lda, g.K, 0, (mt + gridDim.x) * ROWS, g.M, zeros, wave, lane);
                 const int ab = cur * TILE;
-                if (XF == 1) {                  // bare barrier: a __syncthreads() would drain the prefetch just issued
-                    xform(ab, kc);
-                    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-                }
 #pragma unroll
                 for (int ks = 0; ks < 8; ++ks) {
                     if (kc * 8 + ks < ksteps) {
@@ -253,9 +218,9 @@ __global__ __launch_bounds__(256, ROWS == 64 ? 2 : 1) void k_gemm_nt_bf16(const 
 #pragma unroll
                         for (int j = 0; j < 8; ++j) {
                             float v = cv[j] + cb[j];
-                            if (XF == 2) v = prelu(fmaf(v, csc[j], csh[j]), csl[j]);
+                            if (OUT == OUT_ACT) v = prelu(fmaf(v, csc[j], csh[j]), csl[j]);
                             o[j] = ncol + j < g.N ? f2bf(v) : (bf16)0;                   // channels beyond N: zero (written later)
-                            if (XF != 2) { const float x = bf2f(o[j]); f1[j] += x; f2[j] += x * x; }
+                            if (OUT != OUT_ACT) { const float x = bf2f(o[j]); f1[j] += x; f2[j] += x * x; }
                         }
                         *reinterpret_cast<u16x8*>(reinterpret_cast<bf16*>(g.Out) + m * g.ldo + g.n_off + ncol) = o;
                     } else {
@@ -286,7 +251,7 @@ __global__ __launch_bounds__(256, ROWS == 64 ? 2 : 1) void k_gemm_nt_bf16(const 
         }
         __syncthreads();
     }
-    if (XF == 2 || g.part == nullptr) return;
+    if (OUT == OUT_ACT || g.part == nullptr) return;
     // reduce over the 16 row groups: 4 per wave by shuffles (lanes differing in bits 4,5), then across waves through LDS
     constexpr int NS = EPI == EPI_FWD ? 2 : 3;
 #pragma unroll
@@ -374,18 +339,17 @@ int gemm_nt_bf16(const GemmNtArgs& a, const char* label, hipStream_t st) {
     if (!gemm_nt_ok(a)) return -2;
     if (a.part != nullptr && a.nblk != gemm_nt_nblk(a)) { fprintf(stderr, "tcvn: gemm_nt nblk mismatch\n"); return -3; }
     const int rows = nt_rows(a);
-    const size_t smem = 2 * rows * 256 + (size_t)rows * CLD * 4 + (a.epi == EPI_FWD && a.asc != nullptr ? 3 * ((a.K + 7) & ~7) * 4 : 0);
+    const size_t smem = 2 * rows * 256 + (size_t)rows * CLD * 4;
     static bool attr = false;
     if (!attr) {
-        const void* fns[10] = {reinterpret_cast<const void*>(k_gemm_nt_bf16<EPI_FWD, KS_FWD, 128, 2>),
-                              reinterpret_cast<const void*>(k_gemm_nt_bf16<EPI_FWD, KS_FWD_SMALL, 64, 2>),reinterpret_cast<const void*>(k_gemm_nt_bf16<EPI_FWD, KS_FWD, 128>),
+        const void* fns[8] = {reinterpret_cast<const void*>(k_gemm_nt_bf16<EPI_FWD, KS_FWD, 128, OUT_ACT>),
+                              reinterpret_cast<const void*>(k_gemm_nt_bf16<EPI_FWD, KS_FWD_SMALL, 64, OUT_ACT>),
+                              reinterpret_cast<const void*>(k_gemm_nt_bf16<EPI_FWD, KS_FWD, 128>),
                               reinterpret_cast<const void*>(k_gemm_nt_bf16<EPI_FWD, KS_FWD_SMALL, 64>),
                               reinterpret_cast<const void*>(k_gemm_nt_bf16<EPI_DGRAD, KS_DGRAD, 64>),
                               reinterpret_cast<const void*>(k_gemm_nt_bf16<EPI_DGRAD, KS_DGRAD_SMALL, 64>),
                               reinterpret_cast<const void*>(k_gemm_nt_bf16<EPI_DGRAD_POOL, KS_POOL, 128>),
-                              reinterpret_cast<const void*>(k_gemm_nt_bf16<EPI_DGRAD_POOL, KS_POOL_SMALL, 64>),
-                              reinterpret_cast<const void*>(k_gemm_nt_bf16<EPI_FWD, KS_FWD, 128, 1>),
-                              reinterpret_cast<const void*>(k_gemm_nt_bf16<EPI_FWD, KS_FWD_SMALL, 64, 1>)};
+                              reinterpret_cast<const void*>(k_gemm_nt_bf16<EPI_DGRAD_POOL, KS_POOL_SMALL, 64>)};
         for (const void* f : fns) TCVN_CHECK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr = true;
     }
@@ -396,13 +360,10 @@ int gemm_nt_bf16(const GemmNtArgs& a, const char* label, hipStream_t st) {
     const double bytes = (double)a.M * 2.0 * (a.K + (a.epi == EPI_FWD ? (double)a.N : 2.0 * px * a.N));
     ProfScope ps(label, 2.0 * a.M * (double)a.N * a.K, bytes, st);
     const dim3 grid(gemm_nt_nblk(a), cdiv(a.N, 128));
-    const bool xf = a.epi == EPI_FWD && a.asc != nullptr;
     const bool oact = a.epi == EPI_FWD && a.osc != nullptr;
-    if (oact && (xf || a.part != nullptr || !a.osh || !a.osl)) return -2;      // eval-mode epilogue: no statistics, materialised A
-    if (oact && a.Kp <= KS_FWD_SMALL * 16) hipLaunchKernelGGL((k_gemm_nt_bf16<EPI_FWD, KS_FWD_SMALL, 64, 2>), grid, dim3(256), smem, st, a);
-    else if (oact) hipLaunchKernelGGL((k_gemm_nt_bf16<EPI_FWD, KS_FWD, 128, 2>), grid, dim3(256), smem, st, a);
-    else if (xf && a.Kp <= KS_FWD_SMALL * 16) hipLaunchKernelGGL((k_gemm_nt_bf16<EPI_FWD, KS_FWD_SMALL, 64, 1>), grid, dim3(256), smem, st, a);
-    else if (xf) hipLaunchKernelGGL((k_gemm_nt_bf16<EPI_FWD, KS_FWD, 128, 1>), grid, dim3(256), smem, st, a);
+    if (oact && (a.part != nullptr || !a.osh || !a.osl)) return -2;      // eval-mode epilogue: no statistics
+    if (oact && a.Kp <= KS_FWD_SMALL * 16) hipLaunchKernelGGL((k_gemm_nt_bf16<EPI_FWD, KS_FWD_SMALL, 64, OUT_ACT>), grid, dim3(256), smem, st, a);
+    else if (oact) hipLaunchKernelGGL((k_gemm_nt_bf16<EPI_FWD, KS_FWD, 128, OUT_ACT>), grid, dim3(256), smem, st, a);
     else if (a.epi == EPI_FWD && a.Kp <= KS_FWD_SMALL * 16) hipLaunchKernelGGL((k_gemm_nt_bf16<EPI_FWD, KS_FWD_SMALL, 64>), grid, dim3(256), smem, st, a);
     else if (a.epi == EPI_FWD) hipLaunchKernelGGL((k_gemm_nt_bf16<EPI_FWD, KS_FWD, 128>), grid, dim3(256), smem, st, a);
     else if (a.epi == EPI_DGRAD && a.Kp <= KS_DGRAD_SMALL * 16) hipLaunchKernelGGL((k_gemm_nt_bf16<EPI_DGRAD, KS_DGRAD_SMALL, 64>), grid, dim3(256), smem, st, a);

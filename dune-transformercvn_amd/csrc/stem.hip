@@ -339,6 +339,7 @@ constexpr int ST_TH = 8, ST_TW = 16;                        // output tile
 constexpr int ST_PR = 2 * ST_TH + 5, ST_PW = 40;            // patch rows, patch pitch in pixels (37 used)
 constexpr int ST_CP = 72;                                   // C tile pitch in bf16 (64 + 8: lane halves on different banks)
 
+#ifdef TCVN_DEBUG_KNOBS   // the first version: validation build only, the bit-identical reference of k_stem_fwd2_bf16 (TCVN_STEM_FWD_V1)
 __global__ __launch_bounds__(256, 2) void k_stem_fwd_bf16(const ConvFwdArgs g, int n_img, int tiles_x, int tiles_y) {
     __shared__ __attribute__((aligned(16))) unsigned short patch[2][ST_PR * ST_PW * 4];
     __shared__ __attribute__((aligned(16))) unsigned short ctile[ST_TH * ST_TW * ST_CP];
@@ -469,6 +470,7 @@ __global__ __launch_bounds__(256, 2) void k_stem_fwd_bf16(const ConvFwdArgs g, i
         }
     }
 }
+#endif
 // ---------------------------------------------------------------------------------------------------------------------
 // conv0 forward, second version.  Same tile, patch and contraction order as k_stem_fwd_bf16; what changed is everything around the
 // 28 MFMAs, which was ~1 100 instructions per wave and tile (the kernel wrote its 1 GB at 1.36 TB/s, issue-bound):
@@ -685,9 +687,15 @@ int stem_fwd_nblk(const ConvFwdArgs& a) {
 int stem_fwd_bf16(const ConvFwdArgs& a, hipStream_t st) {
     const int n_img = a.M / (a.H * a.W);
     ProfScope ps("k_stem_fwd_bf16", 2.0 * a.M * (double)a.N * a.K, (double)a.M * 2.0 * (a.N + 4.0 * a.C), st);
-    [[maybe_unused]] static const bool old_kernel = TCVN_KNOB_SET("TCVN_STEM_FWD_V1");         // validation build: the first version
-    if (old_kernel) hipLaunchKernelGGL(k_stem_fwd_bf16, dim3(stem_fwd_nblk(a)), dim3(256), 0, st, a, n_img, cdiv(a.W, ST_TW), cdiv(a.H, ST_TH));
-    else hipLaunchKernelGGL(k_stem_fwd2_bf16, dim3(stem_fwd_nblk(a)), dim3(256), 0, st, a, n_img, cdiv(a.W, ST_TW), cdiv(a.H, ST_TH));
+#ifdef TCVN_DEBUG_KNOBS
+    static const bool v1 = TCVN_KNOB_SET("TCVN_STEM_FWD_V1");         // validation build: the first version
+    if (v1) {
+        hipLaunchKernelGGL(k_stem_fwd_bf16, dim3(stem_fwd_nblk(a)), dim3(256), 0, st, a, n_img, cdiv(a.W, ST_TW), cdiv(a.H, ST_TH));
+        TCVN_LAUNCH_CHECK();
+        return 0;
+    }
+#endif
+    hipLaunchKernelGGL(k_stem_fwd2_bf16, dim3(stem_fwd_nblk(a)), dim3(256), 0, st, a, n_img, cdiv(a.W, ST_TW), cdiv(a.H, ST_TH));
     TCVN_LAUNCH_CHECK();
     return 0;
 }

@@ -5,17 +5,21 @@
 #include <stdio.h>
 #include <stdlib.h>
 
-// Validation / ablation switches exist only in builds made with -DTCVN_DEBUG_KNOBS (`make debug` -> libtcvn_hip_dbg.so, used by
-// the tests that compare kernel variants).  The default library reads no environment variable and contains none of the
-// work-dropping branches: TCVN_KNOB_* fold to constants and the compiler removes the code behind them.
+// Validation switches exist only in builds made with -DTCVN_DEBUG_KNOBS (`make debug` -> libtcvn_hip_dbg.so, used by the tests that
+// compare kernel variants).  The default library reads no environment variable: TCVN_KNOB_SET folds to false and the compiler removes
+// the code behind it.  Every switch is set by some test:
+//   TCVN_DISABLE_TILE       generic kernels instead of the bf16 tile / GEMM paths
+//   TCVN_FWD_STRIP          3x3 forward: the strip kernel instead of the pair / ring kernels
+//   TCVN_DGRAD3_ANY_SIZE    3x3 data gradient: the consecutive-tile kernel at any size
+//   TCVN_NO_ACT_FUSE        3x3: the materialised activation instead of the in-LDS one
+//   TCVN_NO_FWD1_FUSE       1x1 forward: k_act_bf16 + the NT GEMM instead of the fused kernel
+//   TCVN_NO_BWD1_FUSE       1x1 forward and backward: the unfused kernels
+//   TCVN_NO_LF              the BatchNorm link kernels instead of link-free statistics
+//   TCVN_DENSE_STEM, TCVN_SPARSE_STEM_TRAIN, TCVN_NO_STEM_SKIP, TCVN_POOL0_BWD_FLAT, TCVN_STEM_FWD_V1    stem variants
 #ifdef TCVN_DEBUG_KNOBS
-#define TCVN_KNOB_INT(name) (getenv(name) ? atoi(getenv(name)) : 0)
 #define TCVN_KNOB_SET(name) (getenv(name) != nullptr)
-#define TCVN_DBG_BIT(v, bit) (((v) & (bit)) != 0)
 #else
-#define TCVN_KNOB_INT(name) 0
 #define TCVN_KNOB_SET(name) false
-#define TCVN_DBG_BIT(v, bit) false
 #endif
 
 namespace tcvn {

@@ -26,7 +26,6 @@ struct ConvFwdArgs {
     void* Out; long ldo; int n_off;
     const void* Wfrag;               // optional: the same weights in MFMA fragment order (bf16 fast paths)
     const void* Aact;                // optional: bf16 copy of A with the BN+PReLU already applied (k_act_bf16)
-    int dbg;                         // timing-ablation bits (TCVN_DBG env, validation builds only): 1 no DMA, 2 no MFMA, 4 no epilogue
     const void* zeros;               // >= 256 B of zeros in device memory (source of padding rows for LDS-DMA)
     double* part; int nblk;          // [nblk][N][2]; nblk = grid.x
     float drop_p; uint64_t seed; uint32_t stream_id;
@@ -220,8 +219,7 @@ int slab_reduce4(const SlabJob* jobs, int n, hipStream_t st);                  /
 struct GemmTnArgs { const void* L; long ldl; int Li; const void* R; long ldr; int Rj; long M; float* C; long ldc; const void* zeros;
                     float* slab; long slab_bytes;        // slab: scratch for per-slice partial tiles (no contended atomics)
                     int Ci;                              // rows of C written (<= Li; L columns in [Ci, Li) are zero padding)
-                    SlabJob extra;                       // optional second reduction folded into this GEMM's slab reduction
-                    const float *rsc, *rsh, *rsl; int Rreal; };   // optional: R is raw, transform prelu(rsc*x + rsh, rsl) in LDS
+                    SlabJob extra; };                    // optional second reduction folded into this GEMM's slab reduction
 // dst[i] += sum_s slab[s*count + i]   (deterministic reduction of per-workgroup partial results)
 int slab_reduce(const float* slab, int nslab, long count, float* dst, hipStream_t st, long stride = 0);   // stride 0 = count
 bool gemm_tn_ok(const GemmTnArgs& a);
@@ -236,8 +234,6 @@ struct GemmNtArgs {
     const void* Wfrag; int Kp;               // weights [N][Kp] in MFMA fragment order
     const void* zeros;
     const float* bias; void* Out; long ldo; int n_off;             // EPI_FWD
-    const float *asc, *ash, *asl; int Kreal;                       // EPI_FWD, optional: A is raw, transform prelu(asc*x + ash, asl) in LDS;
-                                                                   // channels >= Kreal are zeroed
     const float *osc, *osh, *osl;                                  // EPI_FWD, optional (eval mode, part == nullptr): Out = prelu(osc*(C + bias) + osh, osl)
                                                                    // -- the consumer's BatchNorm (running statistics) + PReLU applied in the epilogue
     const void* Xin; long ldxin; const float *sc, *sh, *sl;        // EPI_DGRAD*: BatchNorm input + its table
@@ -273,9 +269,6 @@ struct Bwd1x1Args {
 bool bwd1x1_fused_ok(const Bwd1x1Args& a);
 int bwd1x1_fused_nblk(const Bwd1x1Args& a);
 int bwd1x1_fused_launch(const Bwd1x1Args& a, hipStream_t st);
-bool bwd1x1_wide_ok(const Bwd1x1Args& a);       // bwd1x1_wide.hip: the same launch interface for 128 < cin <= 512 (called through bwd1x1_fused_*)
-int bwd1x1_wide_nblk(const Bwd1x1Args& a);
-int bwd1x1_wide_launch(const Bwd1x1Args& a, hipStream_t st);
 int bwd1x1_fused_reduce(const Bwd1x1Args& a, float* dWk, float* dbias, const SlabJob* extra, hipStream_t st, const BnBwdLinkArgs* link = nullptr);   // slab reductions into dWk [128][ldc], dbias [128]
                                                                                                   // (+ up to two more jobs in the same launch)
 

@@ -28,15 +28,16 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_product_library_has_no_environment_switches():
-    """The shipped library must not change behaviour with the environment: the validation / ablation knobs (TCVN_DBG,
-    TCVN_DISABLE_TILE, ...) exist only in the -DTCVN_DEBUG_KNOBS build (libtcvn_hip_dbg.so)."""
+    """The shipped library must not change behaviour with the environment: the validation switches (TCVN_DISABLE_TILE,
+    TCVN_FWD_STRIP, ...) exist only in the -DTCVN_DEBUG_KNOBS build (libtcvn_hip_dbg.so)."""
     import subprocess
     from transformercvn.hip import _lib
     assert os.path.basename(_lib.LIB_PATH) == "libtcvn_hip.so"
     undefined = subprocess.run(["nm", "-D", "--undefined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
     assert "getenv" not in undefined
     blob = open(_lib.LIB_PATH, "rb").read()
-    for knob in (b"TCVN_DBG", b"TCVN_DISABLE_TILE", b"TCVN_XA_ONTHEFLY", b"TCVN_BWD_SERIAL", b"TCVN_POOL0_BWD_FLAT", b"TCVN_DENSE_STEM", b"TCVN_SPARSE_STEM_TRAIN"):
+    for knob in (b"TCVN_DBG", b"TCVN_DISABLE_TILE", b"TCVN_XA_ONTHEFLY", b"TCVN_BWD_SERIAL", b"TCVN_POOL0_BWD_FLAT", b"TCVN_DENSE_STEM", b"TCVN_SPARSE_STEM_TRAIN",
+                 b"TCVN_FWD_STRIP", b"TCVN_DGRAD3_ANY_SIZE"):
         assert knob not in blob, knob
     # ... and the Python loader binds the product library whatever the environment says (the debug build is selected only by an
     # explicit _libselect.use() call in a test child process)

@@ -270,7 +270,7 @@ result = dict(out=out, taps=taps, grads=grads)
 
 
 def test_bf16_fallback_variants_match_default_variants():
-    """The strip forward kernel (TCVN_DBG=32: used when a map is wider than the 512-row LDS ring allows) and the flat pool0
+    """The strip forward kernel (TCVN_FWD_STRIP: used when a map is wider than the 512-row LDS ring allows) and the flat pool0
     backward (TCVN_POOL0_BWD_FLAT) against the default ring / tiled variants in a separate process: same arithmetic, different
     staging, so the forward must agree to bf16-rounding level."""
     import subprocess, sys, os
@@ -292,7 +292,7 @@ n_img = int(batch[7].sum())
 d_out = torch.randn(n_img, O.embed_dims(cfg)[0], generator=torch.Generator().manual_seed(5))
 out, taps, grads = T._run_bf16(cfg, sd, batch, True, d_out)
 result = dict(out=out, taps=taps, grads=grads)
-""", dict(TCVN_DBG="32", TCVN_POOL0_BWD_FLAT="1"))
+""", dict(TCVN_FWD_STRIP="1", TCVN_POOL0_BWD_FLAT="1"))
     e_out = ((out - ref["out"]).norm() / ref["out"].norm()).item()
     e_tap = max(((taps[k] - ref["taps"][k]).norm() / ref["taps"][k].norm()).item() for k in taps)
     k0 = "features.conv0.weight"
@@ -344,7 +344,7 @@ result = dict(c0=eng.tap('conv0').clone().cpu(), d1=eng.tap('dense1').float().cp
 
 def test_bf16_consecutive_tile_dgrad_matches_two_workgroup_kernel():
     """k_conv3x3_dgrad3_bf16 (consecutive tiles, eff ring, wave-private epilogue, dropout keep words; the product takes it from 8 tiles
-    per workgroup on, TCVN_DBG=8192 on the validation build forces it at this test's size, separate process) against
+    per workgroup on, TCVN_DGRAD3_ANY_SIZE on the validation build forces it at this test's size, separate process) against
     k_conv3x3_dgrad2_bf16 with dropout ON and the same seed: identical masks, identical bf16 products, different summation order in
     the fp32 statistics -- every gradient tensor must agree to bf16-rounding level.  (At BASELINE config 2's size the kernel is
     checked against the reference's numbers by tests/test_fullsize_gpu.py.)"""
@@ -368,7 +368,7 @@ n_img = int(batch[7].sum())
 d_out = torch.randn(n_img, O.embed_dims(cfg)[0], generator=torch.Generator().manual_seed(5))
 out, taps, grads = T._run_bf16(cfg, sd, batch, True, d_out)
 result = dict(out=out, taps=taps, grads=grads)
-""", dict(TCVN_DBG="8192"))
+""", dict(TCVN_DGRAD3_ANY_SIZE="1"))
     assert torch.equal(out, ref["out"])                   # same forward kernels, same masks
     errs = []
     for k, v in grads.items():
@@ -712,7 +712,9 @@ result = dict(out=out, taps=taps, grads=grads)
 @pytest.mark.parametrize("init_ch,structure,hw", [(200, [4], (104, 72)),      # cin 200..296: two and three column slices, resident and streamed forward chunks
                                                   (100, [3], (104, 72)),      # cin 100, 132, 164: a last partial 8-channel chunk (cin % 8 == 4)
                                                   (256, [6], (56, 40)),       # cin 256..416: two, three and (last layer) four column slices
-                                                  (250, [10], (56, 40))])     # cin 250..538 (cin % 8 == 2): up to four slices, K extents 256..544 (> 512: the forward falls back, backward five slices)
+                                                  (250, [10], (56, 40)),      # cin 250..538 (cin % 8 == 2): up to four slices, K extents 256..544 (> 512: the forward falls back, backward five slices)
+                                                  (136, [4], (104, 72)),      # cin 136..232: two slices, the second one 8..104 channels wide
+                                                  (232, [3], (104, 72))])     # cin 232, 264, 296: the last two three slices wide
 def test_fused_1x1_kernels_on_odd_widths_and_partial_tiles(init_ch, structure, hw):
     """The fused 1x1 forward / backward kernels against the kernels they replace (TCVN_NO_BWD1_FUSE on the validation build disables both) on
     layer widths and pixel counts the tutorial structure does not reach: channel counts that are not multiples of 8 (the last 16-B chunk of a row
@@ -767,43 +769,3 @@ result = dict(out=out, taps=taps, grads=grads)
     assert not worse, worse[:8]
     if len(structure) == 1 and structure[0] <= 4:
         assert errs[0][0] < 3e-2, errs[:6]
-
-
-@pytest.mark.parametrize("init_ch,structure,hw", [(136, [4], (104, 72)),      # cin 136..232: two slices, the second one 8..104 channels wide
-                                                  (232, [3], (104, 72)),      # cin 232, 264, 296: the last two three slices wide (three register sets of G rows)
-                                                  (256, [6], (56, 40))])      # cin 256..416: the last layer four slices wide; 351 pixels per image (partial tiles)
-def test_wide_1x1_backward_matches_the_per_slice_kernel(init_ch, structure, hw):
-    """Round 5: k_bwd1x1_wide_bf16<NS> (one workgroup per pixel tile walks the NS column slices of a layer with 128 < cin <= 512: DU / Y
-    fetched and EY formed once per pixel, every operand prefetched on a fixed schedule behind counted waits; opt-in on the validation build,
-    TCVN_BWD1_WIDE -- it measured slower than what it was to replace) against k_bwd1x1_fused_bf16 (one workgroup per
-    (tile, slice), the product path).  Element for element the same expressions with the same
-    roundings; what differs is the grouping of the fp32 partial sums (statistics, weight-gradient tiles: another tile -> workgroup map)."""
-    over = dict(densenet_structure=structure, initial_pixel_dim=init_ch, pixel_shape=hw, num_encoder_layers=2, dropout=0.1, pixel_noise_std=0.0)
-    from variant_utils import run_on_debug_build
-    body = f"""
-import test_densenet_gpu as T
-from oracle import tcvn_oracle as O
-cfg = O.tutorial_config(**{over!r})
-batch = O.synthetic_batch([2, 1], 41, cfg, event_hits=(60, 200), prong_hits=(20, 120))
-sd = O.fill_state(cfg, 19)
-n_img = int(batch[7].sum())
-d_out = torch.randn(n_img, O.embed_dims(cfg)[0], generator=torch.Generator().manual_seed(12))
-out, taps, grads = T._run_bf16(cfg, sd, batch, True, d_out)
-result = dict(out=out, grads=grads)
-"""
-    base = run_on_debug_build(body, dict(TCVN_NO_LF="1", TCVN_BWD1_WIDE="1"))
-    ref = run_on_debug_build(body, dict(TCVN_NO_LF="1"))
-    assert torch.equal(base["out"], ref["out"])                      # the forward pass does not involve the kernel
-    is_bias = lambda k: k.endswith(("conv0.bias", "conv1.bias", "conv2.bias", "conv.bias"))      # exact-zero gradients: rounding noise only
-    errs = sorted(((((base["grads"][k] - ref["grads"][k]).norm() / ref["grads"][k].norm().clamp_min(1e-30)).item(), k)
-                   for k in base["grads"] if ref["grads"][k].abs().max() > 0 and not is_bias(k)), reverse=True)
-    print(f"wide vs per-slice fused 1x1 backward, init {init_ch} {structure}: largest gradient differences", errs[:4])
-    assert all(torch.isfinite(g).all() for g in base["grads"].values())
-    # the network's last layer runs first in backward, on identical inputs: its own results (1x1 weight gradient; norm1 / PReLU1 parameter
-    # gradients, which are the launch's statistics) agree to summation order ...
-    last = f"features.dense1.layers.{structure[0] - 1}.bottleneck_block."
-    own = {k: e for e, k in errs if last in k}
-    print("the last layer's own gradients:", own)
-    assert len(own) == 4 and max(own.values()) < 1e-5, own
-    # ... below it the tables differ by an fp32 ulp here and there, single bf16 roundings of G flip, and ill-conditioned sums amplify that
-    assert errs[0][0] < 3e-2, errs[:8]

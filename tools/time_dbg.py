@@ -1,6 +1,6 @@
 """A/B timing on the VALIDATION build (libtcvn_hip_dbg.so honours the TCVN_* switches in the environment): the config-2 bf16 step of
 bench.py, N timed steps + one serialised survey step with per-kernel event timings.  Not a benchmark of the product library.
-    TCVN_XA_ONTHEFLY=1 python tools/time_dbg.py [steps]"""
+    TCVN_NO_LF=1 python tools/time_dbg.py [steps]"""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "dune-transformercvn_amd")]
