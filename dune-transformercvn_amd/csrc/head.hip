@@ -12,6 +12,7 @@
 #include "head_plan.h"
 #include "tcvn_rows.h"
 #include "tcvn_encoder.h"
+#include "tcvn_explain.h"
 
 using namespace tcvn;
 
@@ -429,7 +430,29 @@ combined:
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-struct tcvn_head { HeadPlan plan; int last_np = 0; explicit tcvn_head(const tcvn_head_cfg& c) : plan(c) {} };
+struct tcvn_head {
+    HeadPlan plan;
+    int last_np = 0, last_b = 0, last_p = -1;      // shape of the last forward / encode: what tcvn_head_attention may export
+    explicit tcvn_head(const tcvn_head_cfg& c) : plan(c) {}
+};
+
+namespace {
+// Workspace of the leave-one-prong-out scan: job list, slot -> job map, the logits of every job, and one pass (at most
+// TCVN_LOO_MAX_PASS sequences) of variant rows + head workspace.
+struct LooLayout { long jobs, src, lg, vrow, head, total; int cap; };
+void loo_layout(const HeadPlan& plan, int B, int P, LooLayout& o) {
+    Bump b;
+    const long slots = (long)B * (1 + P);
+    o.cap = (int)(slots < TCVN_LOO_MAX_PASS ? slots : TCVN_LOO_MAX_PASS);
+    o.jobs = b.take(slots * 4); o.src = b.take(slots * 4); o.lg = b.take(slots * plan.cfg.event_classes * 4);
+    o.vrow = b.take((long)o.cap * (1 + P) * 4);
+    HLayout L;
+    plan.layout(o.cap, P, 0, L);
+    o.head = b.take(L.total);
+    o.total = b.off;
+}
+}  // namespace
+
 
 extern "C" {
 int tcvn_head_create(const tcvn_head_cfg* cfg, tcvn_head** out) {
@@ -456,7 +479,7 @@ int64_t tcvn_head_workspace_bytes(const tcvn_head* p, int batch, int max_prongs,
 }
 int tcvn_head_forward(tcvn_head* p, int batch, int max_prongs, int n_prongs, const float* rows, const int32_t* tok_row,
                       float* event_logits, float* prong_logits, void* ws, int64_t ws_bytes, int train, uint64_t seed, void* stream) {
-    p->last_np = n_prongs;
+    p->last_np = n_prongs; p->last_b = batch; p->last_p = max_prongs;
     return p->plan.forward(batch, max_prongs, n_prongs, rows, tok_row, event_logits, prong_logits, reinterpret_cast<char*>(ws),
                            ws_bytes, train, seed, reinterpret_cast<hipStream_t>(stream));
 }
@@ -483,6 +506,7 @@ int tcvn_head_encode(tcvn_head* p, int batch, int max_prongs, const float* token
     if ((rc = permute_rows(tokens, X0, batch, S, D, 0, st))) return rc;            // [B,S,D] -> sequence-major rows
     if ((rc = mask_rows(X0, tok_row, X0, batch, S, D, st))) return rc;             // embeddings * sequence_mask (:69)
     if ((rc = p->plan.encode(batch, max_prongs, tok_row, w, L, train, seed, st))) return rc;
+    p->last_np = 0; p->last_b = batch; p->last_p = max_prongs;
     TCVN_CHECK(hipMemcpyAsync(hidden, w + L.HID, (size_t)S * batch * D * 4, hipMemcpyDeviceToDevice, st));
     return 0;
 }
@@ -496,6 +520,86 @@ int tcvn_head_decode(tcvn_head* p, int batch, int max_prongs, const float* hidde
     const int D = p->plan.cfg.hidden_dim, S = 1 + max_prongs;
     TCVN_CHECK(hipMemcpyAsync(w + L.HID, hidden, (size_t)S * batch * D * 4, hipMemcpyDeviceToDevice, st));
     return p->plan.decode(batch, max_prongs, event_logits, prong_logits, w, L, train, seed, st);
+}
+
+/* explanation entry points: see include/tcvn_hip.h */
+int tcvn_head_attention(tcvn_head* p, int batch, int max_prongs, const int32_t* tok_row, const void* ws, int64_t ws_bytes,
+                        float* weights, void* stream) {
+    if (!p || !tok_row || !ws || !weights || batch <= 0 || max_prongs < 0 || 1 + max_prongs > 64) {
+        fprintf(stderr, "tcvn: head_attention: bad argument (NULL pointer, batch < 1 or more than 64 tokens)\n");
+        return -1;
+    }
+    if (batch != p->last_b || max_prongs != p->last_p) {
+        fprintf(stderr, "tcvn: head_attention: no forward / encode of shape (batch %d, max_prongs %d) precedes this call\n", batch, max_prongs);
+        return -15;
+    }
+    HLayout L;
+    p->plan.layout(batch, max_prongs, p->last_np, L);
+    if (ws_bytes < L.total) {
+        fprintf(stderr, "tcvn: head_attention: workspace of %lld bytes, the forward's has %ld\n", (long long)ws_bytes, L.total);
+        return -12;
+    }
+    const int nl = p->plan.cfg.n_layers;
+    if (nl < 1) { fprintf(stderr, "tcvn: head_attention: the encoder has no layer\n"); return -1; }
+    const long stride = nl > 1 ? L.lay[1].probs - L.lay[0].probs : 0;       // every layer takes the same buffers: constant stride
+    for (int l = 1; l < nl; ++l)
+        if (L.lay[l].probs - L.lay[l - 1].probs != stride) return -16;
+    return attn_export(reinterpret_cast<const char*>(ws), L.lay[0].probs, stride, tok_row, weights, nl, batch, p->plan.cfg.heads,
+                       1 + max_prongs, reinterpret_cast<hipStream_t>(stream));
+}
+int64_t tcvn_head_leave_one_out_workspace_bytes(const tcvn_head* p, int batch, int max_prongs) {
+    if (!p || batch <= 0 || max_prongs < 0 || 1 + max_prongs > 64) return -1;
+    LooLayout o;
+    loo_layout(p->plan, batch, max_prongs, o);
+    return o.total;
+}
+int tcvn_head_leave_one_out(tcvn_head* p, int batch, int max_prongs, const float* tokens, const int32_t* tok_row, float* event_logits,
+                            float* loo, void* ws, int64_t ws_bytes, void* stream) {
+    if (!p || !tokens || !tok_row || !event_logits || !ws || (max_prongs > 0 && !loo) || batch <= 0 || max_prongs < 0 ||
+        1 + max_prongs > 64) {
+        fprintf(stderr, "tcvn: head_leave_one_out: bad argument (NULL pointer, batch < 1 or more than 64 tokens)\n");
+        return -1;
+    }
+    LooLayout o;
+    loo_layout(p->plan, batch, max_prongs, o);
+    if (ws_bytes < o.total) {
+        fprintf(stderr, "tcvn: head_leave_one_out: workspace of %lld bytes, %ld needed\n", (long long)ws_bytes, o.total);
+        return -12;
+    }
+    if (!p->plan.bound) { fprintf(stderr, "tcvn: head_leave_one_out: parameters are not bound\n"); return -11; }
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int B = batch, P = max_prongs, S = 1 + P, D = p->plan.cfg.hidden_dim, Ce = p->plan.cfg.event_classes;
+    char* w = reinterpret_cast<char*>(ws);
+    // the variant list depends on the mask: read it back (a few KB) and build the jobs on the host
+    std::vector<int32_t> tr((size_t)B * S), jobs, src((size_t)B * S);
+    TCVN_CHECK(hipMemcpyAsync(tr.data(), tok_row, tr.size() * 4, hipMemcpyDeviceToHost, st));
+    TCVN_CHECK(hipStreamSynchronize(st));
+    for (int b = 0; b < B; ++b) { jobs.push_back(b * S); src[(size_t)b * S] = b; }          // jobs 0 .. B-1: the unablated events
+    for (int b = 0; b < B; ++b)
+        for (int s = 1; s < S; ++s) {
+            const bool valid = tr[(size_t)b * S + s] >= 0;
+            src[(size_t)b * S + s] = valid ? (int32_t)jobs.size() : b;
+            if (valid) jobs.push_back(b * S + s);
+        }
+    const int J = (int)jobs.size();
+    int* d_jobs = reinterpret_cast<int*>(w + o.jobs);
+    int* d_src = reinterpret_cast<int*>(w + o.src);
+    int* d_vrow = reinterpret_cast<int*>(w + o.vrow);
+    float* lg = reinterpret_cast<float*>(w + o.lg);
+    TCVN_CHECK(hipMemcpyAsync(d_jobs, jobs.data(), (size_t)J * 4, hipMemcpyHostToDevice, st));
+    TCVN_CHECK(hipMemcpyAsync(d_src, src.data(), src.size() * 4, hipMemcpyHostToDevice, st));
+    TCVN_CHECK(hipStreamSynchronize(st));                                                   // the host vectors are pageable
+    int rc;
+    for (int off = 0; off < J; off += o.cap) {
+        const int n = J - off < o.cap ? J - off : o.cap;
+        HLayout L;
+        p->plan.layout(n, P, 0, L);
+        char* hw = w + o.head;
+        if ((rc = loo_gather(tokens, tok_row, d_jobs + off, reinterpret_cast<float*>(hw + L.X[0]), d_vrow, n, S, D, st))) return rc;
+        if ((rc = p->plan.encode(n, P, d_vrow, hw, L, 0, 0, st))) return rc;
+        if ((rc = p->plan.decode(n, P, lg + (long)off * Ce, nullptr, hw, L, 0, 0, st))) return rc;
+    }
+    return loo_scatter(lg, d_src, event_logits, loo, B, S, Ce, st);
 }
 
 int tcvn_head_loss(tcvn_head* p, int batch, int max_prongs, const float* event_logits, const float* prong_logits,

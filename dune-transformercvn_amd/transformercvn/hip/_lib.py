@@ -21,6 +21,8 @@ _libselect._bound = True
 
 MODE_F32, MODE_BF16 = 0, 1
 SLOT_PARAM, SLOT_BUFFER, SLOT_COUNTER = 0, 1, 2
+FUSE_MEAN, FUSE_MAX = 0, 1          # TCVN_FUSE_*: head fusion of the attention rollout
+LOO_MAX_PASS = 256                  # TCVN_LOO_MAX_PASS: sequences per encoder pass of the leave-one-prong-out scan
 
 
 class DenseNetCfg(C.Structure):
@@ -91,6 +93,10 @@ def _load():
     sig("tcvn_head_embed", i32, vp, i32, i32, i32, vp, vp, vp, vp, i64, i32, u64, vp)
     sig("tcvn_head_encode", i32, vp, i32, i32, vp, vp, vp, vp, i64, i32, u64, vp)
     sig("tcvn_head_decode", i32, vp, i32, i32, vp, vp, vp, vp, i64, i32, u64, vp)
+    sig("tcvn_head_attention", i32, vp, i32, i32, vp, vp, i64, vp, vp)
+    sig("tcvn_attention_rollout", i32, vp, vp, i32, i32, i32, i32, i32, vp, vp)
+    sig("tcvn_head_leave_one_out_workspace_bytes", i64, vp, i32, i32)
+    sig("tcvn_head_leave_one_out", i32, vp, i32, i32, vp, vp, vp, vp, vp, i64, vp)
     sig("tcvn_linear_forward", i32, vp, i64, vp, vp, vp, i64, i32, i32, i32, vp)
     sig("tcvn_rows_bn_prelu_forward", i32, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp, i32, f32, u64, C.c_uint32, vp)
     sig("tcvn_linear_backward", i32, vp, i64, vp, i64, vp, vp, i64, vp, vp, i32, i32, i32, vp)
@@ -128,6 +134,7 @@ EXPORTS = [
     "tcvn_densenet_bind", "tcvn_densenet_workspace_bytes", "tcvn_densenet_forward", "tcvn_densenet_backward",
     "tcvn_densenet_tap", "tcvn_densenet_num_blocks", "tcvn_densenet_backward_blocks", "tcvn_head_create", "tcvn_head_destroy", "tcvn_head_num_slots", "tcvn_head_slot", "tcvn_head_bind",
     "tcvn_head_workspace_bytes", "tcvn_head_forward", "tcvn_head_loss", "tcvn_head_backward",
+    "tcvn_head_attention", "tcvn_attention_rollout", "tcvn_head_leave_one_out_workspace_bytes", "tcvn_head_leave_one_out",
 ]
 
 lib = _load()

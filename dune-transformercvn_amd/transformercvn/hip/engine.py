@@ -189,6 +189,8 @@ class HeadEngine(_Plan):
         self.cfg = cfg
         check(lib.tcvn_head_create(C.byref(cfg), C.byref(self.handle)), "head_create")
         self._shape = (0, 0, 0)
+        self._last = (0, -1)                 # (batch, max_prongs) of the last forward / encode on self._ws: what attention() exports
+        self._loo_ws: Optional[torch.Tensor] = None
 
     def forward(self, rows: torch.Tensor, tok_row: torch.Tensor, batch: int, max_prongs: int, n_prongs: int, train: bool,
                 seed: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -198,6 +200,7 @@ class HeadEngine(_Plan):
         ev = torch.empty(batch, self.cfg.event_classes, device=rows.device)
         pr = torch.empty(batch, max_prongs, self.cfg.prong_classes, device=rows.device)
         self._shape = (batch, max_prongs, n_prongs)
+        self._last = (batch, max_prongs)
         check(lib.tcvn_head_forward(self.handle, batch, max_prongs, n_prongs, _ptr(rows), _ptr(tok_row), _ptr(ev), _ptr(pr),
                                     _ptr(ws), ws.numel(), int(train), C.c_uint64(seed), _stream_ptr()), "head_forward")
         return ev, pr
@@ -223,6 +226,7 @@ class HeadEngine(_Plan):
         assert tok_row.dtype == torch.int32 and tok_row.is_contiguous() and tok_row.shape == (batch, S)
         ws = self._stage_ws(batch, S - 1, 0, tokens.device)
         hidden = torch.empty(S, batch, D, device=tokens.device)
+        self._last = (batch, S - 1)
         check(lib.tcvn_head_encode(self.handle, batch, S - 1, _ptr(tokens), _ptr(tok_row), _ptr(hidden), _ptr(ws), ws.numel(),
                                    int(train), C.c_uint64(seed), _stream_ptr()), "head_encode")
         return hidden
@@ -237,6 +241,39 @@ class HeadEngine(_Plan):
         check(lib.tcvn_head_decode(self.handle, batch, S - 1, _ptr(hidden), _ptr(ev), _ptr(pr), _ptr(ws), ws.numel(), int(train),
                                    C.c_uint64(seed), _stream_ptr()), "head_decode")
         return ev, pr
+
+    def attention(self, tok_row: torch.Tensor) -> torch.Tensor:
+        """tcvn_head_attention: the attention probabilities [layers, B, heads, S, S] (pre-dropout; padded rows / columns zero) of the
+        last forward / encode of this engine.  Reads the workspace only: a training step's backward may still follow."""
+        batch, max_prongs = self._last
+        if self._ws is None or max_prongs < 0:
+            raise RuntimeError("HeadEngine.attention: no forward or encode has run on this engine")
+        if not tok_row.is_cuda:
+            raise RuntimeError("transformercvn (MI355X build): the attention export runs on the GPU only; there is no CPU fallback")
+        S = 1 + max_prongs
+        assert tok_row.dtype == torch.int32 and tok_row.is_contiguous() and tok_row.shape == (batch, S)
+        weights = torch.empty(self.cfg.n_layers, batch, self.cfg.heads, S, S, device=tok_row.device)
+        check(lib.tcvn_head_attention(self.handle, batch, max_prongs, _ptr(tok_row), _ptr(self._ws), self._ws.numel(), _ptr(weights),
+                                      _stream_ptr()), "head_attention")
+        return weights
+
+    def leave_one_out(self, tokens: torch.Tensor, tok_row: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """tcvn_head_leave_one_out: tokens [B, S, hidden] -> (event_logits [B, Ce], loo_event_logits [B, S-1, Ce]), eval arithmetic.
+        Runs in a workspace of its own: the engine's forward workspace is left as it is."""
+        batch, S, D = tokens.shape
+        assert D == self.cfg.hidden_dim and tokens.dtype == torch.float32 and tokens.is_contiguous()
+        assert tok_row.dtype == torch.int32 and tok_row.is_contiguous() and tok_row.shape == (batch, S)
+        need = lib.tcvn_head_leave_one_out_workspace_bytes(self.handle, batch, S - 1)
+        if need < 0:
+            raise RuntimeError(f"libtcvn_hip: head_leave_one_out_workspace_bytes rejects batch {batch}, {S} tokens")
+        if self._loo_ws is None or self._loo_ws.numel() < need or self._loo_ws.device != tokens.device:
+            self._loo_ws = None
+            self._loo_ws = torch.empty(need + 4096, dtype=torch.uint8, device=tokens.device)
+        ev = torch.empty(batch, self.cfg.event_classes, device=tokens.device)
+        loo = torch.empty(batch, S - 1, self.cfg.event_classes, device=tokens.device)
+        check(lib.tcvn_head_leave_one_out(self.handle, batch, S - 1, _ptr(tokens), _ptr(tok_row), _ptr(ev), _ptr(loo),
+                                          _ptr(self._loo_ws), self._loo_ws.numel(), _stream_ptr()), "head_leave_one_out")
+        return ev, loo
 
     def loss(self, ev: torch.Tensor, pr: torch.Tensor, event_targets: torch.Tensor, prong_targets: torch.Tensor):
         """-> (losses[3] = total/event/prong, accs[2], d_event_logits, d_prong_logits), all on the device."""

@@ -84,6 +84,7 @@ class HipRuntime:
         self.grad_ready_hook = None          # called as hook(tag) when a gradient segment is final ("head", "event", "prong")
         self.segments: Dict[str, Tuple[int, int]] = {}
         self.offsets: Dict[str, Tuple[int, int]] = {}
+        self._head_in = None                 # (rows, tok_row, B, P, n_prongs) of the last forward()
 
     # ---------------------------------------------------------------------------------------------------------------
     # flat arenas
@@ -249,6 +250,7 @@ class HipRuntime:
                                    seed ^ 0x2222, prong_px.value_mode, prong_px.noise_std if training else 0.0)
             main.wait_stream(side)
             ev, pr = self.head.forward(rows, tok_row, B, P, n_prongs, training, seed ^ 0x3333)
+            self._head_in = (rows, tok_row, B, P, n_prongs)      # kept for leave_one_prong_out (the tokens are rebuilt from the rows)
             if training:
                 self.flat_nbt += self._nbt_inc
         if not (training and torch.is_grad_enabled()):
@@ -296,8 +298,9 @@ class HipRuntime:
                 self.flat_nbt += self._nbt_inc_embed
             return self.head.embed(rows, token_rows(prong_mask, B), B, P, n_prongs, training, seed ^ 0x3333)
 
-    def encode(self, tokens: Tensor, mask: Tensor, training: bool = False) -> Tensor:
-        """ProngCustomBertEncoder.forward: tokens [B, S, hidden], mask [B, S] -> hidden [S, B, hidden] (masked)."""
+    def encode(self, tokens: Tensor, mask: Tensor, training: bool = False, return_attention: bool = False):
+        """ProngCustomBertEncoder.forward: tokens [B, S, hidden], mask [B, S] -> hidden [S, B, hidden] (masked); with
+        return_attention also the attention probabilities [L, B, H, S, S] of that run (pre-dropout, see tcvn_head_attention)."""
         self.ensure_bound()
         with torch.no_grad():
             dev = self.flat_param.device
@@ -306,7 +309,48 @@ class HipRuntime:
             tok = torch.where(mask.to(dev), 0, -1).to(torch.int32).contiguous()
             seed = (self.seed * 1000003 + self.step) & 0x7FFFFFFFFFFFFFFF
             self.step += 1
-            return self.head.encode(tokens.detach().float().contiguous(), tok, training, seed ^ 0x3333)
+            hidden = self.head.encode(tokens.detach().float().contiguous(), tok, training, seed ^ 0x3333)
+            if not return_attention:
+                return hidden
+            return hidden, self.head.attention(tok)
+
+    # ---------------------------------------------------------------------------------------------------------------
+    # explaining a prediction (forward only): attention maps and the leave-one-prong-out scan
+    # ---------------------------------------------------------------------------------------------------------------
+    def forward_with_attention(self, features: Tensor, extra: Tensor, event_px: SparsePixels, event_mask: Tensor,
+                               prong_px: SparsePixels, prong_mask: Tensor,
+                               counts: Optional[Tuple[int, int]] = None) -> Tuple[Tensor, Tensor, Tensor]:
+        """forward() plus the attention probabilities [L, B, H, 1+P, 1+P] of that very run: plain tensors, no autograd graph.
+        Honours network.training as forward() does (in train mode this IS one more training-mode forward: running statistics and
+        the step counter advance); the probabilities are pre-dropout."""
+        with torch.no_grad():
+            ev, pr = self.forward(features, extra, event_px, event_mask, prong_px, prong_mask, counts)
+            return ev, pr, self.head.attention(self._head_in[1])
+
+    def leave_one_prong_out(self, tokens: Tensor, mask: Tensor) -> Tuple[Tensor, Tensor]:
+        """tokens [B, S, hidden], mask [B, S] -> (event_logits [B, Ce], loo_event_logits [B, S-1, Ce]) in eval arithmetic: row [b, p]
+        is event b's logits with prong slot p masked out (rows of padded slots repeat event_logits[b])."""
+        self.ensure_bound()
+        with torch.no_grad():
+            if not tokens.is_cuda:
+                raise RuntimeError("transformercvn (MI355X build): the encoder runs on the GPU only; there is no CPU fallback")
+            tok = torch.where(mask.to(self.flat_param.device), 0, -1).to(torch.int32).contiguous()
+            return self.head.leave_one_out(tokens.detach().float().contiguous(), tok)
+
+    def forward_leave_one_prong_out(self, features: Tensor, extra: Tensor, event_px: SparsePixels, event_mask: Tensor,
+                                    prong_px: SparsePixels, prong_mask: Tensor,
+                                    counts: Optional[Tuple[int, int]] = None) -> Tuple[Tensor, Tensor, Tensor]:
+        """Eval-mode forward() plus the scan over its tokens -> (event_logits, prong_logits, loo_event_logits [B, P, Ce]).  The
+        DenseNets run once; the scan adds one encoder + event-decoder sequence per valid prong.  event_logits are the scan's own
+        unablated rows (the same kernels on the same tokens as forward()'s), so padded slots of the scan equal them exactly."""
+        if self.network.training:
+            raise RuntimeError("leave_one_prong_out explains an eval-mode prediction: call network.eval() first")
+        with torch.no_grad():
+            _, pr = self.forward(features, extra, event_px, event_mask, prong_px, prong_mask, counts)
+            rows, tok_row, B, P, n_prongs = self._head_in
+            tokens = self.head.embed(rows, tok_row, B, P, n_prongs, False, 0)
+            ev, loo = self.head.leave_one_out(tokens, tok_row)
+            return ev, pr, loo
 
     def _backward(self, st: dict, d_ev: Tensor, d_pr: Tensor):
         """Backward of the fused step in the order the gradient segments become final -- token path, event embedder (side

@@ -42,3 +42,14 @@ class ProngCustomBertEncoder(nn.Module):
         if net is None:
             raise RuntimeError("ProngCustomBertEncoder.forward needs the owning NeutrinoBaseNetwork (its HIP runtime holds the plan)")
         return net.hip_runtime().encode(embeddings, mask, self.training)
+
+    @torch.jit.unused
+    def attention(self, embeddings: Tensor, mask: Tensor) -> Tuple[Tensor, Tensor]:
+        """(tokens [B, S, D], mask [B, S] bool) -> (hidden [S, B, D], weights [L, B, H, S, S]): forward()'s hidden states and the
+        attention probabilities of that run -- what nn.MultiheadAttention(need_weights=True, average_attn_weights=False) returns in
+        every layer of the reference's stack, before attention dropout; padded rows and columns are zero.  No autograd graph."""
+        from transformercvn.hip.owners import owner_of
+        net = owner_of(self)
+        if net is None:
+            raise RuntimeError("ProngCustomBertEncoder.attention needs the owning NeutrinoBaseNetwork (its HIP runtime holds the plan)")
+        return net.hip_runtime().encode(embeddings, mask, self.training, return_attention=True)

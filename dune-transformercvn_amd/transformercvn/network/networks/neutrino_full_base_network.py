@@ -145,3 +145,30 @@ class NeutrinoBaseNetwork(nn.Module):
         if not isinstance(prong_pixels, SparsePixels):
             prong_pixels = SparsePixels.from_dense(prong_pixels)
         return self.hip_runtime().forward(features, extra, event_pixels, event_mask, prong_pixels, prong_mask, counts)
+
+    # ---- explaining a prediction (eager only; forward only, no autograd graph) -----------------------------------------------------
+    @torch.jit.unused
+    def forward_with_attention(self, features: Tensor, extra: Tensor, event_pixels: Tensor, event_mask: Tensor, prong_pixels: Tensor,
+                               prong_mask: Tensor, counts: Optional[Tuple[int, int]] = None) -> Tuple[Tensor, Tensor, Tensor]:
+        """forward() -> (event_logits, prong_logits, weights [L, B, H, 1+P, 1+P]): weights[l, b, h, i, j] is the probability with which
+        token i of event b attends to token j in head h of encoder layer l (token 0 the event, token 1+p prong slot p; pre-dropout;
+        padded rows and columns zero).  transformercvn.hip.attention.rollout turns them into per-prong relevances."""
+        if not isinstance(event_pixels, SparsePixels):
+            event_pixels = SparsePixels.from_dense(event_pixels)
+        if not isinstance(prong_pixels, SparsePixels):
+            prong_pixels = SparsePixels.from_dense(prong_pixels)
+        return self.hip_runtime().forward_with_attention(features, extra, event_pixels, event_mask, prong_pixels, prong_mask, counts)
+
+    @torch.jit.unused
+    def leave_one_prong_out(self, features: Tensor, extra: Tensor, event_pixels: Tensor, event_mask: Tensor, prong_pixels: Tensor,
+                            prong_mask: Tensor, counts: Optional[Tuple[int, int]] = None) -> Tuple[Tensor, Tensor, Tensor]:
+        """Eval mode only -> (event_logits, prong_logits, loo_event_logits [B, P, Ce]): loo_event_logits[b, p] is event_logits[b]
+        recomputed without prong slot p (padded slots repeat event_logits[b])."""
+        if self.training:
+            raise RuntimeError("leave_one_prong_out explains an eval-mode prediction: call .eval() first")
+        if not isinstance(event_pixels, SparsePixels):
+            event_pixels = SparsePixels.from_dense(event_pixels)
+        if not isinstance(prong_pixels, SparsePixels):
+            prong_pixels = SparsePixels.from_dense(prong_pixels)
+        return self.hip_runtime().forward_leave_one_prong_out(features, extra, event_pixels, event_mask, prong_pixels, prong_mask,
+                                                              counts)

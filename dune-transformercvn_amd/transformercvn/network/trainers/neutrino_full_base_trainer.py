@@ -151,6 +151,34 @@ class NeutrinoFullBaseTrainer(NeutrinoBase, ABC):
         prong_pixels = self.preprocess_pixels(prong_coords, prong_values, shape)
         return self.network(features, extra, event_pixels, event_mask, prong_pixels, prong_mask, counts)
 
+    def _network_inputs(self, features: Tensor, extra: Tensor, event_coords: Tensor, event_values: Tensor, event_mask: Tensor,
+                        prong_coords: Tensor, prong_values: Tensor, prong_mask: Tensor):
+        """forward()'s preprocessing (feature normalisation, pixel bundles) for the explanation calls below."""
+        if torch.is_tensor(self.mean) and features.numel() and not self.options.disable_smart_features:
+            features = features.clone()
+            features[prong_mask] = (features[prong_mask] - self.mean) / self.std
+            extra = (extra - self.extra_mean) / self.extra_std
+        shape = self.training_dataset.pixel_shape
+        event_pixels = self.preprocess_pixels(event_coords, event_values, shape)
+        prong_pixels = self.preprocess_pixels(prong_coords, prong_values, shape)
+        return features, extra, event_pixels, event_mask, prong_pixels, prong_mask
+
+    def forward_with_attention(self, features: Tensor, extra: Tensor, event_coords: Tensor, event_values: Tensor, event_mask: Tensor,
+                               prong_coords: Tensor, prong_values: Tensor, prong_mask: Tensor,
+                               counts=None) -> Tuple[Tensor, Tensor, Tensor]:
+        """forward() -> (event_logits, prong_logits, weights [L, B, H, 1+P, 1+P]); see NeutrinoBaseNetwork.forward_with_attention."""
+        return self.network.forward_with_attention(*self._network_inputs(features, extra, event_coords, event_values, event_mask,
+                                                                         prong_coords, prong_values, prong_mask), counts)
+
+    def leave_one_prong_out(self, features: Tensor, extra: Tensor, event_coords: Tensor, event_values: Tensor, event_mask: Tensor,
+                            prong_coords: Tensor, prong_values: Tensor, prong_mask: Tensor,
+                            counts=None) -> Tuple[Tensor, Tensor, Tensor]:
+        """Eval mode only -> (event_logits, prong_logits, loo_event_logits [B, P, Ce]); see NeutrinoBaseNetwork.leave_one_prong_out."""
+        if self.training:
+            raise RuntimeError("leave_one_prong_out explains an eval-mode prediction: call .eval() first")
+        return self.network.leave_one_prong_out(*self._network_inputs(features, extra, event_coords, event_values, event_mask,
+                                                                      prong_coords, prong_values, prong_mask), counts)
+
     def shared_step(self, batch):
         (features, extra, ev_c, ev_v, ev_m, pr_c, pr_v, pr_m, ev_t, pr_t) = batch[:10]
         counts = batch[10] if len(batch) > 10 else None               # optional host-side (max_prongs, n_prongs): avoids syncs

@@ -180,6 +180,36 @@ int tcvn_head_encode(tcvn_head* p, int batch, int max_prongs, const float* token
 int tcvn_head_decode(tcvn_head* p, int batch, int max_prongs, const float* hidden, float* event_logits, float* prong_logits,
                      void* workspace, int64_t workspace_bytes, int train, uint64_t seed, void* stream);
 
+/* Explaining a prediction (forward only; nothing here changes a forward, a backward or a parameter).
+ *   attention   weights [layers, batch, heads, S, S] fp32, S = 1 + max_prongs: the probability with which token i attends to token j
+ *               (softmax over j of q_i.k_j / sqrt(head_dim), padded keys excluded, BEFORE attention dropout) -- what
+ *               nn.MultiheadAttention(need_weights=True, average_attn_weights=False) returns inside the reference's encoder layers.
+ *               Token 0 is the event, token 1 + p prong slot p.  Columns of padded keys and rows of padded queries are exactly 0.
+ *               Exports what the last tcvn_head_forward / tcvn_head_encode (train or eval, either encoder path) left in `workspace`;
+ *               batch / max_prongs must be that call's.  The workspace is read, never written: a backward may still follow.
+ *   rollout     [batch, S, S] = A^_{L-1} ... A^_0 with A^_l = rownorm(0.5 fuse_h(weights[l]) + 0.5 I_valid) (Abnar & Zuidema 2020);
+ *               I_valid has ones at valid tokens only, so padded tokens have zero rows and columns.  rollout[b, 0, 1 + p] is the
+ *               relevance of prong slot p for the event token.  One workgroup per event, S <= 64.
+ *   leave one out   event_logits [batch, Ce] and loo_event_logits [batch, max_prongs, Ce]: row [b, p] is event_logits[b] recomputed
+ *               with prong slot p masked out (token zeroed, key padded; the encoder has no positional encoding, so this IS the event
+ *               without that prong); rows of padded slots are copies of event_logits[b].  Eval arithmetic (no dropout).  tokens
+ *               [batch, S, hidden] as tcvn_head_embed returns them.  The variants (one sequence per valid prong) run through the
+ *               encoder and the event decoder in passes of at most TCVN_LOO_MAX_PASS sequences; workspace:
+ *               tcvn_head_leave_one_out_workspace_bytes.  The call reads tok_row back to build the variant list, so it
+ *               synchronises with `stream` (not capturable into a graph).
+ * Argument errors (NULL, S > 64, layers < 1, unknown fusion, workspace too small or of another shape) return non-zero before any
+ * device call and print one "tcvn:" line. */
+#define TCVN_FUSE_MEAN 0
+#define TCVN_FUSE_MAX 1
+#define TCVN_LOO_MAX_PASS 256
+int tcvn_head_attention(tcvn_head* p, int batch, int max_prongs, const int32_t* tok_row, const void* workspace,
+                        int64_t workspace_bytes, float* weights, void* stream);
+int tcvn_attention_rollout(const float* weights, const int32_t* tok_row, int layers, int batch, int heads, int seq, int head_fusion,
+                           float* rollout, void* stream);
+int64_t tcvn_head_leave_one_out_workspace_bytes(const tcvn_head* p, int batch, int max_prongs);
+int tcvn_head_leave_one_out(tcvn_head* p, int batch, int max_prongs, const float* tokens, const int32_t* tok_row,
+                            float* event_logits, float* loo_event_logits, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Row operators behind the holder modules' own forward() (forward only, fp32):
  *   y = x W^T + b (torch.nn.Linear layout; bias may be NULL)                      -- layers/prong_decoder.py:15-16
  *   y = dropout(prelu(batchnorm1d(x)))  with batch statistics + running-stat update when train != 0, running statistics

@@ -1,0 +1,66 @@
+"""What do the explanation calls cost at the --ragged-inference shape (batch 32, 1-16 prongs/event, bf16 embedders, eval mode)?
+Times forward(), forward_with_attention() and leave_one_prong_out() on the same batch with device events around synchronised work,
+interleaved, and prints one JSON line with the medians.
+
+    python tools/explain_cost.py [--batch 32 --reps 15 --precision bf16]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "dune-transformercvn_amd")]
+import bench  # noqa: E402
+from transformercvn.options import Options  # noqa: E402
+from transformercvn.network.trainers.neutrino_full_dense_trainer import NeutrinoFullDenseTrainer  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--reps", type=int, default=15)
+    ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32"])
+    args = ap.parse_args()
+    dev = torch.device("cuda:0")
+    opt = Options.load(os.path.join(bench.PKG, "option_files", "tutorial_densenet_synthetic.json"))
+    opt.batch_size, opt.num_gpu, opt.hip_precision, opt.seed = args.batch, 1, args.precision, 1234
+    opt.training_file = "synthetic:64:8"
+    torch.manual_seed(0)
+    model = NeutrinoFullDenseTrainer(opt).to(dev)
+    model.eval()
+    batch = bench.make_batch(args.batch, (1, 16), 1234, dev)
+    width, n_prongs = batch[10]
+    f, x, ec, ev, em, pc, pv, pm = batch[:8]
+    inputs = (f[:, :width].contiguous(), x, ec, ev, em, pc, pv, pm[:, :width].contiguous(), (args.batch, n_prongs))   # as shared_step trims them
+    calls = {"forward": model.forward, "forward_with_attention": model.forward_with_attention,
+             "leave_one_prong_out": model.leave_one_prong_out}
+    times = {k: [] for k in calls}
+    with torch.no_grad():
+        for _ in range(3):
+            for fn in calls.values():
+                fn(*inputs)
+        torch.cuda.synchronize()
+        for _ in range(args.reps):
+            for name, fn in calls.items():
+                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                t0.record()
+                fn(*inputs)
+                t1.record()
+                t1.synchronize()
+                times[name].append(t0.elapsed_time(t1))
+    out = {"shape": {"batch": args.batch, "tokens": 1 + width, "valid_prongs": n_prongs, "precision": args.precision},
+           "reps": args.reps}
+    for name, ts in times.items():
+        out[name + "_ms"] = {"median": round(statistics.median(ts), 3), "min": round(min(ts), 3), "max": round(max(ts), 3)}
+    cfg = model.network.hip_runtime().head.cfg
+    out["weights_bytes"] = cfg.n_layers * args.batch * cfg.heads * (1 + width) ** 2 * 4
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
