@@ -13,6 +13,7 @@
 #include "tcvn_rows.h"
 #include "tcvn_encoder.h"
 #include "tcvn_explain.h"
+#include "tcvn_occlude.h"
 
 using namespace tcvn;
 
@@ -451,6 +452,20 @@ void loo_layout(const HeadPlan& plan, int B, int P, LooLayout& o) {
     o.head = b.take(L.total);
     o.total = b.off;
 }
+// Workspace of one pass of the occlusion scan (at most TCVN_OCC_MAX_PASS variants): variant rows, their combined embedding as one-token
+// sequences (E: the Zc / C / cstat / X[0] part of a head layout) and the head workspace of the variant sequences.
+struct OccHeadLayout { long vrows, ident, vrow, head, total; HLayout E; };
+void occ_head_layout(const HeadPlan& plan, int P, OccHeadLayout& o) {
+    Bump b;
+    const long cap = TCVN_OCC_MAX_PASS, D = plan.cfg.hidden_dim;
+    o.vrows = b.take(cap * plan.cfg.in_dim * 4); o.ident = b.take(cap * 4); o.vrow = b.take(cap * (1 + P) * 4);
+    o.E.Zc = b.take(cap * D * 4); o.E.C = b.take(cap * D * 4); o.E.cstat = b.take(2 * D * 4);
+    o.E.X.assign(1, b.take(cap * D * 4));
+    HLayout L;
+    plan.layout((int)cap, P, 0, L);
+    o.head = b.take(L.total);
+    o.total = b.off;
+}
 }  // namespace
 
 
@@ -600,6 +615,50 @@ int tcvn_head_leave_one_out(tcvn_head* p, int batch, int max_prongs, const float
         if ((rc = p->plan.decode(n, P, lg + (long)off * Ce, nullptr, hw, L, 0, 0, st))) return rc;
     }
     return loo_scatter(lg, d_src, event_logits, loo, B, S, Ce, st);
+}
+
+int64_t tcvn_head_occlusion_workspace_bytes(const tcvn_head* p, int max_prongs) {
+    if (!p || max_prongs < 0 || 1 + max_prongs > 64) return -1;
+    OccHeadLayout o;
+    occ_head_layout(p->plan, max_prongs, o);
+    return o.total;
+}
+int tcvn_head_occlusion(tcvn_head* p, int batch, int max_prongs, int n_prongs, const float* rows, const float* tokens,
+                        const int32_t* tok_row, int n, const int32_t* vimg, const int32_t* index, int row_base, const float* emb,
+                        int64_t emb_ld, int col0, int width, float* occluded_event_logits, float* occluded_prong_logits, void* ws,
+                        int64_t ws_bytes, void* stream) {
+    if (!p || !rows || !tokens || !tok_row || !vimg || !index || !emb || !occluded_event_logits || !ws ||
+        (max_prongs > 0 && !occluded_prong_logits) || batch <= 0 || max_prongs < 0 || 1 + max_prongs > 64 || n_prongs < 0 || n < 1 ||
+        n > TCVN_OCC_MAX_PASS || row_base < 0 || row_base > batch + n_prongs || col0 < 0 || width < 1 ||
+        col0 + width > p->plan.cfg.in_dim || emb_ld < width) {
+        fprintf(stderr, "tcvn: head_occlusion: bad argument (NULL pointer, batch < 1, more than 64 tokens, n outside 1..%d or columns outside the row)\n",
+                TCVN_OCC_MAX_PASS);
+        return -1;
+    }
+    OccHeadLayout o;
+    occ_head_layout(p->plan, max_prongs, o);
+    if (ws_bytes < o.total) {
+        fprintf(stderr, "tcvn: head_occlusion: workspace of %lld bytes, %ld needed\n", (long long)ws_bytes, o.total);
+        return -12;
+    }
+    if (!p->plan.bound) { fprintf(stderr, "tcvn: head_occlusion: parameters are not bound\n"); return -11; }
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int P = max_prongs, S = 1 + P, D = p->plan.cfg.hidden_dim;
+    char* w = reinterpret_cast<char*>(ws);
+    float* vrows = reinterpret_cast<float*>(w + o.vrows);
+    int* ident = reinterpret_cast<int*>(w + o.ident);
+    int* d_vrow = reinterpret_cast<int*>(w + o.vrow);
+    int rc;
+    if ((rc = occ_rows(rows, vimg, row_base, emb, emb_ld, col0, width, vrows, ident, n, p->plan.cfg.in_dim, batch + n_prongs, st))) return rc;
+    if ((rc = p->plan.embed(n, 0, 0, vrows, ident, w, o.E, 0, 0, st))) return rc;           // n one-token sequences -> E.X[0] [n][D]
+    HLayout L;
+    p->plan.layout(n, P, 0, L);
+    char* hw = w + o.head;
+    if ((rc = occ_gather(tokens, tok_row, index, reinterpret_cast<const float*>(w + o.E.X[0]), reinterpret_cast<float*>(hw + L.X[0]),
+                         d_vrow, n, batch, S, D, st)))
+        return rc;
+    if ((rc = p->plan.encode(n, P, d_vrow, hw, L, 0, 0, st))) return rc;
+    return p->plan.decode(n, P, occluded_event_logits, occluded_prong_logits, hw, L, 0, 0, st);
 }
 
 int tcvn_head_loss(tcvn_head* p, int batch, int max_prongs, const float* event_logits, const float* prong_logits,

@@ -23,6 +23,8 @@ MODE_F32, MODE_BF16 = 0, 1
 SLOT_PARAM, SLOT_BUFFER, SLOT_COUNTER = 0, 1, 2
 FUSE_MEAN, FUSE_MAX = 0, 1          # TCVN_FUSE_*: head fusion of the attention rollout
 LOO_MAX_PASS = 256                  # TCVN_LOO_MAX_PASS: sequences per encoder pass of the leave-one-prong-out scan
+OCC_MAX_PASS = 256                  # TCVN_OCC_MAX_PASS: maps per embedder / token-path pass of the occlusion scan
+OCC_TARGET_EVENT, OCC_TARGET_PRONG = 0, 1      # TCVN_OCC_TARGET_*: which logits the occlusion heat map is taken from
 
 
 class DenseNetCfg(C.Structure):
@@ -97,6 +99,12 @@ def _load():
     sig("tcvn_attention_rollout", i32, vp, vp, i32, i32, i32, i32, i32, vp, vp)
     sig("tcvn_head_leave_one_out_workspace_bytes", i64, vp, i32, i32)
     sig("tcvn_head_leave_one_out", i32, vp, i32, i32, vp, vp, vp, vp, vp, i64, vp)
+    sig("tcvn_occlusion_workspace_bytes", i64, i32, i32, i32, i32, i32, i32)
+    sig("tcvn_occlusion_variants", i32, vp, i64, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp, i64, P(i64), i64, vp)
+    sig("tcvn_occlusion_build_pass", i32, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, vp, vp, i64, i32, i32, vp, vp, i64, vp)
+    sig("tcvn_head_occlusion_workspace_bytes", i64, vp, i32)
+    sig("tcvn_head_occlusion", i32, vp, i32, i32, i32, vp, vp, vp, i32, vp, vp, i32, vp, i64, i32, i32, vp, vp, vp, i64, vp)
+    sig("tcvn_occlusion_heatmap", i32, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp)
     sig("tcvn_linear_forward", i32, vp, i64, vp, vp, vp, i64, i32, i32, i32, vp)
     sig("tcvn_rows_bn_prelu_forward", i32, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp, i32, f32, u64, C.c_uint32, vp)
     sig("tcvn_linear_backward", i32, vp, i64, vp, i64, vp, vp, i64, vp, vp, i32, i32, i32, vp)
@@ -135,6 +143,8 @@ EXPORTS = [
     "tcvn_densenet_tap", "tcvn_densenet_num_blocks", "tcvn_densenet_backward_blocks", "tcvn_head_create", "tcvn_head_destroy", "tcvn_head_num_slots", "tcvn_head_slot", "tcvn_head_bind",
     "tcvn_head_workspace_bytes", "tcvn_head_forward", "tcvn_head_loss", "tcvn_head_backward",
     "tcvn_head_attention", "tcvn_attention_rollout", "tcvn_head_leave_one_out_workspace_bytes", "tcvn_head_leave_one_out",
+    "tcvn_occlusion_workspace_bytes", "tcvn_occlusion_variants", "tcvn_occlusion_build_pass", "tcvn_head_occlusion_workspace_bytes",
+    "tcvn_head_occlusion", "tcvn_occlusion_heatmap",
 ]
 
 lib = _load()

@@ -107,6 +107,54 @@ class _EmbedderEngine(_Plan):
         check(self._fn("backward")(self.handle, self._n, _ptr(d_out), d_out.stride(0), _ptr(ws), ws.numel(), _stream_ptr()),
               f"{self._prefix}_backward")
 
+    # ---- occlusion scan: variant hit lists of one COO list and their passes through this embedder (eval arithmetic) -----------------
+    def occlusion_variants(self, coords: torch.Tensor, n_img: int, shape: Tuple[int, int], tile: Tuple[int, int],
+                           img_bs: torch.Tensor, max_pass: int):
+        """tcvn_occlusion_variants -> (V, unsorted, bad, bounds, vimg [V], index [V, 4]); bounds[k] .. bounds[k + 1] are the rows of
+        pass k in the variants' hit lists.  One synchronisation.  Keeps the list's workspace for occlusion_build()."""
+        assert coords.dtype == torch.int32 and coords.is_contiguous() and img_bs.dtype == torch.int32 and img_bs.shape == (n_img, 2)
+        (H, W), (th, tw) = shape, tile
+        cells = n_img * (-(-H // th)) * (-(-W // tw))
+        need = lib.tcvn_occlusion_workspace_bytes(n_img, H, W, th, tw, max_pass)
+        if need < 0:
+            raise RuntimeError(f"libtcvn_hip: occlusion_workspace_bytes rejects {n_img} maps of {H}x{W} in tiles of {th}x{tw}")
+        dev = coords.device
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        vimg = torch.empty(cells, dtype=torch.int32, device=dev)
+        index = torch.empty(cells, 4, dtype=torch.int32, device=dev)
+        words = 4 + -(-cells // max_pass) + 1
+        host = (C.c_int64 * words)()
+        check(lib.tcvn_occlusion_variants(_ptr(coords), coords.shape[0], n_img, H, W, th, tw, _ptr(img_bs.contiguous()), max_pass,
+                                          _ptr(vimg), _ptr(index), _ptr(ws), ws.numel(), host, words, _stream_ptr()),
+              "occlusion_variants")
+        V = int(host[0])
+        self._occ_list = (ws, vimg, n_img, H, W, th, tw, max_pass)
+        return V, bool(host[1]), bool(host[2]), [int(host[4 + k]) for k in range(-(-V // max_pass) + 1)], vimg[:V], index[:V]
+
+    def occlusion_build(self, coords: torch.Tensor, values: torch.Tensor, first: int, count: int, out_coords: torch.Tensor,
+                        out_values: torch.Tensor):
+        """tcvn_occlusion_build_pass: the hit lists of variants first .. first + count - 1 of the last occlusion_variants()."""
+        ws, vimg, n_img, H, W, th, tw, max_pass = self._occ_list
+        assert out_coords.dtype == torch.int32 and out_coords.is_contiguous() and out_values.is_contiguous()
+        assert out_values.dtype == torch.float32 and out_values.shape == (out_coords.shape[0], values.shape[1])
+        check(lib.tcvn_occlusion_build_pass(_ptr(coords), _ptr(values), coords.shape[0], values.shape[1], n_img, H, W, th, tw, max_pass,
+                                            _ptr(vimg), _ptr(ws), ws.numel(), first, count, _ptr(out_coords), _ptr(out_values),
+                                            out_coords.shape[0], _stream_ptr()), "occlusion_build_pass")
+
+    def occlusion_forward(self, coords: torch.Tensor, values: torch.Tensor, nnz: int, n_img: int, out: torch.Tensor,
+                          log_pixels: int = 0):
+        """The plan's eval forward over one pass of variant maps (the first nnz rows of coords / values; nnz = 0: empty maps), in a
+        workspace of its own: what the last forward() left for backward() and tap() stays as it is."""
+        assert coords.dtype == torch.int32 and coords.is_contiguous() and values.dtype == torch.float32 and values.is_contiguous()
+        assert out.dtype == torch.float32 and out.stride(1) == 1 and out.shape == (n_img, self.out_dim) and nnz <= coords.shape[0]
+        need = self.workspace_bytes(n_img, False)
+        ws = getattr(self, "_occ_ws", None)
+        if ws is None or ws.numel() < need or ws.device != coords.device:
+            self._occ_ws = None
+            self._occ_ws = ws = torch.empty(need + 4096, dtype=torch.uint8, device=coords.device)
+        check(self._fn("forward")(self.handle, n_img, _ptr(coords), _ptr(values), nnz, int(log_pixels), 0.0, _ptr(out), out.stride(0),
+                                  _ptr(ws), ws.numel(), 0, C.c_uint64(0), _stream_ptr()), f"{self._prefix}_forward")
+
     def tap(self, name: str) -> torch.Tensor:
         """NHWC view [n,h,w,c] of an intermediate of the last forward (validation only)."""
         off, n, h, w, c, ld, es = C.c_int64(), C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_int()
@@ -191,6 +239,7 @@ class HeadEngine(_Plan):
         self._shape = (0, 0, 0)
         self._last = (0, -1)                 # (batch, max_prongs) of the last forward / encode on self._ws: what attention() exports
         self._loo_ws: Optional[torch.Tensor] = None
+        self._occ_ws: Optional[torch.Tensor] = None
 
     def forward(self, rows: torch.Tensor, tok_row: torch.Tensor, batch: int, max_prongs: int, n_prongs: int, train: bool,
                 seed: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -274,6 +323,31 @@ class HeadEngine(_Plan):
         check(lib.tcvn_head_leave_one_out(self.handle, batch, S - 1, _ptr(tokens), _ptr(tok_row), _ptr(ev), _ptr(loo),
                                           _ptr(self._loo_ws), self._loo_ws.numel(), _stream_ptr()), "head_leave_one_out")
         return ev, loo
+
+    def occlusion_pass(self, rows: torch.Tensor, tokens: torch.Tensor, tok_row: torch.Tensor, n_prongs: int, vimg: torch.Tensor,
+                       index: torch.Tensor, row_base: int, emb: torch.Tensor, col0: int, occ_ev: torch.Tensor, occ_pr: torch.Tensor):
+        """tcvn_head_occlusion: one pass of n variants (vimg [n], index [n, 4], emb [n, width] embedder outputs) through combined
+        embedding, encoder and decoders -> occ_ev [n, Ce], occ_pr [n, P, Cp].  Workspace of its own, as leave_one_out has."""
+        batch, S, D = tokens.shape
+        n, width = emb.shape
+        assert D == self.cfg.hidden_dim and tokens.dtype == torch.float32 and tokens.is_contiguous()
+        assert rows.dtype == torch.float32 and rows.is_contiguous() and rows.shape == (batch + n_prongs, self.cfg.in_dim)
+        assert tok_row.dtype == torch.int32 and tok_row.is_contiguous() and tok_row.shape == (batch, S)
+        assert vimg.dtype == torch.int32 and vimg.is_contiguous() and vimg.shape == (n,)
+        assert index.dtype == torch.int32 and index.is_contiguous() and index.shape == (n, 4)
+        assert emb.dtype == torch.float32 and emb.stride(1) == 1
+        assert occ_ev.is_contiguous() and occ_ev.shape == (n, self.cfg.event_classes)
+        assert occ_pr.is_contiguous() and occ_pr.shape == (n, S - 1, self.cfg.prong_classes)
+        need = lib.tcvn_head_occlusion_workspace_bytes(self.handle, S - 1)
+        if need < 0:
+            raise RuntimeError(f"libtcvn_hip: head_occlusion_workspace_bytes rejects {S} tokens")
+        if self._occ_ws is None or self._occ_ws.numel() < need or self._occ_ws.device != tokens.device:
+            self._occ_ws = None
+            self._occ_ws = torch.empty(need + 4096, dtype=torch.uint8, device=tokens.device)
+        check(lib.tcvn_head_occlusion(self.handle, batch, S - 1, n_prongs, _ptr(rows), _ptr(tokens), _ptr(tok_row), n, _ptr(vimg),
+                                      _ptr(index), row_base, _ptr(emb), emb.stride(0), col0, width, _ptr(occ_ev),
+                                      _ptr(occ_pr if S > 1 else None), _ptr(self._occ_ws), self._occ_ws.numel(), _stream_ptr()),
+              "head_occlusion")
 
     def loss(self, ev: torch.Tensor, pr: torch.Tensor, event_targets: torch.Tensor, prong_targets: torch.Tensor):
         """-> (losses[3] = total/event/prong, accs[2], d_event_logits, d_prong_logits), all on the device."""

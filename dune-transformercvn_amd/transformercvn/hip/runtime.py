@@ -352,6 +352,86 @@ class HipRuntime:
             ev, loo = self.head.leave_one_out(tokens, tok_row)
             return ev, pr, loo
 
+    def forward_occlusion(self, features: Tensor, extra: Tensor, event_px: SparsePixels, event_mask: Tensor, prong_px: SparsePixels,
+                          prong_mask: Tensor, counts: Optional[Tuple[int, int]] = None, tile: Tuple[int, int] = (16, 16),
+                          maps: str = "all", max_maps_per_pass: int = 256):
+        """Eval-mode forward() plus the occlusion scan over its pixel maps -> occlusion.OcclusionResult.  One variant per (event,
+        token slot, tile that holds a hit): that map without the hits of that tile goes through its embedder (passes of at most
+        max_maps_per_pass maps), replaces its token in the event's sequence and goes through encoder and decoders.  Counts as ONE
+        forward() for the step counter; the head's forward workspace (attention probabilities) is left as forward() wrote it."""
+        from . import occlusion
+        tile, maps, max_pass = occlusion.check_args(tile, maps, max_maps_per_pass)
+        if self.network.training:
+            raise RuntimeError("occlusion_maps explains an eval-mode prediction: call network.eval() first")
+        with torch.no_grad():
+            ev, pr = self.forward(features, extra, event_px, event_mask, prong_px, prong_mask, counts)
+            rows, tok_row, B, P, n_prongs = self._head_in
+            dev = rows.device
+            tokens = self.head.embed(rows, tok_row, B, P, n_prongs, False, 0)
+            pe = self.network.prong_embedding
+            feat, pix = pe.feature_embedding_dim, pe.pixel_embedding_dim
+            H, W = self.pixel_shape
+            grid = (-(-H // tile[0]), -(-W // tile[1]))
+            parts = []
+            if maps in ("all", "event"):
+                bs = torch.stack((torch.arange(B, device=dev), torch.zeros(B, dtype=torch.int64, device=dev)), 1).to(torch.int32)
+                parts.append(self._occlude(self.ev_engine, event_px, B, bs, 0, 0, tile, max_pass, rows, tokens, tok_row, n_prongs))
+            if maps in ("all", "prongs") and n_prongs > 0:
+                i1, i2 = prong_mask.to(dev).nonzero(as_tuple=True)             # packed prong order: the embedder's image order
+                bs = torch.stack((i1, 1 + i2), 1).to(torch.int32)
+                parts.append(self._occlude(self.pr_engine, prong_px, n_prongs, bs, B, feat, tile, max_pass, rows, tokens, tok_row,
+                                           n_prongs))
+            if parts:
+                index, occ_ev, occ_pr = (torch.cat([p[i] for p in parts]) for i in range(3))
+            else:
+                index = torch.empty(0, 4, dtype=torch.int32, device=dev)
+                occ_ev, occ_pr = ev.new_empty(0, ev.shape[1]), pr.new_empty(0, P, pr.shape[2])
+            if len(parts) > 1:                    # the two lists are ordered by (b, s, ty, tx) each: merge them into that order
+                i64 = index.long()
+                key = ((i64[:, 0] * (1 + P) + i64[:, 1]) * grid[0] + i64[:, 2]) * grid[1] + i64[:, 3]
+                order = torch.argsort(key)
+                index, occ_ev, occ_pr = index[order].contiguous(), occ_ev[order].contiguous(), occ_pr[order].contiguous()
+            return occlusion.OcclusionResult(ev, pr, index, occ_ev, occ_pr, grid, tile)
+
+    def _occlude(self, engine, px: SparsePixels, n_img: int, img_bs: Tensor, row_base: int, col0: int, tile, max_pass: int,
+                 rows: Tensor, tokens: Tensor, tok_row: Tensor, n_prongs: int):
+        """The scan over the maps of one embedder -> (index [V, 4], occluded_event_logits [V, Ce], occluded_prong_logits [V, P, Cp])
+        in the embedder's image order.  The embedder writes [col0, col0 + engine.out_dim) of its maps' rows."""
+        dev = rows.device
+        coords, values = px.coords.to(dev), px.values.to(dev)
+        shape = self.pixel_shape
+        V, unsorted, bad, bounds, vimg, index = engine.occlusion_variants(coords, n_img, shape, tile, img_bs, max_pass)
+        if unsorted or bad:
+            # the variant build walks each image's hits as one range: drop what the embedders drop, then a STABLE sort by image (the
+            # order inside an image decides which of two hits on one pixel wins)
+            c = coords.long()
+            keep = (c[:, 0] >= 0) & (c[:, 0] < n_img) & (c[:, 1] >= 0) & (c[:, 1] < shape[0]) & (c[:, 2] >= 0) & (c[:, 2] < shape[1])
+            coords, values = coords[keep], values[keep]
+            order = torch.sort(coords[:, 0], stable=True).indices
+            coords, values = coords[order].contiguous(), values[order].contiguous()
+            V, unsorted, bad, bounds, vimg, index = engine.occlusion_variants(coords, n_img, shape, tile, img_bs, max_pass)
+            if unsorted or bad:
+                raise RuntimeError("occlusion_maps: the hit list is still unsorted after sorting it")
+        B, S, _ = tokens.shape
+        occ_ev = torch.empty(V, self.head.cfg.event_classes, device=dev)
+        occ_pr = torch.empty(V, S - 1, self.head.cfg.prong_classes, device=dev)
+        if V == 0:
+            return index, occ_ev, occ_pr
+        cap = max(1, max(bounds[k + 1] - bounds[k] for k in range(len(bounds) - 1)))
+        out_coords = torch.empty(cap, 3, dtype=torch.int32, device=dev)
+        out_values = torch.empty(cap, values.shape[1], dtype=torch.float32, device=dev)
+        emb = torch.empty(min(max_pass, V), engine.out_dim, device=dev)
+        for k in range(len(bounds) - 1):
+            first = k * max_pass
+            n = min(max_pass, V - first)
+            nnz = bounds[k + 1] - bounds[k]
+            if nnz > 0:
+                engine.occlusion_build(coords, values, first, n, out_coords, out_values)
+            engine.occlusion_forward(out_coords, out_values, nnz, n, emb[:n], px.value_mode)
+            self.head.occlusion_pass(rows, tokens, tok_row, n_prongs, vimg[first:first + n], index[first:first + n], row_base, emb[:n],
+                                     col0, occ_ev[first:first + n], occ_pr[first:first + n])
+        return index, occ_ev, occ_pr
+
     def _backward(self, st: dict, d_ev: Tensor, d_pr: Tensor):
         """Backward of the fused step in the order the gradient segments become final -- token path, event embedder (side
         stream), prong embedder -- reporting each to ``grad_ready_hook`` so that its all-reduce overlaps with what is left."""

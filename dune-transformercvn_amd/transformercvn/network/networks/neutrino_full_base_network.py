@@ -172,3 +172,21 @@ class NeutrinoBaseNetwork(nn.Module):
             prong_pixels = SparsePixels.from_dense(prong_pixels)
         return self.hip_runtime().forward_leave_one_prong_out(features, extra, event_pixels, event_mask, prong_pixels, prong_mask,
                                                               counts)
+
+    @torch.jit.unused
+    def occlusion_maps(self, features: Tensor, extra: Tensor, event_pixels: Tensor, event_mask: Tensor, prong_pixels: Tensor,
+                       prong_mask: Tensor, counts: Optional[Tuple[int, int]] = None, tile: Tuple[int, int] = (16, 16),
+                       maps: str = "all", max_maps_per_pass: int = 256):
+        """Eval mode only -> transformercvn.hip.occlusion.OcclusionResult: the prediction, and for every (event, token slot, tile of
+        that slot's pixel map that holds a hit) the prediction with the hits of that tile removed from that map.  maps: "all",
+        "event" (the events' own maps) or "prongs".  transformercvn.hip.occlusion.heatmap turns the result into [B, 1+P, Ht, Wt]."""
+        from transformercvn.hip import occlusion
+        occlusion.check_args(tile, maps, max_maps_per_pass)
+        if self.training:
+            raise RuntimeError("occlusion_maps explains an eval-mode prediction: call .eval() first")
+        if not isinstance(event_pixels, SparsePixels):
+            event_pixels = SparsePixels.from_dense(event_pixels)
+        if not isinstance(prong_pixels, SparsePixels):
+            prong_pixels = SparsePixels.from_dense(prong_pixels)
+        return self.hip_runtime().forward_occlusion(features, extra, event_pixels, event_mask, prong_pixels, prong_mask, counts,
+                                                    tile, maps, max_maps_per_pass)

@@ -179,6 +179,19 @@ class NeutrinoFullBaseTrainer(NeutrinoBase, ABC):
         return self.network.leave_one_prong_out(*self._network_inputs(features, extra, event_coords, event_values, event_mask,
                                                                       prong_coords, prong_values, prong_mask), counts)
 
+    def occlusion_maps(self, features: Tensor, extra: Tensor, event_coords: Tensor, event_values: Tensor, event_mask: Tensor,
+                       prong_coords: Tensor, prong_values: Tensor, prong_mask: Tensor, tile: Tuple[int, int] = (16, 16),
+                       maps: str = "all", max_maps_per_pass: int = 256):
+        """Eval mode only -> OcclusionResult (transformercvn.hip.occlusion): which tiles of which pixel maps the prediction rests on;
+        see NeutrinoBaseNetwork.occlusion_maps.  Bad arguments raise ValueError and train mode RuntimeError before any device work."""
+        from transformercvn.hip import occlusion
+        occlusion.check_args(tile, maps, max_maps_per_pass)
+        if self.training:
+            raise RuntimeError("occlusion_maps explains an eval-mode prediction: call .eval() first")
+        return self.network.occlusion_maps(*self._network_inputs(features, extra, event_coords, event_values, event_mask,
+                                                                 prong_coords, prong_values, prong_mask), None, tile, maps,
+                                           max_maps_per_pass)
+
     def shared_step(self, batch):
         (features, extra, ev_c, ev_v, ev_m, pr_c, pr_v, pr_m, ev_t, pr_t) = batch[:10]
         counts = batch[10] if len(batch) > 10 else None               # optional host-side (max_prongs, n_prongs): avoids syncs

@@ -210,6 +210,59 @@ int64_t tcvn_head_leave_one_out_workspace_bytes(const tcvn_head* p, int batch, i
 int tcvn_head_leave_one_out(tcvn_head* p, int batch, int max_prongs, const float* tokens, const int32_t* tok_row,
                             float* event_logits, float* loo_event_logits, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Occlusion maps (forward only, eval arithmetic): which regions of which pixel maps a prediction rests on.
+ *   tile        (tile_h, tile_w) >= 1, need not divide the map: grid_h = ceil(height / tile_h), grid_w = ceil(width / tile_w); the hit
+ *               (y, x) lies in tile (y / tile_h, x / tile_w); the last row / column of tiles may be ragged.
+ *   variant     (b, s, ty, tx): event b, token slot s (0 = the event's own map, 1 + p = the map of valid prong slot p) and a tile of
+ *               that map that holds at least one hit.  Its input is the same event with every hit of that tile removed from that one
+ *               map, all other hits in their original order (duplicate coordinates: the highest index wins, as in the embedders).  A
+ *               tile without hits is no variant: removing nothing changes nothing.  A variant may be an empty map; its token then
+ *               carries the embedding of an image without hits (this is not leave-one-out: the token stays in the sequence).
+ *   variants    one hit list (coords [nnz, 3] = (image, y, x), sorted by image, every hit inside the map) -> the V variants of its
+ *               n_img images ordered by (image, ty, tx): vimg [V] the image, index [V, 4] = (img_bs[image][0], img_bs[image][1], ty,
+ *               tx) with img_bs [n_img, 2] the caller's (b, s) of every image.  vimg and index need room for n_img * grid_h * grid_w
+ *               rows.  host_out (host memory, 4 + ceil(n_img * grid_h * grid_w / max_pass) + 1 words): [0] = V, [1] != 0: the list
+ *               is not sorted by image, [2] != 0: some hit lies outside the images / the map (in both cases nothing else is valid:
+ *               drop those hits, sort stably by image and call again), [3] = hits of all variants together, [4 + k] = first row of
+ *               pass k in the hit lists of the variants (pass k = variants k * max_pass ...; entry ceil(V / max_pass) is the end of
+ *               the last pass).  Occupancy counts are integer atomics: deterministic.  The call synchronises with `stream` once.
+ *   build_pass  writes the hit lists of variants first .. first + count - 1 (count <= max_pass, one pass): out_coords [rows, 3] with
+ *               the image index rewritten to the variant's index inside the pass, out_values [rows, channels] copied untouched;
+ *               rows = host_out[4 + k + 1] - host_out[4 + k]; nothing is written beyond out_rows.  The result goes through
+ *               tcvn_densenet_forward / tcvn_sdxl_forward (train = 0) as `count` images; rows = 0 is a pass of empty maps.
+ *   head_occlusion  one pass through the token path: variant j takes row row_base + vimg[j] of `rows` (the rows of the forward being
+ *               explained) with columns [col0, col0 + width) replaced by emb[j] (the embedder output of the pass, row stride emb_ld),
+ *               goes through the combined embedding as a one-token sequence and replaces token index[j][1] of event index[j][0] in
+ *               `tokens` [batch, S, hidden] (tcvn_head_embed of the same forward); encoder and both decoders then give
+ *               occluded_event_logits [n, Ce] and occluded_prong_logits [n, max_prongs, Cp] (rows of padded slots as
+ *               tcvn_head_decode leaves them).  n <= TCVN_OCC_MAX_PASS; workspace of its own (tcvn_head_occlusion_workspace_bytes), so
+ *               the forward's workspace keeps its attention probabilities.
+ *   heatmap     [batch, 1 + max_prongs, grid_h, grid_w] = softmax(base)[c] - softmax(occluded)[c] at every variant's position,
+ *               exactly 0 elsewhere.  TCVN_OCC_TARGET_EVENT: event logits, c = classes[b] or (classes == NULL) the predicted class of
+ *               event b.  TCVN_OCC_TARGET_PRONG: for s >= 1 the prong logits of slot s - 1 and that slot's predicted class; row s = 0
+ *               stays 0.
+ * Argument errors (NULL, tile < 1, max_pass outside 1..TCVN_OCC_MAX_PASS, S > 64, workspace too small) return non-zero before any
+ * device call and print one "tcvn:" line. */
+#define TCVN_OCC_MAX_PASS 256
+#define TCVN_OCC_TARGET_EVENT 0
+#define TCVN_OCC_TARGET_PRONG 1
+int64_t tcvn_occlusion_workspace_bytes(int n_img, int height, int width, int tile_h, int tile_w, int max_pass);
+int tcvn_occlusion_variants(const int32_t* coords, int64_t nnz, int n_img, int height, int width, int tile_h, int tile_w,
+                            const int32_t* img_bs, int max_pass, int32_t* vimg, int32_t* index, void* workspace,
+                            int64_t workspace_bytes, int64_t* host_out, int64_t host_cap, void* stream);
+int tcvn_occlusion_build_pass(const int32_t* coords, const float* values, int64_t nnz, int channels, int n_img, int height, int width,
+                              int tile_h, int tile_w, int max_pass, const int32_t* vimg, const void* workspace, int64_t workspace_bytes,
+                              int first, int count, int32_t* out_coords, float* out_values, int64_t out_rows, void* stream);
+int64_t tcvn_head_occlusion_workspace_bytes(const tcvn_head* p, int max_prongs);
+int tcvn_head_occlusion(tcvn_head* p, int batch, int max_prongs, int n_prongs, const float* rows, const float* tokens,
+                        const int32_t* tok_row, int n, const int32_t* vimg, const int32_t* index, int row_base, const float* emb,
+                        int64_t emb_ld, int col0, int width, float* occluded_event_logits, float* occluded_prong_logits,
+                        void* workspace, int64_t workspace_bytes, void* stream);
+int tcvn_occlusion_heatmap(const float* event_logits, const float* prong_logits, const float* occluded_event_logits,
+                           const float* occluded_prong_logits, const int32_t* index, int64_t n_variants, int batch, int max_prongs,
+                           int event_classes, int prong_classes, int grid_h, int grid_w, int target, const int32_t* classes,
+                           float* heatmap, void* stream);
+
 /* Row operators behind the holder modules' own forward() (forward only, fp32):
  *   y = x W^T + b (torch.nn.Linear layout; bias may be NULL)                      -- layers/prong_decoder.py:15-16
  *   y = dropout(prelu(batchnorm1d(x)))  with batch statistics + running-stat update when train != 0, running statistics

@@ -1,8 +1,9 @@
 """What do the explanation calls cost at the --ragged-inference shape (batch 32, 1-16 prongs/event, bf16 embedders, eval mode)?
 Times forward(), forward_with_attention() and leave_one_prong_out() on the same batch with device events around synchronised work,
-interleaved, and prints one JSON line with the medians.
+interleaved, and prints one JSON line with the medians.  occlusion_maps() is timed the same way at tiles of 32x32 and 16x16 with its
+number of variants V and of embedder passes (a scan is thousands of maps: it gets --occ-reps repetitions of its own).
 
-    python tools/explain_cost.py [--batch 32 --reps 15 --precision bf16]
+    python tools/explain_cost.py [--batch 32 --reps 15 --occ-reps 3 --precision bf16]
 """
 import argparse
 import json
@@ -23,6 +24,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--reps", type=int, default=15)
+    ap.add_argument("--occ-reps", type=int, default=3, help="repetitions of each occlusion_maps line (0: skip them)")
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32"])
     args = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -57,6 +59,25 @@ def main():
            "reps": args.reps}
     for name, ts in times.items():
         out[name + "_ms"] = {"median": round(statistics.median(ts), 3), "min": round(min(ts), 3), "max": round(max(ts), 3)}
+    for tile in ((32, 32), (16, 16)) if args.occ_reps > 0 else ():
+        ts = []
+        with torch.no_grad():
+            for rep in range(1 + args.occ_reps):                    # the first call allocates the scan's workspaces
+                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                t0.record()
+                res = model.occlusion_maps(*inputs[:8], tile=tile)
+                t1.record()
+                t1.synchronize()
+                if rep:
+                    ts.append(t0.elapsed_time(t1))
+        n_ev = int((res.index[:, 1] == 0).sum())
+        n_pr = res.num_variants - n_ev
+        out[f"occlusion_maps_{tile[0]}x{tile[1]}"] = {
+            "variants": res.num_variants, "event_map_variants": n_ev, "prong_map_variants": n_pr,
+            "passes": -(-n_ev // 256) + -(-n_pr // 256), "reps": args.occ_reps,
+            "ms": {"median": round(statistics.median(ts), 3), "min": round(min(ts), 3), "max": round(max(ts), 3)},
+            "us_per_variant": round(1e3 * statistics.median(ts) / max(1, res.num_variants), 2)}
     cfg = model.network.hip_runtime().head.cfg
     out["weights_bytes"] = cfg.n_layers * args.batch * cfg.heads * (1 + width) ** 2 * 4
     print(json.dumps(out))
