@@ -1673,16 +1673,6 @@ __global__ __launch_bounds__(512, 1) void k_conv3x3_dgrad3_bf16(const ConvDgradA
 }
 static long cu_tiles() { return 256; }      // workgroups of a full persistent grid (one per CU)
 size_t dgrad3_smem() { return size_t(DG_RING) * 64 + DG_TBL * 4 + 448 * 4 + 8 * 32 * DG_CP * 4 + 4 * 18 * 1024; }
-bool dgrad3_ok(const ConvDgradArgs& a, const PadGeom& q) {
-    static const bool any_size = TCVN_KNOB_SET("TCVN_DGRAD3_ANY_SIZE");      // validation build: at any size
-    // from 8 tiles per workgroup on: below that its prologue (72 KB of weights into LDS, the whole first eff image) costs more than the
-    // ring saves (block 3, 816 tiles: 37 us against 32 us for the two-workgroup kernel; block 2, 3 600 tiles: 94 against 102)
-    return a.zeros != nullptr && a.e.N == 32 && (a.e.c_off & 7) == 0 && q.rows() + TP + 8 <= DG_RING &&
-           (q.tiles() >= 8 * cu_tiles() || any_size) &&
-           (reinterpret_cast<uintptr_t>(a.e.G) & 15) == 0 && (reinterpret_cast<uintptr_t>(a.e.X) & 15) == 0 &&
-           (reinterpret_cast<uintptr_t>(a.Xin) & 15) == 0 && (reinterpret_cast<uintptr_t>(a.Gout) & 15) == 0;
-}
-
 size_t dgrad2_smem(const PadGeom& q) { const size_t nr = (q.rows() + 15) & ~15; return 3 * nr * 64 + 2 * nr * 4 + 32 * 132 * 4 + 448 * 4 + ((nr + 63) & ~size_t(63)) * 4; }
 size_t dgrad_smem(const PadGeom& q) { const size_t r4 = (q.rows() + 3) & ~3; return r4 * 68 + 128 * 24 + 64 * 132 * 4; }
 int tile_grid2(long ntiles) {           // two workgroups per CU
@@ -1700,119 +1690,92 @@ int tile_grid(long ntiles) {            // one persistent workgroup per CU
     return (int)ntiles;
 }
 
-}  // namespace
+PadGeom geom_of(int M, int H, int W) { return PadGeom(M / (H * W), H, W); }      // n_img is recovered from M = n*H*W
 
-// n_img is recovered from M = n*H*W
-static bool tile_disabled() {
-    static const bool off = TCVN_KNOB_SET("TCVN_DISABLE_TILE");      // validation switch: force the generic kernels
-    return off;
+// the kernels' dynamic LDS exceeds the 64 KB default: raised once per kernel
+int allow_lds(const void* kernel, int bytes, bool& done) {
+    if (!done) {
+        TCVN_CHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+        done = true;
+    }
+    return 0;
 }
 
-bool conv3x3_tile_enabled() { return !tile_disabled(); }
+}  // namespace
+
+bool conv3x3_tile_enabled() {
+    static const bool off = TCVN_KNOB_SET("TCVN_DISABLE_TILE");      // validation switch: force the generic kernels
+    return !off;
+}
 
 bool conv3x3_tile_ok(const ConvFwdArgs& a) {
-    if (tile_disabled()) return false;
+    if (!conv3x3_tile_enabled()) return false;
     if (a.Wfrag == nullptr || (reinterpret_cast<uintptr_t>(a.Wfrag) & 15) || a.Aact == nullptr || a.zeros == nullptr) return false;
     if (a.mode != MODE_BF16 || a.amode != A_3X3 || a.C != 128 || a.lda != 128 || a.N > 32 || a.Kp != 1152) return false;
     if ((reinterpret_cast<uintptr_t>(a.A) & 15) || (reinterpret_cast<uintptr_t>(a.Wk) & 15)) return false;
     if (a.M % (a.H * a.W) != 0) return false;
-    const PadGeom q(a.M / (a.H * a.W), a.H, a.W);
+    const PadGeom q = geom_of(a.M, a.H, a.W);
     return q.gtot < (1L << 24) && fwd_smem(q) <= 160 * 1024;
 }
-int conv3x3_tile_nblk(const ConvFwdArgs& a) {
-    const PadGeom q(a.M / (a.H * a.W), a.H, a.W);
-    return tile_grid(q.tiles());
-}
-// validation build: TCVN_FWD_STRIP runs the strip kernel (k_conv3x3_fwd_bf16) where the pair or ring kernel would
-static bool fwd_strip_forced() {
-    static const bool on = TCVN_KNOB_SET("TCVN_FWD_STRIP");
-    return on;
-}
-static bool fwd_pair_ok(const ConvFwdArgs& a, const PadGeom& q) {
-    return fwd_pair_smem(q) <= 160 * 1024 && 4 * TP + q.halo + q.Wp + 1 < PAIR_TBL && (long)a.M * a.N < (1L << 32) && !fwd_strip_forced();
+int conv3x3_tile_nblk(const ConvFwdArgs& a) { return tile_grid(geom_of(a.M, a.H, a.W).tiles()); }
+
+// The ONE place that chooses the forward kernel: the launcher switches on it, the DenseNet driver asks it what the launch will do
+Conv3x3Fwd conv3x3_fwd_kernel(const ConvFwdArgs& a) {
+    if (!conv3x3_tile_ok(a)) return CONV3X3_FWD_NONE;
+    static const bool strip_forced = TCVN_KNOB_SET("TCVN_FWD_STRIP");      // validation build: the strip kernel where the pair or ring kernel would run
+    const PadGeom q = geom_of(a.M, a.H, a.W);
+    if (fwd_pair_smem(q) <= 160 * 1024 && 4 * TP + q.halo + q.Wp + 1 < PAIR_TBL && (long)a.M * a.N < (1L << 32) && !strip_forced)
+        return CONV3X3_FWD_PAIR;                    // two waves per SIMD, taps split
+    if (!a.act_fused && ((q.rows() + 3) & ~3) + TP <= RING && !strip_forced) return CONV3X3_FWD_RING;      // consecutive tiles per workgroup, ring image
+    return CONV3X3_FWD_STRIP;
 }
 bool conv3x3_act_fusable(const ConvFwdArgs& a) {
-    if (!conv3x3_tile_ok(a) || a.sc == nullptr || a.sh == nullptr || a.sl == nullptr) return false;
     static const bool off = TCVN_KNOB_SET("TCVN_NO_ACT_FUSE");      // validation build: keep the materialised activation (A/B and variant tests)
-    const PadGeom q(a.M / (a.H * a.W), a.H, a.W);
     // forward: only the pair kernel activates in LDS; backward: the weight-gradient tile kernel (same geometry conditions as conv3x3_wgrad_tile_ok)
-    return !off && fwd_pair_ok(a, q) && wgrad_smem(q) <= 160 * 1024;
-}
-bool conv3x3_fwd_pair(const ConvFwdArgs& a) {          // conv_fwd(a) runs k_conv3x3_fwd_pair_bf16 (the kernel that honours lf / isum_out)
-    if (!conv3x3_tile_ok(a)) return false;
-    return fwd_pair_ok(a, PadGeom(a.M / (a.H * a.W), a.H, a.W));
-}
-bool conv3x3_fwd_writes_keep(const ConvFwdArgs& a) {
-    if (a.keep_out == nullptr || a.drop_p <= 0.f || !conv3x3_tile_ok(a)) return false;
-    return fwd_pair_ok(a, PadGeom(a.M / (a.H * a.W), a.H, a.W));
+    return !off && a.sc != nullptr && a.sh != nullptr && a.sl != nullptr && conv3x3_fwd_kernel(a) == CONV3X3_FWD_PAIR &&
+           wgrad_smem(geom_of(a.M, a.H, a.W)) <= 160 * 1024;
 }
 int conv3x3_fwd_tile(const ConvFwdArgs& a, hipStream_t st) {
-    const int n_img = a.M / (a.H * a.W);
-    const PadGeom q(n_img, a.H, a.W);
-    const int ntiles = (int)q.tiles();
-    const int nb = tile_grid(ntiles);
-    const size_t smem = fwd_smem(q);
-    static bool attr = false;
-    if (!attr) {
-        TCVN_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv3x3_fwd_bf16), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       160 * 1024));
-        attr = true;
-    }
+    const PadGeom q = geom_of(a.M, a.H, a.W);
+    const int n_img = a.M / (a.H * a.W), ntiles = (int)q.tiles(), nb = tile_grid(ntiles);
+    const Conv3x3Fwd k = conv3x3_fwd_kernel(a);
+    // only the pair kernel derives / adds link-free statistics (lf, isum_out) and activates in LDS (conv3x3_act_fusable)
+    if (k == CONV3X3_FWD_NONE || (k != CONV3X3_FWD_PAIR && (a.lf.isum != nullptr || a.isum_out != nullptr || a.act_fused))) return -2;
+    static bool attr_pair = false, attr_ring = false, attr_strip = false;
     ProfScope ps("k_conv3x3_fwd_bf16", 2.0 * a.M * (double)a.N * a.K, (double)a.M * 2.0 * (a.C + a.N), st);   // read 128 ch, write N ch
-    if (fwd_pair_ok(a, q)) {   // two waves per SIMD, taps split
-        static bool attr3 = false;
-        if (!attr3) {
-            TCVN_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv3x3_fwd_pair_bf16), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           160 * 1024));
-            attr3 = true;
-        }
-        hipLaunchKernelGGL(k_conv3x3_fwd_pair_bf16, dim3(nb), dim3(512), fwd_pair_smem(q), st, a, n_img, ntiles, fwd_pair_ring(q));
-        TCVN_LAUNCH_CHECK();
-        return 0;
+    int rc;
+    switch (k) {
+        case CONV3X3_FWD_PAIR:
+            if ((rc = allow_lds(reinterpret_cast<const void*>(k_conv3x3_fwd_pair_bf16), 160 * 1024, attr_pair))) return rc;
+            hipLaunchKernelGGL(k_conv3x3_fwd_pair_bf16, dim3(nb), dim3(512), fwd_pair_smem(q), st, a, n_img, ntiles, fwd_pair_ring(q));
+            break;
+        case CONV3X3_FWD_RING:
+            if ((rc = allow_lds(reinterpret_cast<const void*>(k_conv3x3_fwd_ring_bf16), 160 * 1024, attr_ring))) return rc;
+            hipLaunchKernelGGL(k_conv3x3_fwd_ring_bf16, dim3(nb), dim3(256), fwd_ring_smem(), st, a, n_img, ntiles);
+            break;
+        default:
+            if ((rc = allow_lds(reinterpret_cast<const void*>(k_conv3x3_fwd_bf16), 160 * 1024, attr_strip))) return rc;
+            hipLaunchKernelGGL(k_conv3x3_fwd_bf16, dim3(nb), dim3(256), fwd_smem(q), st, a, n_img, ntiles, (nb >= 8 && nb % 8 == 0) ? 1 : 0);
     }
-    if (a.lf.isum != nullptr || a.isum_out != nullptr) return -2;            // only the pair kernel derives / adds link-free statistics (conv3x3_fwd_pair)
-    if (!a.act_fused && ((q.rows() + 3) & ~3) + TP <= RING && !fwd_strip_forced()) {       // consecutive tiles per workgroup, ring image
-        static bool attr2 = false;
-        if (!attr2) {
-            TCVN_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv3x3_fwd_ring_bf16), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           160 * 1024));
-            attr2 = true;
-        }
-        hipLaunchKernelGGL(k_conv3x3_fwd_ring_bf16, dim3(nb), dim3(256), fwd_ring_smem(), st, a, n_img, ntiles);
-        TCVN_LAUNCH_CHECK();
-        return 0;
-    }
-    if (a.act_fused) return -2;                                               // only the pair kernel activates in LDS (conv3x3_act_fusable)
-    hipLaunchKernelGGL(k_conv3x3_fwd_bf16, dim3(nb), dim3(256), smem, st, a, n_img, ntiles, (nb >= 8 && nb % 8 == 0) ? 1 : 0);
     TCVN_LAUNCH_CHECK();
     return 0;
 }
-
-}  // namespace tcvn
-
-namespace tcvn {
-using namespace t3;
 
 bool conv3x3_wgrad_tile_ok(const ConvWgradArgs& a) {
     const ConvFwdArgs& fa = a.fa;
     if (!conv3x3_tile_enabled() || a.mode != MODE_BF16 || fa.amode != A_3X3 || fa.C != 128 || a.e.N > 32) return false;
     if (fa.Aact == nullptr || fa.zeros == nullptr || (a.e.ldg & 7) || (a.e.ldx & 7) || (a.e.c_off & 1)) return false;
     if (fa.M % (fa.H * fa.W) != 0) return false;
-    const PadGeom q(fa.M / (fa.H * fa.W), fa.H, fa.W);
+    const PadGeom q = geom_of(fa.M, fa.H, fa.W);
     return q.gtot < (1L << 24) && wgrad_smem(q) <= 160 * 1024 && (long)fa.M * a.e.N < (1L << 32);
 }
 
 int conv3x3_wgrad_tile(const ConvWgradArgs& a, hipStream_t st) {
-    const int n_img = a.fa.M / (a.fa.H * a.fa.W);
-    const PadGeom q(n_img, a.fa.H, a.fa.W);
-    const int ntiles = (int)q.tiles();
-    const int nb = tile_grid(ntiles);
+    const PadGeom q = geom_of(a.fa.M, a.fa.H, a.fa.W);
+    const int n_img = a.fa.M / (a.fa.H * a.fa.W), ntiles = (int)q.tiles(), nb = tile_grid(ntiles);
     static bool attr = false;
-    if (!attr) {
-        TCVN_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv3x3_wgrad_bf16), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       160 * 1024));
-        attr = true;
-    }
+    int rc;
+    if ((rc = allow_lds(reinterpret_cast<const void*>(k_conv3x3_wgrad_bf16), 160 * 1024, attr))) return rc;
     if (a.slab == nullptr || (long)nb * (9 * 128 * 32 + 32) * 4 > a.slab_bytes || a.dbias == nullptr) return -3;
     {
         ProfScope ps("k_conv3x3_wgrad_bf16", 2.0 * a.fa.M * (double)a.e.N * a.fa.K, (double)a.fa.M * 2.0 * (a.fa.C + 2 * a.e.N), st);   // YA + (G, x) slices
@@ -1820,62 +1783,56 @@ int conv3x3_wgrad_tile(const ConvWgradArgs& a, hipStream_t st) {
         TCVN_LAUNCH_CHECK();
     }
     // weight partials [nb][9*128*32] -> dWk and bias partials [nb][32] -> dbias[0:N) (32-wide rows, zero beyond N): one launch
-    SlabJob jb{};
-    if (a.dbias != nullptr) jb = slab_job(a.slab + (long)nb * (9 * 128 * 32), nb, a.e.N, a.dbias, 32);
-    if (a.deferred != nullptr) { a.deferred[0] = slab_job(a.slab, nb, 9 * 128 * 32, a.dWk, 0); a.deferred[1] = jb; return 0; }
-    return slab_reduce2(slab_job(a.slab, nb, 9 * 128 * 32, a.dWk, 0), jb, st);
+    const SlabJob jw = slab_job(a.slab, nb, 9 * 128 * 32, a.dWk, 0), jb = slab_job(a.slab + (long)nb * (9 * 128 * 32), nb, a.e.N, a.dbias, 32);
+    if (a.deferred != nullptr) { a.deferred[0] = jw; a.deferred[1] = jb; return 0; }
+    return slab_reduce2(jw, jb, st);
 }
-
-}  // namespace tcvn
-
-namespace tcvn {
-using namespace t3;
 
 bool conv3x3_dgrad_tile_ok(const ConvDgradArgs& a) {
     if (!conv3x3_tile_enabled() || a.mode != MODE_BF16 || a.dmode != DG_3X3 || a.N != 128 || a.e.N > 32 || a.Kp != 288) return false;
     if (a.Wfrag == nullptr || a.accumulate || a.ldxin != 128 || a.ldgo != 128) return false;
     if ((a.e.ldg & 7) || (a.e.ldx & 7) || (a.e.c_off & 1) || a.M % (a.H * a.W) != 0) return false;
-    const PadGeom q(a.M / (a.H * a.W), a.H, a.W);
-    return q.gtot < (1L << 24) && (long)a.M * a.e.N < (1L << 32);
+    return geom_of(a.M, a.H, a.W).gtot < (1L << 24) && (long)a.M * a.e.N < (1L << 32);
 }
-bool conv3x3_dgrad_writes_ey(const ConvDgradArgs& a) {
-    if (a.ey_out == nullptr || !conv3x3_dgrad_tile_ok(a)) return false;
-    return dgrad3_ok(a, PadGeom(a.M / (a.H * a.W), a.H, a.W));
+// The ONE place that chooses the data-gradient kernel (as conv3x3_fwd_kernel for the forward)
+Conv3x3Dgrad conv3x3_dgrad_kernel(const ConvDgradArgs& a) {
+    if (!conv3x3_dgrad_tile_ok(a)) return CONV3X3_DGRAD_NONE;
+    static const bool any_size = TCVN_KNOB_SET("TCVN_DGRAD3_ANY_SIZE");      // validation build: the consecutive-tile kernel at any size
+    const PadGeom q = geom_of(a.M, a.H, a.W);
+    // both LDS-DMA kernels need the concat slice 16-B aligned and all 32 channels present
+    const bool dma = a.zeros != nullptr && a.e.N == 32 && (a.e.c_off & 7) == 0 &&
+                     (reinterpret_cast<uintptr_t>(a.e.G) & 15) == 0 && (reinterpret_cast<uintptr_t>(a.e.X) & 15) == 0;
+    // consecutive tiles, eff ring, wave-private epilogue -- from 8 tiles per workgroup on: below that its prologue (72 KB of weights into LDS, the
+    // whole first eff image) costs more than the ring saves (block 3, 816 tiles: 37 us against 32 us for the two-workgroup kernel; block 2,
+    // 3 600 tiles: 94 against 102)
+    if (dma && q.rows() + TP + 8 <= DG_RING && (q.tiles() >= 8 * cu_tiles() || any_size) &&
+        (reinterpret_cast<uintptr_t>(a.Xin) & 15) == 0 && (reinterpret_cast<uintptr_t>(a.Gout) & 15) == 0)
+        return CONV3X3_DGRAD_CONSEC;
+    return dma && dgrad2_smem(q) <= 80 * 1024 ? CONV3X3_DGRAD_PIPELINED : CONV3X3_DGRAD_TWO_WG;
 }
-int conv3x3_dgrad_tile_nblk(const ConvDgradArgs& a) {
-    const PadGeom q(a.M / (a.H * a.W), a.H, a.W);
-    return dgrad3_ok(a, q) ? tile_grid(q.tiles()) : tile_grid2(q.tiles());      // one 512-thread workgroup per CU, or two of 256
+int conv3x3_dgrad_tile_nblk(const ConvDgradArgs& a) {      // one 512-thread workgroup per CU, or two of 256
+    const long ntiles = geom_of(a.M, a.H, a.W).tiles();
+    return conv3x3_dgrad_kernel(a) == CONV3X3_DGRAD_CONSEC ? tile_grid(ntiles) : tile_grid2(ntiles);
 }
 int conv3x3_dgrad_tile(const ConvDgradArgs& a, hipStream_t st) {
-    const int n_img = a.M / (a.H * a.W);
-    const PadGeom q(n_img, a.H, a.W);
-    const int ntiles = (int)q.tiles();
+    const PadGeom q = geom_of(a.M, a.H, a.W);
+    const int n_img = a.M / (a.H * a.W), ntiles = (int)q.tiles(), nb = tile_grid2(ntiles), swz = (nb >= 8 && nb % 8 == 0) ? 1 : 0;
+    static bool attr_consec = false, attr_pipe = false;
     ProfScope ps("k_conv3x3_dgrad_bf16", 2.0 * a.M * (double)a.N * 9 * a.e.N, (double)a.M * 2.0 * (2 * a.e.N + 2 * a.N), st);   // (G, x) slices in; Y in, DU out
-    if (dgrad3_ok(a, q)) {                 // consecutive tiles, eff ring, wave-private epilogue
-        static bool attr3 = false;
-        if (!attr3) {
-            TCVN_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv3x3_dgrad3_bf16), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            attr3 = true;
-        }
-        hipLaunchKernelGGL(k_conv3x3_dgrad3_bf16, dim3(tile_grid(ntiles)), dim3(512), dgrad3_smem(), st, a, n_img, ntiles);
-        TCVN_LAUNCH_CHECK();
-        return 0;
+    int rc;
+    switch (conv3x3_dgrad_kernel(a)) {
+        case CONV3X3_DGRAD_NONE: return -2;
+        case CONV3X3_DGRAD_CONSEC:
+            if ((rc = allow_lds(reinterpret_cast<const void*>(k_conv3x3_dgrad3_bf16), 160 * 1024, attr_consec))) return rc;
+            hipLaunchKernelGGL(k_conv3x3_dgrad3_bf16, dim3(tile_grid(ntiles)), dim3(512), dgrad3_smem(), st, a, n_img, ntiles);
+            break;
+        case CONV3X3_DGRAD_PIPELINED:
+            if ((rc = allow_lds(reinterpret_cast<const void*>(k_conv3x3_dgrad2_bf16), 80 * 1024, attr_pipe))) return rc;
+            hipLaunchKernelGGL(k_conv3x3_dgrad2_bf16, dim3(nb), dim3(256), dgrad2_smem(q), st, a, n_img, ntiles, swz);
+            break;
+        case CONV3X3_DGRAD_TWO_WG:
+            hipLaunchKernelGGL(k_conv3x3_dgrad_bf16, dim3(nb), dim3(256), dgrad_smem(q), st, a, n_img, ntiles, swz);
     }
-    const int nb = tile_grid2(ntiles);
-    // pipelined variant: needs the concat slice 16-B aligned for the LDS-DMA and all 32 channels present
-    if (a.zeros != nullptr && a.e.N == 32 && (a.e.c_off & 7) == 0 && dgrad2_smem(q) <= 80 * 1024 &&
-        (reinterpret_cast<uintptr_t>(a.e.G) & 15) == 0 && (reinterpret_cast<uintptr_t>(a.e.X) & 15) == 0) {
-        static bool attr = false;
-        if (!attr) {
-            TCVN_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv3x3_dgrad2_bf16), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-            attr = true;
-        }
-        hipLaunchKernelGGL(k_conv3x3_dgrad2_bf16, dim3(nb), dim3(256), dgrad2_smem(q), st, a, n_img, ntiles, (nb >= 8 && nb % 8 == 0) ? 1 : 0);
-        TCVN_LAUNCH_CHECK();
-        return 0;
-    }
-    hipLaunchKernelGGL(k_conv3x3_dgrad_bf16, dim3(nb), dim3(256), dgrad_smem(q), st, a, n_img, ntiles,
-                       (nb >= 8 && nb % 8 == 0) ? 1 : 0);
     TCVN_LAUNCH_CHECK();
     return 0;
 }

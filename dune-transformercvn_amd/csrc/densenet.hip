@@ -10,8 +10,6 @@
 #include <vector>
 #include <cstring>
 
-#include "../../include/tcvn_hip.h"
-#include "tcvn_ops.h"
 #include "tcvn_rows.h"
 #include <cstdlib>
 #include "densenet_plan.h"
@@ -93,6 +91,7 @@ DenseNetPlan::DenseNetPlan(const tcvn_densenet_cfg& c) : cfg(c) {
     s_al = add_slot("output_block.relu.weight", cfg.out_dim, TCVN_SLOT_PARAM);
     data.assign(slots.size(), nullptr);
     grad.assign(slots.size(), nullptr);
+    for (const auto& bg : blocks) path.emplace_back(bg.L);
 }
 
 DenseNetPlan::~DenseNetPlan() {
@@ -189,18 +188,7 @@ void DenseNetPlan::layout(int n, bool bwd, Layout& L) const {
     else L.total = b.off;
 }
 
-long DenseNetPlan::tab_floats() const {
-    // (scale, shift) per BN layer, channel count rounded to 8
-    long t = 0;
-    auto add = [&](const BnSlots& s) { t += 2 * round_up(s.C, 8); };
-    add(n0);
-    for (const auto& bg : blocks) {
-        for (const auto& ls : bg.layers) { add(ls.n1); add(ls.n2); }
-        if (bg.has_trans) add(bg.tn);
-    }
-    add(nf);
-    return t;
-}
+long DenseNetPlan::tab_floats() const { return tab_off(nf) + 2 * round_up(nf.C, 8); }      // (scale, shift) per BN layer, channel count rounded to 8; final_norm is the last
 
 // offsets (in floats) of the table of BN layer `s` inside the tabs region: sc at off, sh at off + round_up(C, 8)
 long DenseNetPlan::tab_off(const BnSlots& s) const {
@@ -307,10 +295,6 @@ int DenseNetPlan::bind(void* const* d, void* const* g) {
 // ---------------------------------------------------------------------------------------------------------------------
 // forward
 // ---------------------------------------------------------------------------------------------------------------------
-namespace {
-struct Tab { float* sc; float* sh; };
-}
-
 int DenseNetPlan::upload_descs(char* ws, const Layout& L, hipStream_t st) {
     // Pack descriptors (weights -> kernel layout) and eval-mode BN descriptors live in a small device table that
     // depends on the workspace address; rebuilt only when the workspace base or the bindings change.
@@ -323,11 +307,11 @@ int DenseNetPlan::upload_descs(char* ws, const Layout& L, hipStream_t st) {
         pd.push_back(d);
     }
     std::vector<BnEvalDesc> bd;
-    float* tabs = reinterpret_cast<float*>(ws + L.tabs);
     auto addbn = [&](const BnSlots& s) {
         BnEvalDesc d;
         d.gamma = data[s.w]; d.beta = data[s.b]; d.rm = data[s.rm]; d.rv = data[s.rv];
-        d.sc = tabs + tab_off(s); d.sh = d.sc + round_up(s.C, 8); d.C = s.C;
+        const Tab t = tab(ws, L, s);
+        d.sc = t.sc; d.sh = t.sh; d.C = s.C;
         bd.push_back(d);
     };
     addbn(n0);
@@ -351,6 +335,103 @@ int DenseNetPlan::upload_descs(char* ws, const Layout& L, hipStream_t st) {
     return 0;
 }
 
+Tab DenseNetPlan::tab(char* ws, const Layout& L, const BnSlots& bn) const {
+    float* sc = reinterpret_cast<float*>(ws + L.tabs) + tab_off(bn);
+    return Tab{sc, sc + round_up(bn.C, 8)};
+}
+
+ConvFwdArgs DenseNetPlan::conv0_args(const Step& s) const {
+    const WkEntry& e = wk_find(s_w0, 0);
+    ConvFwdArgs a{};
+    a.mode = cfg.mode; a.amode = A_STEM; a.A = s.ws + s.L.img; a.lda = cfg.in_ch; a.M = s.n * Hc * Wc; a.N = cfg.init_ch;
+    a.K = 49 * cfg.in_ch; a.Kp = e.Kp; a.C = cfg.in_ch; a.H = Hc; a.W = Wc; a.Hin = cfg.H; a.Win = cfg.W;
+    a.Wk = s.ws + s.L.wk + e.off; a.bias = data[s_b0]; a.Out = s.ws + s.L.c0; a.ldo = cfg.init_ch; a.n_off = 0;
+    return a;
+}
+
+ConvFwdArgs DenseNetPlan::conv1_args(const Step& s, int bi, int l) const {      // D[:, 0:cin] -> Y
+    const BlockGeom& bg = blocks[bi];
+    const LayerSlots& ls = bg.layers[l];
+    const WkEntry& e = wk_find(ls.w1, 0);
+    const Tab t = tab(s.ws, s.L, ls.n1);
+    ConvFwdArgs a{};
+    a.mode = cfg.mode; a.amode = A_1X1; a.A = s.ws + s.L.D[bi]; a.lda = bg.ld; a.M = s.n * bg.H * bg.W; a.N = cfg.bn_size * cfg.growth;
+    a.K = ls.cin; a.Kp = e.Kp; a.C = ls.cin; a.H = bg.H; a.W = bg.W; a.sc = t.sc; a.sh = t.sh; a.sl = data[ls.a1];
+    a.Wk = s.ws + s.L.wk + e.off; a.bias = data[ls.b1]; a.Out = s.ws + s.L.Y[bi][l]; a.ldo = a.N; a.n_off = 0;
+    return a;
+}
+
+ConvFwdArgs DenseNetPlan::conv3_args(const Step& s, int bi, int l) const {      // Y -> D[:, cin:cin+g]
+    const BlockGeom& bg = blocks[bi];
+    const LayerSlots& ls = bg.layers[l];
+    const WkEntry& e = wk_find(ls.w2, 0);
+    const Tab t = tab(s.ws, s.L, ls.n2);
+    const int mid = cfg.bn_size * cfg.growth;
+    ConvFwdArgs a{};
+    a.mode = cfg.mode; a.amode = A_3X3; a.A = s.ws + s.L.Y[bi][l]; a.lda = mid; a.M = s.n * bg.H * bg.W; a.N = cfg.growth; a.K = 9 * mid;
+    a.Kp = e.Kp; a.C = mid; a.H = bg.H; a.W = bg.W; a.sc = t.sc; a.sh = t.sh; a.sl = data[ls.a2];
+    a.Wk = s.ws + s.L.wk + e.off; a.bias = data[ls.b2]; a.Out = s.ws + s.L.D[bi]; a.ldo = bg.ld; a.n_off = ls.cin;
+    a.Wfrag = wk_frag(s.ws, s.L, ls.w2, 0);
+    if (cfg.mode == MODE_BF16) { a.zeros = s.ws + s.L.zeros; a.Aact = a.A; }
+    return a;
+}
+
+ConvFwdArgs DenseNetPlan::trans_args(const Step& s, int bi) const {      // D[bi] -> first channels of D[bi + 1]
+    const BlockGeom &bg = blocks[bi], &nb = blocks[bi + 1];
+    const WkEntry& e = wk_find(bg.tw, 0);
+    ConvFwdArgs a{};
+    a.mode = cfg.mode; a.M = s.n * nb.H * nb.W; a.N = bg.Ctot / 2; a.Kp = e.Kp; a.H = nb.H; a.W = nb.W; a.Hin = bg.H; a.Win = bg.W;
+    if (s.L.XP[bi] >= 0 && cfg.mode == MODE_F32) {      // the pooled + activated operand is materialised: a plain 1x1 convolution over it (K padded to ldp: zero columns x zero weights)
+        a.amode = A_1X1; a.A = s.ws + s.L.XP[bi]; a.lda = bg.ldp; a.K = bg.ldp; a.C = bg.ldp;
+    } else {
+        const Tab t = tab(s.ws, s.L, bg.tn);
+        a.amode = A_1X1_POOL; a.A = s.ws + s.L.D[bi]; a.lda = bg.ld; a.K = bg.Ctot; a.C = bg.Ctot; a.sc = t.sc; a.sh = t.sh; a.sl = data[bg.ta];
+    }
+    a.Wk = s.ws + s.L.wk + e.off; a.bias = data[bg.tb]; a.Out = s.ws + s.L.D[bi + 1]; a.ldo = nb.ld; a.n_off = 0;
+    return a;
+}
+
+// index, weights, geometry and BatchNorm0 table of the sparse-aware stem; Out / part (forward) and e / P0 / Q0 / slab / dWk (backward) are the caller's
+StemSparseArgs DenseNetPlan::stem_sparse_args(const Step& s, const int32_t* coords, const float* values, long nnz, int value_mode, float noise_std) const {
+    const WkEntry& e = wk_find(s_w0, 0);
+    const Tab t = tab(s.ws, s.L, n0);
+    StemSparseArgs sa{};
+    sa.coords = coords; sa.values = values; sa.nnz = nnz; sa.n_img = s.n; sa.H = cfg.H; sa.W = cfg.W; sa.Cpix = cfg.in_ch;
+    sa.value_mode = value_mode; sa.noise_std = noise_std; sa.seed = s.seed;
+    stem_sparse_carve(sa, s.ws + s.L.sidx);
+    sa.Wk = s.ws + s.L.wk + e.off; sa.Kp = e.Kp; sa.bias = data[s_b0];
+    sa.Hc = Hc; sa.Wc = Wc; sa.Ho = blocks[0].H; sa.Wo = blocks[0].W;
+    sa.sc = t.sc; sa.sh = t.sh; sa.sl = data[s_a0];
+    return sa;
+}
+
+int DenseNetPlan::link(const Step& s, const BnSlots& bn, int nblk, int part_ld, int c_new0, int n_new, double* bstat, long count,
+                       const long long* isum, long isum_stride) const {
+    if (!s.train) return 0;
+    BnLinkArgs a{};
+    a.isum = isum; a.isum_stride = isum_stride;                  // window sums in fixed-point accumulators (a link-free producer) instead of partial rows
+    a.part = s.part; a.nblk = nblk; a.part_ld = part_ld; a.c_new0 = c_new0; a.n_new = n_new; a.bstat = bstat;
+    a.count = count; a.C = bn.C; a.gamma = data[bn.w]; a.beta = data[bn.b];
+    a.running_mean = data[bn.rm]; a.running_var = data[bn.rv];
+    const Tab t = tab(s.ws, s.L, bn); a.sc = t.sc; a.sh = t.sh; a.train = 1; a.eps = kEps; a.momentum = kMom;
+    return bn_link(a, s.st);
+}
+
+// the table of a BatchNorm over block bi's concat buffer by the link kernel (window sums from the partial rows or from the block's accumulators)
+int DenseNetPlan::link_fresh(const Step& s, const BnSlots& bn, int bi, const FreshStats& fr) const {
+    const BlockGeom& bg = blocks[bi];
+    const long long* isum = fr.isum ? reinterpret_cast<const long long*>(s.ws + s.L.isumD[bi]) + 2 * fr.c0 : nullptr;      // [ld][2], indexed by channel
+    return link(s, bn, fr.nblk, fr.ld, fr.c0, fr.n, reinterpret_cast<double*>(s.ws + s.L.bstatD[bi]), (long)s.n * bg.H * bg.W, isum, 2L * bg.ld);
+}
+
+LfLink DenseNetPlan::lf_link(const Step& s, const BnSlots& bn, const long long* isum, long rep_stride, int c_new0, int n_new, double* bstat, long count) const {
+    LfLink k{};
+    k.isum = isum; k.rep_stride = rep_stride; k.c_new0 = c_new0; k.n_new = n_new; k.bstat = bstat; k.inv_count = 1.0 / (double)count; k.count = count;
+    k.gamma = data[bn.w]; k.beta = data[bn.b]; k.running_mean = data[bn.rm]; k.running_var = data[bn.rv];
+    const Tab t = tab(s.ws, s.L, bn); k.sc_out = t.sc; k.sh_out = t.sh; k.eps = kEps; k.momentum = kMom;
+    return k;
+}
+
 int DenseNetPlan::forward(int n, const int32_t* coords, const float* values, long nnz, int log_pixels, float noise_std,
                           float* out, long out_ld, char* ws, long ws_bytes, int train, uint64_t seed, hipStream_t st) {
     if (!bound) return -11;
@@ -360,43 +441,37 @@ int DenseNetPlan::forward(int n, const int32_t* coords, const float* values, lon
     if (ws_bytes < L.total) { fprintf(stderr, "tcvn: densenet workspace too small (%ld < %ld)\n", ws_bytes, L.total); return -12; }
     int rc;
     if ((rc = upload_descs(ws, L, st))) return rc;
-    const int mode = cfg.mode, g = cfg.growth, mid = cfg.bn_size * cfg.growth;
-    float* tabs = reinterpret_cast<float*>(ws + L.tabs);
-    auto tab = [&](const BnSlots& s) { Tab t; t.sc = tabs + tab_off(s); t.sh = t.sc + round_up(s.C, 8); return t; };
-    double* part = reinterpret_cast<double*>(ws + L.part);
-    const PackDesc* d_pack = reinterpret_cast<const PackDesc*>(d_desc);
-    const BnEvalDesc* d_bn = reinterpret_cast<const BnEvalDesc*>(d_desc + n_pack * sizeof(PackDesc));
-
     // weights -> kernel layout (fp32 -> T); eval: all BN tables from the running statistics in one launch
-    if ((rc = pack_weights(d_pack, n_pack, mode, st))) return rc;
-    if (!train && (rc = bn_eval_tables(d_bn, n_bneval, kEps, st))) return rc;
-
-    auto link = [&](const BnSlots& s, const double* prt, int nblk, int part_ld, int c_new0, int n_new, double* bstat,
-                    long count, const long long* isum = nullptr, long isum_stride = 0) -> int {
-        if (!train) return 0;
-        BnLinkArgs a{};
-        a.isum = isum; a.isum_stride = isum_stride;                  // window sums in fixed-point accumulators (a link-free producer) instead of partial rows
-        a.part = prt; a.nblk = nblk; a.part_ld = part_ld; a.c_new0 = c_new0; a.n_new = n_new; a.bstat = bstat;
-        a.count = count; a.C = s.C; a.gamma = data[s.w]; a.beta = data[s.b];
-        a.running_mean = data[s.rm]; a.running_var = data[s.rv];
-        Tab t = tab(s); a.sc = t.sc; a.sh = t.sh; a.train = 1; a.eps = kEps; a.momentum = kMom;
-        return bn_link(a, st);
-    };
-
-    // ---- stem ----
+    if ((rc = pack_weights(reinterpret_cast<const PackDesc*>(d_desc), n_pack, cfg.mode, st))) return rc;
+    if (!train && (rc = bn_eval_tables(reinterpret_cast<const BnEvalDesc*>(d_desc + n_pack * sizeof(PackDesc)), n_bneval, kEps, st))) return rc;
     // Round 5, link-free BatchNorm statistics (bn_lf.h): the fused 1x1 kernels and the 3x3 pair kernel ADD their per-workgroup sums to
     // fixed-point accumulators and derive their input BatchNorm's table in their own prologue -- no k_bn_link launch between them (120 of
     // the 132 per step and embedder).  TCVN_NO_LF (validation build): the link kernels of rounds 1-4.
     static const bool no_lf = TCVN_KNOB_SET("TCVN_NO_LF");
-    const bool lf_on = train && !no_lf && mode == MODE_BF16 && L.isum_bytes > 0;
+    const bool lf_on = train && !no_lf && cfg.mode == MODE_BF16 && L.isum_bytes > 0;
     TCVN_CHECK(hipMemsetAsync(ws + L.zeros, 0, 1024 + (lf_on ? L.isum_bytes : 0), st));
-    auto lf_of = [&](const BnSlots& s, const long long* isum, long rep_stride, int c_new0, int n_new, double* bstat, long count) {
-        LfLink k{};
-        k.isum = isum; k.rep_stride = rep_stride; k.c_new0 = c_new0; k.n_new = n_new; k.bstat = bstat; k.inv_count = 1.0 / (double)count; k.count = count;
-        k.gamma = data[s.w]; k.beta = data[s.b]; k.running_mean = data[s.rm]; k.running_var = data[s.rv];
-        Tab t = tab(s); k.sc_out = t.sc; k.sh_out = t.sh; k.eps = kEps; k.momentum = kMom;
-        return k;
-    };
+    const Step s{ws, L, st, n, train != 0, seed, reinterpret_cast<double*>(ws + L.part), lf_on, false, 0, false};
+    FreshStats fr{};                  // statistics of the newest channels of the block being built
+    if ((rc = fwd_stem(s, coords, values, nnz, log_pixels, noise_std, fr))) return rc;
+    for (int bi = 0; bi < (int)blocks.size(); ++bi) {
+        for (int l = 0; l < blocks[bi].L; ++l)
+            if ((rc = fwd_layer(s, bi, l, fr))) return rc;
+        if ((rc = fwd_transition(s, bi, fr))) return rc;
+    }
+    if ((rc = fwd_output(s, out, out_ld))) return rc;
+    last_seed = seed; last_n = n; last_coords = coords; last_nnz = nnz;
+    return 0;
+}
+
+// ---- stem: conv0 - BN0 - PReLU0 - AvgPool(3, 2) -> the first channels of block 1 ----
+int DenseNetPlan::fwd_stem(const Step& s, const int32_t* coords, const float* values, long nnz, int log_pixels, float noise_std, FreshStats& fr) {
+    const Layout& L = s.L;
+    const BlockGeom& b0 = blocks[0];
+    const int mode = cfg.mode, n = s.n;
+    const long M0 = (long)n * Hc * Wc;
+    const float noise = s.train ? noise_std : 0.f;
+    double* bstat0 = reinterpret_cast<double*>(s.ws + L.bstat0);
+    int rc;
     // Sparse-aware stem (bf16, 3 -> 64 channels, the hit list fits the index): conv0 + BN0 + PReLU0 + AvgPool straight from the COO
     // list, neither the dense map nor the conv0 output is materialised (stem_sparse.hip).  Otherwise: scatter + dense kernels.
     // Measured on MI355X (256 prong maps / 32 event maps, round 3): inference -- index + pooled pass 0.60 / 0.27 ms against 0.97 / 0.12 ms
@@ -406,39 +481,6 @@ int DenseNetPlan::forward(int n, const int32_t* coords, const float* values, lon
     // can force either (TCVN_DENSE_STEM / TCVN_SPARSE_STEM_TRAIN) for the parity tests of all four sparse passes.
     static const bool dense_stem_knob = TCVN_KNOB_SET("TCVN_DENSE_STEM");
     static const bool sparse_train_knob = TCVN_KNOB_SET("TCVN_SPARSE_STEM_TRAIN");
-    const bool sparse_stem = !dense_stem_knob && (!train || sparse_train_knob) && L.sidx >= 0 &&
-                             stem_sparse_ok(mode, cfg.in_ch, cfg.init_ch, cfg.H, cfg.W, log_pixels, nnz, n, blocks[0].ld);
-    last_sparse_stem = sparse_stem;
-    last_stem_act = false;
-    last_fused_ya = false;
-    last_values = values; last_value_mode = log_pixels; last_noise = train ? noise_std : 0.f;
-    int init_nblk = 0, init_ld = cfg.init_ch;
-    if (sparse_stem) {
-        const BlockGeom& b0 = blocks[0];
-        const WkEntry& e = wk_find(s_w0, 0);
-        StemSparseArgs sa{};
-        sa.coords = coords; sa.values = values; sa.nnz = nnz; sa.n_img = n; sa.H = cfg.H; sa.W = cfg.W; sa.Cpix = cfg.in_ch;
-        sa.value_mode = log_pixels; sa.noise_std = train ? noise_std : 0.f; sa.seed = seed;
-        stem_sparse_carve(sa, ws + L.sidx);
-        sa.Wk = ws + L.wk + e.off; sa.Kp = e.Kp; sa.bias = data[s_b0];
-        sa.Hc = Hc; sa.Wc = Wc; sa.Ho = b0.H; sa.Wo = b0.W;
-        if ((rc = stem_sparse_index(sa, st))) return rc;
-        if (train) {
-            sa.part = part;
-            if ((rc = stem_sparse_stats(sa, st))) return rc;
-            if ((rc = link(n0, part, stem_sparse_stats_grid(sa), cfg.init_ch, 0, cfg.init_ch, reinterpret_cast<double*>(ws + L.bstat0), (long)n * Hc * Wc))) return rc;
-        }
-        Tab t = tab(n0);
-        sa.sc = t.sc; sa.sh = t.sh; sa.sl = data[s_a0]; sa.Out = ws + L.D[0]; sa.ldo = b0.ld; sa.part = train ? part : nullptr;
-        if ((rc = stem_sparse_pool(sa, st))) return rc;
-        init_nblk = stem_sparse_pool_grid(sa);
-    } else {
-    TCVN_CHECK(hipMemsetAsync(ws + L.img, 0, (size_t)n * cfg.H * cfg.W * cfg.in_ch * esz, st));
-    {
-        ScatterArgs a{mode, coords, values, nnz, n, ws + L.img, cfg.H, cfg.W, cfg.in_ch, log_pixels, train ? noise_std : 0.f, seed};
-        if ((rc = scatter_pixels(a, st))) return rc;
-    }
-    const long M0 = (long)n * Hc * Wc;
     // Round 4: the maps are mostly empty, so most conv0 outputs are exactly bf16(bias) (a sum of zeros plus the bias).  stem_mark builds a bitmap
     // of the output positions some hit reaches (~16 % of a prong map's 28 000 at 20-800 hits); the pooling BACKWARD kernel reads one shared row for
     // every other position and does not store their gradient rows (only the hit-list weight gradient reads that tensor).  Bit-identical results.
@@ -446,240 +488,210 @@ int DenseNetPlan::forward(int n, const int32_t* coords, const float* values, lon
     // (prong embedder 271 -> 345 us: its nine loads per pixel turn into a mix of L2 hits and isolated 128-B HBM lines, which DRAM serves far
     // below its streaming rate), the backward gained 10 %, the step did not move (19.65-19.76 against 19.74-19.86 ms).
     static const bool no_stem_skip = TCVN_KNOB_SET("TCVN_NO_STEM_SKIP") || TCVN_KNOB_SET("TCVN_POOL0_BWD_FLAT");   // (the flat backward kernel reads every row)
-    uint32_t* sact = nullptr;
-    const void* cline = ws + L.zeros + 512;                 // the zero page is 1 KB; DMA sources use its first 256 B
-    {
-        const WkEntry& e0 = wk_find(s_w0, 0);
-        ConvFwdArgs probe{};
-        probe.mode = mode; probe.amode = A_STEM; probe.M = (int)M0; probe.N = cfg.init_ch; probe.K = 49 * cfg.in_ch; probe.Kp = e0.Kp; probe.C = cfg.in_ch;
-        probe.H = Hc; probe.W = Wc; probe.Hin = cfg.H; probe.Win = cfg.W; probe.ldo = cfg.init_ch; probe.n_off = 0; probe.Out = ws + L.c0;
-        if (!no_stem_skip && train && L.sact >= 0 && stem_fwd_ok(probe) && (blocks[0].ld & 7) == 0 && coords != nullptr) {
-            sact = reinterpret_cast<uint32_t*>(ws + L.sact);
-            if ((rc = stem_mark(coords, nnz, n, cfg.H, cfg.W, Hc, Wc, sact, data[s_b0], const_cast<void*>(cline), st))) return rc;
+    stem_path = StemPath{};
+    stem_path.sparse = !dense_stem_knob && (!s.train || sparse_train_knob) && L.sidx >= 0 &&
+                       stem_sparse_ok(mode, cfg.in_ch, cfg.init_ch, cfg.H, cfg.W, log_pixels, nnz, n, b0.ld);
+    last_values = values; last_value_mode = log_pixels; last_noise = noise;
+    fr = FreshStats{0, b0.C0, 0, cfg.init_ch, false};
+    if (stem_path.sparse) {
+        StemSparseArgs sa = stem_sparse_args(s, coords, values, nnz, log_pixels, noise);
+        if ((rc = stem_sparse_index(sa, s.st))) return rc;
+        if (s.train) {
+            sa.part = s.part;
+            if ((rc = stem_sparse_stats(sa, s.st))) return rc;
+            if ((rc = link(s, n0, stem_sparse_stats_grid(sa), cfg.init_ch, 0, cfg.init_ch, bstat0, M0))) return rc;
         }
+        sa.Out = s.ws + L.D[0]; sa.ldo = b0.ld; sa.part = s.train ? s.part : nullptr;
+        if ((rc = stem_sparse_pool(sa, s.st))) return rc;
+        fr.nblk = stem_sparse_pool_grid(sa);
+        return 0;
     }
-    last_stem_act = sact != nullptr;
-    {
-        const WkEntry& e = wk_find(s_w0, 0);
-        ConvFwdArgs a{};
-        a.mode = mode; a.amode = A_STEM; a.A = ws + L.img; a.lda = cfg.in_ch; a.M = (int)M0; a.N = cfg.init_ch;
-        a.K = 49 * cfg.in_ch; a.Kp = e.Kp; a.C = cfg.in_ch; a.H = Hc; a.W = Wc; a.Hin = cfg.H; a.Win = cfg.W;
-        a.Wk = ws + L.wk + e.off; a.bias = data[s_b0]; a.Out = ws + L.c0; a.ldo = cfg.init_ch; a.n_off = 0;
-        a.part = train ? part : nullptr; a.nblk = conv_fwd_nblk(a);
-        if ((rc = conv_fwd(a, st))) return rc;
-        if ((rc = link(n0, part, a.nblk, cfg.init_ch, 0, cfg.init_ch, reinterpret_cast<double*>(ws + L.bstat0), M0))) return rc;
-    }
-    {
-        const BlockGeom& b0 = blocks[0];
-        Tab t = tab(n0);
-        Pool0Args a{mode, ws + L.c0, n, Hc, Wc, cfg.init_ch, t.sc, t.sh, data[s_a0], ws + L.D[0], b0.ld, b0.H, b0.W,
-                    train ? part : nullptr, pool0_grid(n, b0.H, b0.W)};
-        if ((rc = pool0_fwd(a, st))) return rc;
-    }
-    init_nblk = pool0_grid(n, blocks[0].H, blocks[0].W);
-    }
-    // statistics of the block's initial channels are described by (init_nblk, init_ld)
-
-    for (size_t bi = 0; bi < blocks.size(); ++bi) {
-        const BlockGeom& bg = blocks[bi];
-        const long M = (long)n * bg.H * bg.W;
-        char* D = ws + L.D[bi];
-        double* bstatD = reinterpret_cast<double*>(ws + L.bstatD[bi]);
-        int new_c0 = 0, new_n = bg.C0, new_nblk = init_nblk, new_ld = init_ld;   // channels whose stats are fresh in `part`
-        long long* isumD = lf_on ? reinterpret_cast<long long*>(ws + L.isumD[bi]) : nullptr;      // [ld][2], indexed by channel
-        bool new_isum = false;                                                    // ... or in isumD (added there by a link-free producer)
-        for (int l = 0; l < bg.L; ++l) {
-            const LayerSlots& ls = bg.layers[l];
-            const bool fast1 = L.XA[bi][l] >= 0;
-            const int cin8 = (int)round_up(ls.cin, 8);
-            // Eval mode (running statistics: no batch reduction between the 1x1 output and its BatchNorm): the 1x1 GEMM's epilogue
-            // applies norm2 + PReLU and writes the activated map the 3x3 tile kernel stages -- the raw bottleneck output Y and the
-            // k_act_bf16 pass over it (512 B per pixel and layer, one launch) do not exist.  Train mode needs Y for the statistics.
-            bool fuse_ya = false;
-            if (mode == MODE_BF16 && !train && fast1) {
-                ConvFwdArgs c3{};
-                c3.mode = mode; c3.amode = A_3X3; c3.A = ws + L.Y[bi][l]; c3.lda = mid; c3.M = (int)M; c3.N = g; c3.K = 9 * mid;
-                c3.Kp = wk_find(ls.w2, 0).Kp; c3.C = mid; c3.H = bg.H; c3.W = bg.W; c3.Wk = ws + L.wk + wk_find(ls.w2, 0).off;
-                c3.Wfrag = wk_frag(ws, L, ls.w2, 0); c3.Aact = ws + L.YA[bi][l]; c3.zeros = ws + L.zeros;
-                fuse_ya = conv3x3_tile_ok(c3);
-            }
-            if (fuse_ya) last_fused_ya = true;
-            if (xa_skipped.size() != blocks.size()) xa_skipped.assign(blocks.size(), std::vector<char>());
-            if ((int)xa_skipped[bi].size() != bg.L) xa_skipped[bi].assign(bg.L, 0);
-            xa_skipped[bi][l] = 0;
-            // Train mode (round 4): the 1x1 runs on the RAW concat buffer, norm1 + PReLU1 applied to the landed LDS tiles (fwd1x1_fused.hip);
-            // the fused 1x1 backward kernel rebuilds that activation from x, so the activated copy XA is neither written nor read.
-            static const bool no_fuse1 = TCVN_KNOB_SET("TCVN_NO_FWD1_FUSE") || TCVN_KNOB_SET("TCVN_NO_BWD1_FUSE");
-            bool lf2 = false;                  // the 3x3 pair kernel derives norm2's table itself (no link launch in front of it)
-            bool n1_linked = false;
-            auto link_n1 = [&]() -> int {      // norm1's table by the link kernel (window sums from the partial rows or from isumD)
-                n1_linked = true;
-                return link(ls.n1, part, new_nblk, new_ld, new_c0, new_n, bstatD, M, new_isum ? isumD + 2 * new_c0 : nullptr, 2L * bg.ld);
-            };
-            if ((train || fuse_ya) && fast1 && !no_fuse1 && mid == 128 && mode == MODE_BF16) {
-                const WkEntry& e = wk_find(ls.w1, 0, 1);
-                Tab t1 = tab(ls.n1);
-                Fwd1x1Args fa{};
-                fa.Xin = D; fa.ldx = bg.ld; fa.cin = ls.cin; fa.sc = t1.sc; fa.sh = t1.sh; fa.sl = data[ls.a1]; fa.M = M;
-                fa.Wfrag = ws + L.wk + e.off; fa.Kp = e.Kp; fa.bias = data[ls.b1]; fa.Out = ws + L.Y[bi][l]; fa.zeros = ws + L.zeros;
-                fa.part = train ? part : nullptr; fa.nblk = fwd1x1_fused_nblk(fa);
-                if (!train) {                  // eval: norm2 + PReLU2 in the epilogue, the activated map is the only output (as k_gemm_nt_bf16<.., XF = 2>)
-                    Tab t2 = tab(ls.n2);
-                    fa.osc = t2.sc; fa.osh = t2.sh; fa.osl = data[ls.a2]; fa.Out = ws + L.YA[bi][l];
-                }
-                // train mode: the activated copy XA is only dropped when the backward's fused 1x1 kernel will accept this layer (it rebuilds
-                // the activation from x); otherwise the step would die in backward after the forward has already run
-                if (fwd1x1_fused_ok(fa) && (!train || bwd1x1_fusable((int)bi, l, M, ws, L))) {
-                    long long* isumY = lf_on ? reinterpret_cast<long long*>(ws + L.isumY[bi][l]) : nullptr;
-                    // link-free consumer of norm1: the fresh window was added to isumD by the previous layer's 3x3 kernel (the block's first
-                    // layer follows a transition / the stem, whose statistics still leave as partial rows: link kernel)
-                    if (lf_on && new_isum) fa.lf = lf_of(ls.n1, isumD + 2 * new_c0, 2L * bg.ld, new_c0, new_n, bstatD, M);
-                    else if ((rc = link_n1())) return rc;
-                    fa.isum_out = isumY; fa.isum_stride = 2L * mid;       // link-free producer of norm2's statistics
-                    if ((rc = fwd1x1_fused(fa, st))) return rc;
-                    // norm2's consumer: the 3x3 pair kernel with the activation in LDS derives the table itself; anything else takes the link kernel
-                    if (isumY != nullptr) {
-                        ConvFwdArgs c3{};
-                        c3.mode = mode; c3.amode = A_3X3; c3.A = ws + L.Y[bi][l]; c3.lda = mid; c3.M = (int)M; c3.N = g; c3.K = 9 * mid;
-                        c3.Kp = wk_find(ls.w2, 0).Kp; c3.C = mid; c3.H = bg.H; c3.W = bg.W; c3.Wk = ws + L.wk + wk_find(ls.w2, 0).off;
-                        c3.Wfrag = wk_frag(ws, L, ls.w2, 0); c3.Aact = ws + L.Y[bi][l]; c3.zeros = ws + L.zeros;
-                        Tab t2 = tab(ls.n2);
-                        c3.sc = t2.sc; c3.sh = t2.sh; c3.sl = data[ls.a2];
-                        lf2 = conv3x3_act_fusable(c3) && conv3x3_fwd_pair(c3);
-                    }
-                    if (!lf2 && (rc = link(ls.n2, part, fa.nblk, mid, 0, mid, reinterpret_cast<double*>(ws + L.bstatY[bi][l]), M, isumY, 2L * mid))) return rc;
-                    xa_skipped[bi][l] = 1;
-                    goto conv3;
-                }
-            }
-            if (!n1_linked && (rc = link_n1())) return rc;
-            if (fast1) {     // activated copy of the 1x1 input: operand of the bf16 GEMMs (forward, weight gradient)
-                Tab t1 = tab(ls.n1);
-                ActArgs act{D, bg.ld, M, ls.cin, t1.sc, t1.sh, data[ls.a1], ws + L.XA[bi][l], cin8};
-                if ((rc = act_bf16(act, st))) return rc;
-            }
-            if (fast1) {   // bottleneck 1x1 on the NT GEMM: XA x W1^T -> Y
-                const WkEntry& e = wk_find(ls.w1, 0, 1);
-                GemmNtArgs a{};
-                a.epi = EPI_FWD; a.A = ws + L.XA[bi][l]; a.lda = cin8; a.K = cin8; a.M = M; a.N = mid;
-                a.Wfrag = ws + L.wk + e.off; a.Kp = e.Kp; a.zeros = ws + L.zeros; a.bias = data[ls.b1];
-                a.Out = ws + L.Y[bi][l]; a.ldo = mid; a.n_off = 0; a.part = train ? part : nullptr; a.nblk = gemm_nt_nblk(a);
-                if (fuse_ya) {                 // eval: norm2 + PReLU in the GEMM epilogue, the activated map is the only output
-                    Tab t2 = tab(ls.n2);
-                    a.osc = t2.sc; a.osh = t2.sh; a.osl = data[ls.a2]; a.Out = ws + L.YA[bi][l];
-                }
-                if ((rc = gemm_nt_bf16(a, "k_gemm_nt_bf16<fwd1x1>", st))) return rc;
-                if ((rc = link(ls.n2, part, a.nblk, mid, 0, mid, reinterpret_cast<double*>(ws + L.bstatY[bi][l]), M))) return rc;
-            } else {   // bottleneck 1x1: D[:, 0:cin] -> Y
-                const WkEntry& e = wk_find(ls.w1, 0);
-                Tab t = tab(ls.n1);
-                ConvFwdArgs a{};
-                a.mode = mode; a.amode = A_1X1; a.A = D; a.lda = bg.ld; a.M = (int)M; a.N = mid; a.K = ls.cin; a.Kp = e.Kp;
-                a.C = ls.cin; a.H = bg.H; a.W = bg.W; a.sc = t.sc; a.sh = t.sh; a.sl = data[ls.a1];
-                a.Wk = ws + L.wk + e.off; a.bias = data[ls.b1]; a.Out = ws + L.Y[bi][l]; a.ldo = mid; a.n_off = 0;
-                a.part = train ? part : nullptr; a.nblk = conv_fwd_nblk(a);
-                if ((rc = conv_fwd(a, st))) return rc;
-                if ((rc = link(ls.n2, part, a.nblk, mid, 0, mid, reinterpret_cast<double*>(ws + L.bstatY[bi][l]), M))) return rc;
-            }
-        conv3:
-            {   // 3x3: Y -> D[:, cin:cin+g]
-                const WkEntry& e = wk_find(ls.w2, 0);
-                Tab t = tab(ls.n2);
-                ConvFwdArgs a{};
-                a.mode = mode; a.amode = A_3X3; a.A = ws + L.Y[bi][l]; a.lda = mid; a.M = (int)M; a.N = g; a.K = 9 * mid;
-                a.Kp = e.Kp; a.C = mid; a.H = bg.H; a.W = bg.W; a.sc = t.sc; a.sh = t.sh; a.sl = data[ls.a2];
-                a.Wk = ws + L.wk + e.off; a.bias = data[ls.b2]; a.Out = D; a.ldo = bg.ld; a.n_off = ls.cin;
-                a.Wfrag = wk_frag(ws, L, ls.w2, 0);
-                if (act_fused.size() != blocks.size()) act_fused.assign(blocks.size(), std::vector<char>());
-                if ((int)act_fused[bi].size() != bg.L) act_fused[bi].assign(bg.L, 0);
-                act_fused[bi][l] = 0;
-                if (mode == MODE_BF16) {
-                    a.zeros = ws + L.zeros;
-                    // Round 4: norm2 + PReLU are applied INSIDE the 3x3 kernel (and inside the layer's weight-gradient kernel): the raw
-                    // bottleneck map is staged by LDS-DMA and the wave that fetched a row activates it in LDS once -- the activated copy YA
-                    // (256 B written + 256 B read per pixel and layer) and the k_act_bf16 launch over Y do not exist.  Bit-identical images.
-                    a.Aact = ws + L.Y[bi][l];
-                    if (!fuse_ya && conv3x3_act_fusable(a)) { a.act_fused = 1; act_fused[bi][l] = 1; }
-                    else {                     // materialise prelu(bn(Y)) once; the tile kernel stages it by LDS-DMA
-                        if (!fuse_ya) {
-                            ActArgs act{ws + L.Y[bi][l], mid, M, mid, t.sc, t.sh, data[ls.a2], ws + L.YA[bi][l], mid};
-                            if ((rc = act_bf16(act, st))) return rc;
-                        }
-                        a.Aact = ws + L.YA[bi][l];
-                    }
-                }
-                a.part = train ? part : nullptr;
-                a.drop_p = train ? cfg.dropout : 0.f; a.seed = seed; a.stream_id = (uint32_t)(bi * 64 + l + 1);
-                a.nblk = conv_fwd_nblk(a);
-                if (lf2) {                     // (decided above on the same arguments: pair kernel + in-LDS activation)
-                    if (!a.act_fused) { fprintf(stderr, "tcvn: link-free norm2 without the in-LDS activation\n"); return -17; }
-                    a.lf = lf_of(ls.n2, reinterpret_cast<long long*>(ws + L.isumY[bi][l]), 2L * mid, 0, mid, reinterpret_cast<double*>(ws + L.bstatY[bi][l]), M);
-                }
-                const bool out_isum = lf_on && mode == MODE_BF16 && conv3x3_fwd_pair(a) && g <= 32;      // link-free producer of the new channels' statistics
-                if (out_isum) { a.isum_out = isumD + 2 * ls.cin; a.isum_stride = 2L * bg.ld; }
-                if (train && !L.KM[bi].empty()) {           // the pair kernel leaves the keep flags it drew for the backward kernels
-                    a.keep_out = reinterpret_cast<uint32_t*>(ws + L.KM[bi][l]);
-                    if (keep_valid.size() != blocks.size()) keep_valid.assign(blocks.size(), std::vector<char>());
-                    if ((int)keep_valid[bi].size() != bg.L) keep_valid[bi].assign(bg.L, 0);
-                    keep_valid[bi][l] = conv3x3_fwd_writes_keep(a) ? 1 : 0;
-                }
-                if ((rc = conv_fwd(a, st))) return rc;
-                new_c0 = ls.cin; new_n = g; new_nblk = a.nblk; new_ld = g; new_isum = out_isum;
-            }
-        }
-        if (bg.has_trans) {
-            const BlockGeom& nb = blocks[bi + 1];
-            if ((rc = link(bg.tn, part, new_nblk, new_ld, new_c0, new_n, bstatD, M, new_isum ? isumD + 2 * new_c0 : nullptr, 2L * bg.ld))) return rc;
-            const WkEntry& e = wk_find(bg.tw, 0);
-            Tab t = tab(bg.tn);
-            const long Mn = (long)n * nb.H * nb.W;
-            const bool fastt = L.XP[bi] >= 0 && mode == MODE_BF16;
-            const bool mat32 = L.XP[bi] >= 0 && mode == MODE_F32;
-            if (fastt || mat32) {
-                ActPoolArgs ap{D, bg.ld, n, bg.H, bg.W, bg.Ctot, t.sc, t.sh, data[bg.ta], ws + L.XP[bi], bg.ldp};
-                if ((rc = fastt ? act_pool_bf16(ap, st) : act_pool_f32(ap, st))) return rc;
-            }
-            if (fastt) {
-                const WkEntry& ef = wk_find(bg.tw, 0, 1);
-                GemmNtArgs ga{};
-                ga.epi = EPI_FWD; ga.A = ws + L.XP[bi]; ga.lda = bg.ldp; ga.K = bg.ldp; ga.M = Mn; ga.N = bg.Ctot / 2;
-                ga.Wfrag = ws + L.wk + ef.off; ga.Kp = ef.Kp; ga.zeros = ws + L.zeros; ga.bias = data[bg.tb];
-                ga.Out = ws + L.D[bi + 1]; ga.ldo = nb.ld; ga.n_off = 0; ga.part = train ? part : nullptr; ga.nblk = gemm_nt_nblk(ga);
-                if ((rc = gemm_nt_bf16(ga, "k_gemm_nt_bf16<fwdtrans>", st))) return rc;
-                init_nblk = ga.nblk; init_ld = bg.Ctot / 2;
-                continue;
-            }
-            ConvFwdArgs a{};
-            a.mode = mode; a.amode = A_1X1_POOL; a.A = D; a.lda = bg.ld; a.M = (int)Mn; a.N = bg.Ctot / 2; a.K = bg.Ctot;
-            a.Kp = e.Kp; a.C = bg.Ctot; a.H = nb.H; a.W = nb.W; a.Hin = bg.H; a.Win = bg.W;
-            a.sc = t.sc; a.sh = t.sh; a.sl = data[bg.ta];
-            if (mat32) {            // pooled + activated operand materialised above: a plain 1x1 convolution over it (K padded to ldp: zero columns x zero weights)
-                a.amode = A_1X1; a.A = ws + L.XP[bi]; a.lda = bg.ldp; a.K = bg.ldp; a.C = bg.ldp; a.sc = nullptr; a.sh = nullptr; a.sl = nullptr;
-            }
-            a.Wk = ws + L.wk + e.off; a.bias = data[bg.tb]; a.Out = ws + L.D[bi + 1]; a.ldo = nb.ld; a.n_off = 0;
-            a.part = train ? part : nullptr; a.nblk = conv_fwd_nblk(a);
-            if ((rc = conv_fwd(a, st))) return rc;
-            init_nblk = a.nblk; init_ld = bg.Ctot / 2;
-        } else {
-            if ((rc = link(nf, part, new_nblk, new_ld, new_c0, new_n, bstatD, M, new_isum ? isumD + 2 * new_c0 : nullptr, 2L * bg.ld))) return rc;
-            Tab t = tab(nf);
-            HeadPoolArgs a{mode, D, bg.ld, n, bg.H * bg.W, Cf, t.sc, t.sh, data[s_af], reinterpret_cast<float*>(ws + L.F)};
-            if ((rc = head_pool_fwd(a, st))) return rc;
-        }
-    }
-    // ---- output block: Linear(no bias) - BatchNorm1d - PReLU - Dropout (layers/dense_net.py:157-162) ----
-    float* F = reinterpret_cast<float*>(ws + L.F);
-    float* Z = reinterpret_cast<float*>(ws + L.Z);
-    if ((rc = linear_fwd(F, Cf, data[s_wl], nullptr, Z, cfg.out_dim, n, cfg.out_dim, Cf, st))) return rc;
-    float* hs = reinterpret_cast<float*>(ws + L.head_stat);
-    RowsBnArgs r{};
-    r.X = Z; r.ldx = cfg.out_dim; r.R = n; r.C = cfg.out_dim; r.gamma = data[nl.w]; r.beta = data[nl.b]; r.slope = data[s_al];
-    r.running_mean = data[nl.rm]; r.running_var = data[nl.rv]; r.Y = out; r.ldy = out_ld;
-    r.save_mean = hs; r.save_rstd = hs + cfg.out_dim; r.train = train; r.eps = kEps; r.momentum = kMom;
-    r.drop_p = train ? cfg.dropout : 0.f; r.seed = seed; r.stream_id = 0x4000u;
-    if ((rc = rows_bn_fwd(r, st))) return rc;
-    last_seed = seed; last_n = n; last_coords = coords; last_nnz = nnz;
+    TCVN_CHECK(hipMemsetAsync(s.ws + L.img, 0, (size_t)n * cfg.H * cfg.W * cfg.in_ch * esz, s.st));
+    ScatterArgs sc{mode, coords, values, nnz, n, s.ws + L.img, cfg.H, cfg.W, cfg.in_ch, log_pixels, noise, s.seed};
+    if ((rc = scatter_pixels(sc, s.st))) return rc;
+    ConvFwdArgs a = conv0_args(s);
+    stem_path.act_skip = !no_stem_skip && s.train && L.sact >= 0 && stem_fwd_ok(a) && (b0.ld & 7) == 0 && coords != nullptr;
+    if (stem_path.act_skip &&      // (the shared row: the zero page is 1 KB; DMA sources use its first 256 B)
+        (rc = stem_mark(coords, nnz, n, cfg.H, cfg.W, Hc, Wc, reinterpret_cast<uint32_t*>(s.ws + L.sact), data[s_b0], s.ws + L.zeros + 512, s.st))) return rc;
+    a.part = s.train ? s.part : nullptr; a.nblk = conv_fwd_nblk(a);
+    if ((rc = conv_fwd(a, s.st))) return rc;
+    if ((rc = link(s, n0, a.nblk, cfg.init_ch, 0, cfg.init_ch, bstat0, M0))) return rc;
+    const Tab t = tab(s.ws, L, n0);
+    Pool0Args p{mode, s.ws + L.c0, n, Hc, Wc, cfg.init_ch, t.sc, t.sh, data[s_a0], s.ws + L.D[0], b0.ld, b0.H, b0.W,
+                s.train ? s.part : nullptr, pool0_grid(n, b0.H, b0.W)};
+    if ((rc = pool0_fwd(p, s.st))) return rc;
+    fr.nblk = p.nblk;
     return 0;
+}
+
+// The path of dense layer (bi, l) in this call, decided from the layer's 3x3 arguments `c3` (conv3_args) before its first launch.  When the
+// fused 1x1 kernel takes the layer (raw1x1), `f1` holds its arguments (lf / isum_out left to the caller).
+LayerPath DenseNetPlan::layer_path(const Step& s, int bi, int l, const ConvFwdArgs& c3, Fwd1x1Args& f1) const {
+    const Layout& L = s.L;
+    const BlockGeom& bg = blocks[bi];
+    const LayerSlots& ls = bg.layers[l];
+    const long M = (long)s.n * bg.H * bg.W;
+    const bool bf16 = cfg.mode == MODE_BF16, fast1 = L.XA[bi][l] >= 0;
+    const Conv3x3Fwd k3 = bf16 ? conv3x3_fwd_kernel(c3) : CONV3X3_FWD_NONE;
+    LayerPath p;
+    // Eval mode (running statistics: no batch reduction between the 1x1 output and its BatchNorm): the 1x1 GEMM's epilogue
+    // applies norm2 + PReLU and writes the activated map the 3x3 tile kernel stages -- the raw bottleneck output Y and the
+    // k_act_bf16 pass over it (512 B per pixel and layer, one launch) do not exist.  Train mode needs Y for the statistics.
+    p.fuse_ya = !s.train && fast1 && k3 != CONV3X3_FWD_NONE;
+    // Round 4: norm2 + PReLU are applied INSIDE the 3x3 kernel (and inside the layer's weight-gradient kernel): the raw
+    // bottleneck map is staged by LDS-DMA and the wave that fetched a row activates it in LDS once -- the activated copy YA
+    // (256 B written + 256 B read per pixel and layer) and the k_act_bf16 launch over Y do not exist.  Bit-identical images.
+    p.act_fused = bf16 && !p.fuse_ya && conv3x3_act_fusable(c3);
+    // Train mode (round 4): the 1x1 runs on the RAW concat buffer, norm1 + PReLU1 applied to the landed LDS tiles (fwd1x1_fused.hip);
+    // the fused 1x1 backward kernel rebuilds that activation from x, so the activated copy XA is neither written nor read.
+    static const bool no_fuse1 = TCVN_KNOB_SET("TCVN_NO_FWD1_FUSE") || TCVN_KNOB_SET("TCVN_NO_BWD1_FUSE");
+    if ((s.train || p.fuse_ya) && fast1 && !no_fuse1 && cfg.bn_size * cfg.growth == 128 && bf16) {
+        const WkEntry& e = wk_find(ls.w1, 0, 1);
+        const Tab t1 = tab(s.ws, L, ls.n1);
+        f1 = Fwd1x1Args{};
+        f1.Xin = s.ws + L.D[bi]; f1.ldx = bg.ld; f1.cin = ls.cin; f1.sc = t1.sc; f1.sh = t1.sh; f1.sl = data[ls.a1]; f1.M = M;
+        f1.Wfrag = s.ws + L.wk + e.off; f1.Kp = e.Kp; f1.bias = data[ls.b1]; f1.Out = s.ws + L.Y[bi][l]; f1.zeros = s.ws + L.zeros;
+        f1.part = s.train ? s.part : nullptr; f1.nblk = fwd1x1_fused_nblk(f1);
+        if (!s.train) {                // eval: norm2 + PReLU2 in the epilogue, the activated map is the only output (as k_gemm_nt_bf16<.., XF = 2>)
+            f1.osc = c3.sc; f1.osh = c3.sh; f1.osl = c3.sl; f1.Out = s.ws + L.YA[bi][l];
+        }
+        // train mode: the activated copy XA is only dropped when the backward's fused 1x1 kernel will accept this layer (it rebuilds
+        // the activation from x); otherwise the step would die in backward after the forward has already run
+        Bwd1x1Args b1;
+        p.raw1x1 = fwd1x1_fused_ok(f1) && (!s.train || bwd1x1_fill(bi, l, M, s.ws, L, b1));
+    }
+    const bool pair = k3 == CONV3X3_FWD_PAIR;            // the kernel that honours lf / isum_out and fills keep_out
+    // norm2's consumer: the 3x3 pair kernel with the activation in LDS derives the table itself; anything else takes the link kernel
+    p.lf2 = p.raw1x1 && s.lf_on && p.act_fused && pair;
+    p.out_isum = s.lf_on && pair && cfg.growth <= 32;    // link-free producer of the new channels' statistics
+    p.keep_stored = s.train && !L.KM[bi].empty() && pair;
+    return p;
+}
+
+// ---- one dense layer: BN1 - PReLU1 - 1x1 conv -> Y; BN2 - PReLU2 - 3x3 conv - dropout -> D[:, cin:cin+g] ----
+int DenseNetPlan::fwd_layer(const Step& s, int bi, int l, FreshStats& fr) {
+    const Layout& L = s.L;
+    const BlockGeom& bg = blocks[bi];
+    const LayerSlots& ls = bg.layers[l];
+    const long M = (long)s.n * bg.H * bg.W;
+    const int mid = cfg.bn_size * cfg.growth, g = cfg.growth;
+    char* D = s.ws + L.D[bi];
+    char* Y = s.ws + L.Y[bi][l];
+    double* bstatD = reinterpret_cast<double*>(s.ws + L.bstatD[bi]);
+    double* bstatY = reinterpret_cast<double*>(s.ws + L.bstatY[bi][l]);
+    long long* isumD = s.lf_on ? reinterpret_cast<long long*>(s.ws + L.isumD[bi]) : nullptr;      // [ld][2], indexed by channel
+    long long* isumY = s.lf_on ? reinterpret_cast<long long*>(s.ws + L.isumY[bi][l]) : nullptr;
+    int rc;
+    ConvFwdArgs a = conv3_args(s, bi, l);
+    Fwd1x1Args f1;
+    const LayerPath p = path[bi][l] = layer_path(s, bi, l, a, f1);
+    if (p.raw1x1) {
+        // link-free consumer of norm1: the fresh window was added to isumD by the previous layer's 3x3 kernel (the block's first
+        // layer follows a transition / the stem, whose statistics still leave as partial rows: link kernel)
+        if (s.lf_on && fr.isum) f1.lf = lf_link(s, ls.n1, isumD + 2 * fr.c0, 2L * bg.ld, fr.c0, fr.n, bstatD, M);
+        else if ((rc = link_fresh(s, ls.n1, bi, fr))) return rc;
+        f1.isum_out = isumY; f1.isum_stride = 2L * mid;       // link-free producer of norm2's statistics
+        if ((rc = fwd1x1_fused(f1, s.st))) return rc;
+        if (!p.lf2 && (rc = link(s, ls.n2, f1.nblk, mid, 0, mid, bstatY, M, isumY, 2L * mid))) return rc;
+    } else {
+        if ((rc = link_fresh(s, ls.n1, bi, fr))) return rc;
+        int nblk;
+        if (L.XA[bi][l] >= 0) {
+            // activated copy of the 1x1 input: operand of the bf16 GEMMs (forward, weight gradient); bottleneck 1x1 on the NT GEMM: XA x W1^T -> Y
+            const int cin8 = (int)round_up(ls.cin, 8);
+            const Tab t1 = tab(s.ws, L, ls.n1);
+            ActArgs act{D, bg.ld, M, ls.cin, t1.sc, t1.sh, data[ls.a1], s.ws + L.XA[bi][l], cin8};
+            if ((rc = act_bf16(act, s.st))) return rc;
+            const WkEntry& e = wk_find(ls.w1, 0, 1);
+            GemmNtArgs ga{};
+            ga.epi = EPI_FWD; ga.A = s.ws + L.XA[bi][l]; ga.lda = cin8; ga.K = cin8; ga.M = M; ga.N = mid;
+            ga.Wfrag = s.ws + L.wk + e.off; ga.Kp = e.Kp; ga.zeros = s.ws + L.zeros; ga.bias = data[ls.b1];
+            ga.Out = Y; ga.ldo = mid; ga.n_off = 0; ga.part = s.train ? s.part : nullptr; ga.nblk = gemm_nt_nblk(ga);
+            if (p.fuse_ya) {               // eval: norm2 + PReLU in the GEMM epilogue, the activated map is the only output
+                ga.osc = a.sc; ga.osh = a.sh; ga.osl = a.sl; ga.Out = s.ws + L.YA[bi][l];
+            }
+            if ((rc = gemm_nt_bf16(ga, "k_gemm_nt_bf16<fwd1x1>", s.st))) return rc;
+            nblk = ga.nblk;
+        } else {
+            ConvFwdArgs c1 = conv1_args(s, bi, l);
+            c1.part = s.train ? s.part : nullptr; c1.nblk = conv_fwd_nblk(c1);
+            if ((rc = conv_fwd(c1, s.st))) return rc;
+            nblk = c1.nblk;
+        }
+        if ((rc = link(s, ls.n2, nblk, mid, 0, mid, bstatY, M))) return rc;
+    }
+    if (p.act_fused) a.act_fused = 1;
+    else if (cfg.mode == MODE_BF16) {      // materialise prelu(bn(Y)) once (unless the 1x1 epilogue did); the tile kernel stages it by LDS-DMA
+        if (!p.fuse_ya) {
+            ActArgs act{Y, mid, M, mid, a.sc, a.sh, a.sl, s.ws + L.YA[bi][l], mid};
+            if ((rc = act_bf16(act, s.st))) return rc;
+        }
+        a.Aact = s.ws + L.YA[bi][l];
+    }
+    a.part = s.train ? s.part : nullptr;
+    a.drop_p = s.train ? cfg.dropout : 0.f; a.seed = s.seed; a.stream_id = (uint32_t)(bi * 64 + l + 1);
+    a.nblk = conv_fwd_nblk(a);
+    if (p.lf2) {
+        if (!a.act_fused) { fprintf(stderr, "tcvn: link-free norm2 without the in-LDS activation\n"); return -17; }
+        a.lf = lf_link(s, ls.n2, isumY, 2L * mid, 0, mid, bstatY, M);
+    }
+    if (p.out_isum) { a.isum_out = isumD + 2 * ls.cin; a.isum_stride = 2L * bg.ld; }
+    if (s.train && !L.KM[bi].empty()) a.keep_out = reinterpret_cast<uint32_t*>(s.ws + L.KM[bi][l]);      // the pair kernel leaves the keep flags it drew for the backward kernels
+    if ((rc = conv_fwd(a, s.st))) return rc;
+    fr = FreshStats{ls.cin, g, a.nblk, g, p.out_isum};
+    return 0;
+}
+
+// ---- transition: BN - PReLU - 1x1 conv - AvgPool(2) (pool commuted in front of the conv) -> the first channels of block bi + 1;
+//      last block: final_norm - PReLU - global average -> F ----
+int DenseNetPlan::fwd_transition(const Step& s, int bi, FreshStats& fr) {
+    const Layout& L = s.L;
+    const BlockGeom& bg = blocks[bi];
+    char* D = s.ws + L.D[bi];
+    int rc;
+    if ((rc = link_fresh(s, bg.has_trans ? bg.tn : nf, bi, fr))) return rc;
+    if (!bg.has_trans) {
+        const Tab t = tab(s.ws, L, nf);
+        HeadPoolArgs a{cfg.mode, D, bg.ld, s.n, bg.H * bg.W, Cf, t.sc, t.sh, data[s_af], reinterpret_cast<float*>(s.ws + L.F)};
+        return head_pool_fwd(a, s.st);
+    }
+    const BlockGeom& nb = blocks[bi + 1];
+    fr = FreshStats{0, nb.C0, 0, bg.Ctot / 2, false};
+    if (L.XP[bi] >= 0) {
+        const Tab t = tab(s.ws, L, bg.tn);
+        ActPoolArgs ap{D, bg.ld, s.n, bg.H, bg.W, bg.Ctot, t.sc, t.sh, data[bg.ta], s.ws + L.XP[bi], bg.ldp};
+        if ((rc = cfg.mode == MODE_BF16 ? act_pool_bf16(ap, s.st) : act_pool_f32(ap, s.st))) return rc;
+    }
+    if (L.XP[bi] >= 0 && cfg.mode == MODE_BF16) {
+        const WkEntry& ef = wk_find(bg.tw, 0, 1);
+        GemmNtArgs ga{};
+        ga.epi = EPI_FWD; ga.A = s.ws + L.XP[bi]; ga.lda = bg.ldp; ga.K = bg.ldp; ga.M = (long)s.n * nb.H * nb.W; ga.N = bg.Ctot / 2;
+        ga.Wfrag = s.ws + L.wk + ef.off; ga.Kp = ef.Kp; ga.zeros = s.ws + L.zeros; ga.bias = data[bg.tb];
+        ga.Out = s.ws + L.D[bi + 1]; ga.ldo = nb.ld; ga.n_off = 0; ga.part = s.train ? s.part : nullptr; ga.nblk = gemm_nt_nblk(ga);
+        if ((rc = gemm_nt_bf16(ga, "k_gemm_nt_bf16<fwdtrans>", s.st))) return rc;
+        fr.nblk = ga.nblk;
+        return 0;
+    }
+    ConvFwdArgs a = trans_args(s, bi);
+    a.part = s.train ? s.part : nullptr; a.nblk = conv_fwd_nblk(a);
+    if ((rc = conv_fwd(a, s.st))) return rc;
+    fr.nblk = a.nblk;
+    return 0;
+}
+
+// ---- output block: Linear(no bias) - BatchNorm1d - PReLU - Dropout (layers/dense_net.py:157-162) ----
+int DenseNetPlan::fwd_output(const Step& s, float* out, long out_ld) const {
+    float* F = reinterpret_cast<float*>(s.ws + s.L.F);
+    float* Z = reinterpret_cast<float*>(s.ws + s.L.Z);
+    int rc;
+    if ((rc = linear_fwd(F, Cf, data[s_wl], nullptr, Z, cfg.out_dim, s.n, cfg.out_dim, Cf, s.st))) return rc;
+    float* hs = reinterpret_cast<float*>(s.ws + s.L.head_stat);
+    RowsBnArgs r{};
+    r.X = Z; r.ldx = cfg.out_dim; r.R = s.n; r.C = cfg.out_dim; r.gamma = data[nl.w]; r.beta = data[nl.b]; r.slope = data[s_al];
+    r.running_mean = data[nl.rm]; r.running_var = data[nl.rv]; r.Y = out; r.ldy = out_ld;
+    r.save_mean = hs; r.save_rstd = hs + cfg.out_dim; r.train = s.train; r.eps = kEps; r.momentum = kMom;
+    r.drop_p = s.train ? cfg.dropout : 0.f; r.seed = s.seed; r.stream_id = 0x4000u;
+    return rows_bn_fwd(r, s.st);
 }
 
 int DenseNetPlan::tap(int n, const char* name, long* off, int* tn, int* th, int* tw, int* tc, int* tld, int* tes) const {
@@ -687,7 +699,7 @@ int DenseNetPlan::tap(int n, const char* name, long* off, int* tn, int* th, int*
     layout(n, false, L);
     std::string s(name);
     *tn = n; *tes = esz;
-    if ((s == "img" || s == "conv0") && last_sparse_stem && n == last_n) return -1;      // the sparse stem materialises neither
+    if ((s == "img" || s == "conv0") && stem_path.sparse && n == last_n) return -1;      // the sparse stem materialises neither
     if (s == "img") { *off = L.img; *th = cfg.H; *tw = cfg.W; *tc = cfg.in_ch; *tld = cfg.in_ch; return 0; }
     if (s == "conv0") { *off = L.c0; *th = Hc; *tw = Wc; *tc = cfg.init_ch; *tld = cfg.init_ch; return 0; }
     if (s == "condense") { *off = L.F; *th = 1; *tw = 1; *tc = Cf; *tld = Cf; *tes = 4; return 0; }
@@ -716,7 +728,8 @@ int DenseNetPlan::tap(int n, const char* name, long* off, int* tn, int* th, int*
         if (sscanf(s.c_str(), "bottleneck%d.%d", &b, &l) != 2) return -1;
         b -= 1;
         if (b < 0 || b >= (int)blocks.size() || l < 0 || l >= blocks[b].L) return -1;
-        if (last_fused_ya && n == last_n) return -1;             // eval pass with the activation in the GEMM epilogue: no raw Y exists
+        for (const auto& pb : path)                              // eval pass with the activation in some GEMM epilogue: no raw Y exists
+            for (const LayerPath& p : pb) if (n == last_n && p.fuse_ya) return -1;
         *off = L.Y[b][l]; *th = blocks[b].H; *tw = blocks[b].W; *tc = cfg.bn_size * cfg.growth; *tld = *tc;
         return 0;
     }
@@ -727,8 +740,7 @@ int DenseNetPlan::tap(int n, const char* name, long* off, int* tn, int* th, int*
         if (b < 0 || b >= (int)blocks.size() || l < 0 || l >= blocks[b].L) return -1;
         const bool xa = s[0] == 'x';
         if ((xa && (L.XA[b].empty() || L.XA[b][l] < 0)) || (!xa && L.YA[b].empty())) return -1;
-        if (xa && n == last_n && b < (int)xa_skipped.size() && l < (int)xa_skipped[b].size() && xa_skipped[b][l]) return -1;                 // 1x1 ran on the raw buffer
-        if (!xa && n == last_n && b < (int)act_fused.size() && l < (int)act_fused[b].size() && act_fused[b][l]) return -1;   // activated in LDS only
+        if (n == last_n && (xa ? path[b][l].raw1x1 : path[b][l].act_fused)) return -1;      // the 1x1 ran on the raw buffer / the map was activated in LDS only
         *off = xa ? L.XA[b][l] : L.YA[b][l]; *th = blocks[b].H; *tw = blocks[b].W;
         *tc = xa ? blocks[b].layers[l].cin : cfg.bn_size * cfg.growth; *tld = xa ? (int)round_up(*tc, 8) : *tc;
         return 0;

@@ -4,11 +4,10 @@
 #include <vector>
 
 #include "../../include/tcvn_hip.h"
-#include "tcvn_common.h"
+#include "tcvn_ops.h"
 
 namespace tcvn {
 
-struct Bwd1x1Args;
 struct Slot { std::string name; long numel; int kind; };
 struct BnSlots { int w = -1, b = -1, rm = -1, rv = -1, nbt = -1, C = 0, id = -1; };
 struct LayerSlots { BnSlots n1, n2; int a1, w1, b1, a2, w2, b2, cin; };
@@ -42,6 +41,31 @@ struct Layout {
     std::vector<long> G, pqD;
 };
 
+// What the last forward did with one dense layer / with the stem.  DenseNetPlan::layer_path decides a layer's record before the layer's first
+// launch; the forward launches, the backward and tap() read it and never re-derive it.
+struct LayerPath {
+    bool fuse_ya = false;      // eval pass: the 1x1 GEMM's epilogue wrote the activated bottleneck map YA only (no raw Y exists)
+    bool raw1x1 = false;       // the fused 1x1 kernel ran on the raw concat buffer: no activated copy XA of the layer's input exists, backward must
+                               // take the fused 1x1 kernel (which rebuilds it from x)
+    bool act_fused = false;    // the 3x3 pair kernel ran on the RAW bottleneck map (activation applied in LDS, ConvFwdArgs::act_fused): no activated
+                               // copy YA exists, the weight gradient does the same
+    bool lf2 = false;          // the 3x3 pair kernel derived norm2's table itself (no link launch in front of it)
+    bool out_isum = false;     // the 3x3 pair kernel added the new channels' statistics to the block's fixed-point accumulators (link-free producer)
+    bool keep_stored = false;  // train mode: the 3x3 pair kernel stored the dropout keep words it drew (Layout::KM) for the backward kernels
+};
+struct StemPath {
+    bool sparse = false;       // the sparse-aware stem ran: no dense map / conv0 output exists (backward must match)
+    bool act_skip = false;     // the dense stem skipped the conv0-output rows no hit reaches (backward must use the same bitmap)
+};
+struct Tab { float* sc; float* sh; };      // (scale, shift) table of one BatchNorm layer
+// Channels [c0, c0 + n) of a concat buffer whose statistics no BatchNorm table covers yet: `nblk` partial rows of `ld` channels, or (isum) in the block's accumulators
+struct FreshStats { int c0, n, nblk, ld; bool isum; };
+struct Step {                  // values shared by the pieces of one forward or backward call
+    char* ws; const Layout& L; hipStream_t st; int n; bool train; uint64_t seed;
+    double* part; bool lf_on;  // statistics partials (Layout::part forward, Layout::bpart backward); forward: link-free BatchNorm statistics (bn_lf.h)
+    bool side_on; int seq; bool side_busy;      // backward: weight gradients on the side stream; parity of the EY buffer / tail half (reset by drain);
+};                                              // work on the side stream that `st` has not waited for
+
 bool backward_overlap_enabled();
 void set_backward_overlap(int on);
 
@@ -64,14 +88,8 @@ struct DenseNetPlan {
     uint64_t last_seed = 0; int last_n = 0;
     const int32_t* last_coords = nullptr; long last_nnz = 0;     // COO list of the last forward (sparse stem weight gradient)
     const float* last_values = nullptr; int last_value_mode = 0; float last_noise = 0.f;
-    std::vector<std::vector<char>> keep_valid;   // [block][layer]: the last train-mode forward stored the layer's dropout keep words
-    std::vector<std::vector<char>> act_fused;    // [block][layer]: the last forward ran the 3x3 pair kernel on the RAW bottleneck map (activation applied
-                                                 // in LDS, ConvFwdArgs::act_fused): no activated copy YA of that layer exists, the weight gradient does the same
-    std::vector<std::vector<char>> xa_skipped;   // [block][layer]: the last forward ran the fused 1x1 kernel on the raw concat buffer: no activated copy XA of that
-                                                 // layer's input exists, backward must take the fused 1x1 kernel (which rebuilds it from x)
-    bool last_fused_ya = false;          // the last forward was an eval pass whose 1x1 GEMMs wrote the activated bottleneck maps only (no raw Y)
-    bool last_stem_act = false;          // the last forward's dense stem skipped the conv0-output rows no hit reaches (backward must use the same bitmap)
-    bool last_sparse_stem = false;       // the last forward ran the sparse-aware stem: no dense map / conv0 output exists (backward must match)
+    std::vector<std::vector<LayerPath>> path;    // [block][layer] of the last forward
+    StemPath stem_path;
     bool sparse_stem_possible() const;   // plan-level condition (bf16, 3 -> 64 channels); the hit count decides per call
     // weight-gradient side stream of backward (3x3 and 1x1 weight gradients run beside the data-gradient chain)
     hipStream_t side_st = nullptr; hipEvent_t ev_fork_a = nullptr, ev_fork_b = nullptr, ev_done[2] = {nullptr, nullptr}, ev_drain = nullptr;
@@ -95,10 +113,32 @@ struct DenseNetPlan {
     int forward(int n, const int32_t* coords, const float* values, long nnz, int log_pixels, float noise_std, float* out,
                 long out_ld, char* ws, long ws_bytes, int train, uint64_t seed, hipStream_t st);
     int backward(int n, const float* d_out, long d_out_ld, char* ws, long ws_bytes, hipStream_t st, int bi_hi = -1, int bi_lo = 0);
+    // the pieces of forward and of backward, each in launch order
+    int fwd_stem(const Step& s, const int32_t* coords, const float* values, long nnz, int log_pixels, float noise_std, FreshStats& fr);
+    int fwd_layer(const Step& s, int bi, int l, FreshStats& fr);
+    int fwd_transition(const Step& s, int bi, FreshStats& fr);      // the last block: final_norm + global average instead
+    int fwd_output(const Step& s, float* out, long out_ld) const;
+    LayerPath layer_path(const Step& s, int bi, int l, const ConvFwdArgs& c3, Fwd1x1Args& f1) const;
+    int link(const Step& s, const BnSlots& bn, int nblk, int part_ld, int c_new0, int n_new, double* bstat, long count,
+             const long long* isum = nullptr, long isum_stride = 0) const;
+    int link_fresh(const Step& s, const BnSlots& bn, int bi, const FreshStats& fr) const;
+    LfLink lf_link(const Step& s, const BnSlots& bn, const long long* isum, long rep_stride, int c_new0, int n_new, double* bstat, long count) const;
+    int bwd_output(const Step& s, const float* d_out, long d_out_ld) const;
+    int bwd_transition(Step& s, int bi) const;                      // the last block: final_norm + global average instead
+    int bwd_layer(Step& s, int bi, int l) const;
+    int bwd_stem(const Step& s) const;
+    int bwd_link(const Step& s, const BnSlots& bn, int nblk, const double* bstat, long count, float* P, float* Q, int acc, int a_slot) const;
+    int drain(Step& s) const;                                       // `st` waits for everything enqueued on the side stream
+    float* gw_of(const Step& s, int slot) const;                    // kernel-layout weight gradient of a conv weight slot
+    // One argument builder per launch kind: every site that launches the kernel, asks a predicate about the launch or regenerates its operand in
+    // backward (ConvWgradArgs::fa) starts from these; per-step fields (part, nblk, dropout, seed, act_fused / Aact, lf, isum_out, keep_out) are the caller's
+    Tab tab(char* ws, const Layout& L, const BnSlots& bn) const;
+    ConvFwdArgs conv0_args(const Step& s) const, trans_args(const Step& s, int bi) const;
+    ConvFwdArgs conv1_args(const Step& s, int bi, int l) const, conv3_args(const Step& s, int bi, int l) const;   // 1x1 on the generic kernels; 3x3 (bf16: Aact = raw map Y)
+    StemSparseArgs stem_sparse_args(const Step& s, const int32_t* coords, const float* values, long nnz, int value_mode, float noise_std) const;
     // Arguments of the fused 1x1 backward kernel for block bi, layer l (PY / QY / part left to the caller) -- the ONE place that decides whether a
     // layer's backward can take it: the forward asks before it drops the activated copy XA, the backward fills its launch from the same function
     bool bwd1x1_fill(int bi, int l, long M, char* ws, const Layout& L, Bwd1x1Args& fa) const;
-    bool bwd1x1_fusable(int bi, int l, long M, char* ws, const Layout& L) const;
     std::vector<int> unpack_first;   // first unpack descriptor of every block (+ total): partial backward calls unpack their own blocks
     int tap(int n, const char* name, long* off, int* tn, int* th, int* tw, int* tc, int* tld, int* tes) const;
 };

@@ -39,8 +39,8 @@ struct ConvFwdArgs {
                                      // leaving as a partial row in `part`
 };
 int conv_fwd(const ConvFwdArgs& a, hipStream_t st);
-bool conv3x3_fwd_pair(const ConvFwdArgs& a);          // true when conv_fwd(a) runs the pair kernel (the one that honours ConvFwdArgs::lf / isum_out)
-bool conv3x3_fwd_writes_keep(const ConvFwdArgs& a);   // true when conv_fwd(a) runs the kernel that fills keep_out
+enum Conv3x3Fwd { CONV3X3_FWD_NONE = 0, CONV3X3_FWD_STRIP, CONV3X3_FWD_RING, CONV3X3_FWD_PAIR };
+Conv3x3Fwd conv3x3_fwd_kernel(const ConvFwdArgs& a);   // the bf16 padded-tile kernel conv_fwd(a) runs (NONE: another path); only PAIR honours act_fused / lf / isum_out / keep_out
 bool conv3x3_act_fusable(const ConvFwdArgs& a);       // true when both the forward kernel conv_fwd(a) would run and the weight-gradient tile kernel of the
                                                       // same layer can take the raw map (ConvFwdArgs::act_fused)
 int conv_fwd_grid(int M);            // number of M-blocks of the generic kernels for M rows (<= 512)
@@ -141,7 +141,8 @@ struct ConvDgradArgs {
     void* ey_out;                  // optional [M][32] bf16: the consecutive-tile 3x3 kernel stores every eff row it builds (for the weight gradient)
 };
 int conv_dgrad(const ConvDgradArgs& a, hipStream_t st);
-bool conv3x3_dgrad_writes_ey(const ConvDgradArgs& a);   // true when conv_dgrad(a) runs the kernel that fills ey_out
+enum Conv3x3Dgrad { CONV3X3_DGRAD_NONE = 0, CONV3X3_DGRAD_TWO_WG, CONV3X3_DGRAD_PIPELINED, CONV3X3_DGRAD_CONSEC };
+Conv3x3Dgrad conv3x3_dgrad_kernel(const ConvDgradArgs& a);   // the bf16 padded-tile kernel conv_dgrad(a) runs (NONE: another path); only CONSEC (consecutive tiles) fills ey_out
 int conv_dgrad_nblk(const ConvDgradArgs& a);      // grid.x (rows of `part`) conv_dgrad will use (<= 512)
 bool conv3x3_dgrad_tile_ok(const ConvDgradArgs& a);
 int conv3x3_dgrad_tile_nblk(const ConvDgradArgs& a);
