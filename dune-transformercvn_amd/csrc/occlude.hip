@@ -36,6 +36,23 @@ __global__ __launch_bounds__(256) void k_occ_count(const int* __restrict__ coord
     atomicAdd(&nnz_img[img], 1);
 }
 
+// refinement: the same pass, but a hit enters cnt only where the parent level's keep_map is set at its parent tile (tiles of 2*th x 2*tw);
+// nnz_img and the two flags still see every hit, so a variant's surviving hits stay "the whole image minus that one tile"
+__global__ __launch_bounds__(256) void k_occ_count_kept(const int* __restrict__ coords, long nnz, int n_img, int H, int W, int th, int tw,
+                                                        int Wt, int T, const int* __restrict__ img_bs,
+                                                        const unsigned char* __restrict__ keep_map, int B, int S, int pHt, int pWt,
+                                                        int* cnt, int* nnz_img, int* flags) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nnz) return;
+    const int img = coords[3 * i], y = coords[3 * i + 1], x = coords[3 * i + 2];
+    if (i > 0 && coords[3 * (i - 1)] > img) atomicOr(&flags[0], 1);
+    if (img < 0 || img >= n_img || y < 0 || y >= H || x < 0 || x >= W) { atomicOr(&flags[1], 1); return; }
+    atomicAdd(&nnz_img[img], 1);
+    const int b = img_bs[2 * img], s = img_bs[2 * img + 1], py = y / (2 * th), px = x / (2 * tw);
+    if (b < 0 || b >= B || s < 0 || s >= S || py >= pHt || px >= pWt) return;            // no such parent: never a variant
+    if (keep_map[(((long)b * S + s) * pHt + py) * pWt + px]) atomicAdd(&cnt[(long)img * T + (y / th) * Wt + x / tw], 1);
+}
+
 // ---- 2. variant list: ordered compaction of the occupied cells; one workgroup walks the cells in chunks -----------------------------------
 __device__ __forceinline__ long shfl_up64(long v, int d) {
     const int lo = __shfl_up((int)(v & 0xffffffffL), d), hi = __shfl_up((int)(v >> 32), d);
@@ -218,19 +235,21 @@ int64_t tcvn_occlusion_workspace_bytes(int n_img, int height, int width, int til
     return o.total;
 }
 
-int tcvn_occlusion_variants(const int32_t* coords, int64_t nnz, int n_img, int height, int width, int tile_h, int tile_w,
-                            const int32_t* img_bs, int max_pass, int32_t* vimg, int32_t* index, void* workspace,
-                            int64_t workspace_bytes, int64_t* host_out, int64_t host_cap, void* stream) {
+// The variant list of one hit list: flat (keep_map == NULL) or restricted to the children of the parent level's selected tiles.
+static int occ_variant_list(const char* who, const int32_t* coords, int64_t nnz, int n_img, int height, int width, int tile_h, int tile_w,
+                            const int32_t* img_bs, const uint8_t* keep_map, int batch, int max_prongs, int parent_grid_h,
+                            int parent_grid_w, int max_pass, int32_t* vimg, int32_t* index, void* workspace, int64_t workspace_bytes,
+                            int64_t* host_out, int64_t host_cap, void* stream) {
     OccLayout o;
     if ((!coords && nnz > 0) || !img_bs || !vimg || !index || !workspace || !host_out || nnz < 0 || n_img < 1 || height < 1 ||
         width < 1 || tile_h < 1 || tile_w < 1 || max_pass < 1 || max_pass > TCVN_OCC_MAX_PASS ||
         !occ_layout(n_img, height, width, tile_h, tile_w, max_pass, o)) {
-        fprintf(stderr, "tcvn: occlusion_variants: bad argument (NULL pointer, n_img / map / tile < 1, max_pass outside 1..%d or more than 2^31 tiles)\n",
-                TCVN_OCC_MAX_PASS);
+        fprintf(stderr, "tcvn: %s: bad argument (NULL pointer, n_img / map / tile < 1, max_pass outside 1..%d or more than 2^31 tiles)\n",
+                who, TCVN_OCC_MAX_PASS);
         return -1;
     }
     if (workspace_bytes < o.total || host_cap < 4 + o.nb + 1) {
-        fprintf(stderr, "tcvn: occlusion_variants: workspace of %lld bytes (%ld needed) or host buffer of %lld words (%d needed) too small\n",
+        fprintf(stderr, "tcvn: %s: workspace of %lld bytes (%ld needed) or host buffer of %lld words (%d needed) too small\n", who,
                 (long long)workspace_bytes, o.total, (long long)host_cap, 4 + o.nb + 1);
         return -12;
     }
@@ -243,9 +262,13 @@ int tcvn_occlusion_variants(const int32_t* coords, int64_t nnz, int n_img, int h
     long* hdr = reinterpret_cast<long*>(w + o.hdr);
     TCVN_CHECK(hipMemsetAsync(w + o.cnt, 0, (size_t)(o.img_start - o.cnt), st));           // cnt, nnz_img and flags are adjacent
     TCVN_CHECK(hipMemsetAsync(hdr, 0, (size_t)(4 + o.nb + 1) * 8, st));
-    if (nnz > 0) {
+    if (nnz > 0 && !keep_map) {
         hipLaunchKernelGGL(k_occ_count, dim3(cdiv(nnz, 256)), dim3(256), 0, st, coords, (long)nnz, n_img, height, width, tile_h, tile_w,
                            Wt, T, cnt, nnz_img, flags);
+        TCVN_LAUNCH_CHECK();
+    } else if (nnz > 0) {
+        hipLaunchKernelGGL(k_occ_count_kept, dim3(cdiv(nnz, 256)), dim3(256), 0, st, coords, (long)nnz, n_img, height, width, tile_h,
+                           tile_w, Wt, T, img_bs, keep_map, batch, 1 + max_prongs, parent_grid_h, parent_grid_w, cnt, nnz_img, flags);
         TCVN_LAUNCH_CHECK();
     }
     hipLaunchKernelGGL(k_occ_compact, dim3(1), dim3(CT), 0, st, cnt, nnz_img, flags, img_bs, n_img, T, Wt, o.cells, max_pass,
@@ -256,6 +279,29 @@ int tcvn_occlusion_variants(const int32_t* coords, int64_t nnz, int n_img, int h
     TCVN_CHECK(hipMemcpyAsync(host_out, hdr, (size_t)(4 + o.nb + 1) * 8, hipMemcpyDeviceToHost, st));
     TCVN_CHECK(hipStreamSynchronize(st));
     return 0;
+}
+
+int tcvn_occlusion_variants(const int32_t* coords, int64_t nnz, int n_img, int height, int width, int tile_h, int tile_w,
+                            const int32_t* img_bs, int max_pass, int32_t* vimg, int32_t* index, void* workspace,
+                            int64_t workspace_bytes, int64_t* host_out, int64_t host_cap, void* stream) {
+    return occ_variant_list("occlusion_variants", coords, nnz, n_img, height, width, tile_h, tile_w, img_bs, nullptr, 0, 0, 0, 0,
+                            max_pass, vimg, index, workspace, workspace_bytes, host_out, host_cap, stream);
+}
+
+int tcvn_occlusion_refine_variants(const int32_t* coords, int64_t nnz, int n_img, int height, int width, int tile_h, int tile_w,
+                                   const int32_t* img_bs, const uint8_t* keep_map, int batch, int max_prongs, int parent_grid_h,
+                                   int parent_grid_w, int max_pass, int32_t* vimg, int32_t* index, void* workspace,
+                                   int64_t workspace_bytes, int64_t* host_out, int64_t host_cap, void* stream) {
+    // the parent level's tiles are (2 * tile_h, 2 * tile_w): its grid is fixed by the map, and every hit inside the map has a parent
+    if (!keep_map || batch < 1 || max_prongs < 0 || height < 1 || width < 1 || tile_h < 1 || tile_w < 1 || tile_h > 0x3fffffff ||
+        tile_w > 0x3fffffff || parent_grid_h != (height + 2 * tile_h - 1) / (2 * tile_h) ||
+        parent_grid_w != (width + 2 * tile_w - 1) / (2 * tile_w)) {
+        fprintf(stderr, "tcvn: occlusion_refine_variants: bad argument (no keep_map, batch < 1, max_prongs < 0 or a parent grid that is not that of tiles twice the size)\n");
+        return -1;
+    }
+    return occ_variant_list("occlusion_refine_variants", coords, nnz, n_img, height, width, tile_h, tile_w, img_bs, keep_map, batch,
+                            max_prongs, parent_grid_h, parent_grid_w, max_pass, vimg, index, workspace, workspace_bytes, host_out,
+                            host_cap, stream);
 }
 
 int tcvn_occlusion_build_pass(const int32_t* coords, const float* values, int64_t nnz, int channels, int n_img, int height, int width,

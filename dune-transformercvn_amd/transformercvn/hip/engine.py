@@ -110,8 +110,21 @@ class _EmbedderEngine(_Plan):
     # ---- occlusion scan: variant hit lists of one COO list and their passes through this embedder (eval arithmetic) -----------------
     def occlusion_variants(self, coords: torch.Tensor, n_img: int, shape: Tuple[int, int], tile: Tuple[int, int],
                            img_bs: torch.Tensor, max_pass: int):
-        """tcvn_occlusion_variants -> (V, unsorted, bad, bounds, vimg [V], index [V, 4]); bounds[k] .. bounds[k + 1] are the rows of
-        pass k in the variants' hit lists.  One synchronisation.  Keeps the list's workspace for occlusion_build()."""
+        """tcvn_occlusion_variants -> (V, unsorted, bad, bounds, vimg [V], index [V, 4], handle); bounds[k] .. bounds[k + 1] are the rows
+        of pass k in the variants' hit lists.  One synchronisation.  handle: the list's workspace, for occlusion_build()."""
+        return self._occlusion_list(lib.tcvn_occlusion_variants, (), "occlusion_variants", coords, n_img, shape, tile, img_bs, max_pass)
+
+    def occlusion_refine_variants(self, coords: torch.Tensor, n_img: int, shape: Tuple[int, int], tile: Tuple[int, int],
+                                  img_bs: torch.Tensor, max_pass: int, keep_map: torch.Tensor):
+        """tcvn_occlusion_refine_variants: occlusion_variants() at the child tile `tile`, restricted to the tiles of the parent level
+        (tiles twice the size) that keep_map uint8 [B, 1 + P, parent Ht, parent Wt] selects.  Same results and workspace."""
+        assert keep_map.dtype == torch.uint8 and keep_map.is_contiguous() and keep_map.dim() == 4 and keep_map.device == coords.device
+        B, S, pHt, pWt = keep_map.shape
+        return self._occlusion_list(lib.tcvn_occlusion_refine_variants, (_ptr(keep_map), B, S - 1, pHt, pWt), "occlusion_refine_variants",
+                                    coords, n_img, shape, tile, img_bs, max_pass)
+
+    def _occlusion_list(self, fn, parent: tuple, what: str, coords: torch.Tensor, n_img: int, shape: Tuple[int, int], tile: Tuple[int, int],
+                        img_bs: torch.Tensor, max_pass: int):
         assert coords.dtype == torch.int32 and coords.is_contiguous() and img_bs.dtype == torch.int32 and img_bs.shape == (n_img, 2)
         (H, W), (th, tw) = shape, tile
         cells = n_img * (-(-H // th)) * (-(-W // tw))
@@ -124,17 +137,17 @@ class _EmbedderEngine(_Plan):
         index = torch.empty(cells, 4, dtype=torch.int32, device=dev)
         words = 4 + -(-cells // max_pass) + 1
         host = (C.c_int64 * words)()
-        check(lib.tcvn_occlusion_variants(_ptr(coords), coords.shape[0], n_img, H, W, th, tw, _ptr(img_bs.contiguous()), max_pass,
-                                          _ptr(vimg), _ptr(index), _ptr(ws), ws.numel(), host, words, _stream_ptr()),
-              "occlusion_variants")
+        check(fn(_ptr(coords), coords.shape[0], n_img, H, W, th, tw, _ptr(img_bs.contiguous()), *parent, max_pass, _ptr(vimg), _ptr(index),
+                 _ptr(ws), ws.numel(), host, words, _stream_ptr()), what)
         V = int(host[0])
-        self._occ_list = (ws, vimg, n_img, H, W, th, tw, max_pass)
-        return V, bool(host[1]), bool(host[2]), [int(host[4 + k]) for k in range(-(-V // max_pass) + 1)], vimg[:V], index[:V]
+        handle = (ws, vimg, n_img, H, W, th, tw, max_pass)
+        return V, bool(host[1]), bool(host[2]), [int(host[4 + k]) for k in range(-(-V // max_pass) + 1)], vimg[:V], index[:V], handle
 
-    def occlusion_build(self, coords: torch.Tensor, values: torch.Tensor, first: int, count: int, out_coords: torch.Tensor,
+    def occlusion_build(self, handle, coords: torch.Tensor, values: torch.Tensor, first: int, count: int, out_coords: torch.Tensor,
                         out_values: torch.Tensor):
-        """tcvn_occlusion_build_pass: the hit lists of variants first .. first + count - 1 of the last occlusion_variants()."""
-        ws, vimg, n_img, H, W, th, tw, max_pass = self._occ_list
+        """tcvn_occlusion_build_pass: the hit lists of variants first .. first + count - 1 of the list `handle` stands for (the last
+        element of what occlusion_variants() / occlusion_refine_variants() returned for these coords)."""
+        ws, vimg, n_img, H, W, th, tw, max_pass = handle
         assert out_coords.dtype == torch.int32 and out_coords.is_contiguous() and out_values.is_contiguous()
         assert out_values.dtype == torch.float32 and out_values.shape == (out_coords.shape[0], values.shape[1])
         check(lib.tcvn_occlusion_build_pass(_ptr(coords), _ptr(values), coords.shape[0], values.shape[1], n_img, H, W, th, tw, max_pass,

@@ -9,6 +9,7 @@ PyTorch supplies device memory, the current stream and (optionally) torch.distri
 """
 from __future__ import annotations
 
+from types import SimpleNamespace
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -364,54 +365,125 @@ class HipRuntime:
         if self.network.training:
             raise RuntimeError("occlusion_maps explains an eval-mode prediction: call network.eval() first")
         with torch.no_grad():
-            ev, pr = self.forward(features, extra, event_px, event_mask, prong_px, prong_mask, counts)
-            rows, tok_row, B, P, n_prongs = self._head_in
-            dev = rows.device
-            tokens = self.head.embed(rows, tok_row, B, P, n_prongs, False, 0)
-            pe = self.network.prong_embedding
-            feat, pix = pe.feature_embedding_dim, pe.pixel_embedding_dim
-            H, W = self.pixel_shape
-            grid = (-(-H // tile[0]), -(-W // tile[1]))
-            parts = []
-            if maps in ("all", "event"):
-                bs = torch.stack((torch.arange(B, device=dev), torch.zeros(B, dtype=torch.int64, device=dev)), 1).to(torch.int32)
-                parts.append(self._occlude(self.ev_engine, event_px, B, bs, 0, 0, tile, max_pass, rows, tokens, tok_row, n_prongs))
-            if maps in ("all", "prongs") and n_prongs > 0:
-                i1, i2 = prong_mask.to(dev).nonzero(as_tuple=True)             # packed prong order: the embedder's image order
-                bs = torch.stack((i1, 1 + i2), 1).to(torch.int32)
-                parts.append(self._occlude(self.pr_engine, prong_px, n_prongs, bs, B, feat, tile, max_pass, rows, tokens, tok_row,
-                                           n_prongs))
-            if parts:
-                index, occ_ev, occ_pr = (torch.cat([p[i] for p in parts]) for i in range(3))
-            else:
-                index = torch.empty(0, 4, dtype=torch.int32, device=dev)
-                occ_ev, occ_pr = ev.new_empty(0, ev.shape[1]), pr.new_empty(0, P, pr.shape[2])
-            if len(parts) > 1:                    # the two lists are ordered by (b, s, ty, tx) each: merge them into that order
-                i64 = index.long()
-                key = ((i64[:, 0] * (1 + P) + i64[:, 1]) * grid[0] + i64[:, 2]) * grid[1] + i64[:, 3]
-                order = torch.argsort(key)
-                index, occ_ev, occ_pr = index[order].contiguous(), occ_ev[order].contiguous(), occ_pr[order].contiguous()
-            return occlusion.OcclusionResult(ev, pr, index, occ_ev, occ_pr, grid, tile)
+            base = self._occlusion_base(features, extra, event_px, event_mask, prong_px, prong_mask, counts, maps)
+            return self._occlusion_level(base, tile, max_pass)
 
-    def _occlude(self, engine, px: SparsePixels, n_img: int, img_bs: Tensor, row_base: int, col0: int, tile, max_pass: int,
-                 rows: Tensor, tokens: Tensor, tok_row: Tensor, n_prongs: int):
-        """The scan over the maps of one embedder -> (index [V, 4], occluded_event_logits [V, Ce], occluded_prong_logits [V, P, Cp])
-        in the embedder's image order.  The embedder writes [col0, col0 + engine.out_dim) of its maps' rows."""
+    def forward_occlusion_refine(self, features: Tensor, extra: Tensor, event_px: SparsePixels, event_mask: Tensor,
+                                 prong_px: SparsePixels, prong_mask: Tensor, counts: Optional[Tuple[int, int]] = None,
+                                 tile: Tuple[int, int] = (64, 64), levels: int = 3, keep: float = 0.25, target="event", maps: str = "all",
+                                 max_maps_per_pass: int = 256, max_variants: Optional[int] = None):
+        """Eval-mode forward() plus a coarse-to-fine occlusion scan -> occlusion.RefinedOcclusion.  Level 0 is forward_occlusion(tile);
+        level l halves the tiles of level l - 1 and evaluates only the children (that hold a hit) of the variants whose score |h| --
+        heatmap(level, target) -- reaches keep times the largest score of their group (the event, or the map with target "prong").
+        The choice is made on the device (tcvn_occlusion_select); one host read-back per hit list and level.  max_variants bounds
+        the sum of V over the levels: the level that would pass it and all later ones are not run.  Counts as ONE forward()."""
+        from . import occlusion
+        tile, levels, keep, maps, max_pass, max_variants = occlusion.check_refine_args(tile, levels, keep, target, maps, max_maps_per_pass,
+                                                                                       max_variants)
+        B = prong_mask.shape[0]
+        occlusion.parse_target(target, B, self.head.cfg.event_classes)
+        if self.network.training:
+            raise RuntimeError("occlusion_refine explains an eval-mode prediction: call network.eval() first")
+        group = _lib.OCC_GROUP_MAP if isinstance(target, str) and target == "prong" else _lib.OCC_GROUP_EVENT
+        with torch.no_grad():
+            base = self._occlusion_base(features, extra, event_px, event_mask, prong_px, prong_mask, counts, maps)
+            done, heats, evaluated, used, stopped_at, keep_map = [], [], [], 0, None, None
+            for lv in range(levels):
+                budget = None if max_variants is None else max_variants - used
+                res = self._occlusion_level(base, (tile[0] >> lv, tile[1] >> lv), max_pass, keep_map, budget)
+                if res is None:
+                    stopped_at = lv
+                    break
+                used += res.num_variants
+                done.append(res)
+                heats.append(occlusion.heatmap(res, target))
+                evaluated.append(occlusion.mark(res.index, B, base.P, res.grid))
+                if lv + 1 < levels:
+                    keep_map = occlusion.select(heats[-1], res.index, group, keep)
+            occupied = None
+            if done:
+                occupied = torch.zeros(B, 1 + base.P, *done[-1].grid, dtype=torch.uint8, device=base.rows.device)
+                for lst in base.lists:
+                    occlusion.occupancy(lst.coords, lst.n_img, self.pixel_shape, done[-1].tile, lst.img_bs, occupied)
+            return occlusion.RefinedOcclusion(base.ev, base.pr, done, heats, evaluated, occupied, target, keep, stopped_at)
+
+    def _occlusion_base(self, features: Tensor, extra: Tensor, event_px: SparsePixels, event_mask: Tensor, prong_px: SparsePixels,
+                        prong_mask: Tensor, counts, maps: str):
+        """The forward() being explained and what every pass of a scan over it reads: its rows and tokens, and one record per hit list
+        to scan (the event maps and the prong maps go through their own embedder engines, one list after the other)."""
+        ev, pr = self.forward(features, extra, event_px, event_mask, prong_px, prong_mask, counts)
+        rows, tok_row, B, P, n_prongs = self._head_in
         dev = rows.device
-        coords, values = px.coords.to(dev), px.values.to(dev)
+        tokens = self.head.embed(rows, tok_row, B, P, n_prongs, False, 0)
+        feat = self.network.prong_embedding.feature_embedding_dim
+        lists = []
+        if maps in ("all", "event"):
+            bs = torch.stack((torch.arange(B, device=dev), torch.zeros(B, dtype=torch.int64, device=dev)), 1).to(torch.int32)
+            lists.append(SimpleNamespace(engine=self.ev_engine, coords=event_px.coords.to(dev), values=event_px.values.to(dev),
+                                         value_mode=event_px.value_mode, n_img=B, img_bs=bs, row_base=0, col0=0))
+        if maps in ("all", "prongs") and n_prongs > 0:
+            i1, i2 = prong_mask.to(dev).nonzero(as_tuple=True)             # packed prong order: the embedder's image order
+            bs = torch.stack((i1, 1 + i2), 1).to(torch.int32)
+            lists.append(SimpleNamespace(engine=self.pr_engine, coords=prong_px.coords.to(dev), values=prong_px.values.to(dev),
+                                         value_mode=prong_px.value_mode, n_img=n_prongs, img_bs=bs, row_base=B, col0=feat))
+        return SimpleNamespace(ev=ev, pr=pr, rows=rows, tokens=tokens, tok_row=tok_row, B=B, P=P, n_prongs=n_prongs, lists=lists)
+
+    def _occlusion_level(self, base, tile, max_pass: int, keep_map: Optional[Tensor] = None, budget: Optional[int] = None):
+        """One scan over the maps of `base` at `tile` -> occlusion.OcclusionResult: every tile that holds a hit, or (keep_map: the
+        selection among the variants of the level with tiles twice the size) only the children of the selected tiles.  The variant
+        lists come first; None, before any variant is run, if they hold more than `budget` variants together."""
+        from . import occlusion
+        dev, P = base.rows.device, base.P
+        H, W = self.pixel_shape
+        grid = (-(-H // tile[0]), -(-W // tile[1]))
+        plans = [self._occlusion_list(lst, tile, max_pass, keep_map) for lst in base.lists]
+        if budget is not None and sum(plan.V for plan in plans) > budget:
+            return None
+        parts = [self._occlusion_passes(base, lst, plan, max_pass) for lst, plan in zip(base.lists, plans)]
+        if parts:
+            index, occ_ev, occ_pr = (torch.cat([p[i] for p in parts]) for i in range(3))
+        else:
+            index = torch.empty(0, 4, dtype=torch.int32, device=dev)
+            occ_ev, occ_pr = base.ev.new_empty(0, base.ev.shape[1]), base.pr.new_empty(0, P, base.pr.shape[2])
+        if len(parts) > 1:                    # the two lists are ordered by (b, s, ty, tx) each: merge them into that order
+            i64 = index.long()
+            key = ((i64[:, 0] * (1 + P) + i64[:, 1]) * grid[0] + i64[:, 2]) * grid[1] + i64[:, 3]
+            order = torch.argsort(key)
+            index, occ_ev, occ_pr = index[order].contiguous(), occ_ev[order].contiguous(), occ_pr[order].contiguous()
+        return occlusion.OcclusionResult(base.ev, base.pr, index, occ_ev, occ_pr, grid, tile)
+
+    def _occlusion_list(self, lst, tile, max_pass: int, keep_map: Optional[Tensor]):
+        """The variant list of one hit list (one host read-back).  A list that is unsorted or holds hits outside the maps is replaced
+        in `lst` by its cleaned copy, so later levels of a refinement start from that."""
         shape = self.pixel_shape
-        V, unsorted, bad, bounds, vimg, index = engine.occlusion_variants(coords, n_img, shape, tile, img_bs, max_pass)
+
+        def variants():
+            if keep_map is None:
+                return lst.engine.occlusion_variants(lst.coords, lst.n_img, shape, tile, lst.img_bs, max_pass)
+            return lst.engine.occlusion_refine_variants(lst.coords, lst.n_img, shape, tile, lst.img_bs, max_pass, keep_map)
+        V, unsorted, bad, bounds, vimg, index, handle = variants()
         if unsorted or bad:
             # the variant build walks each image's hits as one range: drop what the embedders drop, then a STABLE sort by image (the
             # order inside an image decides which of two hits on one pixel wins)
+            coords, values = lst.coords, lst.values
             c = coords.long()
-            keep = (c[:, 0] >= 0) & (c[:, 0] < n_img) & (c[:, 1] >= 0) & (c[:, 1] < shape[0]) & (c[:, 2] >= 0) & (c[:, 2] < shape[1])
+            keep = (c[:, 0] >= 0) & (c[:, 0] < lst.n_img) & (c[:, 1] >= 0) & (c[:, 1] < shape[0]) & (c[:, 2] >= 0) & (c[:, 2] < shape[1])
             coords, values = coords[keep], values[keep]
             order = torch.sort(coords[:, 0], stable=True).indices
-            coords, values = coords[order].contiguous(), values[order].contiguous()
-            V, unsorted, bad, bounds, vimg, index = engine.occlusion_variants(coords, n_img, shape, tile, img_bs, max_pass)
+            lst.coords, lst.values = coords[order].contiguous(), values[order].contiguous()
+            V, unsorted, bad, bounds, vimg, index, handle = variants()
             if unsorted or bad:
                 raise RuntimeError("occlusion_maps: the hit list is still unsorted after sorting it")
+        return SimpleNamespace(V=V, bounds=bounds, vimg=vimg, index=index, handle=handle)
+
+    def _occlusion_passes(self, base, lst, plan, max_pass: int):
+        """The variants of one list, pass by pass, through its embedder and the token path -> (index [V, 4], occluded_event_logits
+        [V, Ce], occluded_prong_logits [V, P, Cp]) in the embedder's image order.  The embedder writes [col0, col0 + engine.out_dim)
+        of its maps' rows."""
+        engine, coords, values = lst.engine, lst.coords, lst.values
+        rows, tokens, tok_row = base.rows, base.tokens, base.tok_row
+        dev = rows.device
+        V, bounds, vimg, index = plan.V, plan.bounds, plan.vimg, plan.index
         B, S, _ = tokens.shape
         occ_ev = torch.empty(V, self.head.cfg.event_classes, device=dev)
         occ_pr = torch.empty(V, S - 1, self.head.cfg.prong_classes, device=dev)
@@ -426,10 +498,10 @@ class HipRuntime:
             n = min(max_pass, V - first)
             nnz = bounds[k + 1] - bounds[k]
             if nnz > 0:
-                engine.occlusion_build(coords, values, first, n, out_coords, out_values)
-            engine.occlusion_forward(out_coords, out_values, nnz, n, emb[:n], px.value_mode)
-            self.head.occlusion_pass(rows, tokens, tok_row, n_prongs, vimg[first:first + n], index[first:first + n], row_base, emb[:n],
-                                     col0, occ_ev[first:first + n], occ_pr[first:first + n])
+                engine.occlusion_build(plan.handle, coords, values, first, n, out_coords, out_values)
+            engine.occlusion_forward(out_coords, out_values, nnz, n, emb[:n], lst.value_mode)
+            self.head.occlusion_pass(rows, tokens, tok_row, base.n_prongs, vimg[first:first + n], index[first:first + n], lst.row_base,
+                                     emb[:n], lst.col0, occ_ev[first:first + n], occ_pr[first:first + n])
         return index, occ_ev, occ_pr
 
     def _backward(self, st: dict, d_ev: Tensor, d_pr: Tensor):

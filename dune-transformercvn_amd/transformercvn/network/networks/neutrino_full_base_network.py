@@ -190,3 +190,25 @@ class NeutrinoBaseNetwork(nn.Module):
             prong_pixels = SparsePixels.from_dense(prong_pixels)
         return self.hip_runtime().forward_occlusion(features, extra, event_pixels, event_mask, prong_pixels, prong_mask, counts,
                                                     tile, maps, max_maps_per_pass)
+
+    @torch.jit.unused
+    def occlusion_refine(self, features: Tensor, extra: Tensor, event_pixels: Tensor, event_mask: Tensor, prong_pixels: Tensor,
+                         prong_mask: Tensor, counts: Optional[Tuple[int, int]] = None, tile: Tuple[int, int] = (64, 64),
+                         levels: int = 3, keep: float = 0.25, target="event", maps: str = "all", max_maps_per_pass: int = 256,
+                         max_variants: Optional[int] = None):
+        """Eval mode only -> transformercvn.hip.occlusion.RefinedOcclusion: occlusion_maps coarse to fine.  Level l uses tiles
+        (tile[0] >> l, tile[1] >> l); level 0 is occlusion_maps(tile), every later level evaluates only the children of the variants
+        whose |heat| (heatmap(level, target)) reached keep times the largest of their event (target "prong": of their map).
+        max_variants bounds the sum of variants over the levels.  result.heatmap() -> [B, 1+P, Hf, Wf] on the finest grid run."""
+        from transformercvn.hip import occlusion
+        occlusion.check_refine_args(tile, levels, keep, target, maps, max_maps_per_pass, max_variants)
+        # explicit classes against the model, before the runtime and its native plans exist (a tensor on the device is read back)
+        occlusion.parse_target(target, prong_mask.shape[0], self.event_decoder.hidden_layer.out_features)
+        if self.training:
+            raise RuntimeError("occlusion_refine explains an eval-mode prediction: call .eval() first")
+        if not isinstance(event_pixels, SparsePixels):
+            event_pixels = SparsePixels.from_dense(event_pixels)
+        if not isinstance(prong_pixels, SparsePixels):
+            prong_pixels = SparsePixels.from_dense(prong_pixels)
+        return self.hip_runtime().forward_occlusion_refine(features, extra, event_pixels, event_mask, prong_pixels, prong_mask, counts,
+                                                           tile, levels, keep, target, maps, max_maps_per_pass, max_variants)

@@ -192,6 +192,22 @@ class NeutrinoFullBaseTrainer(NeutrinoBase, ABC):
                                                                  prong_coords, prong_values, prong_mask), None, tile, maps,
                                            max_maps_per_pass)
 
+    def occlusion_refine(self, features: Tensor, extra: Tensor, event_coords: Tensor, event_values: Tensor, event_mask: Tensor,
+                         prong_coords: Tensor, prong_values: Tensor, prong_mask: Tensor, tile: Tuple[int, int] = (64, 64),
+                         levels: int = 3, keep: float = 0.25, target="event", maps: str = "all", max_maps_per_pass: int = 256,
+                         max_variants=None):
+        """Eval mode only -> RefinedOcclusion (transformercvn.hip.occlusion): occlusion_maps coarse to fine, refining only the tiles
+        that matter; see NeutrinoBaseNetwork.occlusion_refine.  Bad arguments raise ValueError and train mode RuntimeError before any
+        device work."""
+        from transformercvn.hip import occlusion
+        occlusion.check_refine_args(tile, levels, keep, target, maps, max_maps_per_pass, max_variants)
+        occlusion.parse_target(target, prong_mask.shape[0], self.network.event_decoder.hidden_layer.out_features)
+        if self.training:
+            raise RuntimeError("occlusion_refine explains an eval-mode prediction: call .eval() first")
+        return self.network.occlusion_refine(*self._network_inputs(features, extra, event_coords, event_values, event_mask,
+                                                                   prong_coords, prong_values, prong_mask), None, tile, levels, keep,
+                                             target, maps, max_maps_per_pass, max_variants)
+
     def shared_step(self, batch):
         (features, extra, ev_c, ev_v, ev_m, pr_c, pr_v, pr_m, ev_t, pr_t) = batch[:10]
         counts = batch[10] if len(batch) > 10 else None               # optional host-side (max_prongs, n_prongs): avoids syncs

@@ -263,6 +263,44 @@ int tcvn_occlusion_heatmap(const float* event_logits, const float* prong_logits,
                            int event_classes, int prong_classes, int grid_h, int grid_w, int target, const int32_t* classes,
                            float* heatmap, void* stream);
 
+/* Coarse-to-fine occlusion maps: level l uses tiles (tile_h >> l, tile_w >> l) and evaluates only the children of the variants of
+ * level l - 1 that were selected.  Level 0 is the flat scan above.
+ *   select      heat [batch, 1 + max_prongs, grid_h, grid_w] (tcvn_occlusion_heatmap of one level) and that level's index [V, 4] ->
+ *               keep_map uint8 of the same shape: 1 at the variants to refine, 0 everywhere else.  score = |h| at the variant's
+ *               position; m = the largest score of the variant's group (TCVN_OCC_GROUP_EVENT: all variants of event b;
+ *               TCVN_OCC_GROUP_MAP: those of the map (b, s)); selected iff score >= keep * m (float32, one multiplication) and
+ *               (keep == 0 or score > 0).  keep in [0, 1]; keep == 0 selects every variant.  group_max: batch * (1 + max_prongs)
+ *               words of scratch (the maxima, as float bit patterns, taken with an integer atomicMax: order-independent).
+ *   refine_variants  tcvn_occlusion_variants at the child tile (tile_h, tile_w), restricted by the parent level's keep_map
+ *               [batch, 1 + max_prongs, parent_grid_h, parent_grid_w] (the grid of tiles (2 tile_h, 2 tile_w), checked): a hit counts
+ *               towards its tile only if keep_map[b][s][y / (2 tile_h)][x / (2 tile_w)] != 0 with (b, s) = img_bs[image].  The variants
+ *               are therefore the children (2 ty + i, 2 tx + j) of the selected tiles that hold a hit, ordered by (image, ty, tx).
+ *               Same outputs, workspace layout (tcvn_occlusion_workspace_bytes at the child tile) and host_out as
+ *               tcvn_occlusion_variants; tcvn_occlusion_build_pass serves the list unchanged: a variant's hits are still the whole
+ *               image minus that one tile.
+ *   mark        evaluated uint8 [batch, 1 + max_prongs, grid_h, grid_w]: 1 at the positions of index [V, 4], 0 elsewhere.
+ *   occupancy   sets occupied[b][s][y / tile_h][x / tile_w] = 1 for every hit inside the map ((b, s) = img_bs[image]); the caller
+ *               clears the map first and may call once per hit list.
+ *   paint       out [batch, 1 + max_prongs, gh, gw] on the grid of the last of `levels` levels (host arrays heat[l], evaluated[l],
+ *               grid_h[l], grid_w[l]; grid l = ceil(last grid / 2^(levels - 1 - l)), checked): a cell with occupied != 0 takes the
+ *               stored heat value of the deepest level whose evaluated tile contains it, every other cell exactly 0.
+ * Argument errors return non-zero before any device call and print one "tcvn:" line. */
+#define TCVN_OCC_GROUP_EVENT 0
+#define TCVN_OCC_GROUP_MAP 1
+#define TCVN_OCC_MAX_LEVELS 16
+int tcvn_occlusion_select(const float* heat, const int32_t* index, int64_t n_variants, int batch, int max_prongs, int grid_h,
+                          int grid_w, int group, float keep, uint32_t* group_max, uint8_t* keep_map, void* stream);
+int tcvn_occlusion_refine_variants(const int32_t* coords, int64_t nnz, int n_img, int height, int width, int tile_h, int tile_w,
+                                   const int32_t* img_bs, const uint8_t* keep_map, int batch, int max_prongs, int parent_grid_h,
+                                   int parent_grid_w, int max_pass, int32_t* vimg, int32_t* index, void* workspace,
+                                   int64_t workspace_bytes, int64_t* host_out, int64_t host_cap, void* stream);
+int tcvn_occlusion_mark(const int32_t* index, int64_t n_variants, int batch, int max_prongs, int grid_h, int grid_w, uint8_t* evaluated,
+                        void* stream);
+int tcvn_occlusion_occupancy(const int32_t* coords, int64_t nnz, int n_img, int height, int width, int tile_h, int tile_w,
+                             const int32_t* img_bs, int batch, int max_prongs, uint8_t* occupied, void* stream);
+int tcvn_occlusion_paint(int levels, const float* const* heat, const uint8_t* const* evaluated, const int32_t* grid_h,
+                         const int32_t* grid_w, const uint8_t* occupied, int batch, int max_prongs, float* out, void* stream);
+
 /* Row operators behind the holder modules' own forward() (forward only, fp32):
  *   y = x W^T + b (torch.nn.Linear layout; bias may be NULL)                      -- layers/prong_decoder.py:15-16
  *   y = dropout(prelu(batchnorm1d(x)))  with batch statistics + running-stat update when train != 0, running statistics

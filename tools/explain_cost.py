@@ -1,9 +1,10 @@
 """What do the explanation calls cost at the --ragged-inference shape (batch 32, 1-16 prongs/event, bf16 embedders, eval mode)?
 Times forward(), forward_with_attention() and leave_one_prong_out() on the same batch with device events around synchronised work,
-interleaved, and prints one JSON line with the medians.  occlusion_maps() is timed the same way at tiles of 32x32 and 16x16 with its
-number of variants V and of embedder passes (a scan is thousands of maps: it gets --occ-reps repetitions of its own).
+interleaved, and prints one JSON line with the medians.  occlusion_maps() is timed the same way at tiles of 32x32, 16x16 and 8x8 with
+its number of variants V and of embedder passes (a scan is thousands of maps: it gets --occ-reps repetitions of its own), and beside
+them occlusion_refine(tile=(64, 64), levels=4) -- the same 8x8 grid, coarse to fine -- for every --keep, with V per level.
 
-    python tools/explain_cost.py [--batch 32 --reps 15 --occ-reps 3 --precision bf16]
+    python tools/explain_cost.py [--batch 32 --reps 15 --occ-reps 3 --precision bf16 --keep 0.25]
 """
 import argparse
 import json
@@ -26,6 +27,7 @@ def main():
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--occ-reps", type=int, default=3, help="repetitions of each occlusion_maps line (0: skip them)")
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32"])
+    ap.add_argument("--keep", type=float, nargs="*", default=[0.25], help="keep of each occlusion_refine line (none: skip them)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     opt = Options.load(os.path.join(bench.PKG, "option_files", "tutorial_densenet_synthetic.json"))
@@ -38,6 +40,24 @@ def main():
     width, n_prongs = batch[10]
     f, x, ec, ev, em, pc, pv, pm = batch[:8]
     inputs = (f[:, :width].contiguous(), x, ec, ev, em, pc, pv, pm[:, :width].contiguous(), (args.batch, n_prongs))   # as shared_step trims them
+
+    def timed(call):
+        ts = []
+        with torch.no_grad():
+            for rep in range(1 + args.occ_reps):                    # the first call allocates the scan's workspaces
+                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                t0.record()
+                res = call()
+                t1.record()
+                t1.synchronize()
+                if rep:
+                    ts.append(t0.elapsed_time(t1))
+        return res, ts
+
+    def ms(ts):
+        return {"median": round(statistics.median(ts), 3), "min": round(min(ts), 3), "max": round(max(ts), 3)}
+
     calls = {"forward": model.forward, "forward_with_attention": model.forward_with_attention,
              "leave_one_prong_out": model.leave_one_prong_out}
     times = {k: [] for k in calls}
@@ -58,26 +78,20 @@ def main():
     out = {"shape": {"batch": args.batch, "tokens": 1 + width, "valid_prongs": n_prongs, "precision": args.precision},
            "reps": args.reps}
     for name, ts in times.items():
-        out[name + "_ms"] = {"median": round(statistics.median(ts), 3), "min": round(min(ts), 3), "max": round(max(ts), 3)}
-    for tile in ((32, 32), (16, 16)) if args.occ_reps > 0 else ():
-        ts = []
-        with torch.no_grad():
-            for rep in range(1 + args.occ_reps):                    # the first call allocates the scan's workspaces
-                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                torch.cuda.synchronize()
-                t0.record()
-                res = model.occlusion_maps(*inputs[:8], tile=tile)
-                t1.record()
-                t1.synchronize()
-                if rep:
-                    ts.append(t0.elapsed_time(t1))
+        out[name + "_ms"] = ms(ts)
+    for tile in ((32, 32), (16, 16), (8, 8)) if args.occ_reps > 0 else ():
+        res, ts = timed(lambda: model.occlusion_maps(*inputs[:8], tile=tile))
         n_ev = int((res.index[:, 1] == 0).sum())
         n_pr = res.num_variants - n_ev
         out[f"occlusion_maps_{tile[0]}x{tile[1]}"] = {
             "variants": res.num_variants, "event_map_variants": n_ev, "prong_map_variants": n_pr,
             "passes": -(-n_ev // 256) + -(-n_pr // 256), "reps": args.occ_reps,
-            "ms": {"median": round(statistics.median(ts), 3), "min": round(min(ts), 3), "max": round(max(ts), 3)},
-            "us_per_variant": round(1e3 * statistics.median(ts) / max(1, res.num_variants), 2)}
+            "ms": ms(ts), "us_per_variant": round(1e3 * statistics.median(ts) / max(1, res.num_variants), 2)}
+    for keep in args.keep if args.occ_reps > 0 else ():
+        res, ts = timed(lambda: model.occlusion_refine(*inputs[:8], tile=(64, 64), levels=4, keep=keep))
+        out[f"occlusion_refine_64x64_levels4_keep{keep:g}"] = {
+            "variants_per_level": [level.num_variants for level in res.levels], "variants": res.num_variants, "reps": args.occ_reps,
+            "ms": ms(ts), "us_per_variant": round(1e3 * statistics.median(ts) / max(1, res.num_variants), 2)}
     cfg = model.network.hip_runtime().head.cfg
     out["weights_bytes"] = cfg.n_layers * args.batch * cfg.heads * (1 + width) ** 2 * 4
     print(json.dumps(out))
