@@ -8,7 +8,6 @@
 
 namespace tcvn {
 
-struct Slot { std::string name; long numel; int kind; };
 struct BnSlots { int w = -1, b = -1, rm = -1, rv = -1, nbt = -1, C = 0, id = -1; };
 struct LayerSlots { BnSlots n1, n2; int a1, w1, b1, a2, w2, b2, cin; };
 struct BlockGeom {

@@ -19,15 +19,15 @@ using namespace tcvn;
 
 namespace {
 constexpr float kEps = 1e-5f, kMom = 0.1f;
+// Dropout stream ids: forward draws and backward replays the mask of (seed, stream id, element)
+constexpr uint32_t kSidCombined = 0x5000u;
+constexpr uint32_t sid_enc(int l, int k) { return 0x6000u + l * 8 + k; }     // encoder layer l; k = 0 attention probabilities, 1 attention branch, 2 activation, 3 feed-forward branch
+constexpr uint32_t sid_dec(int i) { return 0x7000u + (uint32_t)i; }           // prong decoder layer i
 
 __global__ void k_combine_loss(const float* oe, const float* op, float ew, float* losses, float* accs) {
     losses[0] = ew * oe[0] + (1.f - ew) * op[0];
     losses[1] = oe[0]; losses[2] = op[0];
     accs[0] = oe[1]; accs[1] = op[1];
-}
-__global__ void k_scale(float* x, long n, float s) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) x[i] *= s;
 }
 struct Bump {
     long off = 0;
@@ -54,10 +54,11 @@ HeadPlan::HeadPlan(const tcvn_head_cfg& c) : cfg(c) {
     const std::string ce = "prong_embedding.combined_embedding";
     // LinearBlock (layers/prong_feature_embedding.py:7-33): Linear(bias = not linear_batch_norm) - BatchNorm1d | Identity - PReLU | ReLU - Dropout
     const bool bn = !cfg.no_linear_bn, prelu_act = !cfg.linear_relu;
-    cw = add_slot(ce + ".linear.weight", (long)D * cfg.in_dim, TCVN_SLOT_PARAM);
-    if (!bn) cb = add_slot(ce + ".linear.bias", D, TCVN_SLOT_PARAM);
-    if (bn) cn = add_bn(ce + ".norm", D);
-    if (prelu_act) ca = add_slot(ce + ".activation.weight", D, TCVN_SLOT_PARAM);
+    comb.in = cfg.in_dim; comb.out = D; comb.sid = kSidCombined; comb.drop = true;
+    comb.w = add_slot(ce + ".linear.weight", (long)D * cfg.in_dim, TCVN_SLOT_PARAM);
+    if (!bn) comb.b = add_slot(ce + ".linear.bias", D, TCVN_SLOT_PARAM);
+    if (bn) comb.n = add_bn(ce + ".norm", D);
+    if (prelu_act) comb.a = add_slot(ce + ".activation.weight", D, TCVN_SLOT_PARAM);
     for (int l = 0; l < cfg.n_layers; ++l) {
         const std::string p = "encoder.encoder.layers." + std::to_string(l);
         HLayer L;
@@ -81,7 +82,7 @@ HeadPlan::HeadPlan(const tcvn_head_cfg& c) : cfg(c) {
     for (int i = 0; i < cfg.n_dec; ++i) {
         const std::string p = "prong_decoder.hidden_layers.";
         HDec d;
-        d.in = in; d.out = cfg.dec_dims[i];
+        d.in = in; d.out = cfg.dec_dims[i]; d.sid = sid_dec(i); d.drop = cfg.dropout_modules != 0;
         // create_linear_block (layers/encoder.py:10-24): [Linear, BatchNorm1d?, PReLU | ReLU, Dropout?] -- the Sequential indices follow
         d.w = add_slot(p + std::to_string(idx) + ".weight", (long)d.out * d.in, TCVN_SLOT_PARAM);
         d.b = add_slot(p + std::to_string(idx) + ".bias", d.out, TCVN_SLOT_PARAM);
@@ -145,289 +146,309 @@ void HeadPlan::layout(int B, int P, int nP, HLayout& L) const {
     L.total = b.off;
 }
 
-// ---- stage 1: combined embedding (LinearBlock over event + packed prong rows) and the token gather -> L.X[0] ------------
-int HeadPlan::embed(int B, int P, int nP, const float* rows, const int32_t* tok_row, char* ws, const HLayout& L, int train,
-                    uint64_t seed, hipStream_t st) {
-    const int D = cfg.hidden_dim, S = 1 + P, R = B + nP;
-    const float dp = train ? cfg.dropout : 0.f;
-    auto F = [&](long off) { return reinterpret_cast<float*>(ws + off); };
-    int rc;
-    if ((rc = linear_fwd(rows, cfg.in_dim, data[cw], cb >= 0 ? data[cb] : nullptr, F(L.Zc), D, R, D, cfg.in_dim, st))) return rc;
-    RowsBnArgs r{};
-    r.X = F(L.Zc); r.ldx = D; r.R = R; r.C = D; r.slope = ca >= 0 ? data[ca] : nullptr; r.no_norm = cfg.no_linear_bn;
-    if (!r.no_norm) { r.gamma = data[cn.w]; r.beta = data[cn.b]; r.running_mean = data[cn.rm]; r.running_var = data[cn.rv]; }
-    r.Y = F(L.C); r.ldy = D;
-    r.save_mean = F(L.cstat); r.save_rstd = F(L.cstat) + D; r.train = train; r.eps = kEps; r.momentum = kMom;
-    r.drop_p = dp; r.seed = seed; r.stream_id = 0x5000u;
-    if ((rc = rows_bn_fwd(r, st))) return rc;
-    return gather_tokens(F(L.C), tok_row, F(L.X[0]), B, S, D, st);
-}
-
-// ---- stage 2: transformer encoder, L.X[0] (sequence-major tokens, padding rows zero) -> L.HID (masked) ------------------
-int HeadPlan::encode(int B, int P, const int32_t* tok_row, char* ws, const HLayout& L, int train, uint64_t seed, hipStream_t st) {
-    const int D = cfg.hidden_dim, S = 1 + P, T = S * B, H = cfg.heads, hd = D / H;
-    const float dp = train ? cfg.dropout : 0.f;
-    auto F = [&](long off) { return reinterpret_cast<float*>(ws + off); };
-    int rc;
-    if (fused_encoder && encoder_fused_ok(S, D, H, cfg.n_layers, cfg.norm_first)) {      // one launch for the whole stack (+ mask)
-        EncFusedArgs a{};
-        a.X0 = F(L.X[0]); a.tok_row = tok_row; a.HID = F(L.HID); a.B = B; a.S = S; a.H = H; a.L = cfg.n_layers; a.gelu = cfg.gelu;
-        a.save = 1; a.eps = kEps; a.drop_p = dp; a.seed = seed;
-        for (int l = 0; l < cfg.n_layers; ++l) {
-            const HLayer& W = layers[l];
-            const HLayBuf& q = L.lay[l];
-            a.w[l] = EncLayerW{data[W.win], data[W.bin], data[W.wo], data[W.bo], data[W.w1], data[W.b1], data[W.w2], data[W.b2],
-                               data[W.g1], data[W.be1], data[W.g2], data[W.be2]};
-            a.buf[l] = EncLayerBuf{F(q.qkv), F(q.probs), F(q.ctx), F(q.xh1), F(q.rstd1), F(q.x1), F(q.hpre), F(q.hact), F(q.xh2),
-                                   F(q.rstd2), F(L.X[l + 1])};
-        }
-        return encoder_fused_fwd(a, st);
-    }
-    if (cfg.norm_first) {
-        // pre-norm variant (prong_custom_bert_encoder.py:45-52 with transformer_norm_first): x += drop(sa(LN1(x))); x += drop(ff(LN2(x))).
-        // LN(x) is add_ln_fwd with a zero residual branch (t0 is scratch of the backward pass, free here).
-        float* zero = F(L.t0);
-        TCVN_CHECK(hipMemsetAsync(zero, 0, (size_t)T * D * 4, st));
-        for (int l = 0; l < cfg.n_layers; ++l) {
-            const HLayer& W = layers[l];
-            const HLayBuf& q = L.lay[l];
-            const uint32_t sid = 0x6000u + l * 8;
-            AddLnArgs n1{F(L.X[l]), zero, data[W.g1], data[W.be1], F(q.h1), F(q.xh1), F(q.rstd1), T, D, kEps, 0.f, seed, sid + 1};
-            if ((rc = add_ln_fwd(n1, st))) return rc;
-            if ((rc = linear_fwd(F(q.h1), D, data[W.win], data[W.bin], F(q.qkv), 3 * D, T, 3 * D, D, st))) return rc;
-            AttnArgs a{F(q.qkv), tok_row, F(q.probs), F(q.ctx), B, S, H, hd, dp, seed, sid};
-            if ((rc = attn_fwd(a, st))) return rc;
-            if ((rc = linear_fwd(F(q.ctx), D, data[W.wo], data[W.bo], F(q.ao), D, T, D, D, st))) return rc;
-            if ((rc = add_drop(F(L.X[l]), F(q.ao), F(q.x1), (long)T * D, dp, seed, sid + 1, st))) return rc;
-            AddLnArgs n2{F(q.x1), zero, data[W.g2], data[W.be2], F(q.h2), F(q.xh2), F(q.rstd2), T, D, kEps, 0.f, seed, sid + 3};
-            if ((rc = add_ln_fwd(n2, st))) return rc;
-            if ((rc = linear_fwd(F(q.h2), D, data[W.w1], data[W.b1], F(q.hpre), D, T, D, D, st))) return rc;
-            if ((rc = act_fwd(F(q.hpre), F(q.hact), (long)T * D, cfg.gelu, dp, seed, sid + 2, st))) return rc;
-            if ((rc = linear_fwd(F(q.hact), D, data[W.w2], data[W.b2], F(q.f), D, T, D, D, st))) return rc;
-            if ((rc = add_drop(F(q.x1), F(q.f), F(L.X[l + 1]), (long)T * D, dp, seed, sid + 3, st))) return rc;
-        }
-        return mask_rows(F(L.X[cfg.n_layers]), tok_row, F(L.HID), B, S, D, st);
-    }
-    for (int l = 0; l < cfg.n_layers; ++l) {
-        const HLayer& W = layers[l];
-        const HLayBuf& q = L.lay[l];
-        const uint32_t sid = 0x6000u + l * 8;
-        if ((rc = linear_fwd(F(L.X[l]), D, data[W.win], data[W.bin], F(q.qkv), 3 * D, T, 3 * D, D, st))) return rc;
-        AttnArgs a{F(q.qkv), tok_row, F(q.probs), F(q.ctx), B, S, H, hd, dp, seed, sid};
-        if ((rc = attn_fwd(a, st))) return rc;
-        if ((rc = linear_fwd(F(q.ctx), D, data[W.wo], data[W.bo], F(q.ao), D, T, D, D, st))) return rc;
-        AddLnArgs n1{F(L.X[l]), F(q.ao), data[W.g1], data[W.be1], F(q.x1), F(q.xh1), F(q.rstd1), T, D, kEps, dp, seed, sid + 1};
-        if ((rc = add_ln_fwd(n1, st))) return rc;
-        if ((rc = linear_fwd(F(q.x1), D, data[W.w1], data[W.b1], F(q.hpre), D, T, D, D, st))) return rc;
-        if ((rc = act_fwd(F(q.hpre), F(q.hact), (long)T * D, cfg.gelu, dp, seed, sid + 2, st))) return rc;
-        if ((rc = linear_fwd(F(q.hact), D, data[W.w2], data[W.b2], F(q.f), D, T, D, D, st))) return rc;
-        AddLnArgs n2{F(q.x1), F(q.f), data[W.g2], data[W.be2], F(L.X[l + 1]), F(q.xh2), F(q.rstd2), T, D, kEps, dp, seed, sid + 3};
-        if ((rc = add_ln_fwd(n2, st))) return rc;
-    }
-    return mask_rows(F(L.X[cfg.n_layers]), tok_row, F(L.HID), B, S, D, st);
-}
-
-// ---- stage 3: event decoder on token 0, prong decoder on tokens 1..P of L.HID -------------------------------------------
-int HeadPlan::decode(int B, int P, float* ev_logits, float* pr_logits, char* ws, const HLayout& L, int train, uint64_t seed,
-                     hipStream_t st) {
-    const int D = cfg.hidden_dim, TP = P * B;
-    const float dp = train ? cfg.dropout : 0.f;
-    auto F = [&](long off) { return reinterpret_cast<float*>(ws + off); };
-    int rc;
-    if (ev_logits && (rc = linear_fwd(F(L.HID), D, data[ew], data[eb], ev_logits, cfg.event_classes, B, cfg.event_classes, D, st))) return rc;
-    if (!pr_logits || TP == 0) return 0;
-    const float* in = F(L.HID) + (long)B * D;
-    int inw = D;
-    for (size_t i = 0; i < dec.size(); ++i) {
-        const HDec& d = dec[i];
-        if ((rc = linear_fwd(in, inw, data[d.w], data[d.b], F(L.Zd[i]), d.out, TP, d.out, d.in, st))) return rc;
-        RowsBnArgs r{};
-        r.X = F(L.Zd[i]); r.ldx = d.out; r.R = TP; r.C = d.out; r.slope = d.a >= 0 ? data[d.a] : nullptr; r.no_norm = cfg.no_linear_bn;
-        if (!r.no_norm) { r.gamma = data[d.n.w]; r.beta = data[d.n.b]; r.running_mean = data[d.n.rm]; r.running_var = data[d.n.rv]; }
-        r.Y = F(L.Ad[i]); r.ldy = d.out;
-        r.save_mean = F(L.dstat[i]); r.save_rstd = F(L.dstat[i]) + d.out; r.train = train; r.eps = kEps; r.momentum = kMom;
-        r.drop_p = cfg.dropout_modules ? dp : 0.f; r.seed = seed; r.stream_id = 0x7000u + (uint32_t)i;
-        if ((rc = rows_bn_fwd(r, st))) return rc;
-        in = F(L.Ad[i]); inw = d.out;
-    }
-    if ((rc = linear_fwd(in, inw, data[ow], data[ob], F(L.LG), cfg.prong_classes, TP, cfg.prong_classes, cfg.dec_out_in, st))) return rc;
-    return permute_rows(F(L.LG), pr_logits, B, P, cfg.prong_classes, 1, st);
-}
-
-int HeadPlan::check(int B, int P, int nP, long ws_bytes, HLayout& L) const {
+// ---- the step: what check() was, plus every shape constant the drivers derive from (B, P, nP) ---------------------------------
+int HeadPlan::step(int B, int P, int nP, void* ws, long ws_bytes, int train, uint64_t seed, hipStream_t st, HeadStep& s) const {
     if (!bound) return -11;
     if (cfg.dec_out_in != dec_width) { fprintf(stderr, "tcvn: prong decoder width mismatch (reference would fail too)\n"); return -21; }
     if (B <= 0 || P < 0 || nP < 0 || 1 + P > 64) return -1;          // attention kernel: sequences up to 64 tokens
-    layout(B, P, nP, L);
-    return ws_bytes < L.total ? -12 : 0;
+    s.B = B; s.P = P; s.nP = nP; s.S = 1 + P; s.T = s.S * B; s.R = B + nP; s.TP = P * B;
+    s.ws = reinterpret_cast<char*>(ws); s.train = train; s.seed = seed; s.dp = train ? cfg.dropout : 0.f; s.st = st;
+    layout(B, P, nP, s.L);
+    return ws_bytes < s.L.total ? -12 : 0;
+}
+
+// The ONE place that chooses the encoder's kernels: encode() and backward() switch on it
+EncPath HeadPlan::enc_path(int S) const {
+    if (fused_encoder && encoder_fused_ok(S, cfg.hidden_dim, cfg.heads, cfg.n_layers, cfg.norm_first)) return EncPath::FUSED;
+    return cfg.norm_first ? EncPath::PRE_NORM : EncPath::POST_NORM;
+}
+
+// ---- launch arguments shared by forward and backward ----------------------------------------------------------------------
+EncLayerW HeadPlan::enc_w(int l) const {
+    const HLayer& W = layers[l];
+    return EncLayerW{data[W.win], data[W.bin], data[W.wo], data[W.bo], data[W.w1], data[W.b1], data[W.w2], data[W.b2],
+                     data[W.g1], data[W.be1], data[W.g2], data[W.be2]};
+}
+EncLayerBuf HeadPlan::enc_buf(const HeadStep& s, int l) const {
+    const HLayBuf& q = s.L.lay[l];
+    return EncLayerBuf{s.F(q.qkv), s.F(q.probs), s.F(q.ctx), s.F(q.xh1), s.F(q.rstd1), s.F(q.x1), s.F(q.hpre), s.F(q.hact), s.F(q.xh2),
+                       s.F(q.rstd2), s.F(s.L.X[l + 1])};
+}
+// LinearBlock behind its Linear: X [rows][d.out] -> Y, batch statistics kept at stat; the backward takes dY back to dX
+RowsBnArgs HeadPlan::block_fwd(const HDec& d, const HeadStep& s, long X, long Y, long stat, int rows) const {
+    RowsBnArgs r{};
+    r.X = s.F(X); r.ldx = d.out; r.R = rows; r.C = d.out; r.slope = d.a >= 0 ? data[d.a] : nullptr; r.no_norm = cfg.no_linear_bn;
+    if (!r.no_norm) { r.gamma = data[d.n.w]; r.beta = data[d.n.b]; r.running_mean = data[d.n.rm]; r.running_var = data[d.n.rv]; }
+    r.Y = s.F(Y); r.ldy = d.out;
+    r.save_mean = s.F(stat); r.save_rstd = s.F(stat) + d.out; r.train = s.train; r.eps = kEps; r.momentum = kMom;
+    r.drop_p = d.drop ? s.dp : 0.f; r.seed = s.seed; r.stream_id = d.sid;
+    return r;
+}
+RowsBnBwdArgs HeadPlan::block_bwd(const HDec& d, const HeadStep& s, long X, long dY, long stat, long dX, int rows) const {
+    RowsBnBwdArgs r{};
+    r.X = s.F(X); r.ldx = d.out; r.dY = s.F(dY); r.lddy = d.out; r.R = rows; r.C = d.out;
+    r.no_norm = cfg.no_linear_bn; r.slope = d.a >= 0 ? data[d.a] : nullptr; r.dslope = d.a >= 0 ? grad[d.a] : nullptr;
+    if (!r.no_norm) { r.gamma = data[d.n.w]; r.beta = data[d.n.b]; r.dgamma = grad[d.n.w]; r.dbeta = grad[d.n.b]; }
+    r.save_mean = s.F(stat); r.save_rstd = s.F(stat) + d.out;
+    r.dX = s.F(dX); r.lddx = d.out;
+    r.drop_p = d.drop ? s.dp : 0.f; r.seed = s.seed; r.stream_id = d.sid;
+    return r;
+}
+// The prong decoder chain: layer i (i == n_dec: the output layer) reads the prong tokens of HID (i == 0) or the block before it, and
+// its input gradient goes to the prong rows of dHID or to the scratch t0 that the block before reads as its dY.
+DecIn HeadPlan::dec_in(const HeadStep& s, int i) const {
+    const long hid_prongs = (long)s.B * cfg.hidden_dim;
+    if (i == 0) return DecIn{s.F(s.L.HID) + hid_prongs, s.F(s.L.dHID) + hid_prongs, cfg.hidden_dim};
+    return DecIn{s.F(s.L.Ad[i - 1]), s.F(s.L.t0), dec[i - 1].out};
+}
+
+// ---- stage 1: combined embedding (LinearBlock over event + packed prong rows) and the token gather -> L.X[0] ------------
+int HeadPlan::embed(const HeadStep& s, const float* rows, const int32_t* tok_row) const {
+    const HLayout& L = s.L;
+    const int D = cfg.hidden_dim;
+    if (int rc = linear_fwd(rows, cfg.in_dim, data[comb.w], comb.b >= 0 ? data[comb.b] : nullptr, s.F(L.Zc), D, s.R, D, cfg.in_dim, s.st)) return rc;
+    if (int rc = rows_bn_fwd(block_fwd(comb, s, L.Zc, L.C, L.cstat, s.R), s.st)) return rc;
+    return gather_tokens(s.F(L.C), tok_row, s.F(L.X[0]), s.B, s.S, D, s.st);
+}
+
+// ---- stage 2: transformer encoder, L.X[0] (sequence-major tokens, padding rows zero) -> L.HID (masked) ------------------
+int HeadPlan::encode(const HeadStep& s, const int32_t* tok_row) const {
+    switch (enc_path(s.S)) {
+    case EncPath::FUSED: {                                      // one launch for the whole stack (+ mask)
+        EncFusedArgs a{};
+        a.X0 = s.F(s.L.X[0]); a.tok_row = tok_row; a.HID = s.F(s.L.HID); a.B = s.B; a.S = s.S; a.H = cfg.heads; a.L = cfg.n_layers;
+        a.gelu = cfg.gelu; a.save = 1; a.eps = kEps; a.drop_p = s.dp; a.seed = s.seed;
+        for (int l = 0; l < cfg.n_layers; ++l) { a.w[l] = enc_w(l); a.buf[l] = enc_buf(s, l); }
+        return encoder_fused_fwd(a, s.st);
+    }
+    case EncPath::POST_NORM: return encode_post(s, tok_row);
+    case EncPath::PRE_NORM: return encode_pre(s, tok_row);
+    }
+    return -1;
+}
+int HeadPlan::encode_post(const HeadStep& s, const int32_t* tok_row) const {
+    const HLayout& L = s.L;
+    const int D = cfg.hidden_dim, T = s.T, H = cfg.heads, hd = D / H;
+    for (int l = 0; l < cfg.n_layers; ++l) {
+        const HLayer& W = layers[l];
+        const HLayBuf& q = L.lay[l];
+        if (int rc = linear_fwd(s.F(L.X[l]), D, data[W.win], data[W.bin], s.F(q.qkv), 3 * D, T, 3 * D, D, s.st)) return rc;
+        AttnArgs a{s.F(q.qkv), tok_row, s.F(q.probs), s.F(q.ctx), s.B, s.S, H, hd, s.dp, s.seed, sid_enc(l, 0)};
+        if (int rc = attn_fwd(a, s.st)) return rc;
+        if (int rc = linear_fwd(s.F(q.ctx), D, data[W.wo], data[W.bo], s.F(q.ao), D, T, D, D, s.st)) return rc;
+        AddLnArgs n1{s.F(L.X[l]), s.F(q.ao), data[W.g1], data[W.be1], s.F(q.x1), s.F(q.xh1), s.F(q.rstd1), T, D, kEps, s.dp, s.seed, sid_enc(l, 1)};
+        if (int rc = add_ln_fwd(n1, s.st)) return rc;
+        if (int rc = linear_fwd(s.F(q.x1), D, data[W.w1], data[W.b1], s.F(q.hpre), D, T, D, D, s.st)) return rc;
+        if (int rc = act_fwd(s.F(q.hpre), s.F(q.hact), (long)T * D, cfg.gelu, s.dp, s.seed, sid_enc(l, 2), s.st)) return rc;
+        if (int rc = linear_fwd(s.F(q.hact), D, data[W.w2], data[W.b2], s.F(q.f), D, T, D, D, s.st)) return rc;
+        AddLnArgs n2{s.F(q.x1), s.F(q.f), data[W.g2], data[W.be2], s.F(L.X[l + 1]), s.F(q.xh2), s.F(q.rstd2), T, D, kEps, s.dp, s.seed, sid_enc(l, 3)};
+        if (int rc = add_ln_fwd(n2, s.st)) return rc;
+    }
+    return mask_rows(s.F(L.X[cfg.n_layers]), tok_row, s.F(L.HID), s.B, s.S, D, s.st);
+}
+// pre-norm variant (prong_custom_bert_encoder.py:45-52 with transformer_norm_first): x += drop(sa(LN1(x))); x += drop(ff(LN2(x))).
+// LN(x) is add_ln_fwd with a zero residual branch (t0 is scratch of the backward pass, free here).
+int HeadPlan::encode_pre(const HeadStep& s, const int32_t* tok_row) const {
+    const HLayout& L = s.L;
+    const int D = cfg.hidden_dim, T = s.T, H = cfg.heads, hd = D / H;
+    float* zero = s.F(L.t0);
+    TCVN_CHECK(hipMemsetAsync(zero, 0, (size_t)T * D * 4, s.st));
+    for (int l = 0; l < cfg.n_layers; ++l) {
+        const HLayer& W = layers[l];
+        const HLayBuf& q = L.lay[l];
+        AddLnArgs n1{s.F(L.X[l]), zero, data[W.g1], data[W.be1], s.F(q.h1), s.F(q.xh1), s.F(q.rstd1), T, D, kEps, 0.f, s.seed, sid_enc(l, 1)};
+        if (int rc = add_ln_fwd(n1, s.st)) return rc;
+        if (int rc = linear_fwd(s.F(q.h1), D, data[W.win], data[W.bin], s.F(q.qkv), 3 * D, T, 3 * D, D, s.st)) return rc;
+        AttnArgs a{s.F(q.qkv), tok_row, s.F(q.probs), s.F(q.ctx), s.B, s.S, H, hd, s.dp, s.seed, sid_enc(l, 0)};
+        if (int rc = attn_fwd(a, s.st)) return rc;
+        if (int rc = linear_fwd(s.F(q.ctx), D, data[W.wo], data[W.bo], s.F(q.ao), D, T, D, D, s.st)) return rc;
+        if (int rc = add_drop(s.F(L.X[l]), s.F(q.ao), s.F(q.x1), (long)T * D, s.dp, s.seed, sid_enc(l, 1), s.st)) return rc;
+        AddLnArgs n2{s.F(q.x1), zero, data[W.g2], data[W.be2], s.F(q.h2), s.F(q.xh2), s.F(q.rstd2), T, D, kEps, 0.f, s.seed, sid_enc(l, 3)};
+        if (int rc = add_ln_fwd(n2, s.st)) return rc;
+        if (int rc = linear_fwd(s.F(q.h2), D, data[W.w1], data[W.b1], s.F(q.hpre), D, T, D, D, s.st)) return rc;
+        if (int rc = act_fwd(s.F(q.hpre), s.F(q.hact), (long)T * D, cfg.gelu, s.dp, s.seed, sid_enc(l, 2), s.st)) return rc;
+        if (int rc = linear_fwd(s.F(q.hact), D, data[W.w2], data[W.b2], s.F(q.f), D, T, D, D, s.st)) return rc;
+        if (int rc = add_drop(s.F(q.x1), s.F(q.f), s.F(L.X[l + 1]), (long)T * D, s.dp, s.seed, sid_enc(l, 3), s.st)) return rc;
+    }
+    return mask_rows(s.F(L.X[cfg.n_layers]), tok_row, s.F(L.HID), s.B, s.S, D, s.st);
+}
+
+// ---- stage 3: event decoder on token 0, prong decoder on tokens 1..P of L.HID -------------------------------------------
+int HeadPlan::decode(const HeadStep& s, float* ev_logits, float* pr_logits) const {
+    const HLayout& L = s.L;
+    const int D = cfg.hidden_dim, TP = s.TP, n_dec = (int)dec.size();
+    if (ev_logits)
+        if (int rc = linear_fwd(s.F(L.HID), D, data[ew], data[eb], ev_logits, cfg.event_classes, s.B, cfg.event_classes, D, s.st)) return rc;
+    if (!pr_logits || TP == 0) return 0;
+    for (int i = 0; i < n_dec; ++i) {
+        const HDec& d = dec[i];
+        const DecIn in = dec_in(s, i);
+        if (int rc = linear_fwd(in.x, in.w, data[d.w], data[d.b], s.F(L.Zd[i]), d.out, TP, d.out, d.in, s.st)) return rc;
+        if (int rc = rows_bn_fwd(block_fwd(d, s, L.Zd[i], L.Ad[i], L.dstat[i], TP), s.st)) return rc;
+    }
+    const DecIn in = dec_in(s, n_dec);
+    if (int rc = linear_fwd(in.x, in.w, data[ow], data[ob], s.F(L.LG), cfg.prong_classes, TP, cfg.prong_classes, cfg.dec_out_in, s.st)) return rc;
+    return permute_rows(s.F(L.LG), pr_logits, s.B, s.P, cfg.prong_classes, 1, s.st);
 }
 
 int HeadPlan::forward(int B, int P, int nP, const float* rows, const int32_t* tok_row, float* ev_logits, float* pr_logits,
-                      char* ws, long ws_bytes, int train, uint64_t seed, hipStream_t st) {
-    HLayout L;
-    int rc;
-    if ((rc = check(B, P, nP, ws_bytes, L))) return rc;
-    if ((rc = embed(B, P, nP, rows, tok_row, ws, L, train, seed, st))) return rc;
-    if ((rc = encode(B, P, tok_row, ws, L, train, seed, st))) return rc;
-    if ((rc = decode(B, P, ev_logits, pr_logits, ws, L, train, seed, st))) return rc;
-    last_seed = seed; last_train = train;
+                      void* ws, long ws_bytes, int train, uint64_t seed, hipStream_t st) {
+    HeadStep s;
+    if (int rc = step(B, P, nP, ws, ws_bytes, train, seed, st, s)) return rc;
+    if (int rc = embed(s, rows, tok_row)) return rc;
+    if (int rc = encode(s, tok_row)) return rc;
+    if (int rc = decode(s, ev_logits, pr_logits)) return rc;
+    last_seed = seed;
     return 0;
 }
 
 int HeadPlan::loss(int B, int P, const float* ev_logits, const float* pr_logits, const int64_t* et, const int8_t* pt, float* losses,
                    float* accs, float* dEv, float* dPr, hipStream_t st) {
-    int rc;
     float* lb = accs + 2;                       // accs has room for 2 + 4 floats (scratch behind the two accuracies)
-    if ((rc = focal_i64(ev_logits, et, B, cfg.event_classes, cfg.gamma, cfg.event_weight, dEv, lb, st))) return rc;
-    if ((rc = focal_i8(pr_logits, pt, B * P, cfg.prong_classes, cfg.gamma, 1.f - cfg.event_weight, dPr, lb + 2, st))) return rc;
+    if (int rc = focal_i64(ev_logits, et, B, cfg.event_classes, cfg.gamma, cfg.event_weight, dEv, lb, st)) return rc;
+    if (int rc = focal_i8(pr_logits, pt, B * P, cfg.prong_classes, cfg.gamma, 1.f - cfg.event_weight, dPr, lb + 2, st)) return rc;
     hipLaunchKernelGGL(k_combine_loss, dim3(1), dim3(1), 0, st, lb, lb + 2, cfg.event_weight, losses, accs);
     TCVN_LAUNCH_CHECK();
     return 0;
 }
 
+// ---- backward: decoders -> dHID, mask, encoder (one of three paths) -> d X[0], combined embedding -> d_rows ----------------
 int HeadPlan::backward(int B, int P, int nP, const float* rows, const int32_t* tok_row, const float* dEv, const float* dPr,
-                       float* d_rows, char* ws, long ws_bytes, hipStream_t st) {
-    if (!bound) return -11;
-    for (size_t i = 0; i < slots.size(); ++i)
-        if (slots[i].kind == TCVN_SLOT_PARAM && grad[i] == nullptr) return -14;
-    HLayout L;
-    layout(B, P, nP, L);
-    if (ws_bytes < L.total) return -12;
-    const int D = cfg.hidden_dim, S = 1 + P, T = S * B, R = B + nP, TP = P * B, H = cfg.heads, hd = D / H;
-    const int Ce = cfg.event_classes, Cp = cfg.prong_classes;
-    const float dp = cfg.dropout;
-    const uint64_t seed = last_seed;
-    auto F = [&](long off) { return reinterpret_cast<float*>(ws + off); };
-    int rc;
-    // ---- prong decoder ----
-    if ((rc = permute_rows(dPr, F(L.dLG), B, P, Cp, 0, st))) return rc;
-    float* dHID = F(L.dHID);
-    const float* last_in = dec.empty() ? F(L.HID) + (long)B * D : F(L.Ad[dec.size() - 1]);
-    const int last_w = dec.empty() ? D : dec.back().out;
-    if ((rc = linear_bwd_dw(F(L.dLG), Cp, last_in, last_w, grad[ow], grad[ob], TP, Cp, last_w, st))) return rc;
-    float* dA = F(L.t0);
-    float* dZ = F(L.t1);
-    float* dst0 = dec.empty() ? dHID + (long)B * D : dA;
-    if ((rc = linear_bwd_dx(F(L.dLG), Cp, data[ow], dst0, dec.empty() ? D : last_w, TP, Cp, last_w, 0, st))) return rc;
-    for (int i = (int)dec.size() - 1; i >= 0; --i) {
+                       float* d_rows, void* ws, long ws_bytes, hipStream_t st) {
+    if (bound)                                   // an unbound plan is the step's -11, which comes first
+        for (size_t i = 0; i < slots.size(); ++i)
+            if (slots[i].kind == TCVN_SLOT_PARAM && grad[i] == nullptr) return -14;
+    // train = 1 always: backward replays the masks of cfg.dropout whatever the forward's train flag was (the backward of an
+    // eval-mode forward is not supported; callers run it after train-mode forwards only)
+    HeadStep s;
+    if (int rc = step(B, P, nP, ws, ws_bytes, 1, last_seed, st, s)) return rc;
+    if (int rc = decoders_bwd(s, dEv, dPr)) return rc;
+    float* dX = s.F(s.L.t2);
+    if (int rc = mask_rows(s.F(s.L.dHID), tok_row, dX, B, s.S, cfg.hidden_dim, st)) return rc;
+    int rc = 0;
+    switch (enc_path(s.S)) {
+    case EncPath::FUSED: rc = encoder_bwd_fused(s, dX, s.F(s.L.t3)); dX = s.F(s.L.t3); break;
+    case EncPath::POST_NORM: rc = encoder_bwd_post(s, dX); break;
+    case EncPath::PRE_NORM: rc = encoder_bwd_pre(s, dX); break;
+    }
+    return rc ? rc : embed_bwd(s, dX, rows, tok_row, d_rows);
+}
+
+// prong decoder (output layer, then the blocks last to first) and event decoder -> dHID
+int HeadPlan::decoders_bwd(const HeadStep& s, const float* dEv, const float* dPr) const {
+    const HLayout& L = s.L;
+    const int D = cfg.hidden_dim, TP = s.TP, Ce = cfg.event_classes, Cp = cfg.prong_classes, n_dec = (int)dec.size();
+    if (int rc = permute_rows(dPr, s.F(L.dLG), s.B, s.P, Cp, 0, s.st)) return rc;
+    const DecIn last = dec_in(s, n_dec);
+    if (int rc = linear_bwd_dw(s.F(L.dLG), Cp, last.x, last.w, grad[ow], grad[ob], TP, Cp, last.w, s.st)) return rc;
+    if (int rc = linear_bwd_dx(s.F(L.dLG), Cp, data[ow], last.dx, last.w, TP, Cp, last.w, 0, s.st)) return rc;
+    float* dZ = s.F(L.t1);
+    for (int i = n_dec - 1; i >= 0; --i) {
         const HDec& d = dec[i];
-        RowsBnBwdArgs r{};
-        r.X = F(L.Zd[i]); r.ldx = d.out; r.dY = dA; r.lddy = d.out; r.R = TP; r.C = d.out;
-        r.no_norm = cfg.no_linear_bn; r.slope = d.a >= 0 ? data[d.a] : nullptr; r.dslope = d.a >= 0 ? grad[d.a] : nullptr;
-        if (!r.no_norm) { r.gamma = data[d.n.w]; r.beta = data[d.n.b]; r.dgamma = grad[d.n.w]; r.dbeta = grad[d.n.b]; }
-        r.save_mean = F(L.dstat[i]); r.save_rstd = F(L.dstat[i]) + d.out;
-        r.dX = dZ; r.lddx = d.out;
-        r.drop_p = cfg.dropout_modules ? dp : 0.f; r.seed = seed; r.stream_id = 0x7000u + (uint32_t)i;
-        if ((rc = rows_bn_bwd(r, st))) return rc;
-        const float* in = i == 0 ? F(L.HID) + (long)B * D : F(L.Ad[i - 1]);
-        const int inw = i == 0 ? D : dec[i - 1].out;
-        if ((rc = linear_bwd_dw(dZ, d.out, in, inw, grad[d.w], grad[d.b], TP, d.out, d.in, st))) return rc;
-        float* dIn = i == 0 ? dHID + (long)B * D : dA;
-        if ((rc = linear_bwd_dx(dZ, d.out, data[d.w], dIn, inw, TP, d.out, d.in, 0, st))) return rc;
+        const DecIn in = dec_in(s, i);
+        if (int rc = rows_bn_bwd(block_bwd(d, s, L.Zd[i], L.t0, L.dstat[i], L.t1, TP), s.st)) return rc;       // dY: what layer i + 1 left in t0
+        if (int rc = linear_bwd_dw(dZ, d.out, in.x, in.w, grad[d.w], grad[d.b], TP, d.out, d.in, s.st)) return rc;
+        if (int rc = linear_bwd_dx(dZ, d.out, data[d.w], in.dx, in.w, TP, d.out, d.in, 0, s.st)) return rc;
     }
-    // ---- event decoder ----
-    if ((rc = linear_bwd_dw(dEv, Ce, F(L.HID), D, grad[ew], grad[eb], B, Ce, D, st))) return rc;
-    if ((rc = linear_bwd_dx(dEv, Ce, data[ew], dHID, D, B, Ce, D, 0, st))) return rc;
-    // ---- encoder ----
-    float* dX = F(L.t2);
-    if ((rc = mask_rows(dHID, tok_row, dX, B, S, D, st))) return rc;
-    if (fused_encoder && encoder_fused_ok(S, D, H, cfg.n_layers, cfg.norm_first)) {
-        // chain kernel (one workgroup per event) + grouped weight-gradient launch; dX is rewritten in place (t3 -> t2 not needed)
-        EncFusedBwdArgs a{};
-        a.dY = dX; a.dX = F(L.t3); a.lnp = F(L.lnp); a.B = B; a.S = S; a.H = H; a.L = cfg.n_layers; a.gelu = cfg.gelu;
-        a.drop_p = dp; a.seed = seed;
-        EncWgradArgs w{};
-        w.T = T; w.B = B; w.L = cfg.n_layers; w.lnp = F(L.lnp);
-        int nj = 0, nt = 0;
-        for (int l = 0; l < cfg.n_layers; ++l) {
-            const HLayer& W = layers[l];
-            const HLayBuf& q = L.lay[l];
-            a.w[l] = EncLayerW{data[W.win], data[W.bin], data[W.wo], data[W.bo], data[W.w1], data[W.b1], data[W.w2], data[W.b2],
-                               data[W.g1], data[W.be1], data[W.g2], data[W.be2]};
-            a.buf[l] = EncLayerBuf{F(q.qkv), F(q.probs), F(q.ctx), F(q.xh1), F(q.rstd1), F(q.x1), F(q.hpre), F(q.hact), F(q.xh2),
-                                   F(q.rstd2), F(L.X[l + 1])};
-            a.g[l] = EncLayerGrad{F(q.g_dqkv), F(q.g_dao), F(q.g_dhp), F(q.g_df)};
-            w.job[nj++] = EncWgradJob{F(q.g_dqkv), 3 * D, F(L.X[l]), grad[W.win], grad[W.bin], 3 * D / 32};
-            w.job[nj++] = EncWgradJob{F(q.g_dao), D, F(q.ctx), grad[W.wo], grad[W.bo], D / 32};
-            w.job[nj++] = EncWgradJob{F(q.g_dhp), D, F(q.x1), grad[W.w1], grad[W.b1], D / 32};
-            w.job[nj++] = EncWgradJob{F(q.g_df), D, F(q.hact), grad[W.w2], grad[W.b2], D / 32};
-            nt += 3 * D / 32 + 3 * (D / 32);
-            w.ln_dst[l][0] = grad[W.g1]; w.ln_dst[l][1] = grad[W.be1]; w.ln_dst[l][2] = grad[W.g2]; w.ln_dst[l][3] = grad[W.be2];
-        }
-        w.n_jobs = nj; w.n_tiles = nt;
-        if ((rc = encoder_fused_bwd(a, w, st))) return rc;
-        dX = F(L.t3);
-        goto combined;
+    if (int rc = linear_bwd_dw(dEv, Ce, s.F(L.HID), D, grad[ew], grad[eb], s.B, Ce, D, s.st)) return rc;
+    return linear_bwd_dx(dEv, Ce, data[ew], s.F(L.dHID), D, s.B, Ce, D, 0, s.st);
+}
+
+// chain kernel (one workgroup per event) + grouped weight-gradient launch: dY = d HID (masked) -> dX = d X[0]
+int HeadPlan::encoder_bwd_fused(const HeadStep& s, const float* dY, float* dX) const {
+    const HLayout& L = s.L;
+    const int D = cfg.hidden_dim;
+    EncFusedBwdArgs a{};
+    a.dY = dY; a.dX = dX; a.lnp = s.F(L.lnp); a.B = s.B; a.S = s.S; a.H = cfg.heads; a.L = cfg.n_layers; a.gelu = cfg.gelu;
+    a.drop_p = s.dp; a.seed = s.seed;
+    EncWgradArgs w{};
+    w.T = s.T; w.B = s.B; w.L = cfg.n_layers; w.lnp = s.F(L.lnp);
+    int nj = 0, nt = 0;
+    for (int l = 0; l < cfg.n_layers; ++l) {
+        const HLayer& W = layers[l];
+        const HLayBuf& q = L.lay[l];
+        a.w[l] = enc_w(l); a.buf[l] = enc_buf(s, l);
+        a.g[l] = EncLayerGrad{s.F(q.g_dqkv), s.F(q.g_dao), s.F(q.g_dhp), s.F(q.g_df)};
+        w.job[nj++] = EncWgradJob{s.F(q.g_dqkv), 3 * D, s.F(L.X[l]), grad[W.win], grad[W.bin], 3 * D / 32};
+        w.job[nj++] = EncWgradJob{s.F(q.g_dao), D, s.F(q.ctx), grad[W.wo], grad[W.bo], D / 32};
+        w.job[nj++] = EncWgradJob{s.F(q.g_dhp), D, s.F(q.x1), grad[W.w1], grad[W.b1], D / 32};
+        w.job[nj++] = EncWgradJob{s.F(q.g_df), D, s.F(q.hact), grad[W.w2], grad[W.b2], D / 32};
+        nt += 3 * D / 32 + 3 * (D / 32);
+        w.ln_dst[l][0] = grad[W.g1]; w.ln_dst[l][1] = grad[W.be1]; w.ln_dst[l][2] = grad[W.g2]; w.ln_dst[l][3] = grad[W.be2];
     }
-    {
-    float* d1 = F(L.t3);
-    float* dR = F(L.t0);
-    float* dT = F(L.t1);
-    if (cfg.norm_first) {
-        // dX = d x_{l+1}.  d x1 = dX + LN2'(d h2) ; d x_l = d x1 + LN1'(d h1); the dropped branches carry drop * gradient.
-        float* dS = F(L.dHID);                                   // LayerNorm input gradients (dHID is consumed by now)
-        for (int l = cfg.n_layers - 1; l >= 0; --l) {
-            const HLayer& W = layers[l];
-            const HLayBuf& q = L.lay[l];
-            const uint32_t sid = 0x6000u + l * 8;
-            const long n = (long)T * D;
-            if ((rc = mul_drop(dX, dR, n, dp, seed, sid + 3, st))) return rc;                               // dR = d f
-            if ((rc = linear_bwd_dw(dR, D, F(q.hact), D, grad[W.w2], grad[W.b2], T, D, D, st))) return rc;
-            if ((rc = linear_bwd_dx(dR, D, data[W.w2], dT, D, T, D, D, 0, st))) return rc;                  // dT = d hact
-            if ((rc = act_bwd(F(q.hpre), dT, dR, n, cfg.gelu, dp, seed, sid + 2, st))) return rc;           // dR = d hpre
-            if ((rc = linear_bwd_dw(dR, D, F(q.h2), D, grad[W.w1], grad[W.b1], T, D, D, st))) return rc;
-            if ((rc = linear_bwd_dx(dR, D, data[W.w1], dT, D, T, D, D, 0, st))) return rc;                  // dT = d h2
-            AddLnBwdArgs n2{dT, F(q.xh2), F(q.rstd2), data[W.g2], dS, d1, grad[W.g2], grad[W.be2], T, D, 0.f, seed, sid + 3};
-            if ((rc = add_ln_bwd(n2, st))) return rc;                                                       // dS = LN2 input gradient
-            if ((rc = add_inplace(dX, dS, n, st))) return rc;                                               // dX = d x1
-            if ((rc = mul_drop(dX, dR, n, dp, seed, sid + 1, st))) return rc;                               // dR = d ao
-            if ((rc = linear_bwd_dw(dR, D, F(q.ctx), D, grad[W.wo], grad[W.bo], T, D, D, st))) return rc;
-            if ((rc = linear_bwd_dx(dR, D, data[W.wo], dT, D, T, D, D, 0, st))) return rc;                  // dT = d ctx
-            AttnBwdArgs ab{F(q.qkv), F(q.probs), dT, dR, B, S, H, hd, dp, seed, sid};                       // dR = d qkv [T, 3D]
-            if ((rc = attn_bwd(ab, st))) return rc;
-            if ((rc = linear_bwd_dw(dR, 3 * D, F(q.h1), D, grad[W.win], grad[W.bin], T, 3 * D, D, st))) return rc;
-            if ((rc = linear_bwd_dx(dR, 3 * D, data[W.win], dT, D, T, 3 * D, D, 0, st))) return rc;         // dT = d h1
-            AddLnBwdArgs n1{dT, F(q.xh1), F(q.rstd1), data[W.g1], dS, d1, grad[W.g1], grad[W.be1], T, D, 0.f, seed, sid + 1};
-            if ((rc = add_ln_bwd(n1, st))) return rc;
-            if ((rc = add_inplace(dX, dS, n, st))) return rc;                                               // dX = d x_l
-        }
-    } else
+    w.n_jobs = nj; w.n_tiles = nt;
+    return encoder_fused_bwd(a, w, s.st);
+}
+
+// post-norm layers, last to first: dX = d x_{l+1} on entry, d x_l on exit (in place)
+int HeadPlan::encoder_bwd_post(const HeadStep& s, float* dX) const {
+    const HLayout& L = s.L;
+    const int D = cfg.hidden_dim, T = s.T, H = cfg.heads, hd = D / H;
+    float *d1 = s.F(L.t3), *dR = s.F(L.t0), *dT = s.F(L.t1);
     for (int l = cfg.n_layers - 1; l >= 0; --l) {
         const HLayer& W = layers[l];
         const HLayBuf& q = L.lay[l];
-        const uint32_t sid = 0x6000u + l * 8;
-        AddLnBwdArgs n2{dX, F(q.xh2), F(q.rstd2), data[W.g2], d1, dR, grad[W.g2], grad[W.be2], T, D, dp, seed, sid + 3};
-        if ((rc = add_ln_bwd(n2, st))) return rc;                                   // d1 = d(x1) residual, dR = d(f)
-        if ((rc = linear_bwd_dw(dR, D, F(q.hact), D, grad[W.w2], grad[W.b2], T, D, D, st))) return rc;
-        if ((rc = linear_bwd_dx(dR, D, data[W.w2], dT, D, T, D, D, 0, st))) return rc;      // dT = d(hact)
-        if ((rc = act_bwd(F(q.hpre), dT, dR, (long)T * D, cfg.gelu, dp, seed, sid + 2, st))) return rc;   // dR = d(hpre)
-        if ((rc = linear_bwd_dw(dR, D, F(q.x1), D, grad[W.w1], grad[W.b1], T, D, D, st))) return rc;
-        if ((rc = linear_bwd_dx(dR, D, data[W.w1], d1, D, T, D, D, 1, st))) return rc;      // d1 += through FFN
-        AddLnBwdArgs n1{d1, F(q.xh1), F(q.rstd1), data[W.g1], dX, dR, grad[W.g1], grad[W.be1], T, D, dp, seed, sid + 1};
-        if ((rc = add_ln_bwd(n1, st))) return rc;                                   // dX = d(x_l) residual, dR = d(ao)
-        if ((rc = linear_bwd_dw(dR, D, F(q.ctx), D, grad[W.wo], grad[W.bo], T, D, D, st))) return rc;
-        if ((rc = linear_bwd_dx(dR, D, data[W.wo], dT, D, T, D, D, 0, st))) return rc;      // dT = d(ctx)
-        AttnBwdArgs ab{F(q.qkv), F(q.probs), dT, dR, B, S, H, hd, dp, seed, sid};       // dR = d(qkv) [T, 3D]
-        if ((rc = attn_bwd(ab, st))) return rc;
-        if ((rc = linear_bwd_dw(dR, 3 * D, F(L.X[l]), D, grad[W.win], grad[W.bin], T, 3 * D, D, st))) return rc;
-        if ((rc = linear_bwd_dx(dR, 3 * D, data[W.win], dX, D, T, 3 * D, D, 1, st))) return rc;
+        AddLnBwdArgs n2{dX, s.F(q.xh2), s.F(q.rstd2), data[W.g2], d1, dR, grad[W.g2], grad[W.be2], T, D, s.dp, s.seed, sid_enc(l, 3)};
+        if (int rc = add_ln_bwd(n2, s.st)) return rc;                                   // d1 = d(x1) residual, dR = d(f)
+        if (int rc = linear_bwd_dw(dR, D, s.F(q.hact), D, grad[W.w2], grad[W.b2], T, D, D, s.st)) return rc;
+        if (int rc = linear_bwd_dx(dR, D, data[W.w2], dT, D, T, D, D, 0, s.st)) return rc;      // dT = d(hact)
+        if (int rc = act_bwd(s.F(q.hpre), dT, dR, (long)T * D, cfg.gelu, s.dp, s.seed, sid_enc(l, 2), s.st)) return rc;   // dR = d(hpre)
+        if (int rc = linear_bwd_dw(dR, D, s.F(q.x1), D, grad[W.w1], grad[W.b1], T, D, D, s.st)) return rc;
+        if (int rc = linear_bwd_dx(dR, D, data[W.w1], d1, D, T, D, D, 1, s.st)) return rc;      // d1 += through FFN
+        AddLnBwdArgs n1{d1, s.F(q.xh1), s.F(q.rstd1), data[W.g1], dX, dR, grad[W.g1], grad[W.be1], T, D, s.dp, s.seed, sid_enc(l, 1)};
+        if (int rc = add_ln_bwd(n1, s.st)) return rc;                                   // dX = d(x_l) residual, dR = d(ao)
+        if (int rc = linear_bwd_dw(dR, D, s.F(q.ctx), D, grad[W.wo], grad[W.bo], T, D, D, s.st)) return rc;
+        if (int rc = linear_bwd_dx(dR, D, data[W.wo], dT, D, T, D, D, 0, s.st)) return rc;      // dT = d(ctx)
+        AttnBwdArgs ab{s.F(q.qkv), s.F(q.probs), dT, dR, s.B, s.S, H, hd, s.dp, s.seed, sid_enc(l, 0)};       // dR = d(qkv) [T, 3D]
+        if (int rc = attn_bwd(ab, s.st)) return rc;
+        if (int rc = linear_bwd_dw(dR, 3 * D, s.F(L.X[l]), D, grad[W.win], grad[W.bin], T, 3 * D, D, s.st)) return rc;
+        if (int rc = linear_bwd_dx(dR, 3 * D, data[W.win], dX, D, T, 3 * D, D, 1, s.st)) return rc;
     }
+    return 0;
+}
+
+// pre-norm layers, last to first, dX in place: d x1 = dX + LN2'(d h2); d x_l = d x1 + LN1'(d h1); the dropped branches carry
+// drop * gradient
+int HeadPlan::encoder_bwd_pre(const HeadStep& s, float* dX) const {
+    const HLayout& L = s.L;
+    const int D = cfg.hidden_dim, T = s.T, H = cfg.heads, hd = D / H;
+    const long n = (long)T * D;
+    float *d1 = s.F(L.t3), *dR = s.F(L.t0), *dT = s.F(L.t1);
+    float* dS = s.F(L.dHID);                                   // LayerNorm input gradients (dHID is consumed by now)
+    for (int l = cfg.n_layers - 1; l >= 0; --l) {
+        const HLayer& W = layers[l];
+        const HLayBuf& q = L.lay[l];
+        if (int rc = mul_drop(dX, dR, n, s.dp, s.seed, sid_enc(l, 3), s.st)) return rc;                         // dR = d f
+        if (int rc = linear_bwd_dw(dR, D, s.F(q.hact), D, grad[W.w2], grad[W.b2], T, D, D, s.st)) return rc;
+        if (int rc = linear_bwd_dx(dR, D, data[W.w2], dT, D, T, D, D, 0, s.st)) return rc;                  // dT = d hact
+        if (int rc = act_bwd(s.F(q.hpre), dT, dR, n, cfg.gelu, s.dp, s.seed, sid_enc(l, 2), s.st)) return rc;   // dR = d hpre
+        if (int rc = linear_bwd_dw(dR, D, s.F(q.h2), D, grad[W.w1], grad[W.b1], T, D, D, s.st)) return rc;
+        if (int rc = linear_bwd_dx(dR, D, data[W.w1], dT, D, T, D, D, 0, s.st)) return rc;                  // dT = d h2
+        AddLnBwdArgs n2{dT, s.F(q.xh2), s.F(q.rstd2), data[W.g2], dS, d1, grad[W.g2], grad[W.be2], T, D, 0.f, s.seed, sid_enc(l, 3)};
+        if (int rc = add_ln_bwd(n2, s.st)) return rc;                                                       // dS = LN2 input gradient
+        if (int rc = add_inplace(dX, dS, n, s.st)) return rc;                                               // dX = d x1
+        if (int rc = mul_drop(dX, dR, n, s.dp, s.seed, sid_enc(l, 1), s.st)) return rc;                         // dR = d ao
+        if (int rc = linear_bwd_dw(dR, D, s.F(q.ctx), D, grad[W.wo], grad[W.bo], T, D, D, s.st)) return rc;
+        if (int rc = linear_bwd_dx(dR, D, data[W.wo], dT, D, T, D, D, 0, s.st)) return rc;                  // dT = d ctx
+        AttnBwdArgs ab{s.F(q.qkv), s.F(q.probs), dT, dR, s.B, s.S, H, hd, s.dp, s.seed, sid_enc(l, 0)};     // dR = d qkv [T, 3D]
+        if (int rc = attn_bwd(ab, s.st)) return rc;
+        if (int rc = linear_bwd_dw(dR, 3 * D, s.F(q.h1), D, grad[W.win], grad[W.bin], T, 3 * D, D, s.st)) return rc;
+        if (int rc = linear_bwd_dx(dR, 3 * D, data[W.win], dT, D, T, 3 * D, D, 0, s.st)) return rc;         // dT = d h1
+        AddLnBwdArgs n1{dT, s.F(q.xh1), s.F(q.rstd1), data[W.g1], dS, d1, grad[W.g1], grad[W.be1], T, D, 0.f, s.seed, sid_enc(l, 1)};
+        if (int rc = add_ln_bwd(n1, s.st)) return rc;
+        if (int rc = add_inplace(dX, dS, n, s.st)) return rc;                                               // dX = d x_l
     }
-combined:
-    // ---- combined embedding ----
-    if ((rc = scatter_tokens_bwd(dX, tok_row, F(L.dC), B, S, D, st))) return rc;
-    {
-        RowsBnBwdArgs r{};
-        r.X = F(L.Zc); r.ldx = D; r.dY = F(L.dC); r.lddy = D; r.R = R; r.C = D;
-        r.no_norm = cfg.no_linear_bn; r.slope = ca >= 0 ? data[ca] : nullptr; r.dslope = ca >= 0 ? grad[ca] : nullptr;
-        if (!r.no_norm) { r.gamma = data[cn.w]; r.beta = data[cn.b]; r.dgamma = grad[cn.w]; r.dbeta = grad[cn.b]; }
-        r.save_mean = F(L.cstat); r.save_rstd = F(L.cstat) + D;
-        r.dX = F(L.dZc); r.lddx = D;
-        r.drop_p = dp; r.seed = seed; r.stream_id = 0x5000u;
-        if ((rc = rows_bn_bwd(r, st))) return rc;
-    }
-    if ((rc = linear_bwd_dw(F(L.dZc), D, rows, cfg.in_dim, grad[cw], cb >= 0 ? grad[cb] : nullptr, R, D, cfg.in_dim, st))) return rc;
-    return linear_bwd_dx(F(L.dZc), D, data[cw], d_rows, cfg.in_dim, R, D, cfg.in_dim, 0, st);
+    return 0;
+}
+
+// combined embedding: d X[0] -> token scatter -> LinearBlock -> Linear -> d_rows
+int HeadPlan::embed_bwd(const HeadStep& s, const float* dX0, const float* rows, const int32_t* tok_row, float* d_rows) const {
+    const HLayout& L = s.L;
+    const int D = cfg.hidden_dim;
+    if (int rc = scatter_tokens_bwd(dX0, tok_row, s.F(L.dC), s.B, s.S, D, s.st)) return rc;
+    if (int rc = rows_bn_bwd(block_bwd(comb, s, L.Zc, L.dC, L.cstat, L.dZc, s.R), s.st)) return rc;
+    if (int rc = linear_bwd_dw(s.F(L.dZc), D, rows, cfg.in_dim, grad[comb.w], comb.b >= 0 ? grad[comb.b] : nullptr, s.R, D, cfg.in_dim, s.st)) return rc;
+    return linear_bwd_dx(s.F(L.dZc), D, data[comb.w], d_rows, cfg.in_dim, s.R, D, cfg.in_dim, 0, s.st);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -495,46 +516,36 @@ int64_t tcvn_head_workspace_bytes(const tcvn_head* p, int batch, int max_prongs,
 int tcvn_head_forward(tcvn_head* p, int batch, int max_prongs, int n_prongs, const float* rows, const int32_t* tok_row,
                       float* event_logits, float* prong_logits, void* ws, int64_t ws_bytes, int train, uint64_t seed, void* stream) {
     p->last_np = n_prongs; p->last_b = batch; p->last_p = max_prongs;
-    return p->plan.forward(batch, max_prongs, n_prongs, rows, tok_row, event_logits, prong_logits, reinterpret_cast<char*>(ws),
-                           ws_bytes, train, seed, reinterpret_cast<hipStream_t>(stream));
+    return p->plan.forward(batch, max_prongs, n_prongs, rows, tok_row, event_logits, prong_logits, ws, ws_bytes, train, seed,
+                           reinterpret_cast<hipStream_t>(stream));
 }
 /* stage entry points (forward only): see include/tcvn_hip.h */
 int tcvn_head_embed(tcvn_head* p, int batch, int max_prongs, int n_prongs, const float* rows, const int32_t* tok_row, float* tokens,
                     void* ws, int64_t ws_bytes, int train, uint64_t seed, void* stream) {
-    HLayout L;
-    int rc;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if ((rc = p->plan.check(batch, max_prongs, n_prongs, ws_bytes, L))) return rc;
-    char* w = reinterpret_cast<char*>(ws);
-    if ((rc = p->plan.embed(batch, max_prongs, n_prongs, rows, tok_row, w, L, train, seed, st))) return rc;
-    return permute_rows(reinterpret_cast<float*>(w + L.X[0]), tokens, batch, 1 + max_prongs, p->plan.cfg.hidden_dim, 1, st);
+    HeadStep s;
+    if (int rc = p->plan.step(batch, max_prongs, n_prongs, ws, ws_bytes, train, seed, reinterpret_cast<hipStream_t>(stream), s)) return rc;
+    if (int rc = p->plan.embed(s, rows, tok_row)) return rc;
+    return permute_rows(s.F(s.L.X[0]), tokens, batch, s.S, p->plan.cfg.hidden_dim, 1, s.st);
 }
 int tcvn_head_encode(tcvn_head* p, int batch, int max_prongs, const float* tokens, const int32_t* tok_row, float* hidden, void* ws,
                      int64_t ws_bytes, int train, uint64_t seed, void* stream) {
-    HLayout L;
-    int rc;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if ((rc = p->plan.check(batch, max_prongs, 0, ws_bytes, L))) return rc;
-    char* w = reinterpret_cast<char*>(ws);
-    const int D = p->plan.cfg.hidden_dim, S = 1 + max_prongs;
-    float* X0 = reinterpret_cast<float*>(w + L.X[0]);
-    if ((rc = permute_rows(tokens, X0, batch, S, D, 0, st))) return rc;            // [B,S,D] -> sequence-major rows
-    if ((rc = mask_rows(X0, tok_row, X0, batch, S, D, st))) return rc;             // embeddings * sequence_mask (:69)
-    if ((rc = p->plan.encode(batch, max_prongs, tok_row, w, L, train, seed, st))) return rc;
+    HeadStep s;
+    if (int rc = p->plan.step(batch, max_prongs, 0, ws, ws_bytes, train, seed, reinterpret_cast<hipStream_t>(stream), s)) return rc;
+    const int D = p->plan.cfg.hidden_dim;
+    float* X0 = s.F(s.L.X[0]);
+    if (int rc = permute_rows(tokens, X0, batch, s.S, D, 0, s.st)) return rc;          // [B,S,D] -> sequence-major rows
+    if (int rc = mask_rows(X0, tok_row, X0, batch, s.S, D, s.st)) return rc;           // embeddings * sequence_mask (:69)
+    if (int rc = p->plan.encode(s, tok_row)) return rc;
     p->last_np = 0; p->last_b = batch; p->last_p = max_prongs;
-    TCVN_CHECK(hipMemcpyAsync(hidden, w + L.HID, (size_t)S * batch * D * 4, hipMemcpyDeviceToDevice, st));
+    TCVN_CHECK(hipMemcpyAsync(hidden, s.F(s.L.HID), (size_t)s.T * D * 4, hipMemcpyDeviceToDevice, s.st));
     return 0;
 }
 int tcvn_head_decode(tcvn_head* p, int batch, int max_prongs, const float* hidden, float* event_logits, float* prong_logits,
                      void* ws, int64_t ws_bytes, int train, uint64_t seed, void* stream) {
-    HLayout L;
-    int rc;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if ((rc = p->plan.check(batch, max_prongs, 0, ws_bytes, L))) return rc;
-    char* w = reinterpret_cast<char*>(ws);
-    const int D = p->plan.cfg.hidden_dim, S = 1 + max_prongs;
-    TCVN_CHECK(hipMemcpyAsync(w + L.HID, hidden, (size_t)S * batch * D * 4, hipMemcpyDeviceToDevice, st));
-    return p->plan.decode(batch, max_prongs, event_logits, prong_logits, w, L, train, seed, st);
+    HeadStep s;
+    if (int rc = p->plan.step(batch, max_prongs, 0, ws, ws_bytes, train, seed, reinterpret_cast<hipStream_t>(stream), s)) return rc;
+    TCVN_CHECK(hipMemcpyAsync(s.F(s.L.HID), hidden, (size_t)s.T * p->plan.cfg.hidden_dim * 4, hipMemcpyDeviceToDevice, s.st));
+    return p->plan.decode(s, event_logits, prong_logits);
 }
 
 /* explanation entry points: see include/tcvn_hip.h */
@@ -604,15 +615,13 @@ int tcvn_head_leave_one_out(tcvn_head* p, int batch, int max_prongs, const float
     TCVN_CHECK(hipMemcpyAsync(d_jobs, jobs.data(), (size_t)J * 4, hipMemcpyHostToDevice, st));
     TCVN_CHECK(hipMemcpyAsync(d_src, src.data(), src.size() * 4, hipMemcpyHostToDevice, st));
     TCVN_CHECK(hipStreamSynchronize(st));                                                   // the host vectors are pageable
-    int rc;
     for (int off = 0; off < J; off += o.cap) {
         const int n = J - off < o.cap ? J - off : o.cap;
-        HLayout L;
-        p->plan.layout(n, P, 0, L);
-        char* hw = w + o.head;
-        if ((rc = loo_gather(tokens, tok_row, d_jobs + off, reinterpret_cast<float*>(hw + L.X[0]), d_vrow, n, S, D, st))) return rc;
-        if ((rc = p->plan.encode(n, P, d_vrow, hw, L, 0, 0, st))) return rc;
-        if ((rc = p->plan.decode(n, P, lg + (long)off * Ce, nullptr, hw, L, 0, 0, st))) return rc;
+        HeadStep s;                                                                         // eval arithmetic in the pass's own head workspace
+        if (int rc = p->plan.step(n, P, 0, w + o.head, ws_bytes - o.head, 0, 0, st, s)) return rc;
+        if (int rc = loo_gather(tokens, tok_row, d_jobs + off, s.F(s.L.X[0]), d_vrow, n, S, D, st)) return rc;
+        if (int rc = p->plan.encode(s, d_vrow)) return rc;
+        if (int rc = p->plan.decode(s, lg + (long)off * Ce, nullptr)) return rc;
     }
     return loo_scatter(lg, d_src, event_logits, loo, B, S, Ce, st);
 }
@@ -635,7 +644,7 @@ int tcvn_head_occlusion(tcvn_head* p, int batch, int max_prongs, int n_prongs, c
                 TCVN_OCC_MAX_PASS);
         return -1;
     }
-    OccHeadLayout o;
+    OccHeadLayout o{};
     occ_head_layout(p->plan, max_prongs, o);
     if (ws_bytes < o.total) {
         fprintf(stderr, "tcvn: head_occlusion: workspace of %lld bytes, %ld needed\n", (long long)ws_bytes, o.total);
@@ -648,17 +657,15 @@ int tcvn_head_occlusion(tcvn_head* p, int batch, int max_prongs, int n_prongs, c
     float* vrows = reinterpret_cast<float*>(w + o.vrows);
     int* ident = reinterpret_cast<int*>(w + o.ident);
     int* d_vrow = reinterpret_cast<int*>(w + o.vrow);
-    int rc;
-    if ((rc = occ_rows(rows, vimg, row_base, emb, emb_ld, col0, width, vrows, ident, n, p->plan.cfg.in_dim, batch + n_prongs, st))) return rc;
-    if ((rc = p->plan.embed(n, 0, 0, vrows, ident, w, o.E, 0, 0, st))) return rc;           // n one-token sequences -> E.X[0] [n][D]
-    HLayout L;
-    p->plan.layout(n, P, 0, L);
-    char* hw = w + o.head;
-    if ((rc = occ_gather(tokens, tok_row, index, reinterpret_cast<const float*>(w + o.E.X[0]), reinterpret_cast<float*>(hw + L.X[0]),
-                         d_vrow, n, batch, S, D, st)))
-        return rc;
-    if ((rc = p->plan.encode(n, P, d_vrow, hw, L, 0, 0, st))) return rc;
-    return p->plan.decode(n, P, occluded_event_logits, occluded_prong_logits, hw, L, 0, 0, st);
+    if (int rc = occ_rows(rows, vimg, row_base, emb, emb_ld, col0, width, vrows, ident, n, p->plan.cfg.in_dim, batch + n_prongs, st)) return rc;
+    HeadStep e, s;                      // e: n one-token sequences embedded in the scan's own buffers; s: the variant sequences (eval arithmetic)
+    if (int rc = p->plan.step(n, 0, 0, w, ws_bytes, 0, 0, st, e)) return rc;
+    e.L = o.E;
+    if (int rc = p->plan.embed(e, vrows, ident)) return rc;                                   // -> E.X[0] [n][D]
+    if (int rc = p->plan.step(n, P, 0, w + o.head, ws_bytes - o.head, 0, 0, st, s)) return rc;
+    if (int rc = occ_gather(tokens, tok_row, index, e.F(o.E.X[0]), s.F(s.L.X[0]), d_vrow, n, batch, S, D, st)) return rc;
+    if (int rc = p->plan.encode(s, d_vrow)) return rc;
+    return p->plan.decode(s, occluded_event_logits, occluded_prong_logits);
 }
 
 int tcvn_head_loss(tcvn_head* p, int batch, int max_prongs, const float* event_logits, const float* prong_logits,
@@ -670,8 +677,8 @@ int tcvn_head_loss(tcvn_head* p, int batch, int max_prongs, const float* event_l
 int tcvn_head_backward(tcvn_head* p, int batch, int max_prongs, int n_prongs, const float* rows, const int32_t* tok_row,
                        const float* d_event_logits, const float* d_prong_logits, float* d_rows, void* ws, int64_t ws_bytes,
                        void* stream) {
-    return p->plan.backward(batch, max_prongs, n_prongs, rows, tok_row, d_event_logits, d_prong_logits, d_rows,
-                            reinterpret_cast<char*>(ws), ws_bytes, reinterpret_cast<hipStream_t>(stream));
+    return p->plan.backward(batch, max_prongs, n_prongs, rows, tok_row, d_event_logits, d_prong_logits, d_rows, ws, ws_bytes,
+                            reinterpret_cast<hipStream_t>(stream));
 }
 }
 

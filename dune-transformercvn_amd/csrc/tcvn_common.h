@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <string>
 
 // Validation switches exist only in builds made with -DTCVN_DEBUG_KNOBS (`make debug` -> libtcvn_hip_dbg.so, used by the tests that
 // compare kernel variants).  The default library reads no environment variable: TCVN_KNOB_SET folds to false and the compiler removes
@@ -180,6 +181,9 @@ __device__ __forceinline__ float wave_max(float v) {
             return (int)e_;                                                                \
         }                                                                                  \
     } while (0)
+
+// one entry of a plan's slot table (tcvn_*_slot): parameter, buffer or counter, bound by index
+struct Slot { std::string name; long numel; int kind; };
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 static inline long round_up(long a, long b) { return (a + b - 1) / b * b; }

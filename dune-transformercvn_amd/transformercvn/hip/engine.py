@@ -258,7 +258,7 @@ class HeadEngine(_Plan):
                 seed: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
         assert rows.dtype == torch.float32 and rows.is_contiguous() and rows.shape == (batch + n_prongs, self.cfg.in_dim)
         assert tok_row.dtype == torch.int32 and tok_row.is_contiguous() and tok_row.shape == (batch, 1 + max_prongs)
-        ws = self.workspace(lib.tcvn_head_workspace_bytes(self.handle, batch, max_prongs, n_prongs), rows.device)
+        ws = self._stage_ws(batch, max_prongs, n_prongs, rows.device)
         ev = torch.empty(batch, self.cfg.event_classes, device=rows.device)
         pr = torch.empty(batch, max_prongs, self.cfg.prong_classes, device=rows.device)
         self._shape = (batch, max_prongs, n_prongs)

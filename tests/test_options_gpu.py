@@ -108,6 +108,15 @@ def test_transformer_norm_first_train_step():
     print("norm_first: worst rel L2 gradient error", worst, "over", seen, "tensors")
 
 
+def test_no_prong_decoder_layers_train_step():
+    """num_prong_decoder_layers = 0: the prong decoder is its output layer alone, reading the encoder's hidden rows directly."""
+    cfg = O.tutorial_config(**dict(SMALL, num_prong_decoder_layers=0))
+    worst, seen, grads, named = _step_vs_oracle(cfg, O.synthetic_batch([2, 4, 1], 33, cfg))
+    k = "network.prong_decoder.output_layer.weight"
+    assert grads[k].abs().max() > 1e-6 and named[k].grad.abs().max() > 1e-6
+    print("no prong decoder layers: worst rel L2 gradient error", worst, "over", seen, "tensors")
+
+
 def test_one_hot_pixels_train_step():
     cfg = O.tutorial_config(**dict(SMALL, one_hot_pixels=True))
     worst, seen, _, _ = _step_vs_oracle(cfg, O.synthetic_batch([1, 2], 35, cfg, event_hits=(200, 400), prong_hits=(20, 100)))
