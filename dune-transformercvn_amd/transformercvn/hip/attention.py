@@ -13,6 +13,7 @@ from torch import Tensor
 
 from . import _lib
 from ._lib import lib, check
+from .native import ptr, stream_ptr
 
 HEAD_FUSIONS = {"mean": _lib.FUSE_MEAN, "max": _lib.FUSE_MAX}
 
@@ -32,8 +33,8 @@ def rollout(weights: Tensor, mask: Tensor, head_fusion: str = "mean") -> Tensor:
     w = weights.detach().float().contiguous()
     tok = torch.where(mask.to(w.device).bool(), 0, -1).to(torch.int32).contiguous()
     out = torch.empty(B, S, S, device=w.device)
-    check(lib.tcvn_attention_rollout(C.c_void_p(w.data_ptr()), C.c_void_p(tok.data_ptr()), L, B, H, S, HEAD_FUSIONS[head_fusion],
-                                     C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream(w.device).cuda_stream)),
+    check(lib.tcvn_attention_rollout(ptr(w), ptr(tok), L, B, H, S, HEAD_FUSIONS[head_fusion],
+                                     ptr(out), stream_ptr(w.device)),
           "attention_rollout")
     return out
 

@@ -8,14 +8,8 @@ import torch
 
 from . import _lib
 from ._lib import lib, check
-
-
-def _stream_ptr() -> C.c_void_p:
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _ptr(t: Optional[torch.Tensor]) -> C.c_void_p:
-    return C.c_void_p(0 if t is None else t.data_ptr())
+from .occlusion import VariantPlan
+from .native import gpu_only, ptr as _ptr, stream_ptr as _stream_ptr
 
 
 class _Plan:
@@ -64,11 +58,20 @@ class _Plan:
         check(self._fn("bind")(self.handle, d, g), "bind")
         self._keep = keep
 
+    def _scratch(self, slot: str, need: int, device, slack: float = 1.0) -> torch.Tensor:
+        """The workspace kept in attribute `slot` (declared None in __init__), of at least `need` bytes on `device`.  One that is too
+        small or elsewhere is released first and replaced by int(need * slack) + 4096 bytes."""
+        ws = getattr(self, slot)
+        if ws is None or ws.numel() < need or ws.device != device:
+            ws = None
+            setattr(self, slot, None)
+            ws = torch.empty(int(need * slack) + 4096, dtype=torch.uint8, device=device)
+            setattr(self, slot, ws)
+        return ws
+
     def workspace(self, nbytes: int, device) -> torch.Tensor:
-        if self._ws is None or self._ws.numel() < nbytes or self._ws.device != device:
-            self._ws = None
-            self._ws = torch.empty(int(nbytes * 1.05) + 4096, dtype=torch.uint8, device=device)
-        return self._ws
+        """The step workspace self._ws: what forward() leaves in it is read by backward(), tap() and attention()."""
+        return self._scratch("_ws", nbytes, device, 1.05)
 
     def __del__(self):
         try:
@@ -85,6 +88,7 @@ class _EmbedderEngine(_Plan):
     def __init__(self):
         super().__init__()
         self._n = 0
+        self._occ_ws: Optional[torch.Tensor] = None
 
     def workspace_bytes(self, n_img: int, with_backward: bool) -> int:
         return self._fn("workspace_bytes")(self.handle, n_img, int(with_backward))
@@ -92,30 +96,38 @@ class _EmbedderEngine(_Plan):
     def forward(self, coords: torch.Tensor, values: torch.Tensor, n_img: int, out: torch.Tensor, train: bool, seed: int = 0,
                 log_pixels: bool = False, noise_std: float = 0.0):
         """coords int32 [nnz,3], values fp32 [nnz,C]; out: fp32 2-d view with row stride out.stride(0)."""
-        assert coords.dtype == torch.int32 and coords.is_contiguous() and values.dtype == torch.float32 and values.is_contiguous()
-        assert out.dtype == torch.float32 and out.stride(1) == 1 and out.shape == (n_img, self.out_dim)
-        ws = self.workspace(self.workspace_bytes(n_img, train), coords.device)
+        self._forward("_ws", 1.05, coords, values, coords.shape[0], n_img, out, log_pixels, noise_std, train, seed)
         self._n = n_img
         self._inputs = (coords, values)          # backward reads the COO list again (sparse stem weight gradient)
-        check(self._fn("forward")(self.handle, n_img, _ptr(coords), _ptr(values), coords.shape[0], int(log_pixels),
-                                  float(noise_std), _ptr(out), out.stride(0), _ptr(ws), ws.numel(), int(train),
-                                  C.c_uint64(seed), _stream_ptr()), f"{self._prefix}_forward")
+
+    def _forward(self, slot: str, slack: float, coords: torch.Tensor, values: torch.Tensor, nnz: int, n_img: int, out: torch.Tensor,
+                 log_pixels, noise_std: float, train: bool, seed: int):
+        """tcvn_*_forward over the first nnz rows of coords / values, in the workspace of `slot`."""
+        assert coords.dtype == torch.int32 and coords.is_contiguous() and values.dtype == torch.float32 and values.is_contiguous()
+        self._check_out(out, n_img)
+        ws = self._scratch(slot, self.workspace_bytes(n_img, train), coords.device, slack)
+        check(self._fn("forward")(self.handle, n_img, _ptr(coords), _ptr(values), nnz, int(log_pixels), float(noise_std), _ptr(out),
+                                  out.stride(0), _ptr(ws), ws.numel(), int(train), C.c_uint64(seed), _stream_ptr()),
+              f"{self._prefix}_forward")
+
+    def _check_out(self, out: torch.Tensor, n_img: int):
+        assert out.dtype == torch.float32 and out.stride(1) == 1 and out.shape == (n_img, self.out_dim)
 
     def backward(self, d_out: torch.Tensor):
-        assert d_out.dtype == torch.float32 and d_out.stride(1) == 1 and d_out.shape == (self._n, self.out_dim)
+        self._check_out(d_out, self._n)
         ws = self._ws
         check(self._fn("backward")(self.handle, self._n, _ptr(d_out), d_out.stride(0), _ptr(ws), ws.numel(), _stream_ptr()),
               f"{self._prefix}_backward")
 
     # ---- occlusion scan: variant hit lists of one COO list and their passes through this embedder (eval arithmetic) -----------------
     def occlusion_variants(self, coords: torch.Tensor, n_img: int, shape: Tuple[int, int], tile: Tuple[int, int],
-                           img_bs: torch.Tensor, max_pass: int):
-        """tcvn_occlusion_variants -> (V, unsorted, bad, bounds, vimg [V], index [V, 4], handle); bounds[k] .. bounds[k + 1] are the rows
-        of pass k in the variants' hit lists.  One synchronisation.  handle: the list's workspace, for occlusion_build()."""
+                           img_bs: torch.Tensor, max_pass: int) -> Tuple[VariantPlan, bool, bool]:
+        """tcvn_occlusion_variants -> (plan, unsorted, bad): the variants of this list (occlusion.VariantPlan; it serves occlusion_build)
+        and whether the list is not ordered by image / holds hits outside the maps.  One synchronisation."""
         return self._occlusion_list(lib.tcvn_occlusion_variants, (), "occlusion_variants", coords, n_img, shape, tile, img_bs, max_pass)
 
     def occlusion_refine_variants(self, coords: torch.Tensor, n_img: int, shape: Tuple[int, int], tile: Tuple[int, int],
-                                  img_bs: torch.Tensor, max_pass: int, keep_map: torch.Tensor):
+                                  img_bs: torch.Tensor, max_pass: int, keep_map: torch.Tensor) -> Tuple[VariantPlan, bool, bool]:
         """tcvn_occlusion_refine_variants: occlusion_variants() at the child tile `tile`, restricted to the tiles of the parent level
         (tiles twice the size) that keep_map uint8 [B, 1 + P, parent Ht, parent Wt] selects.  Same results and workspace."""
         assert keep_map.dtype == torch.uint8 and keep_map.is_contiguous() and keep_map.dim() == 4 and keep_map.device == coords.device
@@ -140,33 +152,24 @@ class _EmbedderEngine(_Plan):
         check(fn(_ptr(coords), coords.shape[0], n_img, H, W, th, tw, _ptr(img_bs.contiguous()), *parent, max_pass, _ptr(vimg), _ptr(index),
                  _ptr(ws), ws.numel(), host, words, _stream_ptr()), what)
         V = int(host[0])
-        handle = (ws, vimg, n_img, H, W, th, tw, max_pass)
-        return V, bool(host[1]), bool(host[2]), [int(host[4 + k]) for k in range(-(-V // max_pass) + 1)], vimg[:V], index[:V], handle
+        bounds = [int(host[4 + k]) for k in range(-(-V // max_pass) + 1)]
+        return VariantPlan(V, bounds, vimg[:V], index[:V], ws, (n_img, H, W, th, tw, max_pass)), bool(host[1]), bool(host[2])
 
-    def occlusion_build(self, handle, coords: torch.Tensor, values: torch.Tensor, first: int, count: int, out_coords: torch.Tensor,
-                        out_values: torch.Tensor):
-        """tcvn_occlusion_build_pass: the hit lists of variants first .. first + count - 1 of the list `handle` stands for (the last
-        element of what occlusion_variants() / occlusion_refine_variants() returned for these coords)."""
-        ws, vimg, n_img, H, W, th, tw, max_pass = handle
+    def occlusion_build(self, plan: VariantPlan, coords: torch.Tensor, values: torch.Tensor, first: int, count: int,
+                        out_coords: torch.Tensor, out_values: torch.Tensor):
+        """tcvn_occlusion_build_pass: the hit lists of variants first .. first + count - 1 of `plan` (what occlusion_variants() /
+        occlusion_refine_variants() returned for these coords)."""
         assert out_coords.dtype == torch.int32 and out_coords.is_contiguous() and out_values.is_contiguous()
         assert out_values.dtype == torch.float32 and out_values.shape == (out_coords.shape[0], values.shape[1])
-        check(lib.tcvn_occlusion_build_pass(_ptr(coords), _ptr(values), coords.shape[0], values.shape[1], n_img, H, W, th, tw, max_pass,
-                                            _ptr(vimg), _ptr(ws), ws.numel(), first, count, _ptr(out_coords), _ptr(out_values),
+        check(lib.tcvn_occlusion_build_pass(_ptr(coords), _ptr(values), coords.shape[0], values.shape[1], *plan.geometry, _ptr(plan.vimg),
+                                            _ptr(plan.ws), plan.ws.numel(), first, count, _ptr(out_coords), _ptr(out_values),
                                             out_coords.shape[0], _stream_ptr()), "occlusion_build_pass")
 
-    def occlusion_forward(self, coords: torch.Tensor, values: torch.Tensor, nnz: int, n_img: int, out: torch.Tensor,
-                          log_pixels: int = 0):
+    def occlusion_forward(self, coords: torch.Tensor, values: torch.Tensor, nnz: int, n_img: int, out: torch.Tensor, log_pixels: int = 0):
         """The plan's eval forward over one pass of variant maps (the first nnz rows of coords / values; nnz = 0: empty maps), in a
         workspace of its own: what the last forward() left for backward() and tap() stays as it is."""
-        assert coords.dtype == torch.int32 and coords.is_contiguous() and values.dtype == torch.float32 and values.is_contiguous()
-        assert out.dtype == torch.float32 and out.stride(1) == 1 and out.shape == (n_img, self.out_dim) and nnz <= coords.shape[0]
-        need = self.workspace_bytes(n_img, False)
-        ws = getattr(self, "_occ_ws", None)
-        if ws is None or ws.numel() < need or ws.device != coords.device:
-            self._occ_ws = None
-            self._occ_ws = ws = torch.empty(need + 4096, dtype=torch.uint8, device=coords.device)
-        check(self._fn("forward")(self.handle, n_img, _ptr(coords), _ptr(values), nnz, int(log_pixels), 0.0, _ptr(out), out.stride(0),
-                                  _ptr(ws), ws.numel(), 0, C.c_uint64(0), _stream_ptr()), f"{self._prefix}_forward")
+        assert nnz <= coords.shape[0]
+        self._forward("_occ_ws", 1.0, coords, values, nnz, n_img, out, log_pixels, 0.0, False, 0)
 
     def tap(self, name: str) -> torch.Tensor:
         """NHWC view [n,h,w,c] of an intermediate of the last forward (validation only)."""
@@ -198,7 +201,7 @@ class DenseNetEngine(_EmbedderEngine):
 
     def backward_part(self, d_out: torch.Tensor, part: int):
         """Backward of dense block `part` alone (call with part = n_parts-1 ... 0): tcvn_densenet_backward_blocks."""
-        assert d_out.dtype == torch.float32 and d_out.stride(1) == 1 and d_out.shape == (self._n, self.out_dim)
+        self._check_out(d_out, self._n)
         ws = self._ws
         check(lib.tcvn_densenet_backward_blocks(self.handle, self._n, _ptr(d_out), d_out.stride(0), _ptr(ws), ws.numel(), part, part,
                                                 _stream_ptr()), "densenet_backward_blocks")
@@ -251,13 +254,12 @@ class HeadEngine(_Plan):
         check(lib.tcvn_head_create(C.byref(cfg), C.byref(self.handle)), "head_create")
         self._shape = (0, 0, 0)
         self._last = (0, -1)                 # (batch, max_prongs) of the last forward / encode on self._ws: what attention() exports
-        self._loo_ws: Optional[torch.Tensor] = None
-        self._occ_ws: Optional[torch.Tensor] = None
+        self._loo_ws = self._occ_ws = None      # scratch workspaces (_scratch) of leave_one_out() and occlusion_pass()
 
     def forward(self, rows: torch.Tensor, tok_row: torch.Tensor, batch: int, max_prongs: int, n_prongs: int, train: bool,
                 seed: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
-        assert rows.dtype == torch.float32 and rows.is_contiguous() and rows.shape == (batch + n_prongs, self.cfg.in_dim)
-        assert tok_row.dtype == torch.int32 and tok_row.is_contiguous() and tok_row.shape == (batch, 1 + max_prongs)
+        self._check_rows(rows, batch + n_prongs)
+        self._check_tok_row(tok_row, batch, 1 + max_prongs)
         ws = self._stage_ws(batch, max_prongs, n_prongs, rows.device)
         ev = torch.empty(batch, self.cfg.event_classes, device=rows.device)
         pr = torch.empty(batch, max_prongs, self.cfg.prong_classes, device=rows.device)
@@ -270,11 +272,22 @@ class HeadEngine(_Plan):
     def _stage_ws(self, batch: int, max_prongs: int, n_prongs: int, device):
         return self.workspace(lib.tcvn_head_workspace_bytes(self.handle, batch, max_prongs, n_prongs), device)
 
+    def _check_rows(self, rows: torch.Tensor, n_rows: int):
+        assert rows.dtype == torch.float32 and rows.is_contiguous() and rows.shape == (n_rows, self.cfg.in_dim)
+
+    def _check_tok_row(self, tok_row: torch.Tensor, batch: int, S: int):
+        assert tok_row.dtype == torch.int32 and tok_row.is_contiguous() and tok_row.shape == (batch, S)
+
+    def _check_tokens(self, tokens: torch.Tensor) -> Tuple[int, int, int]:
+        """tokens [B, S, hidden] (or hidden states [S, B, hidden]) -> its shape."""
+        assert tokens.shape[2] == self.cfg.hidden_dim and tokens.dtype == torch.float32 and tokens.is_contiguous()
+        return tuple(tokens.shape)
+
     def embed(self, rows: torch.Tensor, tok_row: torch.Tensor, batch: int, max_prongs: int, n_prongs: int, train: bool,
               seed: int = 0) -> torch.Tensor:
         """tcvn_head_embed: -> tokens [batch, 1+max_prongs, hidden] (forward only)."""
-        assert rows.dtype == torch.float32 and rows.is_contiguous() and rows.shape == (batch + n_prongs, self.cfg.in_dim)
-        assert tok_row.dtype == torch.int32 and tok_row.is_contiguous() and tok_row.shape == (batch, 1 + max_prongs)
+        self._check_rows(rows, batch + n_prongs)
+        self._check_tok_row(tok_row, batch, 1 + max_prongs)
         ws = self._stage_ws(batch, max_prongs, n_prongs, rows.device)
         tokens = torch.empty(batch, 1 + max_prongs, self.cfg.hidden_dim, device=rows.device)
         check(lib.tcvn_head_embed(self.handle, batch, max_prongs, n_prongs, _ptr(rows), _ptr(tok_row), _ptr(tokens), _ptr(ws),
@@ -283,9 +296,8 @@ class HeadEngine(_Plan):
 
     def encode(self, tokens: torch.Tensor, tok_row: torch.Tensor, train: bool, seed: int = 0) -> torch.Tensor:
         """tcvn_head_encode: tokens [B, S, hidden] -> hidden [S, B, hidden] (forward only)."""
-        batch, S, D = tokens.shape
-        assert D == self.cfg.hidden_dim and tokens.dtype == torch.float32 and tokens.is_contiguous()
-        assert tok_row.dtype == torch.int32 and tok_row.is_contiguous() and tok_row.shape == (batch, S)
+        batch, S, D = self._check_tokens(tokens)
+        self._check_tok_row(tok_row, batch, S)
         ws = self._stage_ws(batch, S - 1, 0, tokens.device)
         hidden = torch.empty(S, batch, D, device=tokens.device)
         self._last = (batch, S - 1)
@@ -295,8 +307,7 @@ class HeadEngine(_Plan):
 
     def decode(self, hidden: torch.Tensor, train: bool = False, seed: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
         """tcvn_head_decode: hidden [S, B, hidden] -> (event_logits [B, Ce], prong_logits [B, S-1, Cp]) (forward only)."""
-        S, batch, D = hidden.shape
-        assert D == self.cfg.hidden_dim and hidden.dtype == torch.float32 and hidden.is_contiguous()
+        S, batch, D = self._check_tokens(hidden)
         ws = self._stage_ws(batch, S - 1, 0, hidden.device)
         ev = torch.empty(batch, self.cfg.event_classes, device=hidden.device)
         pr = torch.empty(batch, S - 1, self.cfg.prong_classes, device=hidden.device)
@@ -310,10 +321,9 @@ class HeadEngine(_Plan):
         batch, max_prongs = self._last
         if self._ws is None or max_prongs < 0:
             raise RuntimeError("HeadEngine.attention: no forward or encode has run on this engine")
-        if not tok_row.is_cuda:
-            raise RuntimeError("transformercvn (MI355X build): the attention export runs on the GPU only; there is no CPU fallback")
+        gpu_only(tok_row, "the attention export")
         S = 1 + max_prongs
-        assert tok_row.dtype == torch.int32 and tok_row.is_contiguous() and tok_row.shape == (batch, S)
+        self._check_tok_row(tok_row, batch, S)
         weights = torch.empty(self.cfg.n_layers, batch, self.cfg.heads, S, S, device=tok_row.device)
         check(lib.tcvn_head_attention(self.handle, batch, max_prongs, _ptr(tok_row), _ptr(self._ws), self._ws.numel(), _ptr(weights),
                                       _stream_ptr()), "head_attention")
@@ -322,30 +332,26 @@ class HeadEngine(_Plan):
     def leave_one_out(self, tokens: torch.Tensor, tok_row: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """tcvn_head_leave_one_out: tokens [B, S, hidden] -> (event_logits [B, Ce], loo_event_logits [B, S-1, Ce]), eval arithmetic.
         Runs in a workspace of its own: the engine's forward workspace is left as it is."""
-        batch, S, D = tokens.shape
-        assert D == self.cfg.hidden_dim and tokens.dtype == torch.float32 and tokens.is_contiguous()
-        assert tok_row.dtype == torch.int32 and tok_row.is_contiguous() and tok_row.shape == (batch, S)
+        batch, S, D = self._check_tokens(tokens)
+        self._check_tok_row(tok_row, batch, S)
         need = lib.tcvn_head_leave_one_out_workspace_bytes(self.handle, batch, S - 1)
         if need < 0:
             raise RuntimeError(f"libtcvn_hip: head_leave_one_out_workspace_bytes rejects batch {batch}, {S} tokens")
-        if self._loo_ws is None or self._loo_ws.numel() < need or self._loo_ws.device != tokens.device:
-            self._loo_ws = None
-            self._loo_ws = torch.empty(need + 4096, dtype=torch.uint8, device=tokens.device)
+        ws = self._scratch("_loo_ws", need, tokens.device)
         ev = torch.empty(batch, self.cfg.event_classes, device=tokens.device)
         loo = torch.empty(batch, S - 1, self.cfg.event_classes, device=tokens.device)
         check(lib.tcvn_head_leave_one_out(self.handle, batch, S - 1, _ptr(tokens), _ptr(tok_row), _ptr(ev), _ptr(loo),
-                                          _ptr(self._loo_ws), self._loo_ws.numel(), _stream_ptr()), "head_leave_one_out")
+                                          _ptr(ws), ws.numel(), _stream_ptr()), "head_leave_one_out")
         return ev, loo
 
     def occlusion_pass(self, rows: torch.Tensor, tokens: torch.Tensor, tok_row: torch.Tensor, n_prongs: int, vimg: torch.Tensor,
                        index: torch.Tensor, row_base: int, emb: torch.Tensor, col0: int, occ_ev: torch.Tensor, occ_pr: torch.Tensor):
         """tcvn_head_occlusion: one pass of n variants (vimg [n], index [n, 4], emb [n, width] embedder outputs) through combined
         embedding, encoder and decoders -> occ_ev [n, Ce], occ_pr [n, P, Cp].  Workspace of its own, as leave_one_out has."""
-        batch, S, D = tokens.shape
+        batch, S, D = self._check_tokens(tokens)
         n, width = emb.shape
-        assert D == self.cfg.hidden_dim and tokens.dtype == torch.float32 and tokens.is_contiguous()
-        assert rows.dtype == torch.float32 and rows.is_contiguous() and rows.shape == (batch + n_prongs, self.cfg.in_dim)
-        assert tok_row.dtype == torch.int32 and tok_row.is_contiguous() and tok_row.shape == (batch, S)
+        self._check_rows(rows, batch + n_prongs)
+        self._check_tok_row(tok_row, batch, S)
         assert vimg.dtype == torch.int32 and vimg.is_contiguous() and vimg.shape == (n,)
         assert index.dtype == torch.int32 and index.is_contiguous() and index.shape == (n, 4)
         assert emb.dtype == torch.float32 and emb.stride(1) == 1
@@ -354,12 +360,10 @@ class HeadEngine(_Plan):
         need = lib.tcvn_head_occlusion_workspace_bytes(self.handle, S - 1)
         if need < 0:
             raise RuntimeError(f"libtcvn_hip: head_occlusion_workspace_bytes rejects {S} tokens")
-        if self._occ_ws is None or self._occ_ws.numel() < need or self._occ_ws.device != tokens.device:
-            self._occ_ws = None
-            self._occ_ws = torch.empty(need + 4096, dtype=torch.uint8, device=tokens.device)
+        ws = self._scratch("_occ_ws", need, tokens.device)
         check(lib.tcvn_head_occlusion(self.handle, batch, S - 1, n_prongs, _ptr(rows), _ptr(tokens), _ptr(tok_row), n, _ptr(vimg),
                                       _ptr(index), row_base, _ptr(emb), emb.stride(0), col0, width, _ptr(occ_ev),
-                                      _ptr(occ_pr if S > 1 else None), _ptr(self._occ_ws), self._occ_ws.numel(), _stream_ptr()),
+                                      _ptr(occ_pr if S > 1 else None), _ptr(ws), ws.numel(), _stream_ptr()),
               "head_occlusion")
 
     def loss(self, ev: torch.Tensor, pr: torch.Tensor, event_targets: torch.Tensor, prong_targets: torch.Tensor):

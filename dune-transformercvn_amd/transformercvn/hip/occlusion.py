@@ -13,20 +13,35 @@ fine.  Level 0 is the flat scan at ``tile``; every later level halves the tiles 
 from __future__ import annotations
 
 import ctypes as C
-from typing import List, Optional, Tuple, Union
+from dataclasses import dataclass, replace
+from typing import Any, List, Optional, Tuple, Union
 
 import torch
 from torch import Tensor
+
+from . import _lib
+from .native import gpu_only as _gpu_only, ptr, ptr_or_null as _vp, stream_ptr as _stream
 
 MAPS = ("all", "event", "prongs")
 MAX_MAPS_PER_PASS = 256             # TCVN_OCC_MAX_PASS
 MAX_LEVELS = 16                     # TCVN_OCC_MAX_LEVELS
 
 
+def whole(v) -> bool:
+    return isinstance(v, int) and not isinstance(v, bool)
+
+
+def _check_target(target, who: str):
+    """What check_refine_args and parse_target both ask of a target: a known name, or integer classes of at most one dimension."""
+    if isinstance(target, str):
+        if target not in ("event", "prong"):
+            raise ValueError(f"{who}: target must be 'event', 'prong', a class index or a [B] tensor of class indices, got {target!r}")
+    elif torch.is_tensor(target) and (target.dtype.is_floating_point or target.dtype == torch.bool or target.dim() > 1):
+        raise ValueError(f"{who}: an explicit target is an integer class index or a [B] integer tensor")
+
+
 def check_args(tile, maps, max_maps_per_pass) -> Tuple[Tuple[int, int], str, int]:
     """Validates the scan's arguments on the host (ValueError) before any device work -> (tile, maps, max_maps_per_pass)."""
-    def whole(v):
-        return isinstance(v, int) and not isinstance(v, bool)
     if not (isinstance(tile, (tuple, list)) and len(tile) == 2 and all(whole(t) and t >= 1 for t in tile)):
         raise ValueError(f"occlusion_maps: tile must be a pair of positive integers (th, tw), got {tile!r}")
     if maps not in MAPS:
@@ -39,8 +54,6 @@ def check_args(tile, maps, max_maps_per_pass) -> Tuple[Tuple[int, int], str, int
 def check_refine_args(tile, levels, keep, target, maps, max_maps_per_pass, max_variants):
     """Validates the arguments of a coarse-to-fine scan on the host (ValueError) before any device work
     -> (tile, levels, keep, maps, max_maps_per_pass, max_variants).  The target's classes are checked against the model by parse_target."""
-    def whole(v):
-        return isinstance(v, int) and not isinstance(v, bool)
     tile, maps, max_maps_per_pass = check_args(tile, maps, max_maps_per_pass)
     if not (whole(levels) and 1 <= levels <= MAX_LEVELS):
         raise ValueError(f"occlusion_refine: levels must be an integer in 1..{MAX_LEVELS}, got {levels!r}")
@@ -48,14 +61,10 @@ def check_refine_args(tile, levels, keep, target, maps, max_maps_per_pass, max_v
         raise ValueError(f"occlusion_refine: both sides of tile {tile} must be divisible by 2 ** (levels - 1) = {1 << (levels - 1)}")
     if isinstance(keep, bool) or not isinstance(keep, (int, float)) or not 0 <= keep <= 1:           # NaN fails the comparison too
         raise ValueError(f"occlusion_refine: keep must be a number in [0, 1], got {keep!r}")
-    if isinstance(target, str):
-        if target not in ("event", "prong"):
-            raise ValueError(f"occlusion_refine: target must be 'event', 'prong', a class index or a [B] tensor of class indices, got {target!r}")
-    elif isinstance(target, bool) or not (whole(target) or torch.is_tensor(target)):
+    _check_target(target, "occlusion_refine")
+    if not (isinstance(target, str) or whole(target) or torch.is_tensor(target)):
         raise ValueError(f"occlusion_refine: target must be 'event', 'prong', a class index or a [B] tensor of class indices, got {target!r}")
-    elif torch.is_tensor(target) and (target.dtype.is_floating_point or target.dtype == torch.bool or target.dim() > 1):
-        raise ValueError("occlusion_refine: an explicit target is an integer class index or a [B] integer tensor")
-    elif whole(target) and target < 0:
+    if whole(target) and target < 0:
         raise ValueError(f"occlusion_refine: a class index is not negative, got {target!r}")
     if max_variants is not None and not (whole(max_variants) and max_variants >= 1):
         raise ValueError(f"occlusion_refine: max_variants must be None or a positive integer, got {max_variants!r}")
@@ -87,14 +96,10 @@ class OcclusionResult:
 
 def parse_target(target, B: int, Ce: int):
     """-> (TCVN_OCC_TARGET_*, None or the [B] tensor of explicit event classes); ValueError for anything else."""
-    from . import _lib
+    classes = target if isinstance(target, str) else torch.as_tensor(target)
+    _check_target(classes, "heatmap")
     if isinstance(target, str):
-        if target not in ("event", "prong"):
-            raise ValueError(f"heatmap: target must be 'event', 'prong', a class index or a [B] tensor of class indices, got {target!r}")
         return (_lib.OCC_TARGET_PRONG if target == "prong" else _lib.OCC_TARGET_EVENT), None
-    classes = torch.as_tensor(target)
-    if classes.dtype.is_floating_point or classes.dtype == torch.bool or classes.dim() > 1:
-        raise ValueError("heatmap: an explicit target is an integer class index or a [B] integer tensor")
     classes = classes.reshape(-1).expand(B) if classes.numel() == 1 else classes
     if classes.shape != (B,) or int(classes.min()) < 0 or int(classes.max()) >= Ce:
         raise ValueError(f"heatmap: explicit classes must be {B} values in 0..{Ce - 1}")
@@ -106,13 +111,11 @@ def heatmap(result: OcclusionResult, target: Union[str, int, Tensor] = "event") 
     hits and at padded prong slots.  target "event": c = each event's predicted event class, from the event logits; an int or a [B]
     integer tensor names the class instead.  target "prong": for s >= 1, c = the predicted class of prong slot s - 1, from the prong
     logits of that slot (how much this region of the prong's map supports the prong's own label); row s = 0 is 0."""
-    from . import _lib
     ev, pr = result.event_logits, result.prong_logits
     B, Ce = ev.shape
     P, Cp = pr.shape[1], pr.shape[2]
     mode, classes = parse_target(target, B, Ce)
-    if not ev.is_cuda:
-        raise RuntimeError("transformercvn (MI355X build): the occlusion heat map runs on the GPU only; there is no CPU fallback")
+    _gpu_only(ev, "the occlusion heat map")
     Ht, Wt = result.grid
     tensors = [ev, pr, result.occluded_event_logits, result.occluded_prong_logits]
     assert all(t.dtype == torch.float32 and t.is_contiguous() and t.device == ev.device for t in tensors)
@@ -125,32 +128,16 @@ def heatmap(result: OcclusionResult, target: Union[str, int, Tensor] = "event") 
     if mode == _lib.OCC_TARGET_PRONG and P == 0:
         return torch.zeros(B, 1, Ht, Wt, device=ev.device)
     out = torch.empty(B, 1 + P, Ht, Wt, device=ev.device)
-    ptr = lambda t: C.c_void_p(0 if t is None or t.numel() == 0 else t.data_ptr())       # noqa: E731
     with torch.cuda.device(ev.device):
-        _lib.check(_lib.lib.tcvn_occlusion_heatmap(ptr(ev), ptr(pr), ptr(tensors[2]), ptr(tensors[3]), ptr(index), V, B, P, Ce, Cp, Ht, Wt,
-                                                   mode, ptr(classes), C.c_void_p(out.data_ptr()),
-                                                   C.c_void_p(torch.cuda.current_stream().cuda_stream)), "occlusion_heatmap")
+        _lib.check(_lib.lib.tcvn_occlusion_heatmap(_vp(ev), _vp(pr), _vp(tensors[2]), _vp(tensors[3]), _vp(index), V, B, P, Ce, Cp, Ht, Wt,
+                                                   mode, _vp(classes), ptr(out), _stream()), "occlusion_heatmap")
     return out
 
 
 # ---- coarse to fine -----------------------------------------------------------------------------------------------------------------------
-def _vp(t):
-    return C.c_void_p(0 if t is None or t.numel() == 0 else t.data_ptr())
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _gpu_only(t: Tensor, what: str):
-    if not t.is_cuda:
-        raise RuntimeError(f"transformercvn (MI355X build): {what} runs on the GPU only; there is no CPU fallback")
-
-
 def select(heat: Tensor, index: Tensor, group: int, keep: float) -> Tensor:
     """tcvn_occlusion_select: the heat map of one level and its index [V, 4] -> keep_map uint8 of the heat map's shape, 1 at the
     variants whose |heat| >= float32(keep) * (largest |heat| of their group) and (keep == 0 or |heat| > 0)."""
-    from . import _lib
     _gpu_only(heat, "the selection of the tiles to refine")
     assert heat.dtype == torch.float32 and heat.is_contiguous() and heat.dim() == 4
     assert index.dtype == torch.int32 and index.is_contiguous() and index.device == heat.device and index.shape[1:] == (4,)
@@ -165,7 +152,6 @@ def select(heat: Tensor, index: Tensor, group: int, keep: float) -> Tensor:
 
 def mark(index: Tensor, B: int, P: int, grid: Tuple[int, int]) -> Tensor:
     """tcvn_occlusion_mark: uint8 [B, 1 + P, Ht, Wt], 1 at the positions of index [V, 4]: the tiles a level evaluated."""
-    from . import _lib
     _gpu_only(index, "marking the evaluated tiles")
     assert index.dtype == torch.int32 and index.is_contiguous() and index.shape[1:] == (4,)
     out = torch.empty(B, 1 + P, *grid, dtype=torch.uint8, device=index.device)
@@ -178,7 +164,6 @@ def mark(index: Tensor, B: int, P: int, grid: Tuple[int, int]) -> Tensor:
 def occupancy(coords: Tensor, n_img: int, shape: Tuple[int, int], tile: Tuple[int, int], img_bs: Tensor, occupied: Tensor):
     """tcvn_occlusion_occupancy: sets occupied uint8 [B, 1 + P, Ht, Wt] to 1 at every tile of every map of this hit list that holds a
     hit (coords int32 [nnz, 3], img_bs int32 [n_img, 2] = (b, s) of every image)."""
-    from . import _lib
     _gpu_only(occupied, "the occupancy of the finest grid")
     B, S, Ht, Wt = occupied.shape
     assert occupied.dtype == torch.uint8 and occupied.is_contiguous() and (Ht, Wt) == (-(-shape[0] // tile[0]), -(-shape[1] // tile[1]))
@@ -193,7 +178,6 @@ def occupancy(coords: Tensor, n_img: int, shape: Tuple[int, int], tile: Tuple[in
 def paint(heats: List[Tensor], evaluated: List[Tensor], occupied: Tensor) -> Tensor:
     """tcvn_occlusion_paint: the levels' heat maps and evaluated maps (coarse to fine, every grid half the next one's, rounded up) ->
     float32 on the last level's grid: a cell with occupied != 0 takes the value of the deepest evaluated tile that contains it."""
-    from . import _lib
     _gpu_only(occupied, "painting the refined heat map")
     n = len(heats)
     assert 1 <= n <= MAX_LEVELS and len(evaluated) == n
@@ -242,3 +226,151 @@ def refined_heatmap(result: RefinedOcclusion) -> Tensor:
     if not result.levels:
         raise ValueError("refined_heatmap: no level was run (max_variants is below the number of variants of level 0)")
     return paint(result.heats, result.evaluated, result.occupied)
+
+
+# ---- the scan driver ------------------------------------------------------------------------------------------------------------------------
+@dataclass(frozen=True)
+class HitList:
+    """One COO hit list of a scan: the maps that go through one embedder, in its image order."""
+    engine: Any                     # that embedder's engine (occlusion_variants / occlusion_refine_variants / _build / _forward, out_dim)
+    coords: Tensor                  # int32 [nnz, 3]: (map, y, x) of every hit
+    values: Tensor                  # float32 [nnz, C]
+    value_mode: int                 # value_mode of the pixel bundle the list came in
+    n_img: int                      # number of maps
+    img_bs: Tensor                  # int32 [n_img, 2]: (b, s) of every map
+    row_base: int                   # row of map 0 in the input rows of the forward
+    col0: int                       # first column of those rows that the embedder writes
+
+
+@dataclass(frozen=True)
+class VariantPlan:
+    """The variants of one hit list at one tile size, as the engine's occlusion_variants / occlusion_refine_variants return them."""
+    V: int                          # number of variants
+    bounds: List[int]               # bounds[k] .. bounds[k + 1]: the rows of pass k in the variants' hit lists
+    vimg: Tensor                    # int32 [V]: the map of every variant
+    index: Tensor                   # int32 [V, 4]: (b, s, ty, tx) of every variant, ascending
+    ws: Tensor                      # the list workspace, which the engine's occlusion_build reads
+    geometry: Tuple[int, ...]       # (n_img, H, W, th, tw, max_pass) the list was made for: occlusion_build repeats them
+
+
+def plan_variants(lst: HitList, shape: Tuple[int, int], tile: Tuple[int, int], max_pass: int,
+                  keep_map: Optional[Tensor] = None) -> Tuple[HitList, VariantPlan]:
+    """The variant list of one hit list (one host read-back): every tile that holds a hit, or (keep_map) the children of the selected
+    tiles of the level above.  -> (the list the plan is for, the plan): `lst` itself, or a cleaned copy if the engine found it unsorted
+    or with hits outside the maps -- the caller keeps that one for the later levels."""
+    def variants(hits):
+        if keep_map is None:
+            return hits.engine.occlusion_variants(hits.coords, hits.n_img, shape, tile, hits.img_bs, max_pass)
+        return hits.engine.occlusion_refine_variants(hits.coords, hits.n_img, shape, tile, hits.img_bs, max_pass, keep_map)
+    plan, unsorted, bad = variants(lst)
+    if unsorted or bad:
+        # the variant build walks each map's hits as one range: drop what the embedders drop, then a STABLE sort by map (the order
+        # inside a map decides which of two hits on one pixel wins)
+        c = lst.coords.long()
+        keep = (c[:, 0] >= 0) & (c[:, 0] < lst.n_img) & (c[:, 1] >= 0) & (c[:, 1] < shape[0]) & (c[:, 2] >= 0) & (c[:, 2] < shape[1])
+        coords, values = lst.coords[keep], lst.values[keep]
+        order = torch.sort(coords[:, 0], stable=True).indices
+        lst = replace(lst, coords=coords[order].contiguous(), values=values[order].contiguous())
+        plan, unsorted, bad = variants(lst)
+        if unsorted or bad:
+            raise RuntimeError("occlusion_maps: the hit list is still unsorted after sorting it")
+    return lst, plan
+
+
+class Scan:
+    """The forward() being explained and what every pass of a scan over it reads: its input rows (`last`: rows, tok_row, B, P, n_prongs
+    of that forward), its logits and tokens, and one HitList per embedder whose maps are scanned, one list after the other."""
+
+    def __init__(self, ev_engine, pr_engine, head, pixel_shape: Tuple[int, int], last, event_logits: Tensor, prong_logits: Tensor,
+                 event_px, prong_px, prong_mask: Tensor, maps: str):
+        self.head, self.shape, self.last, self.ev, self.pr = head, tuple(pixel_shape), last, event_logits, prong_logits
+        B, dev = last.B, last.rows.device
+        self.tokens = head.embed(last.rows, last.tok_row, B, last.P, last.n_prongs, False, 0)
+        self.lists: List[HitList] = []
+        if maps in ("all", "event"):
+            bs = torch.stack((torch.arange(B, device=dev), torch.zeros(B, dtype=torch.int64, device=dev)), 1).to(torch.int32)
+            self.lists.append(HitList(ev_engine, event_px.coords.to(dev), event_px.values.to(dev), event_px.value_mode, B, bs, 0, 0))
+        if maps in ("all", "prongs") and last.n_prongs > 0:
+            i1, i2 = prong_mask.to(dev).nonzero(as_tuple=True)             # packed prong order: the embedder's image order
+            bs = torch.stack((i1, 1 + i2), 1).to(torch.int32)
+            # a prong's pixel embedding sits behind its feature embedding; the event embedder is wider by exactly those columns
+            self.lists.append(HitList(pr_engine, prong_px.coords.to(dev), prong_px.values.to(dev), prong_px.value_mode, last.n_prongs, bs,
+                                      B, ev_engine.out_dim - pr_engine.out_dim))
+
+    def level(self, tile: Tuple[int, int], max_pass: int, keep_map: Optional[Tensor] = None,
+              budget: Optional[int] = None) -> Optional[OcclusionResult]:
+        """One scan at `tile`: every tile that holds a hit, or (keep_map: the selection among the variants of the level with tiles
+        twice the size) only the children of the selected tiles.  The variant lists come first; None, before any variant is run, if
+        they hold more than `budget` variants together."""
+        dev, P = self.last.rows.device, self.last.P
+        grid = (-(-self.shape[0] // tile[0]), -(-self.shape[1] // tile[1]))
+        planned = [plan_variants(lst, self.shape, tile, max_pass, keep_map) for lst in self.lists]
+        self.lists = [lst for lst, _ in planned]
+        if budget is not None and sum(plan.V for _, plan in planned) > budget:
+            return None
+        parts = [self._passes(lst, plan, max_pass) for lst, plan in planned]
+        if parts:
+            index, occ_ev, occ_pr = (torch.cat([p[i] for p in parts]) for i in range(3))
+        else:
+            index = torch.empty(0, 4, dtype=torch.int32, device=dev)
+            occ_ev, occ_pr = self.ev.new_empty(0, self.ev.shape[1]), self.pr.new_empty(0, P, self.pr.shape[2])
+        if len(parts) > 1:                    # the two lists are ordered by (b, s, ty, tx) each: merge them into that order
+            i64 = index.long()
+            key = ((i64[:, 0] * (1 + P) + i64[:, 1]) * grid[0] + i64[:, 2]) * grid[1] + i64[:, 3]
+            order = torch.argsort(key)
+            index, occ_ev, occ_pr = index[order].contiguous(), occ_ev[order].contiguous(), occ_pr[order].contiguous()
+        return OcclusionResult(self.ev, self.pr, index, occ_ev, occ_pr, grid, tile)
+
+    def _passes(self, lst: HitList, plan: VariantPlan, max_pass: int) -> Tuple[Tensor, Tensor, Tensor]:
+        """The variants of one list, pass by pass, through its embedder and the token path -> (index [V, 4], occluded_event_logits
+        [V, Ce], occluded_prong_logits [V, P, Cp]) in the embedder's image order.  The embedder writes [col0, col0 + engine.out_dim)
+        of its maps' rows."""
+        engine, head, last = lst.engine, self.head, self.last
+        dev = last.rows.device
+        V, bounds, vimg, index = plan.V, plan.bounds, plan.vimg, plan.index
+        occ_ev = torch.empty(V, head.cfg.event_classes, device=dev)
+        occ_pr = torch.empty(V, self.tokens.shape[1] - 1, head.cfg.prong_classes, device=dev)
+        if V == 0:
+            return index, occ_ev, occ_pr
+        cap = max(1, max(bounds[k + 1] - bounds[k] for k in range(len(bounds) - 1)))
+        out_coords = torch.empty(cap, 3, dtype=torch.int32, device=dev)
+        out_values = torch.empty(cap, lst.values.shape[1], dtype=torch.float32, device=dev)
+        emb = torch.empty(min(max_pass, V), engine.out_dim, device=dev)
+        for k in range(len(bounds) - 1):
+            first = k * max_pass
+            n = min(max_pass, V - first)
+            nnz = bounds[k + 1] - bounds[k]
+            if nnz > 0:
+                engine.occlusion_build(plan, lst.coords, lst.values, first, n, out_coords, out_values)
+            engine.occlusion_forward(out_coords, out_values, nnz, n, emb[:n], lst.value_mode)
+            head.occlusion_pass(last.rows, self.tokens, last.tok_row, last.n_prongs, vimg[first:first + n], index[first:first + n],
+                                lst.row_base, emb[:n], lst.col0, occ_ev[first:first + n], occ_pr[first:first + n])
+        return index, occ_ev, occ_pr
+
+    def refine(self, tile: Tuple[int, int], levels: int, keep: float, target, max_pass: int,
+               max_variants: Optional[int]) -> RefinedOcclusion:
+        """Coarse to fine: level 0 is level(tile); level l halves the tiles of level l - 1 and evaluates only the children (that hold a
+        hit) of the variants whose score |h| -- heatmap(level, target) -- reaches keep times the largest score of their group (the event,
+        or the map with target "prong").  The choice is made on the device (tcvn_occlusion_select); one host read-back per hit list and
+        level.  max_variants bounds the sum of V over the levels: the level that would pass it and all later ones are not run."""
+        group = _lib.OCC_GROUP_MAP if isinstance(target, str) and target == "prong" else _lib.OCC_GROUP_EVENT
+        B, P = self.last.B, self.last.P
+        done, heats, evaluated, used, stopped_at, keep_map = [], [], [], 0, None, None
+        for lv in range(levels):
+            budget = None if max_variants is None else max_variants - used
+            res = self.level((tile[0] >> lv, tile[1] >> lv), max_pass, keep_map, budget)
+            if res is None:
+                stopped_at = lv
+                break
+            used += res.num_variants
+            done.append(res)
+            heats.append(heatmap(res, target))
+            evaluated.append(mark(res.index, B, P, res.grid))
+            if lv + 1 < levels:
+                keep_map = select(heats[-1], res.index, group, keep)
+        occupied = None
+        if done:
+            occupied = torch.zeros(B, 1 + P, *done[-1].grid, dtype=torch.uint8, device=self.last.rows.device)
+            for lst in self.lists:
+                occupancy(lst.coords, lst.n_img, self.shape, done[-1].tile, lst.img_bs, occupied)
+        return RefinedOcclusion(self.ev, self.pr, done, heats, evaluated, occupied, target, keep, stopped_at)

@@ -14,10 +14,7 @@ import torch
 
 from . import _lib
 from ._lib import check, lib
-
-
-def _ptr(t: torch.Tensor) -> C.c_void_p:
-    return C.c_void_p(t.data_ptr())
+from .native import ptr as _ptr, stream_ptr
 
 
 class FlatAdamW(torch.optim.Optimizer):
@@ -61,7 +58,7 @@ class FlatAdamW(torch.optim.Optimizer):
             raise RuntimeError("FlatAdamW expects one learning rate for both parameter groups (reference: one LambdaLR for both)")
         g0 = self.param_groups[0]
         self._step += 1
-        st = C.c_void_p(torch.cuda.current_stream(rt.flat_param.device).cuda_stream)
+        st = stream_ptr(rt.flat_param.device)
         n = rt.flat_param.numel()
         gss = None
         if self.clip > 0:

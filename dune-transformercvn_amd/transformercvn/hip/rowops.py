@@ -10,15 +10,7 @@ import torch
 from torch import Tensor, nn
 
 from ._lib import lib, check
-
-
-def _need_cuda(t: Tensor, what: str):
-    if not t.is_cuda:
-        raise RuntimeError(f"transformercvn (MI355X build): {what} runs on the GPU only; there is no CPU fallback")
-
-
-def _st() -> C.c_void_p:
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+from .native import gpu_only as _need_cuda, ptr as _p, stream_ptr as _st
 
 
 def linear(x: Tensor, weight: Tensor, bias: Tensor = None) -> Tensor:
@@ -28,14 +20,9 @@ def linear(x: Tensor, weight: Tensor, bias: Tensor = None) -> Tensor:
     w = weight.detach().float().contiguous()
     b = None if bias is None else bias.detach().float().contiguous()
     y = torch.empty(x.shape[0], w.shape[0], device=x.device)
-    check(lib.tcvn_linear_forward(C.c_void_p(x.data_ptr()), x.stride(0), C.c_void_p(w.data_ptr()),
-                                  C.c_void_p(0 if b is None else b.data_ptr()), C.c_void_p(y.data_ptr()), y.stride(0), x.shape[0],
-                                  w.shape[0], w.shape[1], _st()), "linear_forward")
+    check(lib.tcvn_linear_forward(_p(x), x.stride(0), _p(w), _p(b), _p(y), y.stride(0), x.shape[0], w.shape[0], w.shape[1], _st()),
+          "linear_forward")
     return y
-
-
-def _p(t) -> C.c_void_p:
-    return C.c_void_p(0 if t is None else t.data_ptr())
 
 
 def _norm_of(norm):
@@ -52,11 +39,10 @@ def bn_prelu(x: Tensor, norm, slope, training: bool, drop_p: float = 0.0, seed: 
     y = torch.empty_like(x)
     norm = _norm_of(norm)
     scratch = torch.empty(2 * ch, device=x.device)
-    check(lib.tcvn_rows_bn_prelu_forward(C.c_void_p(x.data_ptr()), x.stride(0), rows, ch, _p(norm.weight if norm else None),
+    check(lib.tcvn_rows_bn_prelu_forward(_p(x), x.stride(0), rows, ch, _p(norm.weight if norm else None),
                                          _p(norm.bias if norm else None), _p(slope), _p(norm.running_mean if norm else None),
-                                         _p(norm.running_var if norm else None), C.c_void_p(y.data_ptr()), y.stride(0),
-                                         C.c_void_p(scratch.data_ptr()), int(training), float(drop_p), C.c_uint64(seed),
-                                         C.c_uint32(stream_id), _st()), "rows_bn_prelu_forward")
+                                         _p(norm.running_var if norm else None), _p(y), y.stride(0), _p(scratch), int(training),
+                                         float(drop_p), C.c_uint64(seed), C.c_uint32(stream_id), _st()), "rows_bn_prelu_forward")
     if training and norm is not None:
         norm.num_batches_tracked += 1
     return y
@@ -81,10 +67,10 @@ class FeatureMLP:
             stat = torch.empty(2 * ch, device=z.device)
             p = float(blk.dropout.p) if training else 0.0
             norm, slope = _norm_of(blk.norm), getattr(blk.activation, "weight", None)
-            check(lib.tcvn_rows_bn_prelu_forward(C.c_void_p(z.data_ptr()), z.stride(0), rows, ch, _p(norm.weight if norm else None),
+            check(lib.tcvn_rows_bn_prelu_forward(_p(z), z.stride(0), rows, ch, _p(norm.weight if norm else None),
                                                  _p(norm.bias if norm else None), _p(slope), _p(norm.running_mean if norm else None),
                                                  _p(norm.running_var if norm else None),
-                                                 C.c_void_p(y.data_ptr()), y.stride(0), C.c_void_p(stat.data_ptr()), int(training), p,
+                                                 _p(y), y.stride(0), _p(stat), int(training), p,
                                                  C.c_uint64(seed), C.c_uint32(0x4800 + i), _st()), "rows_bn_prelu_forward")
             if training and norm is not None:
                 norm.num_batches_tracked += 1
@@ -99,17 +85,15 @@ class FeatureMLP:
             rows, ch = z.shape
             dz = torch.empty_like(z)
             norm, slope = _norm_of(blk.norm), getattr(blk.activation, "weight", None)
-            check(lib.tcvn_rows_bn_prelu_backward(C.c_void_p(z.data_ptr()), z.stride(0), C.c_void_p(dy.data_ptr()), dy.stride(0), rows, ch,
+            check(lib.tcvn_rows_bn_prelu_backward(_p(z), z.stride(0), _p(dy), dy.stride(0), rows, ch,
                                                   _p(norm.weight if norm else None), _p(norm.bias if norm else None),
-                                                  _p(slope), C.c_void_p(stat.data_ptr()),
-                                                  C.c_void_p(dz.data_ptr()), dz.stride(0), _p(grads[norm.weight] if norm else None),
+                                                  _p(slope), _p(stat), _p(dz), dz.stride(0), _p(grads[norm.weight] if norm else None),
                                                   _p(grads[norm.bias] if norm else None), _p(grads[slope] if slope is not None else None),
                                                   float(p), C.c_uint64(seed), C.c_uint32(sid), _st()), "rows_bn_prelu_backward")
             dx = torch.empty_like(x)
             gb = grads.get(blk.linear.bias) if blk.linear.bias is not None else None
-            check(lib.tcvn_linear_backward(C.c_void_p(dz.data_ptr()), dz.stride(0), C.c_void_p(x.data_ptr()), x.stride(0),
-                                           C.c_void_p(blk.linear.weight.data_ptr()), C.c_void_p(dx.data_ptr()), dx.stride(0),
-                                           C.c_void_p(grads[blk.linear.weight].data_ptr()), C.c_void_p(0 if gb is None else gb.data_ptr()),
+            check(lib.tcvn_linear_backward(_p(dz), dz.stride(0), _p(x), x.stride(0), _p(blk.linear.weight), _p(dx), dx.stride(0),
+                                           _p(grads[blk.linear.weight]), _p(gb),
                                            rows, blk.linear.weight.shape[0], blk.linear.weight.shape[1], _st()), "linear_backward")
             dy = dx
         self.saved = []

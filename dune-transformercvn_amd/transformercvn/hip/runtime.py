@@ -9,18 +9,35 @@ PyTorch supplies device memory, the current stream and (optionally) torch.distri
 """
 from __future__ import annotations
 
-from types import SimpleNamespace
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 from torch import Tensor, nn
 
-from . import _lib
+from . import _lib, occlusion
 from .engine import DenseNetEngine, HeadEngine
+from .native import gpu_only
 from .pixels import SparsePixels
 from ..network.layers.packed_data import token_rows
 
 PRECISIONS = {"fp32": _lib.MODE_F32, "f32": _lib.MODE_F32, "32": _lib.MODE_F32, "bf16": _lib.MODE_BF16, "16": _lib.MODE_BF16}
+
+
+class StepSeeds(NamedTuple):
+    """The seeds one forward() / embed() / encode() hands to the native plans (validation: tcvn_dropout_keep replays the masks)."""
+    event: int
+    prong: int
+    head: int
+    mlp: int
+
+
+class LastForward(NamedTuple):
+    """What the last forward() left for the explainers: its input rows (the tokens are rebuilt from them) and their layout."""
+    rows: Tensor
+    tok_row: Tensor
+    B: int
+    P: int
+    n_prongs: int
 
 
 class _FusedStep(torch.autograd.Function):
@@ -29,8 +46,7 @@ class _FusedStep(torch.autograd.Function):
     @staticmethod
     def forward(ctx, anchor: Tensor, runtime: "HipRuntime", state: dict):
         ctx.runtime, ctx.state, ctx.anchor = runtime, state, anchor
-        ev, pr = state["event_logits"], state["prong_logits"]
-        return ev, pr
+        return state["event_logits"], state["prong_logits"]
 
     @staticmethod
     def backward(ctx, d_ev: Tensor, d_pr: Tensor):
@@ -85,7 +101,7 @@ class HipRuntime:
         self.grad_ready_hook = None          # called as hook(tag) when a gradient segment is final ("head", "event", "prong")
         self.segments: Dict[str, Tuple[int, int]] = {}
         self.offsets: Dict[str, Tuple[int, int]] = {}
-        self._head_in = None                 # (rows, tok_row, B, P, n_prongs) of the last forward()
+        self._last_forward: Optional[LastForward] = None
 
     # ---------------------------------------------------------------------------------------------------------------
     # flat arenas
@@ -100,83 +116,82 @@ class HipRuntime:
     def ensure_bound(self):
         if not self._needs_rebind():
             return
-        net = self.network
-        params = [(n, p) for n, p in net.named_parameters()]
+        params = [(n, p) for n, p in self.network.named_parameters()]
         dev = params[0][1].device
         if dev.type != "cuda":
             raise RuntimeError("transformercvn (MI355X build): parameters must live on the GPU; there is no CPU fallback")
-        total = sum(p.numel() for _, p in params)
-        flat_p = torch.empty(total, dtype=torch.float32, device=dev)
-        flat_g = torch.zeros(total, dtype=torch.float32, device=dev)
-        off = 0
-        self._grad_views = []
-        offsets = {}
-        for n, p in params:
-            k = p.numel()
-            flat_p[off:off + k].copy_(p.detach().reshape(-1).float())
-            p.data = flat_p[off:off + k].view(p.shape)
-            gv = flat_g[off:off + k].view(p.shape)
+        self._build_arenas(params, dev)
+        self._build_segments()
+        self._bind_plans(params, dev)
+        self._bind_counters(dev)
+
+    def _build_arenas(self, params, dev):
+        """Parameters, their gradients and the floating-point buffers become views of three flat fp32 arenas."""
+        def flatten(named):
+            """One fp32 arena of these tensors, each made a view of its slice -> (arena, {name: (offset, numel)})."""
+            flat = torch.empty(sum(t.numel() for _, t in named), dtype=torch.float32, device=dev)
+            spans, off = {}, 0
+            for n, t in named:
+                k = t.numel()
+                flat[off:off + k].copy_(t.detach().reshape(-1).float())
+                t.data = flat[off:off + k].view(t.shape)
+                spans[n] = (off, k)
+                off += k
+            return flat, spans
+        self.flat_param, self.offsets = flatten(params)          # offsets: name (relative to the network) -> (offset, numel)
+        self.flat_grad = torch.zeros_like(self.flat_param)
+        self._grad_views = [self.flat_grad[off:off + k].view(p.shape) for (_, p), (off, k) in zip(params, self.offsets.values())]
+        for (_, p), gv in zip(params, self._grad_views):
             if p.requires_grad:
                 p.grad = gv
-            self._grad_views.append(gv)
-            offsets[n] = (off, k)
-            off += k
-        bufs = [(n, b) for n, b in net.named_buffers() if b.is_floating_point()]
-        flat_b = torch.empty(sum(b.numel() for _, b in bufs), dtype=torch.float32, device=dev)
-        off = 0
-        for n, b in bufs:
-            k = b.numel()
-            flat_b[off:off + k].copy_(b.reshape(-1).float())
-            b.data = flat_b[off:off + k].view(b.shape)
-            off += k
-        self.flat_param, self.flat_grad, self.flat_buf = flat_p, flat_g, flat_b
-        self.offsets = offsets                        # name (relative to the network) -> (offset, numel) in the arenas
+        self.flat_buf, _ = flatten([(n, b) for n, b in self.network.named_buffers() if b.is_floating_point()])
         ps = [p for _, p in params]
         self._sig = (ps[0].data_ptr(), ps[-1].data_ptr())
         self._params = ps
         self._param_grads = {p: g for p, g in zip(ps, self._grad_views)}       # parameter object -> its gradient view in the arena
-        # gradient segments for overlapped all-reduce: parameters are laid out in registration order
-        def span(prefix):
-            keys = [k for k in offsets if k.startswith(prefix)]
-            lo = min(offsets[k][0] for k in keys)
-            hi = max(offsets[k][0] + offsets[k][1] for k in keys)
-            return lo, hi
-        self.segments = {"event": span("prong_embedding.event_pixel_embedding.")}
+
+    def _build_segments(self):
+        """Gradient segments for the overlapped all-reduce: parameters are laid out in registration order."""
+        offsets = self.offsets
+
+        def span(keys):
+            return min(offsets[k][0] for k in keys), max(offsets[k][0] + offsets[k][1] for k in keys)
+        self.segments = {"event": span([k for k in offsets if k.startswith("prong_embedding.event_pixel_embedding.")])}
         pfx = "prong_embedding.prong_pixel_embedding."
+        whole = span([k for k in offsets if k.startswith(pfx)])
         parts = getattr(self.pr_engine, "n_parts", 0)
         if parts > 1:      # the prong embedder's backward is issued block by block: one exchange segment per dense block
             for part in range(parts):
-                keys = [k for k in offsets if any(k.startswith(pfx + q) for q in self.pr_engine.part_prefixes(part))]
-                self.segments[f"prong{part}"] = (min(offsets[k][0] for k in keys), max(offsets[k][0] + offsets[k][1] for k in keys))
+                self.segments[f"prong{part}"] = span([k for k in offsets
+                                                      if any(k.startswith(pfx + q) for q in self.pr_engine.part_prefixes(part))])
             covered = sum(hi - lo for t, (lo, hi) in self.segments.items() if t.startswith("prong"))
-            assert covered == span(pfx)[1] - span(pfx)[0], "prong embedder segments must tile its parameter span"
+            assert covered == whole[1] - whole[0], "prong embedder segments must tile its parameter span"
         else:
-            self.segments["prong"] = span(pfx)
-        # bind the native plans to the views
-        named_p = dict(net.named_parameters())
-        named_b = {n: b for n, b in net.named_buffers() if b.is_floating_point()}
-        grads = {n: g for (n, _), g in zip(params, self._grad_views)}
+            self.segments["prong"] = whole
 
-        def sub(prefix):
+    def _bind_plans(self, params, dev):
+        """The three native plans are bound to their views of the arenas; the anchor and the position embedding are looked up."""
+        named_p = dict(params)
+        named_b = {n: b for n, b in self.network.named_buffers() if b.is_floating_point()}
+        grads = {n: g for (n, _), g in zip(params, self._grad_views)}
+        for engine, prefix in ((self.ev_engine, "prong_embedding.event_pixel_embedding."),
+                               (self.pr_engine, "prong_embedding.prong_pixel_embedding."), (self.head, "")):
             d = {k[len(prefix):]: v.detach() for k, v in named_p.items() if k.startswith(prefix)}
             d.update({k[len(prefix):]: v for k, v in named_b.items() if k.startswith(prefix)})
-            g = {k[len(prefix):]: v for k, v in grads.items() if k.startswith(prefix)}
-            return d, g
-        d, g = sub("prong_embedding.event_pixel_embedding.")
-        self.ev_engine.bind(d, g)
-        d, g = sub("prong_embedding.prong_pixel_embedding.")
-        self.pr_engine.bind(d, g)
-        d, g = sub("")
-        self.head.bind(d, g)
+            engine.bind(d, {k[len(prefix):]: v for k, v in grads.items() if k.startswith(prefix)})
         self.anchor = torch.zeros(1, device=dev, requires_grad=True)
         self._pos = named_p["prong_embedding.event_position_embedding"]
         self._pos_grad = grads["prong_embedding.event_position_embedding"]
+
+    def _bind_counters(self, dev):
+        """num_batches_tracked of every BatchNorm become views of one int64 arena: one add per step instead of 139.  Also creates
+        the side stream of the event embedder (forward / _backward), once per (re)bind."""
+        net = self.network
         pe = net.prong_embedding
         ran = [m for mod in (pe.event_pixel_embedding, pe.prong_pixel_embedding, pe.combined_embedding, net.prong_decoder)
                for m in mod.modules() if isinstance(m, (nn.BatchNorm1d, nn.BatchNorm2d))]
-        # num_batches_tracked of every BatchNorm become views of one int64 arena: one add per step instead of 139
         all_bn = [m for m in net.modules() if isinstance(m, (nn.BatchNorm1d, nn.BatchNorm2d))]
-        self._side = torch.cuda.Stream(dev, priority=self.side_priority)     # event-embedder stream (forward/_backward)
+        self._side = torch.cuda.Stream(dev, priority=self.side_priority)
         self.flat_nbt = torch.stack([m.num_batches_tracked.to(dev) for m in all_bn]).contiguous()
         ran_ids = {id(m) for m in ran}
         self._nbt_inc = torch.tensor([1 if id(m) in ran_ids else 0 for m in all_bn], dtype=torch.int64, device=dev)
@@ -214,133 +229,117 @@ class HipRuntime:
     # ---------------------------------------------------------------------------------------------------------------
     # forward / backward
     # ---------------------------------------------------------------------------------------------------------------
+    def _next_seeds(self) -> StepSeeds:
+        """The seeds of this call's native plans; advances the step counter.  last_seeds keeps the three that validation replays."""
+        seed = (self.seed * 1000003 + self.step) & 0x7FFFFFFFFFFFFFFF
+        self.step += 1
+        seeds = StepSeeds(event=seed ^ 0x1111, prong=seed ^ 0x2222, head=seed ^ 0x3333, mlp=seed ^ 0x4444)
+        self.last_seeds = {"event": seeds.event, "prong": seeds.prong, "head": seeds.head}
+        return seeds
+
+    def _input_rows(self, features: Tensor, extra: Tensor, event_px: SparsePixels, prong_px: SparsePixels, prong_mask: Tensor,
+                    n_prongs: int, training: bool, seeds: StepSeeds, overlap: bool) -> Tensor:
+        """[B + n_prongs, feat+pix+pos] input rows of the combined embedding (prong_mask on the device).  The two embedders are
+        independent until the token path: with `overlap` the small event DenseNet (B images) runs on the side stream underneath
+        the prong DenseNet (n_prongs images), whose launches alone do not fill the chip in the deep blocks."""
+        pe = self.network.prong_embedding
+        dev = self.flat_param.device
+        B = prong_mask.shape[0]
+        feat, pix, pos = pe.feature_embedding_dim, pe.pixel_embedding_dim, pe.position_embedding_dim
+        event_px.count, prong_px.count = B, n_prongs
+        rows = torch.zeros(B + n_prongs, feat + pix + pos, device=dev)
+        rows[:, feat + pix:] = self._pos            # prongs also get the *event* position embedding (reference quirk)
+        if self.smart_features:                     # layers/prong_feature_embedding.py:73-78: MLP over [features | extra[event]]
+            i1, i2 = prong_mask.nonzero(as_tuple=True)
+            fin = torch.cat((features.to(dev)[i1, i2], extra.to(dev)[i1]), dim=1)
+            rows[B:, :feat] = self._mlp().forward(fin, training, seeds.mlp)
+        main = torch.cuda.current_stream(dev)
+        side = self._side if overlap else main
+        side.wait_stream(main)
+        with torch.cuda.stream(side):
+            self.ev_engine.forward(event_px.coords, event_px.values, B, rows[:B, :feat + pix], training, seeds.event,
+                                   event_px.value_mode, event_px.noise_std if training else 0.0)
+        self.pr_engine.forward(prong_px.coords, prong_px.values, n_prongs, rows[B:, feat:feat + pix], training, seeds.prong,
+                               prong_px.value_mode, prong_px.noise_std if training else 0.0)
+        main.wait_stream(side)
+        return rows
+
     def forward(self, features: Tensor, extra: Tensor, event_px: SparsePixels, event_mask: Tensor, prong_px: SparsePixels,
                 prong_mask: Tensor, counts: Optional[Tuple[int, int]] = None) -> Tuple[Tensor, Tensor]:
         self.ensure_bound()
-        net, opt = self.network, self.options
-        pe = net.prong_embedding
+        pe = self.network.prong_embedding
         dev = self.flat_param.device
-        training = net.training
+        training = self.network.training
         B, P = prong_mask.shape
         n_prongs = int(counts[1]) if counts is not None else int(prong_mask.sum().item())
         prong_mask = prong_mask.to(dev)
-        event_px.count, prong_px.count = B, n_prongs
         tok_row = token_rows(prong_mask, B)
-        feat, pix, pos = pe.feature_embedding_dim, pe.pixel_embedding_dim, pe.position_embedding_dim
-        in_dim = feat + pix + pos
-        seed = (self.seed * 1000003 + self.step) & 0x7FFFFFFFFFFFFFFF
-        self.step += 1
-        # seeds of the three native plans for this step (validation: tcvn_dropout_keep replays the masks from them)
-        self.last_seeds = {"event": seed ^ 0x1111, "prong": seed ^ 0x2222, "head": seed ^ 0x3333}
+        seeds = self._next_seeds()
         with torch.no_grad():
-            rows = torch.zeros(B + n_prongs, in_dim, device=dev)
-            rows[:, feat + pix:] = self._pos            # prongs also get the *event* position embedding (reference quirk)
-            if self.smart_features:                     # layers/prong_feature_embedding.py:73-78: MLP over [features | extra[event]]
-                i1, i2 = prong_mask.nonzero(as_tuple=True)
-                fin = torch.cat((features.to(dev)[i1, i2], extra.to(dev)[i1]), dim=1)
-                rows[B:, :feat] = self._mlp().forward(fin, training, seed ^ 0x4444)
-            # the two embedders are independent until the token path: the small event DenseNet (B images) runs on a side
-            # stream underneath the prong DenseNet (n_prongs images), whose launches alone do not fill the chip in the deep blocks
-            main = torch.cuda.current_stream(dev)
-            side = self._side if self.overlap_embedders else main
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                self.ev_engine.forward(event_px.coords, event_px.values, B, rows[:B, :feat + pix], training, seed ^ 0x1111,
-                                       event_px.value_mode, event_px.noise_std if training else 0.0)
-            self.pr_engine.forward(prong_px.coords, prong_px.values, n_prongs, rows[B:, feat:feat + pix], training,
-                                   seed ^ 0x2222, prong_px.value_mode, prong_px.noise_std if training else 0.0)
-            main.wait_stream(side)
-            ev, pr = self.head.forward(rows, tok_row, B, P, n_prongs, training, seed ^ 0x3333)
-            self._head_in = (rows, tok_row, B, P, n_prongs)      # kept for leave_one_prong_out (the tokens are rebuilt from the rows)
+            rows = self._input_rows(features, extra, event_px, prong_px, prong_mask, n_prongs, training, seeds, self.overlap_embedders)
+            ev, pr = self.head.forward(rows, tok_row, B, P, n_prongs, training, seeds.head)
+            self._last_forward = LastForward(rows, tok_row, B, P, n_prongs)
             if training:
                 self.flat_nbt += self._nbt_inc
         if not (training and torch.is_grad_enabled()):
             return ev, pr
-        state = dict(rows=rows, tok_row=tok_row, B=B, P=P, n_prongs=n_prongs, event_logits=ev, prong_logits=pr,
-                     feat=feat, pix=pix, keep=(event_px, prong_px))      # the COO lists are read again by backward
+        state = dict(self._last_forward._asdict(), event_logits=ev, prong_logits=pr, feat=pe.feature_embedding_dim,
+                     pix=pe.pixel_embedding_dim, keep=(event_px, prong_px))      # the COO lists are read again by backward
         anchor = self.anchor_param if (self.anchor_param is not None and self.anchor_param.device == dev) else self.anchor
         return _FusedStep.apply(anchor, self, state)
 
     # ---------------------------------------------------------------------------------------------------------------
     # stage-by-stage forward (the reference's sub-module call surface; forward only)
     # ---------------------------------------------------------------------------------------------------------------
-    def _rows(self, event_px: SparsePixels, prong_px: SparsePixels, B: int, n_prongs: int, training: bool, seed: int) -> Tensor:
-        """[B + n_prongs, feat+pix+pos] input rows of the combined embedding from the two DenseNet engines."""
-        pe = self.network.prong_embedding
-        dev = self.flat_param.device
-        feat, pix, pos = pe.feature_embedding_dim, pe.pixel_embedding_dim, pe.position_embedding_dim
-        rows = torch.zeros(B + n_prongs, feat + pix + pos, device=dev)
-        rows[:, feat + pix:] = self._pos
-        event_px.count, prong_px.count = B, n_prongs
-        self.ev_engine.forward(event_px.coords, event_px.values, B, rows[:B, :feat + pix], training, seed ^ 0x1111,
-                               event_px.value_mode, event_px.noise_std if training else 0.0)
-        self.pr_engine.forward(prong_px.coords, prong_px.values, n_prongs, rows[B:, feat:feat + pix], training, seed ^ 0x2222,
-                               prong_px.value_mode, prong_px.noise_std if training else 0.0)
-        return rows
-
     def embed(self, features: Tensor, extra: Tensor, event_px: SparsePixels, event_mask: Tensor, prong_px: SparsePixels,
               prong_mask: Tensor, training: bool = False) -> Tensor:
-        """BaseProngEmbedding.forward: -> tokens [B, 1+P, hidden] (padding rows zero)."""
+        """BaseProngEmbedding.forward: -> tokens [B, 1+P, hidden] (padding rows zero).  Both embedders on the current stream."""
         self.ensure_bound()
         with torch.no_grad():
-            dev = self.flat_param.device
-            prong_mask = prong_mask.to(dev)
+            prong_mask = prong_mask.to(self.flat_param.device)
             B, P = prong_mask.shape
             n_prongs = int(prong_mask.sum().item())
-            seed = (self.seed * 1000003 + self.step) & 0x7FFFFFFFFFFFFFFF
-            self.step += 1
-            rows = self._rows(event_px, prong_px, B, n_prongs, training, seed)
-            if self.smart_features:
-                pe = self.network.prong_embedding
-                i1, i2 = prong_mask.nonzero(as_tuple=True)
-                fin = torch.cat((features.to(dev)[i1, i2], extra.to(dev)[i1]), dim=1)
-                rows[B:, :pe.feature_embedding_dim] = self._mlp().forward(fin, training, seed ^ 0x4444)
+            seeds = self._next_seeds()
+            rows = self._input_rows(features, extra, event_px, prong_px, prong_mask, n_prongs, training, seeds, False)
             if training:
                 self.flat_nbt += self._nbt_inc_embed
-            return self.head.embed(rows, token_rows(prong_mask, B), B, P, n_prongs, training, seed ^ 0x3333)
+            return self.head.embed(rows, token_rows(prong_mask, B), B, P, n_prongs, training, seeds.head)
+
+    def _token_map(self, tokens: Tensor, mask: Tensor) -> Tensor:
+        """mask [B, S] -> the int32 tok_row the head engine takes for tokens that are given as such: 0 at a token, -1 at padding."""
+        gpu_only(tokens, "the encoder")
+        return torch.where(mask.to(self.flat_param.device), 0, -1).to(torch.int32).contiguous()
 
     def encode(self, tokens: Tensor, mask: Tensor, training: bool = False, return_attention: bool = False):
         """ProngCustomBertEncoder.forward: tokens [B, S, hidden], mask [B, S] -> hidden [S, B, hidden] (masked); with
         return_attention also the attention probabilities [L, B, H, S, S] of that run (pre-dropout, see tcvn_head_attention)."""
         self.ensure_bound()
         with torch.no_grad():
-            dev = self.flat_param.device
-            if not tokens.is_cuda:
-                raise RuntimeError("transformercvn (MI355X build): the encoder runs on the GPU only; there is no CPU fallback")
-            tok = torch.where(mask.to(dev), 0, -1).to(torch.int32).contiguous()
-            seed = (self.seed * 1000003 + self.step) & 0x7FFFFFFFFFFFFFFF
-            self.step += 1
-            hidden = self.head.encode(tokens.detach().float().contiguous(), tok, training, seed ^ 0x3333)
-            if not return_attention:
-                return hidden
-            return hidden, self.head.attention(tok)
+            tok = self._token_map(tokens, mask)
+            hidden = self.head.encode(tokens.detach().float().contiguous(), tok, training, self._next_seeds().head)
+            return (hidden, self.head.attention(tok)) if return_attention else hidden
 
     # ---------------------------------------------------------------------------------------------------------------
-    # explaining a prediction (forward only): attention maps and the leave-one-prong-out scan
+    # explaining a prediction (forward only): attention maps, the leave-one-prong-out scan, occlusion maps
     # ---------------------------------------------------------------------------------------------------------------
-    def forward_with_attention(self, features: Tensor, extra: Tensor, event_px: SparsePixels, event_mask: Tensor,
-                               prong_px: SparsePixels, prong_mask: Tensor,
-                               counts: Optional[Tuple[int, int]] = None) -> Tuple[Tensor, Tensor, Tensor]:
+    def forward_with_attention(self, features: Tensor, extra: Tensor, event_px: SparsePixels, event_mask: Tensor, prong_px: SparsePixels,
+                               prong_mask: Tensor, counts: Optional[Tuple[int, int]] = None) -> Tuple[Tensor, Tensor, Tensor]:
         """forward() plus the attention probabilities [L, B, H, 1+P, 1+P] of that very run: plain tensors, no autograd graph.
         Honours network.training as forward() does (in train mode this IS one more training-mode forward: running statistics and
         the step counter advance); the probabilities are pre-dropout."""
         with torch.no_grad():
             ev, pr = self.forward(features, extra, event_px, event_mask, prong_px, prong_mask, counts)
-            return ev, pr, self.head.attention(self._head_in[1])
+            return ev, pr, self.head.attention(self._last_forward.tok_row)
 
     def leave_one_prong_out(self, tokens: Tensor, mask: Tensor) -> Tuple[Tensor, Tensor]:
         """tokens [B, S, hidden], mask [B, S] -> (event_logits [B, Ce], loo_event_logits [B, S-1, Ce]) in eval arithmetic: row [b, p]
         is event b's logits with prong slot p masked out (rows of padded slots repeat event_logits[b])."""
         self.ensure_bound()
         with torch.no_grad():
-            if not tokens.is_cuda:
-                raise RuntimeError("transformercvn (MI355X build): the encoder runs on the GPU only; there is no CPU fallback")
-            tok = torch.where(mask.to(self.flat_param.device), 0, -1).to(torch.int32).contiguous()
-            return self.head.leave_one_out(tokens.detach().float().contiguous(), tok)
+            return self.head.leave_one_out(tokens.detach().float().contiguous(), self._token_map(tokens, mask))
 
-    def forward_leave_one_prong_out(self, features: Tensor, extra: Tensor, event_px: SparsePixels, event_mask: Tensor,
-                                    prong_px: SparsePixels, prong_mask: Tensor,
-                                    counts: Optional[Tuple[int, int]] = None) -> Tuple[Tensor, Tensor, Tensor]:
+    def forward_leave_one_prong_out(self, features: Tensor, extra: Tensor, event_px: SparsePixels, event_mask: Tensor, prong_px: SparsePixels,
+                                    prong_mask: Tensor, counts: Optional[Tuple[int, int]] = None) -> Tuple[Tensor, Tensor, Tensor]:
         """Eval-mode forward() plus the scan over its tokens -> (event_logits, prong_logits, loo_event_logits [B, P, Ce]).  The
         DenseNets run once; the scan adds one encoder + event-decoder sequence per valid prong.  event_logits are the scan's own
         unablated rows (the same kernels on the same tokens as forward()'s), so padded slots of the scan equal them exactly."""
@@ -348,161 +347,45 @@ class HipRuntime:
             raise RuntimeError("leave_one_prong_out explains an eval-mode prediction: call network.eval() first")
         with torch.no_grad():
             _, pr = self.forward(features, extra, event_px, event_mask, prong_px, prong_mask, counts)
-            rows, tok_row, B, P, n_prongs = self._head_in
-            tokens = self.head.embed(rows, tok_row, B, P, n_prongs, False, 0)
-            ev, loo = self.head.leave_one_out(tokens, tok_row)
+            last = self._last_forward
+            tokens = self.head.embed(last.rows, last.tok_row, last.B, last.P, last.n_prongs, False, 0)
+            ev, loo = self.head.leave_one_out(tokens, last.tok_row)
             return ev, pr, loo
+
+    def _scan(self, maps: str, *inputs) -> "occlusion.Scan":
+        """forward(*inputs) and the occlusion scan over it (hip/occlusion.py).  However many variants follow, it counts as ONE forward()
+        for the step counter, and the head's forward workspace (attention probabilities) is left as forward() wrote it."""
+        ev, pr = self.forward(*inputs)
+        _, _, event_px, _, prong_px, prong_mask = inputs[:6]
+        return occlusion.Scan(self.ev_engine, self.pr_engine, self.head, self.pixel_shape, self._last_forward, ev, pr, event_px, prong_px,
+                              prong_mask, maps)
 
     def forward_occlusion(self, features: Tensor, extra: Tensor, event_px: SparsePixels, event_mask: Tensor, prong_px: SparsePixels,
                           prong_mask: Tensor, counts: Optional[Tuple[int, int]] = None, tile: Tuple[int, int] = (16, 16),
                           maps: str = "all", max_maps_per_pass: int = 256):
         """Eval-mode forward() plus the occlusion scan over its pixel maps -> occlusion.OcclusionResult.  One variant per (event,
         token slot, tile that holds a hit): that map without the hits of that tile goes through its embedder (passes of at most
-        max_maps_per_pass maps), replaces its token in the event's sequence and goes through encoder and decoders.  Counts as ONE
-        forward() for the step counter; the head's forward workspace (attention probabilities) is left as forward() wrote it."""
-        from . import occlusion
+        max_maps_per_pass maps), replaces its token in the event's sequence and goes through encoder and decoders."""
         tile, maps, max_pass = occlusion.check_args(tile, maps, max_maps_per_pass)
         if self.network.training:
             raise RuntimeError("occlusion_maps explains an eval-mode prediction: call network.eval() first")
         with torch.no_grad():
-            base = self._occlusion_base(features, extra, event_px, event_mask, prong_px, prong_mask, counts, maps)
-            return self._occlusion_level(base, tile, max_pass)
+            return self._scan(maps, features, extra, event_px, event_mask, prong_px, prong_mask, counts).level(tile, max_pass)
 
     def forward_occlusion_refine(self, features: Tensor, extra: Tensor, event_px: SparsePixels, event_mask: Tensor,
                                  prong_px: SparsePixels, prong_mask: Tensor, counts: Optional[Tuple[int, int]] = None,
                                  tile: Tuple[int, int] = (64, 64), levels: int = 3, keep: float = 0.25, target="event", maps: str = "all",
                                  max_maps_per_pass: int = 256, max_variants: Optional[int] = None):
-        """Eval-mode forward() plus a coarse-to-fine occlusion scan -> occlusion.RefinedOcclusion.  Level 0 is forward_occlusion(tile);
-        level l halves the tiles of level l - 1 and evaluates only the children (that hold a hit) of the variants whose score |h| --
-        heatmap(level, target) -- reaches keep times the largest score of their group (the event, or the map with target "prong").
-        The choice is made on the device (tcvn_occlusion_select); one host read-back per hit list and level.  max_variants bounds
-        the sum of V over the levels: the level that would pass it and all later ones are not run.  Counts as ONE forward()."""
-        from . import occlusion
+        """Eval-mode forward() plus a coarse-to-fine occlusion scan over its pixel maps (occlusion.Scan.refine: level 0 is
+        forward_occlusion(tile), every later level halves the tiles and keeps to what matters) -> occlusion.RefinedOcclusion."""
         tile, levels, keep, maps, max_pass, max_variants = occlusion.check_refine_args(tile, levels, keep, target, maps, max_maps_per_pass,
                                                                                        max_variants)
-        B = prong_mask.shape[0]
-        occlusion.parse_target(target, B, self.head.cfg.event_classes)
+        occlusion.parse_target(target, prong_mask.shape[0], self.head.cfg.event_classes)
         if self.network.training:
             raise RuntimeError("occlusion_refine explains an eval-mode prediction: call network.eval() first")
-        group = _lib.OCC_GROUP_MAP if isinstance(target, str) and target == "prong" else _lib.OCC_GROUP_EVENT
         with torch.no_grad():
-            base = self._occlusion_base(features, extra, event_px, event_mask, prong_px, prong_mask, counts, maps)
-            done, heats, evaluated, used, stopped_at, keep_map = [], [], [], 0, None, None
-            for lv in range(levels):
-                budget = None if max_variants is None else max_variants - used
-                res = self._occlusion_level(base, (tile[0] >> lv, tile[1] >> lv), max_pass, keep_map, budget)
-                if res is None:
-                    stopped_at = lv
-                    break
-                used += res.num_variants
-                done.append(res)
-                heats.append(occlusion.heatmap(res, target))
-                evaluated.append(occlusion.mark(res.index, B, base.P, res.grid))
-                if lv + 1 < levels:
-                    keep_map = occlusion.select(heats[-1], res.index, group, keep)
-            occupied = None
-            if done:
-                occupied = torch.zeros(B, 1 + base.P, *done[-1].grid, dtype=torch.uint8, device=base.rows.device)
-                for lst in base.lists:
-                    occlusion.occupancy(lst.coords, lst.n_img, self.pixel_shape, done[-1].tile, lst.img_bs, occupied)
-            return occlusion.RefinedOcclusion(base.ev, base.pr, done, heats, evaluated, occupied, target, keep, stopped_at)
-
-    def _occlusion_base(self, features: Tensor, extra: Tensor, event_px: SparsePixels, event_mask: Tensor, prong_px: SparsePixels,
-                        prong_mask: Tensor, counts, maps: str):
-        """The forward() being explained and what every pass of a scan over it reads: its rows and tokens, and one record per hit list
-        to scan (the event maps and the prong maps go through their own embedder engines, one list after the other)."""
-        ev, pr = self.forward(features, extra, event_px, event_mask, prong_px, prong_mask, counts)
-        rows, tok_row, B, P, n_prongs = self._head_in
-        dev = rows.device
-        tokens = self.head.embed(rows, tok_row, B, P, n_prongs, False, 0)
-        feat = self.network.prong_embedding.feature_embedding_dim
-        lists = []
-        if maps in ("all", "event"):
-            bs = torch.stack((torch.arange(B, device=dev), torch.zeros(B, dtype=torch.int64, device=dev)), 1).to(torch.int32)
-            lists.append(SimpleNamespace(engine=self.ev_engine, coords=event_px.coords.to(dev), values=event_px.values.to(dev),
-                                         value_mode=event_px.value_mode, n_img=B, img_bs=bs, row_base=0, col0=0))
-        if maps in ("all", "prongs") and n_prongs > 0:
-            i1, i2 = prong_mask.to(dev).nonzero(as_tuple=True)             # packed prong order: the embedder's image order
-            bs = torch.stack((i1, 1 + i2), 1).to(torch.int32)
-            lists.append(SimpleNamespace(engine=self.pr_engine, coords=prong_px.coords.to(dev), values=prong_px.values.to(dev),
-                                         value_mode=prong_px.value_mode, n_img=n_prongs, img_bs=bs, row_base=B, col0=feat))
-        return SimpleNamespace(ev=ev, pr=pr, rows=rows, tokens=tokens, tok_row=tok_row, B=B, P=P, n_prongs=n_prongs, lists=lists)
-
-    def _occlusion_level(self, base, tile, max_pass: int, keep_map: Optional[Tensor] = None, budget: Optional[int] = None):
-        """One scan over the maps of `base` at `tile` -> occlusion.OcclusionResult: every tile that holds a hit, or (keep_map: the
-        selection among the variants of the level with tiles twice the size) only the children of the selected tiles.  The variant
-        lists come first; None, before any variant is run, if they hold more than `budget` variants together."""
-        from . import occlusion
-        dev, P = base.rows.device, base.P
-        H, W = self.pixel_shape
-        grid = (-(-H // tile[0]), -(-W // tile[1]))
-        plans = [self._occlusion_list(lst, tile, max_pass, keep_map) for lst in base.lists]
-        if budget is not None and sum(plan.V for plan in plans) > budget:
-            return None
-        parts = [self._occlusion_passes(base, lst, plan, max_pass) for lst, plan in zip(base.lists, plans)]
-        if parts:
-            index, occ_ev, occ_pr = (torch.cat([p[i] for p in parts]) for i in range(3))
-        else:
-            index = torch.empty(0, 4, dtype=torch.int32, device=dev)
-            occ_ev, occ_pr = base.ev.new_empty(0, base.ev.shape[1]), base.pr.new_empty(0, P, base.pr.shape[2])
-        if len(parts) > 1:                    # the two lists are ordered by (b, s, ty, tx) each: merge them into that order
-            i64 = index.long()
-            key = ((i64[:, 0] * (1 + P) + i64[:, 1]) * grid[0] + i64[:, 2]) * grid[1] + i64[:, 3]
-            order = torch.argsort(key)
-            index, occ_ev, occ_pr = index[order].contiguous(), occ_ev[order].contiguous(), occ_pr[order].contiguous()
-        return occlusion.OcclusionResult(base.ev, base.pr, index, occ_ev, occ_pr, grid, tile)
-
-    def _occlusion_list(self, lst, tile, max_pass: int, keep_map: Optional[Tensor]):
-        """The variant list of one hit list (one host read-back).  A list that is unsorted or holds hits outside the maps is replaced
-        in `lst` by its cleaned copy, so later levels of a refinement start from that."""
-        shape = self.pixel_shape
-
-        def variants():
-            if keep_map is None:
-                return lst.engine.occlusion_variants(lst.coords, lst.n_img, shape, tile, lst.img_bs, max_pass)
-            return lst.engine.occlusion_refine_variants(lst.coords, lst.n_img, shape, tile, lst.img_bs, max_pass, keep_map)
-        V, unsorted, bad, bounds, vimg, index, handle = variants()
-        if unsorted or bad:
-            # the variant build walks each image's hits as one range: drop what the embedders drop, then a STABLE sort by image (the
-            # order inside an image decides which of two hits on one pixel wins)
-            coords, values = lst.coords, lst.values
-            c = coords.long()
-            keep = (c[:, 0] >= 0) & (c[:, 0] < lst.n_img) & (c[:, 1] >= 0) & (c[:, 1] < shape[0]) & (c[:, 2] >= 0) & (c[:, 2] < shape[1])
-            coords, values = coords[keep], values[keep]
-            order = torch.sort(coords[:, 0], stable=True).indices
-            lst.coords, lst.values = coords[order].contiguous(), values[order].contiguous()
-            V, unsorted, bad, bounds, vimg, index, handle = variants()
-            if unsorted or bad:
-                raise RuntimeError("occlusion_maps: the hit list is still unsorted after sorting it")
-        return SimpleNamespace(V=V, bounds=bounds, vimg=vimg, index=index, handle=handle)
-
-    def _occlusion_passes(self, base, lst, plan, max_pass: int):
-        """The variants of one list, pass by pass, through its embedder and the token path -> (index [V, 4], occluded_event_logits
-        [V, Ce], occluded_prong_logits [V, P, Cp]) in the embedder's image order.  The embedder writes [col0, col0 + engine.out_dim)
-        of its maps' rows."""
-        engine, coords, values = lst.engine, lst.coords, lst.values
-        rows, tokens, tok_row = base.rows, base.tokens, base.tok_row
-        dev = rows.device
-        V, bounds, vimg, index = plan.V, plan.bounds, plan.vimg, plan.index
-        B, S, _ = tokens.shape
-        occ_ev = torch.empty(V, self.head.cfg.event_classes, device=dev)
-        occ_pr = torch.empty(V, S - 1, self.head.cfg.prong_classes, device=dev)
-        if V == 0:
-            return index, occ_ev, occ_pr
-        cap = max(1, max(bounds[k + 1] - bounds[k] for k in range(len(bounds) - 1)))
-        out_coords = torch.empty(cap, 3, dtype=torch.int32, device=dev)
-        out_values = torch.empty(cap, values.shape[1], dtype=torch.float32, device=dev)
-        emb = torch.empty(min(max_pass, V), engine.out_dim, device=dev)
-        for k in range(len(bounds) - 1):
-            first = k * max_pass
-            n = min(max_pass, V - first)
-            nnz = bounds[k + 1] - bounds[k]
-            if nnz > 0:
-                engine.occlusion_build(plan.handle, coords, values, first, n, out_coords, out_values)
-            engine.occlusion_forward(out_coords, out_values, nnz, n, emb[:n], lst.value_mode)
-            self.head.occlusion_pass(rows, tokens, tok_row, base.n_prongs, vimg[first:first + n], index[first:first + n], lst.row_base,
-                                     emb[:n], lst.col0, occ_ev[first:first + n], occ_pr[first:first + n])
-        return index, occ_ev, occ_pr
+            scan = self._scan(maps, features, extra, event_px, event_mask, prong_px, prong_mask, counts)
+            return scan.refine(tile, levels, keep, target, max_pass, max_variants)
 
     def _backward(self, st: dict, d_ev: Tensor, d_pr: Tensor):
         """Backward of the fused step in the order the gradient segments become final -- token path, event embedder (side

@@ -22,6 +22,11 @@ from transformercvn.network.layers.prong_target_decoder import ProngTargetDecode
 from transformercvn.options import Options
 
 
+def _as_sparse(pixels) -> SparsePixels:
+    """Pixel maps as the HIP runtime takes them: a SparsePixels bundle as it is, dense NCHW maps converted."""
+    return pixels if isinstance(pixels, SparsePixels) else SparsePixels.from_dense(pixels)
+
+
 class BaseProngEmbedding(nn.Module, ABC):
     @abstractmethod
     def create_pixel_embedding(self, options: Options, pixel_dim: int, output_dim: int):
@@ -80,10 +85,7 @@ class BaseProngEmbedding(nn.Module, ABC):
         net = owner_of(self)
         if net is None:
             raise RuntimeError("BaseProngEmbedding.forward needs the owning NeutrinoBaseNetwork (its HIP runtime holds the plans)")
-        if not isinstance(event_pixels, SparsePixels):
-            event_pixels = SparsePixels.from_dense(event_pixels)
-        if not isinstance(prong_pixels, SparsePixels):
-            prong_pixels = SparsePixels.from_dense(prong_pixels)
+        event_pixels, prong_pixels = _as_sparse(event_pixels), _as_sparse(prong_pixels)
         return net.hip_runtime().embed(features, extra, event_pixels, event_mask, prong_pixels, prong_mask, self.training)
 
 
@@ -140,10 +142,7 @@ class NeutrinoBaseNetwork(nn.Module):
     @torch.jit.unused
     def _hip_forward(self, features: Tensor, extra: Tensor, event_pixels: Tensor, event_mask: Tensor, prong_pixels: Tensor,
                      prong_mask: Tensor, counts: Optional[Tuple[int, int]] = None) -> Tuple[Tensor, Tensor]:
-        if not isinstance(event_pixels, SparsePixels):
-            event_pixels = SparsePixels.from_dense(event_pixels)
-        if not isinstance(prong_pixels, SparsePixels):
-            prong_pixels = SparsePixels.from_dense(prong_pixels)
+        event_pixels, prong_pixels = _as_sparse(event_pixels), _as_sparse(prong_pixels)
         return self.hip_runtime().forward(features, extra, event_pixels, event_mask, prong_pixels, prong_mask, counts)
 
     # ---- explaining a prediction (eager only; forward only, no autograd graph) -----------------------------------------------------
@@ -153,10 +152,7 @@ class NeutrinoBaseNetwork(nn.Module):
         """forward() -> (event_logits, prong_logits, weights [L, B, H, 1+P, 1+P]): weights[l, b, h, i, j] is the probability with which
         token i of event b attends to token j in head h of encoder layer l (token 0 the event, token 1+p prong slot p; pre-dropout;
         padded rows and columns zero).  transformercvn.hip.attention.rollout turns them into per-prong relevances."""
-        if not isinstance(event_pixels, SparsePixels):
-            event_pixels = SparsePixels.from_dense(event_pixels)
-        if not isinstance(prong_pixels, SparsePixels):
-            prong_pixels = SparsePixels.from_dense(prong_pixels)
+        event_pixels, prong_pixels = _as_sparse(event_pixels), _as_sparse(prong_pixels)
         return self.hip_runtime().forward_with_attention(features, extra, event_pixels, event_mask, prong_pixels, prong_mask, counts)
 
     @torch.jit.unused
@@ -166,10 +162,7 @@ class NeutrinoBaseNetwork(nn.Module):
         recomputed without prong slot p (padded slots repeat event_logits[b])."""
         if self.training:
             raise RuntimeError("leave_one_prong_out explains an eval-mode prediction: call .eval() first")
-        if not isinstance(event_pixels, SparsePixels):
-            event_pixels = SparsePixels.from_dense(event_pixels)
-        if not isinstance(prong_pixels, SparsePixels):
-            prong_pixels = SparsePixels.from_dense(prong_pixels)
+        event_pixels, prong_pixels = _as_sparse(event_pixels), _as_sparse(prong_pixels)
         return self.hip_runtime().forward_leave_one_prong_out(features, extra, event_pixels, event_mask, prong_pixels, prong_mask,
                                                               counts)
 
@@ -184,10 +177,7 @@ class NeutrinoBaseNetwork(nn.Module):
         occlusion.check_args(tile, maps, max_maps_per_pass)
         if self.training:
             raise RuntimeError("occlusion_maps explains an eval-mode prediction: call .eval() first")
-        if not isinstance(event_pixels, SparsePixels):
-            event_pixels = SparsePixels.from_dense(event_pixels)
-        if not isinstance(prong_pixels, SparsePixels):
-            prong_pixels = SparsePixels.from_dense(prong_pixels)
+        event_pixels, prong_pixels = _as_sparse(event_pixels), _as_sparse(prong_pixels)
         return self.hip_runtime().forward_occlusion(features, extra, event_pixels, event_mask, prong_pixels, prong_mask, counts,
                                                     tile, maps, max_maps_per_pass)
 
@@ -206,9 +196,6 @@ class NeutrinoBaseNetwork(nn.Module):
         occlusion.parse_target(target, prong_mask.shape[0], self.event_decoder.hidden_layer.out_features)
         if self.training:
             raise RuntimeError("occlusion_refine explains an eval-mode prediction: call .eval() first")
-        if not isinstance(event_pixels, SparsePixels):
-            event_pixels = SparsePixels.from_dense(event_pixels)
-        if not isinstance(prong_pixels, SparsePixels):
-            prong_pixels = SparsePixels.from_dense(prong_pixels)
+        event_pixels, prong_pixels = _as_sparse(event_pixels), _as_sparse(prong_pixels)
         return self.hip_runtime().forward_occlusion_refine(features, extra, event_pixels, event_mask, prong_pixels, prong_mask, counts,
                                                            tile, levels, keep, target, maps, max_maps_per_pass, max_variants)

@@ -67,16 +67,14 @@ class NeutrinoFullBaseTrainer(NeutrinoBase, ABC):
         """Install the overlapped arena all-reduce (RCCL via torch.distributed) on the runtime's segment hooks.  Called by
         on_fit_start() under Lightning; custom loops (bench.py) call it after init_process_group.  No-op at world size 1."""
         from transformercvn.hip import distributed as hd
-        from transformercvn.hip.distributed import GradReducer
         if not hd._active(group):
             return None
         rt = self.network.hip_runtime()
         rt.ensure_bound()
         # the ranks may have started from different random weights (the reference sets no seed and relies on DDP's initial
         # broadcast, which here covers the anchor only): rank 0's parameters, BatchNorm buffers and optimizer moments everywhere
-        from transformercvn.hip.distributed import sync_state
-        sync_state(rt, getattr(self, "_flat_optimizer", None), group)
-        self._reducer = GradReducer(rt.flat_grad, rt.segments, group)
+        hd.sync_state(rt, getattr(self, "_flat_optimizer", None), group)
+        self._reducer = hd.GradReducer(rt.flat_grad, rt.segments, group)
         rt.grad_ready_hook = self._reducer.on_ready
         self._dp_group = group
         return self._reducer
@@ -140,20 +138,13 @@ class NeutrinoFullBaseTrainer(NeutrinoBase, ABC):
     def forward(self, features: Tensor, extra: Tensor, event_coords: Tensor, event_values: Tensor, event_mask: Tensor,
                 prong_coords: Tensor, prong_values: Tensor, prong_mask: Tensor, counts=None) -> Tuple[Tensor, Tensor]:
         """-> (event_logits [B, Ce], prong_logits [B, P, Cp]) (reference :90-116).  Inputs are borrowed, never mutated."""
-        dev = event_values.device
-        if torch.is_tensor(self.mean) and features.numel() and not self.options.disable_smart_features:
-            features = features.clone()
-            features[prong_mask] = (features[prong_mask] - self.mean) / self.std
-            extra = (extra - self.extra_mean) / self.extra_std
-        shape = self.training_dataset.pixel_shape
         self.network.hip_runtime().anchor_param = self._ddp_anchor       # the autograd anchor of the fused step (see above)
-        event_pixels = self.preprocess_pixels(event_coords, event_values, shape)
-        prong_pixels = self.preprocess_pixels(prong_coords, prong_values, shape)
-        return self.network(features, extra, event_pixels, event_mask, prong_pixels, prong_mask, counts)
+        return self.network(*self._network_inputs(features, extra, event_coords, event_values, event_mask, prong_coords, prong_values,
+                                                  prong_mask), counts)
 
     def _network_inputs(self, features: Tensor, extra: Tensor, event_coords: Tensor, event_values: Tensor, event_mask: Tensor,
                         prong_coords: Tensor, prong_values: Tensor, prong_mask: Tensor):
-        """forward()'s preprocessing (feature normalisation, pixel bundles) for the explanation calls below."""
+        """Feature normalisation and pixel bundles: what forward() and the explanation calls below hand to the network."""
         if torch.is_tensor(self.mean) and features.numel() and not self.options.disable_smart_features:
             features = features.clone()
             features[prong_mask] = (features[prong_mask] - self.mean) / self.std
