@@ -4,6 +4,7 @@
 // coordinates is "highest index wins"); only tiles that hold a hit are variants.  Integer atomics only: every result is deterministic.
 #include "../../include/tcvn_hip.h"
 #include "tcvn_occlude.h"
+#include "occlude_dev.h"
 
 namespace tcvn {
 
@@ -24,18 +25,7 @@ bool occ_layout(int n_img, int H, int W, int th, int tw, int max_pass, OccLayout
     return true;
 }
 
-// ---- 1. occupancy: one thread per hit -------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_occ_count(const int* __restrict__ coords, long nnz, int n_img, int H, int W, int th, int tw,
-                                                   int Wt, int T, int* cnt, int* nnz_img, int* flags) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= nnz) return;
-    const int img = coords[3 * i], y = coords[3 * i + 1], x = coords[3 * i + 2];
-    if (i > 0 && coords[3 * (i - 1)] > img) atomicOr(&flags[0], 1);                      // the list is not sorted by image
-    if (img < 0 || img >= n_img || y < 0 || y >= H || x < 0 || x >= W) { atomicOr(&flags[1], 1); return; }   // a hit the embedders drop
-    atomicAdd(&cnt[(long)img * T + (y / th) * Wt + x / tw], 1);
-    atomicAdd(&nnz_img[img], 1);
-}
-
+// ---- 1. occupancy: one thread per hit (k_occ_count, occlude_dev.h) ------------------------------------------------------------------
 // refinement: the same pass, but a hit enters cnt only where the parent level's keep_map is set at its parent tile (tiles of 2*th x 2*tw);
 // nnz_img and the two flags still see every hit, so a variant's surviving hits stay "the whole image minus that one tile"
 __global__ __launch_bounds__(256) void k_occ_count_kept(const int* __restrict__ coords, long nnz, int n_img, int H, int W, int th, int tw,
@@ -54,24 +44,7 @@ __global__ __launch_bounds__(256) void k_occ_count_kept(const int* __restrict__ 
 }
 
 // ---- 2. variant list: ordered compaction of the occupied cells; one workgroup walks the cells in chunks -----------------------------------
-__device__ __forceinline__ long shfl_up64(long v, int d) {
-    const int lo = __shfl_up((int)(v & 0xffffffffL), d), hi = __shfl_up((int)(v >> 32), d);
-    return ((long)hi << 32) | (long)(unsigned)lo;
-}
-// exclusive prefix sum over the workgroup (wave64 shuffles, then the wave totals through LDS); total: the sum over all threads
-__device__ __forceinline__ long block_scan_excl(long v, long* wsum, long& total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    long inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const long t = shfl_up64(inc, d); if (lane >= d) inc += t; }
-    __syncthreads();                       // wsum may still be read from the previous call
-    if (lane == 63) wsum[w] = inc;
-    __syncthreads();
-    long base = 0, tot = 0;
-    for (int i = 0; i < nw; ++i) { const long s = wsum[i]; if (i < w) base += s; tot += s; }
-    total = tot;
-    return base + inc - v;
-}
+// (block_scan_excl: occlude_dev.h)
 constexpr int CT = 1024;
 __global__ __launch_bounds__(CT) void k_occ_compact(const int* __restrict__ cnt, const int* __restrict__ nnz_img, const int* flags,
                                                     const int* __restrict__ img_bs, int n_img, int T, int Wt, long cells, int max_pass,
@@ -173,18 +146,6 @@ __global__ void k_occ_gather(const float* tokens, const int* tok_row, const int*
 }
 
 // ---- 6. heat map: softmax(base)[c] - softmax(occluded)[c] at every variant's position -------------------------------------------------
-__device__ __forceinline__ int argmax_row(const float* a, int C) {
-    int c = 0;
-    for (int k = 1; k < C; ++k) if (a[k] > a[c]) c = k;
-    return c;
-}
-__device__ __forceinline__ double softmax_at(const float* a, int C, int c) {
-    float m = a[0];
-    for (int k = 1; k < C; ++k) m = fmaxf(m, a[k]);
-    double s = 0.0;
-    for (int k = 0; k < C; ++k) s += exp((double)a[k] - (double)m);
-    return exp((double)a[c] - (double)m) / s;
-}
 __global__ __launch_bounds__(256) void k_occ_heat(const float* base_ev, const float* base_pr, const float* occ_ev, const float* occ_pr,
                                                   const int* index, long V, int P, int Ce, int Cp, int Ht, int Wt, int prong,
                                                   const int* cls, float* out) {

@@ -27,6 +27,8 @@ OCC_MAX_PASS = 256                  # TCVN_OCC_MAX_PASS: maps per embedder / tok
 OCC_TARGET_EVENT, OCC_TARGET_PRONG = 0, 1      # TCVN_OCC_TARGET_*: which logits the occlusion heat map is taken from
 OCC_GROUP_EVENT, OCC_GROUP_MAP = 0, 1          # TCVN_OCC_GROUP_*: whose largest score a refinement level's variants are held against
 OCC_MAX_LEVELS = 16                 # TCVN_OCC_MAX_LEVELS: levels of one coarse-to-fine occlusion scan
+CURVE_MAX_STEPS, CURVE_MAX_TILES = 64, 4096    # TCVN_CURVE_MAX_*: steps of a deletion / insertion curve, tiles per map it can rank
+CURVE_DELETION, CURVE_INSERTION = 0, 1         # TCVN_CURVE_*: which hits a curve variant keeps
 
 
 class DenseNetCfg(C.Structure):
@@ -113,6 +115,12 @@ def _load():
     sig("tcvn_occlusion_mark", i32, vp, i64, i32, i32, i32, i32, vp, vp)
     sig("tcvn_occlusion_occupancy", i32, vp, i64, i32, i32, i32, i32, i32, vp, i32, i32, vp, vp)
     sig("tcvn_occlusion_paint", i32, i32, P(vp), P(vp), P(i32), P(i32), vp, i32, i32, vp, vp)
+    sig("tcvn_occlusion_curve_workspace_bytes", i64, i32, i32, i32, i32, i32, i32, i32)
+    sig("tcvn_occlusion_curve_variants", i32, vp, i64, i32, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, i64, P(i64),
+        i64, vp)
+    sig("tcvn_occlusion_curve_build_pass", i32, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, i64, i32, i32, vp, vp, i64,
+        vp)
+    sig("tcvn_occlusion_curve", i32, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp)
     sig("tcvn_linear_forward", i32, vp, i64, vp, vp, vp, i64, i32, i32, i32, vp)
     sig("tcvn_rows_bn_prelu_forward", i32, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp, i32, f32, u64, C.c_uint32, vp)
     sig("tcvn_linear_backward", i32, vp, i64, vp, i64, vp, vp, i64, vp, vp, i32, i32, i32, vp)
@@ -154,6 +162,7 @@ EXPORTS = [
     "tcvn_occlusion_workspace_bytes", "tcvn_occlusion_variants", "tcvn_occlusion_build_pass", "tcvn_head_occlusion_workspace_bytes",
     "tcvn_head_occlusion", "tcvn_occlusion_heatmap",
     "tcvn_occlusion_select", "tcvn_occlusion_refine_variants", "tcvn_occlusion_mark", "tcvn_occlusion_occupancy", "tcvn_occlusion_paint",
+    "tcvn_occlusion_curve_workspace_bytes", "tcvn_occlusion_curve_variants", "tcvn_occlusion_curve_build_pass", "tcvn_occlusion_curve",
 ]
 
 lib = _load()

@@ -135,35 +135,63 @@ class _EmbedderEngine(_Plan):
         return self._occlusion_list(lib.tcvn_occlusion_refine_variants, (_ptr(keep_map), B, S - 1, pHt, pWt), "occlusion_refine_variants",
                                     coords, n_img, shape, tile, img_bs, max_pass)
 
-    def _occlusion_list(self, fn, parent: tuple, what: str, coords: torch.Tensor, n_img: int, shape: Tuple[int, int], tile: Tuple[int, int],
-                        img_bs: torch.Tensor, max_pass: int):
+    def occlusion_curve_variants(self, coords: torch.Tensor, n_img: int, shape: Tuple[int, int], tile: Tuple[int, int],
+                                 img_bs: torch.Tensor, max_pass: int, relevance: torch.Tensor, steps: int, mode: int,
+                                 rank: torch.Tensor) -> Tuple[VariantPlan, bool, bool]:
+        """tcvn_occlusion_curve_variants: the steps + 1 deletion / insertion variants (mode: _lib.CURVE_*) of every map of this list
+        that holds a hit, its tiles ranked by relevance float32 [B, 1 + P, Ht, Wt]; the ranks go into rank int32 of the same shape.
+        Same results as occlusion_variants(), with index [V, 4] = (b, s, k, m_k); the plan serves occlusion_curve_build."""
+        for t, dt in ((relevance, torch.float32), (rank, torch.int32)):
+            assert t.dtype == dt and t.is_contiguous() and t.dim() == 4 and t.device == coords.device
+        B, S, Ht, Wt = relevance.shape
+        assert rank.shape == relevance.shape and (Ht, Wt) == (-(-shape[0] // tile[0]), -(-shape[1] // tile[1]))
+        need = lib.tcvn_occlusion_curve_workspace_bytes(n_img, *shape, *tile, steps, max_pass)
+        return self._occlusion_list(lib.tcvn_occlusion_curve_variants, (_ptr(relevance), B, S - 1, steps, mode, _ptr(rank)),
+                                    "occlusion_curve_variants", coords, n_img, shape, tile, img_bs, max_pass, need, n_img * (steps + 1),
+                                    (steps, mode))
+
+    def _occlusion_list(self, fn, extra: tuple, what: str, coords: torch.Tensor, n_img: int, shape: Tuple[int, int], tile: Tuple[int, int],
+                        img_bs: torch.Tensor, max_pass: int, need: Optional[int] = None, rows: Optional[int] = None, geometry: tuple = ()):
+        """One variant-list call.  need / rows: the workspace bytes and the largest number of variants (default: those of the tile
+        scan, one variant per tile); geometry: what the list's build call repeats between the tile and max_pass."""
         assert coords.dtype == torch.int32 and coords.is_contiguous() and img_bs.dtype == torch.int32 and img_bs.shape == (n_img, 2)
         (H, W), (th, tw) = shape, tile
-        cells = n_img * (-(-H // th)) * (-(-W // tw))
-        need = lib.tcvn_occlusion_workspace_bytes(n_img, H, W, th, tw, max_pass)
+        if rows is None:
+            rows = n_img * (-(-H // th)) * (-(-W // tw))
+            need = lib.tcvn_occlusion_workspace_bytes(n_img, H, W, th, tw, max_pass)
         if need < 0:
-            raise RuntimeError(f"libtcvn_hip: occlusion_workspace_bytes rejects {n_img} maps of {H}x{W} in tiles of {th}x{tw}")
+            raise RuntimeError(f"libtcvn_hip: {what}: the workspace query rejects {n_img} maps of {H}x{W} in tiles of {th}x{tw}")
         dev = coords.device
         ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        vimg = torch.empty(cells, dtype=torch.int32, device=dev)
-        index = torch.empty(cells, 4, dtype=torch.int32, device=dev)
-        words = 4 + -(-cells // max_pass) + 1
+        vimg = torch.empty(rows, dtype=torch.int32, device=dev)
+        index = torch.empty(rows, 4, dtype=torch.int32, device=dev)
+        words = 4 + -(-rows // max_pass) + 1
         host = (C.c_int64 * words)()
-        check(fn(_ptr(coords), coords.shape[0], n_img, H, W, th, tw, _ptr(img_bs.contiguous()), *parent, max_pass, _ptr(vimg), _ptr(index),
+        check(fn(_ptr(coords), coords.shape[0], n_img, H, W, th, tw, _ptr(img_bs.contiguous()), *extra, max_pass, _ptr(vimg), _ptr(index),
                  _ptr(ws), ws.numel(), host, words, _stream_ptr()), what)
         V = int(host[0])
         bounds = [int(host[4 + k]) for k in range(-(-V // max_pass) + 1)]
-        return VariantPlan(V, bounds, vimg[:V], index[:V], ws, (n_img, H, W, th, tw, max_pass)), bool(host[1]), bool(host[2])
+        return VariantPlan(V, bounds, vimg[:V], index[:V], ws, (n_img, H, W, th, tw, *geometry, max_pass)), bool(host[1]), bool(host[2])
 
     def occlusion_build(self, plan: VariantPlan, coords: torch.Tensor, values: torch.Tensor, first: int, count: int,
                         out_coords: torch.Tensor, out_values: torch.Tensor):
         """tcvn_occlusion_build_pass: the hit lists of variants first .. first + count - 1 of `plan` (what occlusion_variants() /
         occlusion_refine_variants() returned for these coords)."""
+        self._occlusion_build(lib.tcvn_occlusion_build_pass, "occlusion_build_pass", plan, coords, values, first, count, out_coords,
+                              out_values)
+
+    def occlusion_curve_build(self, plan: VariantPlan, coords: torch.Tensor, values: torch.Tensor, first: int, count: int,
+                              out_coords: torch.Tensor, out_values: torch.Tensor):
+        """tcvn_occlusion_curve_build_pass: the same for a plan of occlusion_curve_variants()."""
+        self._occlusion_build(lib.tcvn_occlusion_curve_build_pass, "occlusion_curve_build_pass", plan, coords, values, first, count,
+                              out_coords, out_values)
+
+    def _occlusion_build(self, fn, what: str, plan: VariantPlan, coords: torch.Tensor, values: torch.Tensor, first: int, count: int,
+                         out_coords: torch.Tensor, out_values: torch.Tensor):
         assert out_coords.dtype == torch.int32 and out_coords.is_contiguous() and out_values.is_contiguous()
         assert out_values.dtype == torch.float32 and out_values.shape == (out_coords.shape[0], values.shape[1])
-        check(lib.tcvn_occlusion_build_pass(_ptr(coords), _ptr(values), coords.shape[0], values.shape[1], *plan.geometry, _ptr(plan.vimg),
-                                            _ptr(plan.ws), plan.ws.numel(), first, count, _ptr(out_coords), _ptr(out_values),
-                                            out_coords.shape[0], _stream_ptr()), "occlusion_build_pass")
+        check(fn(_ptr(coords), _ptr(values), coords.shape[0], values.shape[1], *plan.geometry, _ptr(plan.vimg), _ptr(plan.ws),
+                 plan.ws.numel(), first, count, _ptr(out_coords), _ptr(out_values), out_coords.shape[0], _stream_ptr()), what)
 
     def occlusion_forward(self, coords: torch.Tensor, values: torch.Tensor, nnz: int, n_img: int, out: torch.Tensor, log_pixels: int = 0):
         """The plan's eval forward over one pass of variant maps (the first nnz rows of coords / values; nnz = 0: empty maps), in a

@@ -9,6 +9,10 @@ the softmax probability of one class out as ``[B, 1 + P, Ht, Wt]``.
 ``trainer.occlusion_refine(...)`` / ``network.occlusion_refine(...)`` return a :class:`RefinedOcclusion`: the same scan coarse to
 fine.  Level 0 is the flat scan at ``tile``; every later level halves the tiles and evaluates only the children of the variants whose
 ``|heat|`` reached ``keep`` times the largest of their group.  :func:`refined_heatmap` paints the levels into one map on the finest grid.
+
+``trainer.occlusion_curves(...)`` / ``network.occlusion_curves(...)`` return an :class:`OcclusionCurves`: how faithful a relevance map
+``[B, 1 + P, Ht, Wt]`` is.  Per map, the tiles that hold a hit are ranked by relevance and removed (deletion) or added back (insertion)
+in ``steps`` steps; ``curve()`` is the class probability at every step and ``auc()`` the area under it.
 """
 from __future__ import annotations
 
@@ -25,6 +29,8 @@ from .native import gpu_only as _gpu_only, ptr, ptr_or_null as _vp, stream_ptr a
 MAPS = ("all", "event", "prongs")
 MAX_MAPS_PER_PASS = 256             # TCVN_OCC_MAX_PASS
 MAX_LEVELS = 16                     # TCVN_OCC_MAX_LEVELS
+MAX_STEPS, MAX_TILES = 64, 4096     # TCVN_CURVE_MAX_STEPS, TCVN_CURVE_MAX_TILES
+MODES = ("deletion", "insertion")   # TCVN_CURVE_DELETION, TCVN_CURVE_INSERTION
 
 
 def whole(v) -> bool:
@@ -228,6 +234,110 @@ def refined_heatmap(result: RefinedOcclusion) -> Tensor:
     return paint(result.heats, result.evaluated, result.occupied)
 
 
+# ---- deletion / insertion curves ----------------------------------------------------------------------------------------------------------
+def check_curve_args(relevance, tile, steps, mode, maps, max_maps_per_pass, B: int, P: int, pixel_shape: Tuple[int, int]):
+    """Validates the arguments of occlusion_curves on the host (ValueError) before any device work -> (tile, steps, mode, maps,
+    max_maps_per_pass).  relevance: a float32 tensor [B, 1 + P, Ht, Wt] on the grid of `tile` over pixel_shape (finite; read back once
+    if it lives on the device), or an OcclusionResult / RefinedOcclusion, whose own tile `tile` must then be None or equal to."""
+    who = "occlusion_curves"
+    if isinstance(relevance, (OcclusionResult, RefinedOcclusion)):
+        if isinstance(relevance, RefinedOcclusion) and not relevance.levels:
+            raise ValueError(f"{who}: the RefinedOcclusion ran no level, so it has no heat map")
+        own = relevance.tile if isinstance(relevance, OcclusionResult) else relevance.levels[-1].tile
+        if tile is not None and (not isinstance(tile, (tuple, list)) or tuple(tile) != tuple(own)):
+            raise ValueError(f"{who}: tile {tile!r} is not the tile {tuple(own)} of the result given as relevance")
+        tile = tuple(own)
+        if relevance.prong_logits.shape[:2] != (B, P):
+            raise ValueError(f"{who}: the result given as relevance explains a batch of {tuple(relevance.prong_logits.shape[:2])} "
+                             f"(events, prong slots), the inputs are {(B, P)}")
+    elif not torch.is_tensor(relevance):
+        raise ValueError(f"{who}: relevance must be a float32 tensor [B, 1 + P, Ht, Wt], an OcclusionResult or a RefinedOcclusion")
+    elif tile is None:
+        raise ValueError(f"{who}: a tensor relevance needs the tile its grid belongs to")
+    tile, maps, max_maps_per_pass = check_args(tile, maps, max_maps_per_pass)
+    if not (whole(steps) and 1 <= steps <= MAX_STEPS):
+        raise ValueError(f"{who}: steps must be an integer in 1..{MAX_STEPS}, got {steps!r}")
+    if mode not in MODES:
+        raise ValueError(f"{who}: mode must be one of {MODES}, got {mode!r}")
+    grid = (-(-pixel_shape[0] // tile[0]), -(-pixel_shape[1] // tile[1]))
+    if grid[0] * grid[1] > MAX_TILES:
+        raise ValueError(f"{who}: tiles of {tile} give {grid[0]} x {grid[1]} tiles per map, more than {MAX_TILES}")
+    if torch.is_tensor(relevance):
+        if relevance.dtype != torch.float32 or tuple(relevance.shape) != (B, 1 + P, *grid):
+            raise ValueError(f"{who}: relevance must be float32 {(B, 1 + P, *grid)} (the grid of tile {tile} over {tuple(pixel_shape)}), "
+                             f"got {relevance.dtype} {tuple(relevance.shape)}")
+        if not bool(torch.isfinite(relevance).all()):
+            raise ValueError(f"{who}: relevance must be finite")
+    return tile, int(steps), mode, maps, max_maps_per_pass
+
+
+def relevance_map(relevance) -> Tensor:
+    """The relevance tensor behind the three accepted forms: the tensor itself, heatmap(result, "event") or refined_heatmap(result)."""
+    if isinstance(relevance, OcclusionResult):
+        relevance = heatmap(relevance, "event")
+    elif isinstance(relevance, RefinedOcclusion):
+        relevance = refined_heatmap(relevance)
+    else:
+        return relevance
+    if not bool(torch.isfinite(relevance).all()):
+        raise ValueError("occlusion_curves: the heat map of the result given as relevance is not finite")
+    return relevance
+
+
+class OcclusionCurves:
+    """Deletion / insertion curves of one relevance map.  Plain tensors, no autograd graph.
+
+    event_logits [B, Ce], prong_logits [B, P, Cp]      the unoccluded prediction (what forward() returns for the same input)
+    index int32 [V, 4]                                  (b, s, k, m_k) of every variant, ascending by (b, s, k): map s of event b without
+                                                        (deletion) / with only (insertion) the hits of its m_k top-ranked tiles
+    step_event_logits [V, Ce], step_prong_logits [V, P, Cp]             the prediction of event b under variant v
+    rank int32 [B, 1 + P, Ht, Wt]                       the rank of every tile that holds a hit in its map (relevance descending, ties
+                                                        by ty * Wt + tx ascending); -1 at tiles without hits and at maps not scanned
+    steps, mode, tile = (th, tw), grid = (Ht, Wt)"""
+
+    def __init__(self, event_logits: Tensor, prong_logits: Tensor, index: Tensor, step_event_logits: Tensor, step_prong_logits: Tensor,
+                 rank: Tensor, steps: int, mode: str, tile: Tuple[int, int], grid: Tuple[int, int]):
+        self.event_logits, self.prong_logits, self.index = event_logits, prong_logits, index
+        self.step_event_logits, self.step_prong_logits, self.rank = step_event_logits, step_prong_logits, rank
+        self.steps, self.mode, self.tile, self.grid = int(steps), mode, tuple(tile), tuple(grid)
+
+    @property
+    def num_variants(self) -> int:
+        return int(self.index.shape[0])
+
+    def curve(self, target: Union[str, int, Tensor] = "event") -> Tensor:
+        """float32 [B, 1 + P, steps + 1]: the softmax probability of the target class (as in heatmap) at every step; NaN in the rows
+        of maps without variants, and in row s = 0 with target "prong"."""
+        return curve_and_auc(self, target)[0]
+
+    def auc(self, target: Union[str, int, Tensor] = "event") -> Tensor:
+        """float32 [B, 1 + P]: the trapezoid of curve(target) over x = k / steps; NaN where the curve is (torch.nanmean summarises)."""
+        return curve_and_auc(self, target)[1]
+
+
+def curve_and_auc(result: OcclusionCurves, target: Union[str, int, Tensor] = "event") -> Tuple[Tensor, Tensor]:
+    """tcvn_occlusion_curve -> (curve [B, 1 + P, steps + 1], auc [B, 1 + P]), see OcclusionCurves.curve / .auc."""
+    ev, pr = result.event_logits, result.prong_logits
+    B, Ce = ev.shape
+    P, Cp = pr.shape[1], pr.shape[2]
+    mode, classes = parse_target(target, B, Ce)
+    _gpu_only(ev, "the deletion / insertion curve")
+    tensors = [ev, pr, result.step_event_logits, result.step_prong_logits]
+    assert all(t.dtype == torch.float32 and t.is_contiguous() and t.device == ev.device for t in tensors)
+    index = result.index
+    assert index.dtype == torch.int32 and index.is_contiguous() and index.device == ev.device and index.shape[1] == 4
+    V, K = index.shape[0], result.steps
+    assert result.step_event_logits.shape == (V, Ce) and result.step_prong_logits.shape == (V, P, Cp)
+    if classes is not None:
+        classes = classes.to(ev.device, torch.int32).contiguous()
+    curve = torch.empty(B, 1 + P, K + 1, device=ev.device)
+    auc = torch.empty(B, 1 + P, device=ev.device)
+    with torch.cuda.device(ev.device):
+        _lib.check(_lib.lib.tcvn_occlusion_curve(_vp(ev), _vp(pr), _vp(tensors[2]), _vp(tensors[3]), _vp(index), V, B, P, Ce, Cp, K, mode,
+                                                 _vp(classes), ptr(curve), ptr(auc), _stream()), "occlusion_curve")
+    return curve, auc
+
+
 # ---- the scan driver ------------------------------------------------------------------------------------------------------------------------
 @dataclass(frozen=True)
 class HitList:
@@ -244,21 +354,25 @@ class HitList:
 
 @dataclass(frozen=True)
 class VariantPlan:
-    """The variants of one hit list at one tile size, as the engine's occlusion_variants / occlusion_refine_variants return them."""
+    """The variants of one hit list at one tile size, as the engine's occlusion_variants / occlusion_refine_variants /
+    occlusion_curve_variants return them."""
     V: int                          # number of variants
     bounds: List[int]               # bounds[k] .. bounds[k + 1]: the rows of pass k in the variants' hit lists
     vimg: Tensor                    # int32 [V]: the map of every variant
-    index: Tensor                   # int32 [V, 4]: (b, s, ty, tx) of every variant, ascending
+    index: Tensor                   # int32 [V, 4]: (b, s, ty, tx) -- curves: (b, s, k, m_k) -- of every variant, ascending
     ws: Tensor                      # the list workspace, which the engine's occlusion_build reads
-    geometry: Tuple[int, ...]       # (n_img, H, W, th, tw, max_pass) the list was made for: occlusion_build repeats them
+    geometry: Tuple[int, ...]       # (n_img, H, W, th, tw, [steps, mode,] max_pass) the list was made for: the build call repeats them
 
 
-def plan_variants(lst: HitList, shape: Tuple[int, int], tile: Tuple[int, int], max_pass: int,
-                  keep_map: Optional[Tensor] = None) -> Tuple[HitList, VariantPlan]:
+def plan_variants(lst: HitList, shape: Tuple[int, int], tile: Tuple[int, int], max_pass: int, keep_map: Optional[Tensor] = None,
+                  curve: Optional[tuple] = None) -> Tuple[HitList, VariantPlan]:
     """The variant list of one hit list (one host read-back): every tile that holds a hit, or (keep_map) the children of the selected
-    tiles of the level above.  -> (the list the plan is for, the plan): `lst` itself, or a cleaned copy if the engine found it unsorted
+    tiles of the level above, or (curve = (relevance, steps, mode, rank), see the engine's occlusion_curve_variants) the steps of a
+    deletion / insertion curve.  -> (the list the plan is for, the plan): `lst` itself, or a cleaned copy if the engine found it unsorted
     or with hits outside the maps -- the caller keeps that one for the later levels."""
     def variants(hits):
+        if curve is not None:
+            return hits.engine.occlusion_curve_variants(hits.coords, hits.n_img, shape, tile, hits.img_bs, max_pass, *curve)
         if keep_map is None:
             return hits.engine.occlusion_variants(hits.coords, hits.n_img, shape, tile, hits.img_bs, max_pass)
         return hits.engine.occlusion_refine_variants(hits.coords, hits.n_img, shape, tile, hits.img_bs, max_pass, keep_map)
@@ -302,30 +416,36 @@ class Scan:
         """One scan at `tile`: every tile that holds a hit, or (keep_map: the selection among the variants of the level with tiles
         twice the size) only the children of the selected tiles.  The variant lists come first; None, before any variant is run, if
         they hold more than `budget` variants together."""
-        dev, P = self.last.rows.device, self.last.P
         grid = (-(-self.shape[0] // tile[0]), -(-self.shape[1] // tile[1]))
         planned = [plan_variants(lst, self.shape, tile, max_pass, keep_map) for lst in self.lists]
         self.lists = [lst for lst, _ in planned]
         if budget is not None and sum(plan.V for _, plan in planned) > budget:
             return None
-        parts = [self._passes(lst, plan, max_pass) for lst, plan in planned]
+        index, occ_ev, occ_pr = self._merged([self._passes(lst, plan, max_pass) for lst, plan in planned], grid)
+        return OcclusionResult(self.ev, self.pr, index, occ_ev, occ_pr, grid, tile)
+
+    def _merged(self, parts: List[Tuple[Tensor, Tensor, Tensor]], radix: Tuple[int, int]) -> Tuple[Tensor, Tensor, Tensor]:
+        """What _passes returned for every list -> one (index, event logits, prong logits), ascending by the index rows (b, s, i, j)
+        with i < radix[0] and j < radix[1]."""
+        dev, P = self.last.rows.device, self.last.P
         if parts:
             index, occ_ev, occ_pr = (torch.cat([p[i] for p in parts]) for i in range(3))
         else:
             index = torch.empty(0, 4, dtype=torch.int32, device=dev)
             occ_ev, occ_pr = self.ev.new_empty(0, self.ev.shape[1]), self.pr.new_empty(0, P, self.pr.shape[2])
-        if len(parts) > 1:                    # the two lists are ordered by (b, s, ty, tx) each: merge them into that order
+        if len(parts) > 1:                    # the lists are ordered by their index rows each: merge them into that order
             i64 = index.long()
-            key = ((i64[:, 0] * (1 + P) + i64[:, 1]) * grid[0] + i64[:, 2]) * grid[1] + i64[:, 3]
+            key = ((i64[:, 0] * (1 + P) + i64[:, 1]) * radix[0] + i64[:, 2]) * radix[1] + i64[:, 3]
             order = torch.argsort(key)
             index, occ_ev, occ_pr = index[order].contiguous(), occ_ev[order].contiguous(), occ_pr[order].contiguous()
-        return OcclusionResult(self.ev, self.pr, index, occ_ev, occ_pr, grid, tile)
+        return index, occ_ev, occ_pr
 
-    def _passes(self, lst: HitList, plan: VariantPlan, max_pass: int) -> Tuple[Tensor, Tensor, Tensor]:
+    def _passes(self, lst: HitList, plan: VariantPlan, max_pass: int, build=None) -> Tuple[Tensor, Tensor, Tensor]:
         """The variants of one list, pass by pass, through its embedder and the token path -> (index [V, 4], occluded_event_logits
         [V, Ce], occluded_prong_logits [V, P, Cp]) in the embedder's image order.  The embedder writes [col0, col0 + engine.out_dim)
-        of its maps' rows."""
+        of its maps' rows.  build: the engine call that writes a pass's hit lists from `plan` (default: occlusion_build)."""
         engine, head, last = lst.engine, self.head, self.last
+        build = build or engine.occlusion_build
         dev = last.rows.device
         V, bounds, vimg, index = plan.V, plan.bounds, plan.vimg, plan.index
         occ_ev = torch.empty(V, head.cfg.event_classes, device=dev)
@@ -341,11 +461,26 @@ class Scan:
             n = min(max_pass, V - first)
             nnz = bounds[k + 1] - bounds[k]
             if nnz > 0:
-                engine.occlusion_build(plan, lst.coords, lst.values, first, n, out_coords, out_values)
+                build(plan, lst.coords, lst.values, first, n, out_coords, out_values)
             engine.occlusion_forward(out_coords, out_values, nnz, n, emb[:n], lst.value_mode)
             head.occlusion_pass(last.rows, self.tokens, last.tok_row, last.n_prongs, vimg[first:first + n], index[first:first + n],
                                 lst.row_base, emb[:n], lst.col0, occ_ev[first:first + n], occ_pr[first:first + n])
         return index, occ_ev, occ_pr
+
+    def curves(self, relevance: Tensor, tile: Tuple[int, int], steps: int, mode: str, max_pass: int) -> "OcclusionCurves":
+        """Deletion / insertion curves of relevance float32 [B, 1 + P, Ht, Wt] on the grid of `tile`: the tiles of every scanned map
+        that holds a hit are ranked on the device, and the steps + 1 variants of each map go through the same passes as a level's."""
+        dev, B, P = self.last.rows.device, self.last.B, self.last.P
+        grid = (-(-self.shape[0] // tile[0]), -(-self.shape[1] // tile[1]))
+        assert relevance.shape == (B, 1 + P, *grid) and relevance.dtype == torch.float32
+        relevance = relevance.to(dev).contiguous()
+        rank = torch.full((B, 1 + P, *grid), -1, dtype=torch.int32, device=dev)
+        curve = (relevance, steps, MODES.index(mode), rank)
+        planned = [plan_variants(lst, self.shape, tile, max_pass, curve=curve) for lst in self.lists]
+        self.lists = [lst for lst, _ in planned]
+        parts = [self._passes(lst, plan, max_pass, lst.engine.occlusion_curve_build) for lst, plan in planned]
+        index, step_ev, step_pr = self._merged(parts, (steps + 1, MAX_TILES + 1))
+        return OcclusionCurves(self.ev, self.pr, index, step_ev, step_pr, rank, steps, mode, tile, grid)
 
     def refine(self, tile: Tuple[int, int], levels: int, keep: float, target, max_pass: int,
                max_variants: Optional[int]) -> RefinedOcclusion:

@@ -387,6 +387,21 @@ class HipRuntime:
             scan = self._scan(maps, features, extra, event_px, event_mask, prong_px, prong_mask, counts)
             return scan.refine(tile, levels, keep, target, max_pass, max_variants)
 
+    def forward_occlusion_curves(self, features: Tensor, extra: Tensor, event_px: SparsePixels, event_mask: Tensor,
+                                 prong_px: SparsePixels, prong_mask: Tensor, counts: Optional[Tuple[int, int]] = None, relevance=None,
+                                 tile: Optional[Tuple[int, int]] = None, steps: int = 10, mode: str = "deletion", maps: str = "all",
+                                 max_maps_per_pass: int = 256):
+        """Eval-mode forward() plus the deletion / insertion curves of `relevance` over its pixel maps (occlusion.Scan.curves: per
+        map, the tiles that hold a hit ranked by relevance and removed / added back in `steps` steps) -> occlusion.OcclusionCurves."""
+        tile, steps, mode, maps, max_pass = occlusion.check_curve_args(relevance, tile, steps, mode, maps, max_maps_per_pass,
+                                                                       *prong_mask.shape, self.pixel_shape)
+        if self.network.training:
+            raise RuntimeError("occlusion_curves explains an eval-mode prediction: call network.eval() first")
+        with torch.no_grad():
+            relevance = occlusion.relevance_map(relevance)
+            scan = self._scan(maps, features, extra, event_px, event_mask, prong_px, prong_mask, counts)
+            return scan.curves(relevance, tile, steps, mode, max_pass)
+
     def _backward(self, st: dict, d_ev: Tensor, d_pr: Tensor):
         """Backward of the fused step in the order the gradient segments become final -- token path, event embedder (side
         stream), prong embedder -- reporting each to ``grad_ready_hook`` so that its all-reduce overlaps with what is left."""

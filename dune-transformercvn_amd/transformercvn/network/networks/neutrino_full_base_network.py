@@ -199,3 +199,21 @@ class NeutrinoBaseNetwork(nn.Module):
         event_pixels, prong_pixels = _as_sparse(event_pixels), _as_sparse(prong_pixels)
         return self.hip_runtime().forward_occlusion_refine(features, extra, event_pixels, event_mask, prong_pixels, prong_mask, counts,
                                                            tile, levels, keep, target, maps, max_maps_per_pass, max_variants)
+
+    @torch.jit.unused
+    def occlusion_curves(self, features: Tensor, extra: Tensor, event_pixels: Tensor, event_mask: Tensor, prong_pixels: Tensor,
+                         prong_mask: Tensor, counts: Optional[Tuple[int, int]] = None, relevance=None,
+                         tile: Optional[Tuple[int, int]] = None, steps: int = 10, mode: str = "deletion", maps: str = "all",
+                         max_maps_per_pass: int = 256):
+        """Eval mode only -> transformercvn.hip.occlusion.OcclusionCurves: how faithful a relevance map is.  relevance: float32
+        [B, 1+P, Ht, Wt] on the grid of `tile`, or an OcclusionResult / RefinedOcclusion (its event heat map and its own tile).  In
+        every scanned map the tiles that hold a hit are ranked by relevance (descending, ties by tile index); step k = 0..steps removes
+        ("deletion") or keeps only ("insertion") the hits of the first ceil(k n / steps) of them.  result.curve() is the class
+        probability at every step, result.auc() the area under it: small for a faithful deletion curve, large for insertion."""
+        from transformercvn.hip import occlusion
+        occlusion.check_curve_args(relevance, tile, steps, mode, maps, max_maps_per_pass, *prong_mask.shape, self.pixel_shape)
+        if self.training:
+            raise RuntimeError("occlusion_curves explains an eval-mode prediction: call .eval() first")
+        event_pixels, prong_pixels = _as_sparse(event_pixels), _as_sparse(prong_pixels)
+        return self.hip_runtime().forward_occlusion_curves(features, extra, event_pixels, event_mask, prong_pixels, prong_mask, counts,
+                                                           relevance, tile, steps, mode, maps, max_maps_per_pass)

@@ -199,6 +199,21 @@ class NeutrinoFullBaseTrainer(NeutrinoBase, ABC):
                                                                    prong_coords, prong_values, prong_mask), None, tile, levels, keep,
                                              target, maps, max_maps_per_pass, max_variants)
 
+    def occlusion_curves(self, features: Tensor, extra: Tensor, event_coords: Tensor, event_values: Tensor, event_mask: Tensor,
+                         prong_coords: Tensor, prong_values: Tensor, prong_mask: Tensor, relevance, tile=None, steps: int = 10,
+                         mode: str = "deletion", maps: str = "all", max_maps_per_pass: int = 256):
+        """Eval mode only -> OcclusionCurves (transformercvn.hip.occlusion): the deletion / insertion curves of a relevance map, a
+        measure of how faithful it is; see NeutrinoBaseNetwork.occlusion_curves.  Bad arguments raise ValueError and train mode
+        RuntimeError before any device work."""
+        from transformercvn.hip import occlusion
+        occlusion.check_curve_args(relevance, tile, steps, mode, maps, max_maps_per_pass, *prong_mask.shape,
+                                   self.training_dataset.pixel_shape)
+        if self.training:
+            raise RuntimeError("occlusion_curves explains an eval-mode prediction: call .eval() first")
+        return self.network.occlusion_curves(*self._network_inputs(features, extra, event_coords, event_values, event_mask,
+                                                                   prong_coords, prong_values, prong_mask), None, relevance, tile,
+                                             steps, mode, maps, max_maps_per_pass)
+
     def shared_step(self, batch):
         (features, extra, ev_c, ev_v, ev_m, pr_c, pr_v, pr_m, ev_t, pr_t) = batch[:10]
         counts = batch[10] if len(batch) > 10 else None               # optional host-side (max_prongs, n_prongs): avoids syncs

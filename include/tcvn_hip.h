@@ -301,6 +301,44 @@ int tcvn_occlusion_occupancy(const int32_t* coords, int64_t nnz, int n_img, int 
 int tcvn_occlusion_paint(int levels, const float* const* heat, const uint8_t* const* evaluated, const int32_t* grid_h,
                          const int32_t* grid_w, const uint8_t* occupied, int batch, int max_prongs, float* out, void* stream);
 
+/* Deletion / insertion curves (forward only, eval arithmetic): how faithful a relevance map [batch, 1 + max_prongs, grid_h, grid_w] is.
+ * Per map: the n tiles that hold a hit are ranked by relevance, descending, ties by the tile index ty * grid_w + tx, ascending (-0.0
+ * counts as +0.0; the values are expected to be finite).  Step k = 0..steps uses m_k = (k * n + steps - 1) / steps tiles (integers):
+ * the deletion variant k is the map without the hits of its m_k first tiles, the insertion variant k the map with only those hits;
+ * all other hits keep their order.  A map with at least one hit gives exactly steps + 1 variants, a map without hits none.
+ *   curve_variants  the hit list of tcvn_occlusion_variants and relevance -> the V variants ordered by (image, k): vimg [V] the image,
+ *               index [V, 4] = (img_bs[image][0], img_bs[image][1], k, m_k); both need room for n_img * (steps + 1) rows.  rank
+ *               [batch, 1 + max_prongs, grid_h, grid_w]: the rank of every occupied tile of this list's maps is written at (b, s) =
+ *               img_bs[image]; the caller fills it with -1 first and may call once per hit list.  One workgroup per map sorts 64-bit
+ *               keys (descending-orderable float pattern, tile index) in LDS: grid_h * grid_w <= TCVN_CURVE_MAX_TILES.  host_out
+ *               (4 + ceil(n_img * (steps + 1) / max_pass) + 1 words), the two flags, the pass boundaries and the one synchronisation
+ *               are those of tcvn_occlusion_variants.
+ *   curve_build_pass  tcvn_occlusion_build_pass for these variants: a hit survives iff (rank of its tile < m_k) != (mode is deletion).
+ *               The result goes through the embedder and tcvn_head_occlusion unchanged (the latter reads index[j][0:2] only).
+ *   curve       curve [batch, 1 + max_prongs, steps + 1]: the softmax probability (double precision, as the heat map) of the target
+ *               class at every step, from step_event_logits [V, Ce] / step_prong_logits [V, max_prongs, Cp]; auc [batch, 1 +
+ *               max_prongs] = (p_0 / 2 + p_1 + ... + p_{steps-1} + p_steps / 2) / steps, summed in that order.  target and classes as
+ *               in tcvn_occlusion_heatmap.  Rows without variants are NaN in both (and row s = 0 with TCVN_OCC_TARGET_PRONG).
+ * Argument errors (NULL, tile < 1, steps outside 1..TCVN_CURVE_MAX_STEPS, more than TCVN_CURVE_MAX_TILES tiles per map, unknown mode,
+ * max_pass outside 1..TCVN_OCC_MAX_PASS, workspace too small) return non-zero before any device call and print one "tcvn:" line. */
+#define TCVN_CURVE_MAX_STEPS 64
+#define TCVN_CURVE_MAX_TILES 4096
+#define TCVN_CURVE_DELETION 0
+#define TCVN_CURVE_INSERTION 1
+int64_t tcvn_occlusion_curve_workspace_bytes(int n_img, int height, int width, int tile_h, int tile_w, int steps, int max_pass);
+int tcvn_occlusion_curve_variants(const int32_t* coords, int64_t nnz, int n_img, int height, int width, int tile_h, int tile_w,
+                                  const int32_t* img_bs, const float* relevance, int batch, int max_prongs, int steps, int mode,
+                                  int32_t* rank, int max_pass, int32_t* vimg, int32_t* index, void* workspace,
+                                  int64_t workspace_bytes, int64_t* host_out, int64_t host_cap, void* stream);
+int tcvn_occlusion_curve_build_pass(const int32_t* coords, const float* values, int64_t nnz, int channels, int n_img, int height,
+                                    int width, int tile_h, int tile_w, int steps, int mode, int max_pass, const int32_t* vimg,
+                                    const void* workspace, int64_t workspace_bytes, int first, int count, int32_t* out_coords,
+                                    float* out_values, int64_t out_rows, void* stream);
+int tcvn_occlusion_curve(const float* event_logits, const float* prong_logits, const float* step_event_logits,
+                         const float* step_prong_logits, const int32_t* index, int64_t n_variants, int batch, int max_prongs,
+                         int event_classes, int prong_classes, int steps, int target, const int32_t* classes, float* curve, float* auc,
+                         void* stream);
+
 /* Row operators behind the holder modules' own forward() (forward only, fp32):
  *   y = x W^T + b (torch.nn.Linear layout; bias may be NULL)                      -- layers/prong_decoder.py:15-16
  *   y = dropout(prelu(batchnorm1d(x)))  with batch statistics + running-stat update when train != 0, running statistics

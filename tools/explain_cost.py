@@ -3,6 +3,7 @@ Times forward(), forward_with_attention() and leave_one_prong_out() on the same 
 interleaved, and prints one JSON line with the medians.  occlusion_maps() is timed the same way at tiles of 32x32, 16x16 and 8x8 with
 its number of variants V and of embedder passes (a scan is thousands of maps: it gets --occ-reps repetitions of its own), and beside
 them occlusion_refine(tile=(64, 64), levels=4) -- the same 8x8 grid, coarse to fine -- for every --keep, with V per level.
+occlusion_curves(steps=10) on the 16x16 heat map is timed with its V = 11 x maps (the 16x16 scan that gives the heat map is not in it).
 
     python tools/explain_cost.py [--batch 32 --reps 15 --occ-reps 3 --precision bf16 --keep 0.25]
 """
@@ -87,6 +88,14 @@ def main():
             "variants": res.num_variants, "event_map_variants": n_ev, "prong_map_variants": n_pr,
             "passes": -(-n_ev // 256) + -(-n_pr // 256), "reps": args.occ_reps,
             "ms": ms(ts), "us_per_variant": round(1e3 * statistics.median(ts) / max(1, res.num_variants), 2)}
+    if args.occ_reps > 0:
+        from transformercvn.hip import occlusion  # noqa: E402
+        with torch.no_grad():
+            heat = occlusion.heatmap(model.occlusion_maps(*inputs[:8], tile=(16, 16)), "event")
+        res, ts = timed(lambda: model.occlusion_curves(*inputs[:8], heat, tile=(16, 16), steps=10))
+        out["occlusion_curves_16x16_steps10"] = {
+            "variants": res.num_variants, "maps": res.num_variants // 11, "reps": args.occ_reps, "ms": ms(ts),
+            "us_per_variant": round(1e3 * statistics.median(ts) / max(1, res.num_variants), 2)}
     for keep in args.keep if args.occ_reps > 0 else ():
         res, ts = timed(lambda: model.occlusion_refine(*inputs[:8], tile=(64, 64), levels=4, keep=keep))
         out[f"occlusion_refine_64x64_levels4_keep{keep:g}"] = {
