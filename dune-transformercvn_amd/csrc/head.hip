@@ -14,6 +14,7 @@
 #include "tcvn_encoder.h"
 #include "tcvn_explain.h"
 #include "tcvn_occlude.h"
+#include "tcvn_shapley.h"
 
 using namespace tcvn;
 
@@ -473,6 +474,46 @@ void loo_layout(const HeadPlan& plan, int B, int P, LooLayout& o) {
     o.head = b.take(L.total);
     o.total = b.off;
 }
+// Prong Shapley scan.  The per-event table (ShapTable, tcvn_shapley.h) as the host builds it from tok_row: event b has n[b] valid prong
+// slots (vmask), runs exactly when n <= max_exact, and owns the coalitions offsets[b] .. offsets[b+1]-1: 2^n of them, or empty + full +
+// the M (n-1) proper prefixes of its permutations.
+struct ShapHost { std::vector<int64_t> offsets, vmask; std::vector<int32_t> n, exact; };
+bool shap_shape_ok(int batch, int max_prongs, int max_exact, int samples) {
+    return batch > 0 && batch <= 65535 && max_prongs >= 0 && max_prongs <= 63 && max_exact >= 0 && max_exact <= TCVN_SHAP_MAX_EXACT &&
+           samples >= 1;
+}
+long shap_jobs(int n, int max_exact, int M) { return n <= max_exact ? 1L << n : 2 + (long)M * (n - 1); }
+int shap_read_table(const int32_t* tok_row, int B, int S, int max_exact, int M, hipStream_t st, ShapHost& h) {
+    std::vector<int32_t> tr((size_t)B * S);
+    TCVN_CHECK(hipMemcpyAsync(tr.data(), tok_row, tr.size() * 4, hipMemcpyDeviceToHost, st));
+    TCVN_CHECK(hipStreamSynchronize(st));
+    h.offsets.assign(B + 1, 0); h.vmask.assign(B, 0); h.n.assign(B, 0); h.exact.assign(B, 0);
+    for (int b = 0; b < B; ++b) {
+        for (int s = 1; s < S; ++s)
+            if (tr[(size_t)b * S + s] >= 0) { h.vmask[b] |= (int64_t)1 << (s - 1); ++h.n[b]; }
+        h.exact[b] = h.n[b] <= max_exact;
+        h.offsets[b + 1] = h.offsets[b] + shap_jobs(h.n[b], max_exact, M);
+    }
+    return 0;
+}
+// Workspace: the table's n / vmask, the inverse permutations, the fp64 values of as many coalitions as any mask of this shape can have
+// (the size is asked for before the mask is known), and one pass (at most
+// TCVN_SHAP_MAX_PASS sequences) of variant rows + head workspace.
+struct ShapLayout { long n, vmask, pos, values, vrow, head, total; long cap; };
+void shap_layout(const HeadPlan& plan, int B, int P, int max_exact, int M, ShapLayout& o) {
+    Bump b;
+    long per_event = 1L << (P < max_exact ? P : max_exact);
+    if (P > max_exact && shap_jobs(P, max_exact, M) > per_event) per_event = shap_jobs(P, max_exact, M);
+    const long jmax = per_event * B;
+    o.cap = jmax < TCVN_SHAP_MAX_PASS ? jmax : TCVN_SHAP_MAX_PASS;
+    o.n = b.take((long)B * 4); o.vmask = b.take((long)B * 8); o.pos = b.take((long)B * M * (P > 0 ? P : 1) * 4);
+    o.values = b.take(jmax * plan.cfg.event_classes * 8);
+    o.vrow = b.take(o.cap * (1 + P) * 4);
+    HLayout L;
+    plan.layout((int)o.cap, P, 0, L);
+    o.head = b.take(L.total);
+    o.total = b.off;
+}
 // Workspace of one pass of the occlusion scan (at most TCVN_OCC_MAX_PASS variants): variant rows, their combined embedding as one-token
 // sequences (E: the Zc / C / cstat / X[0] part of a head layout) and the head workspace of the variant sequences.
 struct OccHeadLayout { long vrows, ident, vrow, head, total; HLayout E; };
@@ -624,6 +665,80 @@ int tcvn_head_leave_one_out(tcvn_head* p, int batch, int max_prongs, const float
         if (int rc = p->plan.decode(s, lg + (long)off * Ce, nullptr)) return rc;
     }
     return loo_scatter(lg, d_src, event_logits, loo, B, S, Ce, st);
+}
+
+int64_t tcvn_head_shapley_workspace_bytes(const tcvn_head* p, int batch, int max_prongs, int max_exact, int samples) {
+    if (!p || !shap_shape_ok(batch, max_prongs, max_exact, samples)) return -1;
+    ShapLayout o;
+    shap_layout(p->plan, batch, max_prongs, max_exact, samples, o);
+    return o.total;
+}
+int64_t tcvn_head_shapley_count(int batch, int max_prongs, const int32_t* tok_row, int max_exact, int samples, void* stream) {
+    if (!tok_row || !shap_shape_ok(batch, max_prongs, max_exact, samples)) {
+        fprintf(stderr, "tcvn: head_shapley_count: bad argument (NULL pointer, batch outside 1..65535, max_prongs outside 0..63, max_exact outside 0..%d or samples < 1)\n",
+                TCVN_SHAP_MAX_EXACT);
+        return -1;
+    }
+    ShapHost h;
+    if (shap_read_table(tok_row, batch, 1 + max_prongs, max_exact, samples, reinterpret_cast<hipStream_t>(stream), h)) return -2;
+    return h.offsets[batch];
+}
+int tcvn_head_shapley(tcvn_head* p, int batch, int max_prongs, const float* tokens, const int32_t* tok_row, int max_exact, int samples,
+                      uint64_t seed, int value_kind, float* event_logits, float* phi, float* std_error, float* interaction,
+                      int32_t* exact, int64_t* offsets, int64_t* masks, int32_t* event, float* coalition_logits, int64_t n_coalitions,
+                      int32_t* permutations, void* ws, int64_t ws_bytes, void* stream) {
+    const bool prongs = max_prongs > 0;
+    if (!p || !tokens || !tok_row || !event_logits || !exact || !offsets || !masks || !event || !coalition_logits || !ws ||
+        (prongs && (!phi || !std_error || !interaction || !permutations)) || !shap_shape_ok(batch, max_prongs, max_exact, samples) ||
+        (value_kind != TCVN_SHAP_VALUE_PROB && value_kind != TCVN_SHAP_VALUE_LOGIT) || n_coalitions < batch) {
+        fprintf(stderr, "tcvn: head_shapley: bad argument (NULL pointer, batch outside 1..65535, max_prongs outside 0..63, max_exact outside 0..%d, samples < 1, unknown value kind or fewer coalitions than events)\n",
+                TCVN_SHAP_MAX_EXACT);
+        return -1;
+    }
+    ShapLayout o;
+    shap_layout(p->plan, batch, max_prongs, max_exact, samples, o);
+    if (ws_bytes < o.total) {
+        fprintf(stderr, "tcvn: head_shapley: workspace of %lld bytes, %ld needed\n", (long long)ws_bytes, o.total);
+        return -12;
+    }
+    if (!p->plan.bound) { fprintf(stderr, "tcvn: head_shapley: parameters are not bound\n"); return -11; }
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int B = batch, P = max_prongs, S = 1 + P, M = samples, D = p->plan.cfg.hidden_dim, Ce = p->plan.cfg.event_classes;
+    char* w = reinterpret_cast<char*>(ws);
+    // the coalition count of an event depends on its mask: read tok_row back (a few KB) and build the per-event table on the host
+    ShapHost h;
+    if (int rc = shap_read_table(tok_row, B, S, max_exact, M, st, h)) return rc;
+    const long J = h.offsets[B];
+    if (J != n_coalitions) {
+        fprintf(stderr, "tcvn: head_shapley: outputs sized for %lld coalitions, this mask has %ld (tcvn_head_shapley_count)\n",
+                (long long)n_coalitions, J);
+        return -13;
+    }
+    int32_t* d_n = reinterpret_cast<int32_t*>(w + o.n);
+    int64_t* d_vmask = reinterpret_cast<int64_t*>(w + o.vmask);
+    double* values = reinterpret_cast<double*>(w + o.values);
+    int* d_vrow = reinterpret_cast<int*>(w + o.vrow);
+    TCVN_CHECK(hipMemcpyAsync(offsets, h.offsets.data(), (size_t)(B + 1) * 8, hipMemcpyHostToDevice, st));      // outputs that double as
+    TCVN_CHECK(hipMemcpyAsync(exact, h.exact.data(), (size_t)B * 4, hipMemcpyHostToDevice, st));                // the device's table
+    TCVN_CHECK(hipMemcpyAsync(d_n, h.n.data(), (size_t)B * 4, hipMemcpyHostToDevice, st));
+    TCVN_CHECK(hipMemcpyAsync(d_vmask, h.vmask.data(), (size_t)B * 8, hipMemcpyHostToDevice, st));
+    TCVN_CHECK(hipStreamSynchronize(st));                                                   // the host vectors are pageable
+    const ShapTable t{offsets, d_n, d_vmask, exact};
+    int32_t* d_pos = reinterpret_cast<int32_t*>(w + o.pos);
+    if (int rc = shap_perm(tok_row, permutations, d_pos, B, M, P, seed, st)) return rc;
+    for (long off = 0; off < J; off += o.cap) {
+        const int n = (int)(J - off < o.cap ? J - off : o.cap);
+        HeadStep s;                                                                         // eval arithmetic in the pass's own head workspace
+        if (int rc = p->plan.step(n, P, 0, w + o.head, ws_bytes - o.head, 0, 0, st, s)) return rc;
+        if (int rc = shap_gather(tokens, tok_row, t, permutations, off, n, B, M, S, D, s.F(s.L.X[0]), d_vrow, masks, event, st)) return rc;
+        if (int rc = p->plan.encode(s, d_vrow)) return rc;
+        if (int rc = p->plan.decode(s, coalition_logits + off * Ce, nullptr)) return rc;
+    }
+    if (int rc = shap_full_rows(coalition_logits, t, event_logits, B, Ce, st)) return rc;
+    if (int rc = shap_values(coalition_logits, values, J, Ce, value_kind == TCVN_SHAP_VALUE_PROB, st)) return rc;
+    if (int rc = shap_exact(values, t, phi, std_error, B, P, Ce, st)) return rc;
+    if (int rc = shap_pairs(values, t, interaction, B, P, Ce, st)) return rc;
+    return shap_sampled(values, t, d_pos, phi, std_error, B, M, P, Ce, st);
 }
 
 int64_t tcvn_head_occlusion_workspace_bytes(const tcvn_head* p, int max_prongs) {

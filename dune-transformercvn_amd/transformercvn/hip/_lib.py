@@ -23,6 +23,9 @@ MODE_F32, MODE_BF16 = 0, 1
 SLOT_PARAM, SLOT_BUFFER, SLOT_COUNTER = 0, 1, 2
 FUSE_MEAN, FUSE_MAX = 0, 1          # TCVN_FUSE_*: head fusion of the attention rollout
 LOO_MAX_PASS = 256                  # TCVN_LOO_MAX_PASS: sequences per encoder pass of the leave-one-prong-out scan
+SHAP_MAX_PASS = 1024                # TCVN_SHAP_MAX_PASS: sequences per encoder pass of the prong Shapley scan
+SHAP_MAX_EXACT = 16                 # TCVN_SHAP_MAX_EXACT: the widest event whose 2^n coalitions are all run
+SHAP_VALUE_PROB, SHAP_VALUE_LOGIT = 0, 1       # TCVN_SHAP_VALUE_*: what a coalition is worth, class probability or raw logit
 OCC_MAX_PASS = 256                  # TCVN_OCC_MAX_PASS: maps per embedder / token-path pass of the occlusion scan
 OCC_TARGET_EVENT, OCC_TARGET_PRONG = 0, 1      # TCVN_OCC_TARGET_*: which logits the occlusion heat map is taken from
 OCC_GROUP_EVENT, OCC_GROUP_MAP = 0, 1          # TCVN_OCC_GROUP_*: whose largest score a refinement level's variants are held against
@@ -103,6 +106,9 @@ def _load():
     sig("tcvn_attention_rollout", i32, vp, vp, i32, i32, i32, i32, i32, vp, vp)
     sig("tcvn_head_leave_one_out_workspace_bytes", i64, vp, i32, i32)
     sig("tcvn_head_leave_one_out", i32, vp, i32, i32, vp, vp, vp, vp, vp, i64, vp)
+    sig("tcvn_head_shapley_workspace_bytes", i64, vp, i32, i32, i32, i32)
+    sig("tcvn_head_shapley_count", i64, i32, i32, vp, i32, i32, vp)
+    sig("tcvn_head_shapley", i32, vp, i32, i32, vp, vp, i32, i32, u64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, i64, vp)
     sig("tcvn_occlusion_workspace_bytes", i64, i32, i32, i32, i32, i32, i32)
     sig("tcvn_occlusion_variants", i32, vp, i64, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp, i64, P(i64), i64, vp)
     sig("tcvn_occlusion_build_pass", i32, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, vp, vp, i64, i32, i32, vp, vp, i64, vp)
@@ -163,6 +169,7 @@ EXPORTS = [
     "tcvn_head_occlusion", "tcvn_occlusion_heatmap",
     "tcvn_occlusion_select", "tcvn_occlusion_refine_variants", "tcvn_occlusion_mark", "tcvn_occlusion_occupancy", "tcvn_occlusion_paint",
     "tcvn_occlusion_curve_workspace_bytes", "tcvn_occlusion_curve_variants", "tcvn_occlusion_curve_build_pass", "tcvn_occlusion_curve",
+    "tcvn_head_shapley_workspace_bytes", "tcvn_head_shapley_count", "tcvn_head_shapley",
 ]
 
 lib = _load()

@@ -282,7 +282,7 @@ class HeadEngine(_Plan):
         check(lib.tcvn_head_create(C.byref(cfg), C.byref(self.handle)), "head_create")
         self._shape = (0, 0, 0)
         self._last = (0, -1)                 # (batch, max_prongs) of the last forward / encode on self._ws: what attention() exports
-        self._loo_ws = self._occ_ws = None      # scratch workspaces (_scratch) of leave_one_out() and occlusion_pass()
+        self._loo_ws = self._occ_ws = self._shap_ws = None      # scratch workspaces (_scratch) of leave_one_out(), occlusion_pass(), shapley()
 
     def forward(self, rows: torch.Tensor, tok_row: torch.Tensor, batch: int, max_prongs: int, n_prongs: int, train: bool,
                 seed: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -371,6 +371,31 @@ class HeadEngine(_Plan):
         check(lib.tcvn_head_leave_one_out(self.handle, batch, S - 1, _ptr(tokens), _ptr(tok_row), _ptr(ev), _ptr(loo),
                                           _ptr(ws), ws.numel(), _stream_ptr()), "head_leave_one_out")
         return ev, loo
+
+    def shapley(self, tokens: torch.Tensor, tok_row: torch.Tensor, max_exact: int = 10, samples: int = 64, seed: int = 0,
+                value_kind: int = _lib.SHAP_VALUE_PROB) -> dict:
+        """tcvn_head_shapley: tokens [B, S, hidden] -> the outputs of the prong Shapley scan by name (include/tcvn_hip.h), eval
+        arithmetic.  Workspace of its own, as leave_one_out has."""
+        batch, S, D = self._check_tokens(tokens)
+        self._check_tok_row(tok_row, batch, S)
+        P, Ce, dev = S - 1, self.cfg.event_classes, tokens.device
+        need = lib.tcvn_head_shapley_workspace_bytes(self.handle, batch, P, max_exact, samples)
+        J = lib.tcvn_head_shapley_count(batch, P, _ptr(tok_row), max_exact, samples, _stream_ptr()) if need >= 0 else -1
+        if need < 0 or J < 0:
+            raise RuntimeError(f"libtcvn_hip: head_shapley rejects batch {batch}, {S} tokens, max_exact {max_exact}, samples {samples}")
+        ws = self._scratch("_shap_ws", need, dev)
+        out = dict(event_logits=torch.empty(batch, Ce, device=dev), phi=torch.empty(batch, P, Ce, device=dev),
+                   stderr=torch.empty(batch, P, Ce, device=dev), interaction=torch.empty(batch, P, P, Ce, device=dev),
+                   exact=torch.empty(batch, dtype=torch.int32, device=dev), offsets=torch.empty(batch + 1, dtype=torch.int64, device=dev),
+                   masks=torch.empty(J, dtype=torch.int64, device=dev), event=torch.empty(J, dtype=torch.int32, device=dev),
+                   coalition_logits=torch.empty(J, Ce, device=dev),
+                   permutations=torch.empty(batch, samples, P, dtype=torch.int32, device=dev))
+        prong = lambda name: _ptr(out[name] if P > 0 else None)
+        check(lib.tcvn_head_shapley(self.handle, batch, P, _ptr(tokens), _ptr(tok_row), max_exact, samples, C.c_uint64(seed), value_kind,
+                                    _ptr(out["event_logits"]), prong("phi"), prong("stderr"), prong("interaction"), _ptr(out["exact"]),
+                                    _ptr(out["offsets"]), _ptr(out["masks"]), _ptr(out["event"]), _ptr(out["coalition_logits"]), J,
+                                    prong("permutations"), _ptr(ws), ws.numel(), _stream_ptr()), "head_shapley")
+        return out
 
     def occlusion_pass(self, rows: torch.Tensor, tokens: torch.Tensor, tok_row: torch.Tensor, n_prongs: int, vimg: torch.Tensor,
                        index: torch.Tensor, row_base: int, emb: torch.Tensor, col0: int, occ_ev: torch.Tensor, occ_pr: torch.Tensor):

@@ -14,7 +14,7 @@ from typing import Dict, List, NamedTuple, Optional, Tuple
 import torch
 from torch import Tensor, nn
 
-from . import _lib, occlusion
+from . import _lib, attention, occlusion
 from .engine import DenseNetEngine, HeadEngine
 from .native import gpu_only
 from .pixels import SparsePixels
@@ -351,6 +351,30 @@ class HipRuntime:
             tokens = self.head.embed(last.rows, last.tok_row, last.B, last.P, last.n_prongs, False, 0)
             ev, loo = self.head.leave_one_out(tokens, last.tok_row)
             return ev, pr, loo
+
+    def prong_shapley(self, tokens: Tensor, mask: Tensor, max_exact: int = 10, samples: int = 64, seed: int = 0,
+                      value: str = "prob") -> "attention.ProngShapley":
+        """tokens [B, S, hidden], mask [B, S] -> attention.ProngShapley: the event's class score shared among its prongs, in eval
+        arithmetic.  Events with at most max_exact prongs run all their coalitions, wider ones `samples` permutations."""
+        max_exact, samples, seed, kind = attention.check_shapley_args(max_exact, samples, seed, value)
+        self.ensure_bound()
+        with torch.no_grad():
+            out = self.head.shapley(tokens.detach().float().contiguous(), self._token_map(tokens, mask), max_exact, samples, seed, kind)
+            return attention.ProngShapley(out, value)
+
+    def forward_prong_shapley(self, features: Tensor, extra: Tensor, event_px: SparsePixels, event_mask: Tensor, prong_px: SparsePixels,
+                              prong_mask: Tensor, counts: Optional[Tuple[int, int]] = None, max_exact: int = 10, samples: int = 64,
+                              seed: int = 0, value: str = "prob") -> "attention.ProngShapley":
+        """Eval-mode forward() plus the prong Shapley scan over its tokens -> attention.ProngShapley (prong_logits are forward()'s).  The
+        DenseNets run once; every coalition adds one encoder + event-decoder sequence.  One forward() for the step counter."""
+        max_exact, samples, seed, kind = attention.check_shapley_args(max_exact, samples, seed, value)
+        if self.network.training:
+            raise RuntimeError("prong_shapley explains an eval-mode prediction: call network.eval() first")
+        with torch.no_grad():
+            _, pr = self.forward(features, extra, event_px, event_mask, prong_px, prong_mask, counts)
+            last = self._last_forward
+            tokens = self.head.embed(last.rows, last.tok_row, last.B, last.P, last.n_prongs, False, 0)
+            return attention.ProngShapley(self.head.shapley(tokens, last.tok_row, max_exact, samples, seed, kind), value, pr)
 
     def _scan(self, maps: str, *inputs) -> "occlusion.Scan":
         """forward(*inputs) and the occlusion scan over it (hip/occlusion.py).  However many variants follow, it counts as ONE forward()

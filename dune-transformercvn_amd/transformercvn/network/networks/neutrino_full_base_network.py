@@ -167,6 +167,22 @@ class NeutrinoBaseNetwork(nn.Module):
                                                               counts)
 
     @torch.jit.unused
+    def prong_shapley(self, features: Tensor, extra: Tensor, event_pixels: Tensor, event_mask: Tensor, prong_pixels: Tensor,
+                      prong_mask: Tensor, counts: Optional[Tuple[int, int]] = None, max_exact: int = 10, samples: int = 64, seed: int = 0,
+                      value: str = "prob"):
+        """Eval mode only -> transformercvn.hip.attention.ProngShapley: the Shapley value of every prong for every event class, the one
+        attribution whose prong scores sum to value(all prongs) - value(no prongs).  value: "prob" (class probability) or "logit".
+        Events with at most max_exact (0..16) prongs run all 2^n coalitions and get pairwise interactions too; wider events run `samples`
+        permutations drawn on the device from `seed` and get a standard error instead.  result.for_target() -> [B, P]."""
+        from transformercvn.hip import attention
+        attention.check_shapley_args(max_exact, samples, seed, value)
+        if self.training:
+            raise RuntimeError("prong_shapley explains an eval-mode prediction: call .eval() first")
+        event_pixels, prong_pixels = _as_sparse(event_pixels), _as_sparse(prong_pixels)
+        return self.hip_runtime().forward_prong_shapley(features, extra, event_pixels, event_mask, prong_pixels, prong_mask, counts,
+                                                        max_exact, samples, seed, value)
+
+    @torch.jit.unused
     def occlusion_maps(self, features: Tensor, extra: Tensor, event_pixels: Tensor, event_mask: Tensor, prong_pixels: Tensor,
                        prong_mask: Tensor, counts: Optional[Tuple[int, int]] = None, tile: Tuple[int, int] = (16, 16),
                        maps: str = "all", max_maps_per_pass: int = 256):

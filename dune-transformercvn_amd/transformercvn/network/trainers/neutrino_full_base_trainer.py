@@ -170,6 +170,19 @@ class NeutrinoFullBaseTrainer(NeutrinoBase, ABC):
         return self.network.leave_one_prong_out(*self._network_inputs(features, extra, event_coords, event_values, event_mask,
                                                                       prong_coords, prong_values, prong_mask), counts)
 
+    def prong_shapley(self, features: Tensor, extra: Tensor, event_coords: Tensor, event_values: Tensor, event_mask: Tensor,
+                      prong_coords: Tensor, prong_values: Tensor, prong_mask: Tensor, max_exact: int = 10, samples: int = 64,
+                      seed: int = 0, value: str = "prob"):
+        """Eval mode only -> ProngShapley (transformercvn.hip.attention): the event's class score shared among its prongs; see
+        NeutrinoBaseNetwork.prong_shapley.  Bad keywords raise ValueError and train mode RuntimeError before any device work."""
+        from transformercvn.hip import attention
+        attention.check_shapley_args(max_exact, samples, seed, value)
+        if self.training:
+            raise RuntimeError("prong_shapley explains an eval-mode prediction: call .eval() first")
+        return self.network.prong_shapley(*self._network_inputs(features, extra, event_coords, event_values, event_mask,
+                                                                prong_coords, prong_values, prong_mask), None, max_exact, samples, seed,
+                                          value)
+
     def occlusion_maps(self, features: Tensor, extra: Tensor, event_coords: Tensor, event_values: Tensor, event_mask: Tensor,
                        prong_coords: Tensor, prong_values: Tensor, prong_mask: Tensor, tile: Tuple[int, int] = (16, 16),
                        maps: str = "all", max_maps_per_pass: int = 256):

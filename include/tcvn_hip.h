@@ -210,6 +210,50 @@ int64_t tcvn_head_leave_one_out_workspace_bytes(const tcvn_head* p, int batch, i
 int tcvn_head_leave_one_out(tcvn_head* p, int batch, int max_prongs, const float* tokens, const int32_t* tok_row,
                             float* event_logits, float* loo_event_logits, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Prong Shapley values (forward only, eval arithmetic): the event's class score shared among its prongs.
+ *   coalition   a subset C of the valid prong slots N_b of event b (n = |N_b|, max_prongs <= 63), stored as an int64 mask: bit p set =
+ *               slot p present.  Its sequence is event b's tokens [batch, S, hidden] (tcvn_head_embed) with every absent or padded
+ *               prong token zeroed and padded as a key; token 0, the event's own map, is present whenever tok_row says so.  Its value
+ *               v_c(C) per event class c is the softmax probability (TCVN_SHAP_VALUE_PROB, formed in double precision) or the raw logit
+ *               (TCVN_SHAP_VALUE_LOGIT) of the event decoder on that sequence.
+ *   exact       events with n <= max_exact (0..TCVN_SHAP_MAX_EXACT) run all 2^n coalitions, ordered by the compact index k: bit i of k
+ *               stands for the i-th valid slot in ascending slot order (k = 0 empty, k = 2^n - 1 full; n = 0: one coalition).
+ *               phi[b, p, c] = sum over C in N\{p} of |C|! (n-|C|-1)! / n! (v_c(C + p) - v_c(C)).  interaction[b, p, q, c], p != q: half
+ *               the Shapley interaction index, 1/2 sum over C in N\{p,q} of |C|! (n-|C|-2)! / (n-1)! (v(C+p+q) - v(C+p) - v(C+q) + v(C));
+ *               p = q: phi[b, p] - sum_{q != p} interaction[b, p, q] (the SHAP convention: symmetric, row p sums to phi[b, p]).
+ *               std_error is 0.
+ *   sampled     events with n > max_exact: permutations[b, m] (m < samples) is N_b sorted by (key, slot), key = word 0 of the library's
+ *               Philox-4x32-10 with counter (slot, m, b, 0x53484150) and the 64-bit seed as key, followed by -1 up to max_prongs
+ *               entries (drawn for every event, used by the sampled ones).  The event's coalitions: empty, full, then for every m the
+ *               prefixes of length 1 .. n-1 of permutation m.  phi[b, p, c] is the mean over m of v_c(prefix with p) - v_c(prefix
+ *               before p), std_error the sample standard deviation of those contributions / sqrt(samples) (0 with samples = 1);
+ *               interaction is NaN.
+ *   both        rows and columns of padded slots are exactly 0 in phi, std_error and interaction, and sum_p phi[b, p, c] =
+ *               v_c(full) - v_c(empty).  Values are double precision, every sum is taken in a fixed order without atomics (two runs
+ *               agree bit for bit) and rounded to fp32 once.
+ *   outputs     event_logits [batch, Ce] (the full coalition's row), phi / std_error [batch, max_prongs, Ce], interaction [batch,
+ *               max_prongs, max_prongs, Ce], exact [batch] (1 / 0), offsets [batch + 1] (event b owns coalitions offsets[b] ..
+ *               offsets[b+1]-1), masks [J], event [J], coalition_logits [J, Ce], permutations [batch, samples, max_prongs]; all device
+ *               memory.  J = n_coalitions must be what tcvn_head_shapley_count returns for the same tok_row, max_exact and samples
+ *               (sum over events of 2^n or 2 + samples (n-1)).  With max_prongs = 0 the prong-shaped outputs may be NULL.
+ *   passes      the coalitions run through the encoder and the event decoder in passes of at most TCVN_SHAP_MAX_PASS sequences; job ->
+ *               (event, mask) is resolved on the device from a per-event table.  Both calls read tok_row back, so they synchronise
+ *               with `stream` (not capturable into a graph).  Workspace: tcvn_head_shapley_workspace_bytes, asked for
+ *               before the mask is known and therefore sized for the most coalitions a mask of this shape can have (double-precision values of
+ *               batch x max(2^min(max_prongs, max_exact), 2 + samples (max_prongs - 1)) coalitions, plus one pass): it grows with max_exact.
+ * Argument errors (NULL, batch outside 1..65535, max_prongs > 63, max_exact outside 0..16, samples < 1, unknown value kind, workspace
+ * too small, parameters not bound, n_coalitions not the mask's count) return non-zero before any kernel and print one "tcvn:" line. */
+#define TCVN_SHAP_MAX_PASS 1024
+#define TCVN_SHAP_MAX_EXACT 16
+#define TCVN_SHAP_VALUE_PROB 0
+#define TCVN_SHAP_VALUE_LOGIT 1
+int64_t tcvn_head_shapley_workspace_bytes(const tcvn_head* p, int batch, int max_prongs, int max_exact, int samples);
+int64_t tcvn_head_shapley_count(int batch, int max_prongs, const int32_t* tok_row, int max_exact, int samples, void* stream);
+int tcvn_head_shapley(tcvn_head* p, int batch, int max_prongs, const float* tokens, const int32_t* tok_row, int max_exact, int samples,
+                      uint64_t seed, int value_kind, float* event_logits, float* phi, float* std_error, float* interaction,
+                      int32_t* exact, int64_t* offsets, int64_t* masks, int32_t* event, float* coalition_logits, int64_t n_coalitions,
+                      int32_t* permutations, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Occlusion maps (forward only, eval arithmetic): which regions of which pixel maps a prediction rests on.
  *   tile        (tile_h, tile_w) >= 1, need not divide the map: grid_h = ceil(height / tile_h), grid_w = ceil(width / tile_w); the hit
  *               (y, x) lies in tile (y / tile_h, x / tile_w); the last row / column of tiles may be ragged.

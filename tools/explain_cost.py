@@ -4,8 +4,10 @@ interleaved, and prints one JSON line with the medians.  occlusion_maps() is tim
 its number of variants V and of embedder passes (a scan is thousands of maps: it gets --occ-reps repetitions of its own), and beside
 them occlusion_refine(tile=(64, 64), levels=4) -- the same 8x8 grid, coarse to fine -- for every --keep, with V per level.
 occlusion_curves(steps=10) on the 16x16 heat map is timed with its V = 11 x maps (the 16x16 scan that gives the heat map is not in it).
+prong_shapley() is timed with its default keywords and with max_exact=12, beside leave_one_prong_out: the whole call (forward() included)
+and the coalition scan alone on the same tokens, with the number of coalitions and of encoder passes.
 
-    python tools/explain_cost.py [--batch 32 --reps 15 --occ-reps 3 --precision bf16 --keep 0.25]
+    python tools/explain_cost.py [--batch 32 --reps 15 --occ-reps 3 --shap-reps 5 --precision bf16 --keep 0.25]
 """
 import argparse
 import json
@@ -18,6 +20,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "dune-transformercvn_amd")]
 import bench  # noqa: E402
+from transformercvn.hip import _lib  # noqa: E402
 from transformercvn.options import Options  # noqa: E402
 from transformercvn.network.trainers.neutrino_full_dense_trainer import NeutrinoFullDenseTrainer  # noqa: E402
 
@@ -27,6 +30,7 @@ def main():
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--occ-reps", type=int, default=3, help="repetitions of each occlusion_maps line (0: skip them)")
+    ap.add_argument("--shap-reps", type=int, default=5, help="repetitions of each prong_shapley line (0: skip them)")
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--keep", type=float, nargs="*", default=[0.25], help="keep of each occlusion_refine line (none: skip them)")
     args = ap.parse_args()
@@ -42,10 +46,10 @@ def main():
     f, x, ec, ev, em, pc, pv, pm = batch[:8]
     inputs = (f[:, :width].contiguous(), x, ec, ev, em, pc, pv, pm[:, :width].contiguous(), (args.batch, n_prongs))   # as shared_step trims them
 
-    def timed(call):
+    def timed(call, reps=None):
         ts = []
         with torch.no_grad():
-            for rep in range(1 + args.occ_reps):                    # the first call allocates the scan's workspaces
+            for rep in range(1 + (args.occ_reps if reps is None else reps)):                    # the first call allocates the scan's workspaces
                 t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 torch.cuda.synchronize()
                 t0.record()
@@ -101,7 +105,20 @@ def main():
         out[f"occlusion_refine_64x64_levels4_keep{keep:g}"] = {
             "variants_per_level": [level.num_variants for level in res.levels], "variants": res.num_variants, "reps": args.occ_reps,
             "ms": ms(ts), "us_per_variant": round(1e3 * statistics.median(ts) / max(1, res.num_variants), 2)}
-    cfg = model.network.hip_runtime().head.cfg
+    rt = model.network.hip_runtime()
+    for kw in (dict(), dict(max_exact=12)) if args.shap_reps > 0 else ():
+        res, ts = timed(lambda: model.prong_shapley(*inputs[:8], **kw), args.shap_reps)
+        last = rt._last_forward
+        with torch.no_grad():
+            tokens = rt.head.embed(last.rows, last.tok_row, last.B, last.P, last.n_prongs, False, 0)
+        kind = _lib.SHAP_VALUE_PROB
+        _, scan = timed(lambda: rt.head.shapley(tokens, last.tok_row, kw.get("max_exact", 10), 64, 0, kind), args.shap_reps)
+        J = res.masks.numel()
+        out["prong_shapley" + "".join(f"_{k}{v}" for k, v in kw.items())] = {
+            "coalitions": J, "exact_events": int(res.exact.sum()), "sampled_events": int((~res.exact).sum()),
+            "passes": -(-J // _lib.SHAP_MAX_PASS), "max_pass": _lib.SHAP_MAX_PASS, "reps": args.shap_reps, "ms": ms(ts), "scan_ms": ms(scan),
+            "scan_us_per_coalition": round(1e3 * statistics.median(scan) / J, 3)}
+    cfg = rt.head.cfg
     out["weights_bytes"] = cfg.n_layers * args.batch * cfg.heads * (1 + width) ** 2 * 4
     print(json.dumps(out))
 
