@@ -9,15 +9,28 @@
 // 0 of the consumer also publishes what the backward pass and the module state need: the (scale, shift) table, (mean, biased
 // variance), the running statistics.
 //
-// Fixed point: sum x scaled by 2^24, sum x^2 by 2^16.  Range: |sum x| < 2^39 and sum x^2 < 2^47, i.e. an r.m.s. activation below 8 000
-// over 2 M positions (BatchNorm-ed DenseNet maps are O(1)); resolution per added partial 6e-8 / 1.5e-5 absolute against sums of
-// 10^3..10^7: the mean / variance carry ~1e-10 relative error, far below the fp32 table they feed.
+// Fixed point: sum x scaled by 2^24, sum x^2 by 2^16; resolution per added partial 6e-8 / 1.5e-5 absolute against sums of 10^3..10^7: the
+// mean / variance carry ~1e-10 relative error, far below the fp32 table they feed.
+//
+// Range guard: a workgroup's partial is added only while |sum x| < 2^28 and sum x^2 < 2^36 (LF_MAX1 / LF_MAX2: scaled, both below 2^52).  At
+// most LF_MAX_ADDERS = 1024 workgroups add per channel (the grid caps of the fused 1x1 and the 3x3 pair kernel are static_asserted against
+// it), so a total stays below 2^62 and never wraps.  A partial
+// that is larger, or NaN / Inf, is not added: the workgroup sets bit 62 of its sum-of-squares word instead (LF_BAD, an atomic OR: no add
+// reaches that bit, so OR and add still commute and the result stays order-independent).  The consumer turns a flagged channel into
+// mean = variance = NaN, which poisons the table, the published rows and the running statistics exactly as a NaN partial row poisons
+// the link kernel's: a batch outside the range (or a non-finite one) gives a non-finite step, never a finite wrong one.  In the units
+// of the maps: r.m.s. activation below ~2 500 at 2 M positions (a workgroup's share is <= ~10 000 of them; BatchNorm-ed DenseNet maps are O(1)).
 #pragma once
 #include "tcvn_common.h"
 
 namespace tcvn {
 
 constexpr double LF_S1 = 16777216.0, LF_S2 = 65536.0;       // 2^24, 2^16
+constexpr double LF_MAX1 = 268435456.0, LF_MAX2 = 68719476736.0;      // 2^28, 2^36: the largest partial a workgroup may add
+constexpr int LF_MAX_ADDERS = 1024;                         // workgroups that may add to one channel: the producers' grid functions check their caps against it
+static_assert((double)LF_MAX_ADDERS * LF_MAX1 * LF_S1 <= 4611686018427387904.0 && (double)LF_MAX_ADDERS * LF_MAX2 * LF_S2 <= 4611686018427387904.0,
+              "a channel's total must stay below 2^62: no add may reach the flag bit");
+constexpr long long LF_BAD = 1LL << 62;                     // sum-of-squares word: some partial of this channel was out of range or not finite
 
 // what a consumer kernel needs to derive the (scale, shift) table of its input BatchNorm by itself
 // Replicas: the adds of one address are applied one after the other at the memory side (measured, round 5: 500-768 workgroups adding to
@@ -41,20 +54,33 @@ struct LfLink {
 #ifdef __HIPCC__
 // producer side: this workgroup's per-channel sums -> the accumulators (one call per channel and workgroup)
 __device__ __forceinline__ void lf_add(long long* isum, long rep_stride, int c, double s1, double s2) {
-    const long long a = __double2ll_rn(s1 * LF_S1), b = __double2ll_rn(s2 * LF_S2);
     long long* p = isum + (long)(blockIdx.x % LF_REP) * rep_stride + 2 * c;
-    __hip_atomic_fetch_add(p, a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_fetch_add(p + 1, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (fabs(s1) < LF_MAX1 && s2 < LF_MAX2) {                // false for NaN / Inf too
+        __hip_atomic_fetch_add(p, __double2ll_rn(s1 * LF_S1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_add(p + 1, __double2ll_rn(s2 * LF_S2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    } else __hip_atomic_fetch_or(p + 1, LF_BAD, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-// the window entry of channel index i (relative to the window): sum over the replicas (16-B loads, all in flight together)
-__device__ __forceinline__ void lf_sums(const long long* isum, long rep_stride, int i, long long& a, long long& b) {
+// the window entry of channel index i (relative to the window): sum over the replicas (16-B loads, all in flight together); false when
+// a producer flagged the channel (LF_BAD: a and b are then meaningless)
+__device__ __forceinline__ bool lf_sums(const long long* isum, long rep_stride, int i, long long& a, long long& b) {
     typedef __attribute__((ext_vector_type(2))) long long ll2;
     ll2 v[LF_REP];
 #pragma unroll
     for (int r = 0; r < LF_REP; ++r) v[r] = __builtin_nontemporal_load(reinterpret_cast<const ll2*>(isum + (long)r * rep_stride + 2 * i));
     a = 0; b = 0;
+    long long f = 0;
 #pragma unroll
-    for (int r = 0; r < LF_REP; ++r) { a += v[r].x; b += v[r].y; }
+    for (int r = 0; r < LF_REP; ++r) { a += v[r].x; b += v[r].y & ~LF_BAD; f |= v[r].y; }
+    return (f & LF_BAD) == 0;
+}
+// (mean, biased variance) of window entry i over `count` positions (inv_count = 1 / count); NaN for a flagged channel
+__device__ __forceinline__ void lf_mean_var(const long long* isum, long rep_stride, int i, double inv_count, double& mean, double& var) {
+    long long a, b;
+    const bool ok = lf_sums(isum, rep_stride, i, a, b);
+    mean = (double)a * (inv_count / LF_S1);
+    var = (double)b * (inv_count / LF_S2) - mean * mean;
+    if (var < 0) var = 0;
+    if (!ok) mean = var = __builtin_nan("");
 }
 
 // consumer side: (scale, shift) of channel c < C; `publish` = this is workgroup 0 (one thread per channel calls this)
@@ -62,11 +88,7 @@ __device__ __forceinline__ void lf_table(const LfLink& k, int c, bool publish, f
     double mean, var;
     const bool fresh = c >= k.c_new0 && c < k.c_new0 + k.n_new;
     if (fresh) {
-        long long a, b;
-        lf_sums(k.isum, k.rep_stride, c - k.c_new0, a, b);
-        mean = (double)a * (k.inv_count / LF_S1);
-        var = (double)b * (k.inv_count / LF_S2) - mean * mean;
-        if (var < 0) var = 0;
+        lf_mean_var(k.isum, k.rep_stride, c - k.c_new0, k.inv_count, mean, var);
     } else {
         mean = k.bstat[2 * c]; var = k.bstat[2 * c + 1];
     }

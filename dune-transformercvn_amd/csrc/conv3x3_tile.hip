@@ -1685,6 +1685,7 @@ int tile_grid2(long ntiles) {           // two workgroups per CU
 size_t wgrad_smem(const PadGeom& q) { const size_t r4 = (q.rows() + 3) & ~3; return r4 + TP + 8 <= 512 ? size_t(WG_RING_BYTES) + 2 * TP * 64 + 1024 * 4 + 3 * 128 * 4 : size_t(1) << 30; }
 
 int tile_grid(long ntiles) {            // one persistent workgroup per CU
+    static_assert(256 <= LF_MAX_ADDERS, "bn_lf.h: more workgroups would add to one channel than its range guard allows for (the forward pair kernel's grid)");
     if (ntiles >= 256) return 256;
     if (ntiles >= 8) return (int)(ntiles / 8 * 8);
     return (int)ntiles;

@@ -712,11 +712,22 @@ int DenseNetPlan::tap(int n, const char* name, long* off, int* tn, int* th, int*
         if (b < 0 || b >= (int)blocks.size() || l < 0 || l >= blocks[b].L) return -1;
         *tn = *th = *tw = 1; *off = L.bstatY[b][l]; *tc = *tld = 2 * cfg.bn_size * cfg.growth; *tes = 8; return 0;
     }
+    if (s.rfind("raw:isumy", 0) == 0) {                          // fixed-point accumulators of a bottleneck map whose norm2 the last forward derived link-free (LayerPath::lf2); else no such tap
+        int b = 0, l = 0;
+        if (sscanf(s.c_str(), "raw:isumy%d.%d", &b, &l) != 2) return -1;
+        b -= 1;
+        if (b < 0 || b >= (int)blocks.size() || l < 0 || l >= blocks[b].L || L.isumY.empty() || n != last_n || !path[b][l].lf2) return -1;
+        *tn = *th = *tw = 1; *off = L.isumY[b][l]; *tc = *tld = LF_REP * 2 * cfg.bn_size * cfg.growth; *tes = 8; return 0;
+    }
     if (s.rfind("raw:bstat", 0) == 0) {
         const int b = atoi(s.c_str() + 9) - 1;
+        if (s == "raw:bstat0") { *tn = *th = *tw = 1; *off = L.bstat0; *tc = *tld = cfg.init_ch * 2; *tes = 8; return 0; }      // norm0's rows (conv0 output)
         if (b < 0 || b >= (int)blocks.size()) return -1;
         *tn = *th = *tw = 1; *off = L.bstatD[b]; *tc = *tld = blocks[b].ld * 2; *tes = 8; return 0;
     }
+    // output block: the rows its BatchNorm1d normalises (Linear output, fp32) and, after a train-mode forward, the (mean, 1 / sqrt(var + eps)) rows it saved
+    if (s == "output_linear") { *off = L.Z; *th = 1; *tw = 1; *tc = *tld = cfg.out_dim; *tes = 4; return 0; }
+    if (s == "raw:head_stat") { *tn = *th = *tw = 1; *off = L.head_stat; *tc = *tld = 2 * cfg.out_dim; *tes = 4; return 0; }
     if (s.rfind("dense", 0) == 0) {
         const int b = atoi(s.c_str() + 5) - 1;
         if (b < 0 || b >= (int)blocks.size()) return -1;

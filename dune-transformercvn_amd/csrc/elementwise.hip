@@ -22,11 +22,7 @@ __global__ __launch_bounds__(256) void k_bn_link(const BnLinkArgs a) {
     if (a.train) {
         if (c >= a.c_new0 && c < a.c_new0 + a.n_new && a.isum != nullptr) {
             // the producer added its sums to fixed-point accumulators (bn_lf.h): nothing to reduce
-            long long sa, sb;
-            lf_sums(a.isum, a.isum_stride, c - a.c_new0, sa, sb);
-            mean = (double)sa * ((1.0 / (double)a.count) / LF_S1);
-            var = (double)sb * ((1.0 / (double)a.count) / LF_S2) - mean * mean;
-            if (var < 0) var = 0;
+            lf_mean_var(a.isum, a.isum_stride, c - a.c_new0, 1.0 / (double)a.count, mean, var);
             if (lane == 0) { a.bstat[c * 2] = mean; a.bstat[c * 2 + 1] = var; }
         } else if (c >= a.c_new0 && c < a.c_new0 + a.n_new) {
             double s1 = 0, s2 = 0;

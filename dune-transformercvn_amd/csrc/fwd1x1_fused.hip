@@ -436,7 +436,9 @@ bool fwd1x1_fused_ok(const Fwd1x1Args& a) {
 }
 
 int fwd1x1_fused_nblk(const Fwd1x1Args& a) {
-    const int cap = a.Kp <= 256 ? 768 : 512;         // resident workgroups: three per CU (two for the wide-layer kernel)
+    constexpr int CAP = 768, CAP_WIDE = 512;         // resident workgroups: three per CU (two for the wide-layer kernel)
+    static_assert(CAP <= LF_MAX_ADDERS && CAP_WIDE <= LF_MAX_ADDERS, "bn_lf.h: more workgroups would add to one channel than its range guard allows for");
+    const int cap = a.Kp <= 256 ? CAP : CAP_WIDE;
     const long mt = (a.M + ROWS - 1) / ROWS;
     return (int)(mt < cap ? mt : cap);
 }

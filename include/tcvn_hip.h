@@ -84,7 +84,9 @@ int tcvn_densenet_backward_blocks(tcvn_densenet* p, int n_img, const float* d_ou
                                   int64_t workspace_bytes, int block_hi, int block_lo, void* stream);
 
 /* Debug/validation taps into the workspace of the last forward: name in {"img","conv0","dense<b>","bottleneck<b>.<l>","condense"},
- * in bf16 mode also the materialised operands "xa<b>.<l>" / "ya<b>.<l>" and the raw regions "raw:wk","raw:tabs","raw:bstat<b>";
+ * "output_linear" (the fp32 rows the output block's BatchNorm1d normalises), in bf16 mode also the materialised operands
+ * "xa<b>.<l>" / "ya<b>.<l>", and the raw regions "raw:wk","raw:tabs","raw:bstat<b>" (b = 0: norm0),"raw:ystat<b>.<l>","raw:head_stat",
+ * "raw:isumy<b>.<l>" (exists only where the last forward derived norm2 link-free);
  * returns the byte offset into the workspace and the logical NHWC shape + channel stride + element size. */
 int tcvn_densenet_tap(const tcvn_densenet* p, int n_img, const char* name, int64_t* byte_off, int* n, int* h, int* w,
                       int* c, int* ld, int* elem_bytes);
