@@ -12,9 +12,9 @@
 // the activated input exists in HBM for these kernels: per pixel and layer the backward of the 1x1 moves 512 + 6*cin bytes instead of
 // 1792 + 8*cin (EY written once and read twice, the activated copy read once, x and G as here).
 // The weight-gradient tile (128 x 128 fp32 = 64 accumulator registers per lane) stays in registers for the whole launch and leaves as one
-// slab per workgroup (k_slab_reduce: one y-slice takes up to 512 slabs and sums them in a fixed order, so the weight gradient is the same
-// from run to run; only jobs with more than 512 slabs, and the scalar bias column-sum jobs (64 slabs per y-slice), split over y-slices whose
-// partial sums meet in fp32 atomics, i.e. the last bits of a bias gradient can differ from run to run).
+// slab per workgroup, and so do the bias column sums (`tail`).  k_slab_reduce (elementwise_bwd.hip) adds the slabs of every job -- weight
+// and bias, of any slab count, size and alignment -- in an order fixed by the number of slabs alone and ends in one read-add-write of the
+// gradient, never in an atomic: weight AND bias gradients of the dense layers are the same from run to run.
 #include "tcvn_ops.h"
 #include "prof.h"
 

@@ -5,10 +5,12 @@
 // image (128 + 2*(W+3) rows x 128 channels) is staged ONCE in LDS, then 9 taps x 8 k-steps of v_mfma_f32_32x32x16_bf16
 // read it with row offsets (ds_read_b128, XOR-swizzled, conflict free); weights stream from L2 in fragment order.
 // Algorithmic work per launch: 2 * pixels * 32 * 1152 FLOP; HBM: read 128 ch + write 32 ch per pixel.
+#include <cstddef>
 #include <cstdlib>
 #include <type_traits>
 #include "tile3x3.h"
 #include "prof.h"
+#include "bn_link.h"
 
 namespace tcvn {
 
@@ -720,6 +722,9 @@ __device__ __forceinline__ void wg_kloop(f32x16 (&acc)[9], const char* smem, int
 // value).  Every LDS read of the multiplying waves is a transposed read of four consecutive rows x 64 B: the forward kernels' `row & 15`
 // swizzle put those four rows on the same 16 banks (two- to four-way conflicts on all 160 reads per wave and tile, rocprofv3 round 4:
 // LDS_BANK_CONFLICT = 2.6 x the LDS-active cycles); with row & 3 selecting the 64-B quad they cover all 64 banks.
+constexpr int WGRAD_ARGS_KERNARG_OFFSET = 0;      // ConvWgradArgs is the FIRST argument of k_conv3x3_wgrad_bf16 (its link rider reads it from the segment)
+template <typename F> struct first_arg;
+template <typename A, typename... R> struct first_arg<void (*)(A, R...)> { typedef A type; };
 __global__ __launch_bounds__(512, 1) void k_conv3x3_wgrad_bf16(const ConvWgradArgs g, int n_img, int ntiles) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const ConvFwdArgs& fa = g.fa;
@@ -1111,7 +1116,27 @@ __global__ __launch_bounds__(512, 1) void k_conv3x3_wgrad_bf16(const ConvWgradAr
             g.slab[(long)gridDim.x * (9 * 128 * 32) + blockIdx.x * 32 + tid] = tid < e.N ? sum : 0.f;
         }
     }
+    // A BatchNorm backward link rides at the end of the launch (the dense layers' norm2 link: this kernel reads neither its inputs nor its
+    // outputs, the fused 1x1 backward behind it needs them): one wave per channel, exactly k_bn_bwd_link's arithmetic.  The channels go to
+    // the workgroups from the END of the grid: the tile split gives the first ntiles % nb workgroups one tile more, so the last ones reach
+    // this point a tile time before the others -- unless ntiles % nb == 0, when nobody has slack and the link lengthens the launch by its
+    // own latency (measured: +1.3 us per launch on average, profiles/helper_launches.md).  A grid of 1..15 workgroups loops over the channels.
+    // Its arguments are read HERE, from the kernel's argument segment behind an opaque copy of its address (WGRAD_ARGS_KERNARG_OFFSET: the
+    // position of ConvWgradArgs among the kernel's arguments, checked below the kernel).  Read as g.link, the compiler loads the link's
+    // twelve values at the top of the kernel and holds them through the tile loops: cross-compiled, 39 spilled SGPRs and 204 lane reads
+    // in the kernel's code, against 21 and 64 without the link; read here, 14 and 21 (VGPRs 209 -> 211, no scratch, occupancy 2 in all three).
+    {
+        typedef const char __attribute__((address_space(4)))* kernarg_ptr;
+        kernarg_ptr ka = (kernarg_ptr)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(ka));
+        BnBwdLinkArgs link;
+        __builtin_memcpy(&link, ka + WGRAD_ARGS_KERNARG_OFFSET + offsetof(ConvWgradArgs, link), sizeof(link));
+        if (link.part != nullptr) bn_bwd_link_body(link, gridDim.x - 1 - blockIdx.x, gridDim.x);
+    }
 }
+
+static_assert(std::is_same<first_arg<decltype(&k_conv3x3_wgrad_bf16)>::type, ConvWgradArgs>::value && WGRAD_ARGS_KERNARG_OFFSET == 0,
+              "the link rider of k_conv3x3_wgrad_bf16 reads ConvWgradArgs at WGRAD_ARGS_KERNARG_OFFSET of the argument segment");
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Data gradient: dA[p][c] = sum_tap sum_n eff[p - shift(tap)][n] * W2[n][c][tap]  (128 channels out, K = 9 x 32), followed

@@ -500,6 +500,7 @@ int conv_wgrad(const ConvWgradArgs& a, hipStream_t st) {
         if (!conv3x3_wgrad_tile_ok(a)) { fprintf(stderr, "tcvn: conv_wgrad: tile kernel requested but not applicable\n"); return -4; }
         return conv3x3_wgrad_tile(a, st);
     }
+    if (a.link.part != nullptr) { fprintf(stderr, "tcvn: conv_wgrad: only the tile kernel carries a BatchNorm link\n"); return -5; }
     if (conv3x3_wgrad_f32_ok(a)) return conv3x3_wgrad_f32(a, st);
     if (gemm_tn_f32_ok(a)) return gemm_tn_f32(a, st);               // every fp32 1x1 weight gradient since round 5 (68 launches 6.8 ms against 9.0 ms
     if (conv1x1_wgrad_f32_ok(a)) return conv1x1_wgrad_f32(a, st);   // with the 128-output tile kernel on the bottleneck layers); that kernel serves callers without a slab

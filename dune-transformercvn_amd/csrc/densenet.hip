@@ -727,6 +727,11 @@ int DenseNetPlan::tap(int n, const char* name, long* off, int* tn, int* th, int*
     }
     // output block: the rows its BatchNorm1d normalises (Linear output, fp32) and, after a train-mode forward, the (mean, 1 / sqrt(var + eps)) rows it saved
     if (s == "output_linear") { *off = L.Z; *th = 1; *tw = 1; *tc = *tld = cfg.out_dim; *tes = 4; return 0; }
+    if (s == "raw:grad1") {      // after a backward pass: the gradient accumulator of block 1's concat buffer (what reaches the stem)
+        Layout Lb;
+        layout(n, true, Lb);
+        *off = Lb.G[0]; *th = blocks[0].H; *tw = blocks[0].W; *tc = blocks[0].Ctot; *tld = blocks[0].ld; return 0;
+    }
     if (s == "raw:head_stat") { *tn = *th = *tw = 1; *off = L.head_stat; *tc = *tld = 2 * cfg.out_dim; *tes = 4; return 0; }
     if (s.rfind("dense", 0) == 0) {
         const int b = atoi(s.c_str() + 5) - 1;

@@ -18,6 +18,14 @@ static int g_backward_overlap = 0;
 bool tcvn::backward_overlap_enabled() { return g_backward_overlap != 0; }
 void tcvn::set_backward_overlap(int on) { g_backward_overlap = on; }
 
+#ifdef TCVN_DEBUG_KNOBS
+// Validation build: the (PY, QY) rows of dense layer (block, layer) -- one buffer that every layer of the backward pass overwrites -- are
+// copied to `dst` ([2][bn_size * growth] floats on the device) on the backward's stream once that layer's norm2 link has been issued;
+// dst == nullptr switches the tap off (tests/test_backward_link_rider_gpu.py).
+static struct { int block, layer; float* dst; } g_pq_tap = {0, 0, nullptr};
+extern "C" void tcvn_debug_pq_tap(int block, int layer, float* dst) { g_pq_tap = {block, layer, dst}; }
+#endif
+
 namespace {
 constexpr float kEps = 1e-5f;
 constexpr long kSlabBytes = 48L << 20;      // per-workgroup partial weight gradients (<= 256 x 147 KB) and column sums
@@ -292,6 +300,7 @@ int DenseNetPlan::bwd_layer(Step& s, int bi, int l) const {
     EffSrc e2{G, bg.ld, D, bg.ld, ls.cin, g, P + ls.cin, Q + ls.cin, cfg.dropout, s.seed, (uint32_t)(bi * 64 + l + 1)};
     if (p.keep_stored) e2.keep = reinterpret_cast<const uint32_t*>(s.ws + L.KM[bi][l]);      // keep words of this layer's forward (else: the hash)
     bool ey_valid = false;
+    BnBwdLinkArgs link2{};                 // norm2 backward link (partials of the data gradient below -> PY / QY, which only the 1x1 backward reads)
     {   // conv2 data gradient -> DU (= sc2 * dU2) + norm2 partials (+ the eff rows for the weight gradient below)
         const WkEntry& et = wk_find(ls.w2, 1);
         ConvDgradArgs d{};
@@ -303,7 +312,8 @@ int DenseNetPlan::bwd_layer(Step& s, int bi, int l) const {
         if (ey_valid) d.ey_out = s.ws + L.EY3[bi][l];
         d.nblk = conv_dgrad_nblk(d);
         if ((rc = conv_dgrad(d, st))) return rc;
-        if ((rc = bwd_link(s, ls.n2, d.nblk, reinterpret_cast<const double*>(s.ws + L.bstatY[bi][l]), M, PY, QY, 0, ls.a2))) return rc;
+        link2 = BnBwdLinkArgs{s.part, d.nblk, ls.n2.C, reinterpret_cast<const double*>(s.ws + L.bstatY[bi][l]), M, kEps, data[ls.n2.w],
+                              grad[ls.n2.w], grad[ls.n2.b], grad[ls.a2], PY, QY, 0};
     }
     // Fused 1x1 backward (round 4, bwd1x1_fused.hip): effective gradient formed in LDS, bias / data / weight gradient and the norm1
     // backward epilogue in one pass -- no EY in HBM, no read of the activated copy XA, one launch instead of three.  It writes G, so it
@@ -325,19 +335,30 @@ int DenseNetPlan::bwd_layer(Step& s, int bi, int l) const {
             w3.slab = reinterpret_cast<float*>(s.ws + L.slab); w3.slab_bytes = kSlabBytes;
         }
         const bool par = s.side_on && L.XA[bi][l] >= 0;
+        // The norm2 link rides in the weight-gradient launch when that is the tile kernel on `st` (the kernel reads neither the partials nor
+        // PY / QY, and everything that does follows it on `st`): 60 launches fewer on the chain per step.  Otherwise -- side stream, generic
+        // kernels, fp32 -- it stays a launch of its own in front of the weight gradient.  TCVN_LINK_LAUNCH (validation build): always.
+        static const bool link_launch = TCVN_KNOB_SET("TCVN_LINK_LAUNCH");
+        const bool tile3 = fast3x3 && conv3x3_wgrad_tile_ok(w3);
+        if (!par && tile3 && !link_launch) w3.link = link2;
+        else if ((rc = bn_bwd_link(link2, st))) return rc;
         if (par) {                    // G slice, its (P, Q), the materialised YA and the eff rows are final: fork
             TCVN_CHECK(hipEventRecord(ev_fork_a, st));
             TCVN_CHECK(hipStreamWaitEvent(side_st, ev_fork_a, 0));
             s.side_busy = true;
         }
-        if (!par && fuse1 && fast3x3 && conv3x3_wgrad_tile_ok(w3)) { w3.deferred = w3jobs; w3_deferred = true; }
+        if (!par && fuse1 && tile3) { w3.deferred = w3jobs; w3_deferred = true; }
         if ((rc = conv_wgrad(w3, par ? side_st : st))) return rc;
+#ifdef TCVN_DEBUG_KNOBS
+        if (g_pq_tap.dst != nullptr && g_pq_tap.block == bi && g_pq_tap.layer == l)
+            TCVN_CHECK(hipMemcpyAsync(g_pq_tap.dst, PY, (size_t)2 * mid * sizeof(float), hipMemcpyDeviceToDevice, st));
+#endif
     }
     if (fuse1) {
         // The slab reductions stay on `st` behind the launch (on the side stream, with double-buffered slabs, the step was 0.25 ms LONGER);
         // one launch reduces this kernel's slabs and the 3x3 weight gradient's.
         if ((rc = bwd1x1_fused_launch(fa, st))) return rc;
-        // Round 5: the norm1 link rides in the reduction launch (an extra z-plane of k_slab_reduce_link): both are ~5 us latency-floor
+        // Round 5: the norm1 link rides in the reduction launch (the workgroups behind the last job of k_slab_reduce_link's 1-D grid): both are ~5 us latency-floor
         // launches on the critical chain and independent of each other -- 60 launches fewer per step
         const BnSlots& s1 = ls.n1;
         BnBwdLinkArgs la{s.part, fa.nblk, s1.C, bstatD, M, kEps, data[s1.w], grad[s1.w], grad[s1.b], grad[ls.a1], P, Q, 1};

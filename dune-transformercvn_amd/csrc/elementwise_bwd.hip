@@ -1,54 +1,12 @@
 // HBM-bound helper kernels of the DenseNet backward path.
 #include "tcvn_ops.h"
+#include "bn_link.h"
 
 namespace tcvn {
 
 namespace {
 
-// BatchNorm backward bookkeeping for one norm layer (train mode):
-//   s1 = sum dU, t2 = sum dU*x, s3 = sum dA*min(u,0)   (partials from the dgrad epilogue / pooling backward kernels)
-//   dbeta = s1 ; dgamma = sum dU*xhat = r*(t2 - mu*s1) ; dslope = s3
-//   dx = sc*dU + Px*x + Qx  with  Px = -sc*dgamma*r/M ,  Qx = -sc*s1/M + sc*dgamma*r*mu/M      (sc = gamma*r)
-__device__ __forceinline__ void bn_bwd_link_body(const BnBwdLinkArgs& a, int blk) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int c = blk * 4 + wave;
-    if (c >= a.C) return;
-    // everything the closing arithmetic needs is requested up front, with the partial rows (one round trip instead of two: see k_bn_link)
-    const double mu = a.bstat[c * 2], var = a.bstat[c * 2 + 1];
-    const float gam = a.gamma[c];
-    const float g_dg = a.dgamma[c], g_db = a.dbeta[c], g_ds = a.dslope[c];
-    const float p_old = a.accumulate_pq ? a.P[c] : 0.f, q_old = a.accumulate_pq ? a.Q[c] : 0.f;
-    double s1 = 0, t2 = 0, s3 = 0;
-    int b = lane;
-    // Eight partial rows per trip = every row of a launch with <= 512 workgroups (all of them) in ONE round trip: 24 loads in flight
-    // per lane.  This kernel sits between two convolutions of the critical chain while the other embedder's kernels keep the memory system
-    // busy: each dependent trip cost a full loaded-latency round trip (fp32 mode: 25 us per launch with two trips, 132 launches per step).
-    for (; b < a.nblk; b += 512) {
-        double v[8][3];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int bb = b + 64 * i;
-            const double* p = a.part + ((long)(bb < a.nblk ? bb : b) * a.C + c) * 3;
-            v[i][0] = p[0]; v[i][1] = p[1]; v[i][2] = p[2];
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-            if (b + 64 * i < a.nblk) { s1 += v[i][0]; t2 += v[i][1]; s3 += v[i][2]; }
-    }
-    s1 = wave_sum(s1); t2 = wave_sum(t2); s3 = wave_sum(s3);
-    if (lane != 0) return;
-    const double r = 1.0 / sqrt(var + (double)a.eps);
-    const double dgamma = r * (t2 - mu * s1);
-    const double sc = (double)gam * r;
-    const double M = (double)a.count;
-    a.dgamma[c] = g_dg + (float)dgamma;
-    a.dbeta[c] = g_db + (float)s1;
-    a.dslope[c] = g_ds + (float)s3;
-    const float Px = (float)(-sc * dgamma * r / M);
-    const float Qx = (float)(-sc * s1 / M + sc * dgamma * r * mu / M);
-    a.P[c] = p_old + Px; a.Q[c] = q_old + Qx;
-}
-__global__ __launch_bounds__(256) void k_bn_bwd_link(const BnBwdLinkArgs a) { bn_bwd_link_body(a, blockIdx.x); }
+__global__ __launch_bounds__(256) void k_bn_bwd_link(const BnBwdLinkArgs a) { bn_bwd_link_body(a, blockIdx.x, gridDim.x); }
 
 // global-average head backward: dz = dF/HW on every pixel, then PReLU+BN backward bookkeeping of final_norm
 constexpr int HP_CJ = 4;     // up to 1024 channels with 256 threads
@@ -185,79 +143,105 @@ __global__ __launch_bounds__(256) void k_eff_mat(const EffMatArgs a, int wlog) {
     }
 }
 
-// dst[i] += sum_s slab[s*stride + i]: block = 64 columns x 4 slab lanes; grid.y splits the slabs (<= 16 atomics per element);
-// grid.z selects one of two independent jobs (e.g. a weight-gradient slab and the bias column sums of the same layer: one
-// launch instead of two -- these launches sit at the ~5 us dispatch floor)
-__device__ __forceinline__ void slab_reduce_body(const SlabJob& j, float (*red)[256]) {
-    if (j.count <= 0) return;
-    const int cx = threadIdx.x & 63, sg = threadIdx.x >> 6;
-    if ((int)blockIdx.y >= j.ny) return;                                               // uniform per workgroup
-    const int s0 = blockIdx.y * j.per_y, s1 = min(j.nslab, s0 + j.per_y);
-    const float* __restrict__ slab = j.slab;
-    if (j.v4) {
-        // 16 B per lane: a block covers 128 columns with eight slab lanes, eight loads in flight per thread.  (Round 4: the scalar version
-        // moved the 37.7 MB slabs of a 3x3 weight gradient at 0.7 TB/s.  Round 5: with the slabs split over up to 16 y-slices the launch
-        // spent its time in the fp32 atomics that merge the slices -- 557 K of them per dense layer; one y-slice per job (every launch of
-        // the DenseNet plan: <= 512 slabs) adds into dst directly, in a fixed order: 19.40 -> 19.17 ms per step; the A/B script, tools/r05_ab2.sh, is removed, see git history.)
-        const int cl = threadIdx.x & 31, sl = threadIdx.x >> 5;
-        const long i = ((long)blockIdx.x * 32 + cl) * 4;
-        if ((long)blockIdx.x * 128 >= j.count) return;
-        typedef __attribute__((ext_vector_type(4))) float f4;
-        f4 acc[8];
+// dst[i] += sum_s slab[s*stride + i], up to four independent jobs (and one BatchNorm backward link) in one launch.
+//
+// Grid: 1-D.  Each job owns a contiguous range of workgroups (SlabFirst = the prefix offsets), the link the range behind the
+// last job: every workgroup of the launch has work.  The split is by bytes, not by columns: a workgroup owns SR_COLS = 32 columns (one
+// 128-B line of every slab row) and SR_LANES = 32 slab lanes -- thread = (lane sl = tid / 8, 16-B column group cg = tid % 8).  Lane sl
+// sums the slabs sl, sl + 32, sl + 64, ... eight at a time (eight 16-B loads in flight per thread; 512 slabs = two trips), so a full-size
+// job of the DenseNet plan is 512 (1x1, ldc = 128) to 1 152 (3x3) workgroups on 256 CUs where the column-major split had 128 to 288.
+//
+// Summation order of every output element, a function of nslab alone (not of count, stride, alignment or the other jobs of the launch):
+//   lane partial   p[sl] = ((a0 + a1) + (a2 + a3)) + ((a4 + a5) + (a6 + a7)),  a[q] = slabs sl + 32 * (8 * t + q) in ascending t
+//   wave           the eight lanes of a wave by three exchange steps: lane distance 1, 2, 4
+//   workgroup      the four wave sums through LDS: (w0 + w1) + (w2 + w3)
+//   dst            one read-add-write by the thread that holds the sum
+// No job ends in an atomic.  Slab rows that are not 16-B aligned, counts that are no multiple of 4 and unaligned dst take scalar accesses
+// in the same order; columns in [count, stride) and rows >= nslab are never read.
+// The shape follows from: at most two trips at 512 slabs, at least 2 x 256 workgroups for the smallest full-size job, 128 B contiguous per
+// row access, 256 threads.  Measured: 71 MB in 19.7 us (3.6 TB/s; 23.0 us before); no alternative shape has been timed
+// (profiles/helper_launches.md).
+constexpr int SR_COLS = 32, SR_LANES = 32, SR_THREADS = SR_COLS / 4 * SR_LANES;
+struct SlabFirst { int f1, f2, f3, f4; };      // job i = workgroups [f(i), f(i+1)), f0 = 0; the link from f4 on
+struct SlabLaunch { SlabJob j[4]; SlabFirst F; };      // host side
+typedef __attribute__((ext_vector_type(4))) float sr_f4;
+
+// columns [0, nv) of a row chunk, zeros behind them; VEC: one 16-B load, else nv scalar loads (a column past nv re-reads column 0: no
+// branch between the loads, nothing outside the job's columns is touched)
+template <bool VEC>
+__device__ __forceinline__ sr_f4 slab_row4(const float* p, int nv) {
+    if constexpr (VEC) return *reinterpret_cast<const sr_f4*>(p);
+    const sr_f4 v{p[0], p[nv > 1 ? 1 : 0], p[nv > 2 ? 2 : 0], p[nv > 3 ? 3 : 0]};
+    return sr_f4{v.x, nv > 1 ? v.y : 0.f, nv > 2 ? v.z : 0.f, nv > 3 ? v.w : 0.f};
+}
+// lane sl's slabs sl, sl + SR_LANES, ... -> eight partial sums, eight loads in flight per trip
+template <bool VEC>
+__device__ __forceinline__ void slab_lane_sums(const SlabJob& j, const float* __restrict__ base, int sl, int nv, sr_f4 (&acc)[8]) {
+    for (int k = sl; k < j.nslab; k += 8 * SR_LANES) {
+        sr_f4 v[8];
 #pragma unroll
-        for (int q = 0; q < 8; ++q) acc[q] = f4{0.f, 0.f, 0.f, 0.f};
-        if (i < j.count) {
-            const float* base = slab + i;
-            int k = s0 + sl;
-            for (; k + 56 < s1; k += 64) {
+        for (int q = 0; q < 8; ++q) {                          // a row past the end is replaced by this lane's row k and not added
+            const int kk = k + q * SR_LANES;
+            v[q] = slab_row4<VEC>(base + (long)(kk < j.nslab ? kk : k) * j.stride, nv);
+        }
 #pragma unroll
-                for (int q = 0; q < 8; ++q) acc[q] += *reinterpret_cast<const f4*>(base + (long)(k + 8 * q) * j.stride);
-            }
-            for (; k < s1; k += 8) acc[0] += *reinterpret_cast<const f4*>(base + (long)k * j.stride);
-        }
-        f4 (*red4)[32] = reinterpret_cast<f4 (*)[32]>(&red[0][0]);         // [8][32] f4 = the 4 x 256 floats of `red`
-        red4[sl][cl] = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
-        __syncthreads();
-        if (sl == 0 && i < j.count) {
-            const f4 v = ((red4[0][cl] + red4[1][cl]) + (red4[2][cl] + red4[3][cl])) + ((red4[4][cl] + red4[5][cl]) + (red4[6][cl] + red4[7][cl]));
-            if (j.ny == 1) { f4* d = reinterpret_cast<f4*>(j.dst + i); *d = *d + v; }
-            else { atomicAdd(j.dst + i, v.x); atomicAdd(j.dst + i + 1, v.y); atomicAdd(j.dst + i + 2, v.z); atomicAdd(j.dst + i + 3, v.w); }
-        }
-        return;
+        for (int q = 0; q < 8; ++q)
+            if (k + q * SR_LANES < j.nslab) acc[q] += v[q];
     }
-    const long i = (long)blockIdx.x * 64 + cx;
-    if ((long)blockIdx.x * 64 >= j.count) return;
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-    if (i < j.count) {
-        int k = s0 + sg;
-        for (; k + 12 < s1; k += 16) {
-            a0 += slab[(long)k * j.stride + i]; a1 += slab[(long)(k + 4) * j.stride + i];
-            a2 += slab[(long)(k + 8) * j.stride + i]; a3 += slab[(long)(k + 12) * j.stride + i];
-        }
-        for (; k < s1; k += 4) a0 += slab[(long)k * j.stride + i];
+}
+__device__ __forceinline__ void slab_reduce_body(const SlabJob& j, int wg, sr_f4 (*red)[SR_COLS / 4]) {
+    constexpr int CG = SR_COLS / 4;
+    static_assert(SR_THREADS == 256 && CG == 8, "the wave exchange and the four-wave tree below are written for 32 columns x 32 lanes");
+    const int cg = threadIdx.x % CG, sl = threadIdx.x / CG;
+    const long i = ((long)wg * CG + cg) * 4;
+    const long left = j.count - i;
+    const int nv = left >= 4 ? 4 : (int)left;                   // columns of this thread (<= 0: none)
+    sr_f4 acc[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) acc[q] = sr_f4{0.f, 0.f, 0.f, 0.f};
+    if (nv > 0) {
+        if (j.v4 && nv == 4) slab_lane_sums<true>(j, j.slab + i, sl, nv, acc);
+        else slab_lane_sums<false>(j, j.slab + i, sl, nv, acc);
     }
-    red[sg][cx] = (a0 + a1) + (a2 + a3);
+    sr_f4 s = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
+#pragma unroll
+    for (int d = CG; d < 64; d <<= 1) {                         // the lanes of a wave (32 x 32: thread distance 8, 16, 32)
+        s.x += __shfl_xor(s.x, d); s.y += __shfl_xor(s.y, d); s.z += __shfl_xor(s.z, d); s.w += __shfl_xor(s.w, d);
+    }
+    if ((threadIdx.x & 63) < CG) red[threadIdx.x >> 6][cg] = s;
     __syncthreads();
-    if (sg == 0 && i < j.count) {
-        const float v = (red[0][cx] + red[1][cx]) + (red[2][cx] + red[3][cx]);
-        if (j.ny == 1) j.dst[i] += v; else atomicAdd(j.dst + i, v);
+    if (threadIdx.x < CG && nv > 0) {
+        const sr_f4 v = (red[0][cg] + red[1][cg]) + (red[2][cg] + red[3][cg]);
+        float* d = j.dst + i;
+        if (j.dv4 && nv == 4) { sr_f4* d4 = reinterpret_cast<sr_f4*>(d); *d4 = *d4 + v; }
+        else {
+            d[0] += v.x;
+            if (nv > 1) d[1] += v.y;
+            if (nv > 2) d[2] += v.z;
+            if (nv > 3) d[3] += v.w;
+        }
     }
 }
-__global__ __launch_bounds__(256) void k_slab_reduce(const SlabJob j0, const SlabJob j1, const SlabJob j2, const SlabJob j3) {
-    __shared__ __attribute__((aligned(16))) float red[4][256];
-    slab_reduce_body(blockIdx.z == 0 ? j0 : blockIdx.z == 1 ? j1 : blockIdx.z == 2 ? j2 : j3, red);
+// (the jobs are separate kernel arguments and every field is picked by a select: as one record, or picked by reference, the compiler
+// indexes a private copy of the arguments -- 216 B of scratch per lane)
+#define SR_JOBS const SlabJob j0, const SlabJob j1, const SlabJob j2, const SlabJob j3
+__device__ __forceinline__ void slab_reduce_pick(const SlabJob& j0, const SlabJob& j1, const SlabJob& j2, const SlabJob& j3, const SlabFirst& F, int b) {
+    __shared__ sr_f4 red[SR_THREADS / 64][SR_COLS / 4];
+    const int z = (b >= F.f1) + (b >= F.f2) + (b >= F.f3);
+    const int f = z == 0 ? 0 : z == 1 ? F.f1 : z == 2 ? F.f2 : F.f3;
+#define SR_PICK(m) (z == 0 ? j0.m : z == 1 ? j1.m : z == 2 ? j2.m : j3.m)
+    const SlabJob j{SR_PICK(slab), SR_PICK(dst), SR_PICK(nslab), SR_PICK(count), SR_PICK(stride), SR_PICK(v4), SR_PICK(dv4)};
+#undef SR_PICK
+    slab_reduce_body(j, b - f, red);
 }
-// The same launch with one more z-plane that runs a BatchNorm backward link (round 5): after the fused 1x1 backward kernel both its slab
-// reduction and the norm1 link are ~5 us latency-floor launches on the critical chain, independent of each other (different inputs, different
-// outputs) -- one launch instead of two per dense layer.  Plane `nz` = the link: its first cdiv(C, 4) workgroups of y-slice 0.
-__global__ __launch_bounds__(256) void k_slab_reduce_link(const SlabJob j0, const SlabJob j1, const SlabJob j2, const SlabJob j3, int nz,
-                                                          const BnBwdLinkArgs link) {
-    __shared__ __attribute__((aligned(16))) float red[4][256];
-    if ((int)blockIdx.z == nz) {
-        if (blockIdx.y == 0) bn_bwd_link_body(link, blockIdx.x);
-        return;
-    }
-    slab_reduce_body(blockIdx.z == 0 ? j0 : blockIdx.z == 1 ? j1 : blockIdx.z == 2 ? j2 : j3, red);
+__global__ __launch_bounds__(SR_THREADS) void k_slab_reduce(SR_JOBS, const SlabFirst F) { slab_reduce_pick(j0, j1, j2, j3, F, blockIdx.x); }
+// The same launch with a BatchNorm backward link behind the last job (round 5): after the fused 1x1 backward kernel both its slab
+// reduction and the norm1 link are latency-floor launches on the critical chain, independent of each other (different inputs, different
+// outputs) -- one launch instead of two per dense layer.  The link takes the last cdiv(C, 4) workgroups.
+__global__ __launch_bounds__(SR_THREADS) void k_slab_reduce_link(SR_JOBS, const SlabFirst F, const BnBwdLinkArgs link) {
+    const int b = blockIdx.x;
+    if (b >= F.f4) { bn_bwd_link_body(link, b - F.f4, gridDim.x - F.f4); return; }
+    slab_reduce_pick(j0, j1, j2, j3, F, b);
 }
 
 __global__ void k_unpack(const UnpackDesc* descs) {
@@ -273,7 +257,14 @@ __global__ void k_unpack(const UnpackDesc* descs) {
 
 }  // namespace
 
+#ifdef TCVN_DEBUG_KNOBS
+static long g_link_launches = 0;      // validation build: k_bn_bwd_link launches so far (tests assert which links ride in other launches)
+extern "C" long tcvn_debug_link_launches(void) { return g_link_launches; }
+#endif
 int bn_bwd_link(const BnBwdLinkArgs& a, hipStream_t st) {
+#ifdef TCVN_DEBUG_KNOBS
+    ++g_link_launches;
+#endif
     hipLaunchKernelGGL(k_bn_bwd_link, dim3(cdiv(a.C, 4)), dim3(256), 0, st, a);
     TCVN_LAUNCH_CHECK();
     return 0;
@@ -322,39 +313,42 @@ int eff_materialize_bf16(const EffMatArgs& a, hipStream_t st) {
 }
 
 SlabJob slab_job(const float* slab, int nslab, long count, float* dst, long stride) {
-    SlabJob j{slab, dst, nslab, count, stride > 0 ? stride : count, 1, 1, 0};
+    SlabJob j{slab, dst, nslab, count, stride > 0 ? stride : count, 0, 0};
     if (count <= 0 || nslab <= 0) { j.count = 0; return j; }
-    j.v4 = (count % 4 == 0 && j.stride % 4 == 0 && (reinterpret_cast<uintptr_t>(slab) & 15) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0 && count >= 1024) ? 1 : 0;
-    int ny = cdiv(nslab, j.v4 ? 512 : 64);           // 16-B path: one y-slice up to 512 slabs (no atomics; see slab_reduce_body)
-    if (ny > 16) ny = 16;
-    j.ny = ny; j.per_y = cdiv(nslab, ny);
+    j.v4 = ((nslab == 1 || j.stride % 4 == 0) && (reinterpret_cast<uintptr_t>(slab) & 15) == 0) ? 1 : 0;
+    j.dv4 = (reinterpret_cast<uintptr_t>(dst) & 15) == 0 ? 1 : 0;
     return j;
 }
-// up to four independent jobs in one launch (grid.z); empty jobs (count == 0) are skipped
-int slab_reduce4(const SlabJob* jobs, int n, hipStream_t st) {
-    SlabJob j[4] = {};
-    long gmax = 0; int nymax = 1, nz = 0;
-    for (int i = 0; i < n && i < 4; ++i) {
-        if (jobs[i].count <= 0) continue;
-        j[nz++] = jobs[i];
-        const long g = cdiv(jobs[i].count, jobs[i].v4 ? 128 : 64);
-        gmax = g > gmax ? g : gmax; nymax = jobs[i].ny > nymax ? jobs[i].ny : nymax;
+namespace {
+// workgroup ranges of up to four jobs; empty jobs (count == 0) get an empty range.  Returns the number of workgroups, -1 when it exceeds the grid limit.
+long slab_launch(const SlabJob* jobs, int n, SlabLaunch& L) {
+    L = SlabLaunch{};
+    int* const first[5] = {nullptr, &L.F.f1, &L.F.f2, &L.F.f3, &L.F.f4};
+    long total = 0;
+    for (int i = 0; i < 4; ++i) {
+        if (i < n && jobs[i].count > 0) { L.j[i] = jobs[i]; total += cdiv(jobs[i].count, (long)SR_COLS); }
+        if (total > (1L << 30)) return -1;
+        *first[i + 1] = (int)total;
     }
-    if (nz == 0) return 0;
-    hipLaunchKernelGGL(k_slab_reduce, dim3((unsigned)gmax, nymax, nz), dim3(256), 0, st, j[0], j[1], j[2], j[3]);
+    return total;
+}
+}  // namespace
+// up to four independent jobs in one launch; empty jobs (count == 0) are skipped
+int slab_reduce4(const SlabJob* jobs, int n, hipStream_t st) {
+    SlabLaunch L;
+    const long total = slab_launch(jobs, n, L);
+    if (total < 0) return -2;
+    if (total == 0) return 0;
+    hipLaunchKernelGGL(k_slab_reduce, dim3((unsigned)total), dim3(SR_THREADS), 0, st, L.j[0], L.j[1], L.j[2], L.j[3], L.F);
     TCVN_LAUNCH_CHECK();
     return 0;
 }
 int slab_reduce4_link(const SlabJob* jobs, int n, const BnBwdLinkArgs& link, hipStream_t st) {
-    SlabJob j[4] = {};
-    long gmax = cdiv(link.C, 4); int nymax = 1, nz = 0;
-    for (int i = 0; i < n && i < 4; ++i) {
-        if (jobs[i].count <= 0) continue;
-        j[nz++] = jobs[i];
-        const long g = cdiv(jobs[i].count, jobs[i].v4 ? 128 : 64);
-        gmax = g > gmax ? g : gmax; nymax = jobs[i].ny > nymax ? jobs[i].ny : nymax;
-    }
-    hipLaunchKernelGGL(k_slab_reduce_link, dim3((unsigned)gmax, nymax, nz + 1), dim3(256), 0, st, j[0], j[1], j[2], j[3], nz, link);
+    SlabLaunch L;
+    const long total = slab_launch(jobs, n, L);
+    if (total < 0) return -2;
+    if (total == 0) return bn_bwd_link(link, st);
+    hipLaunchKernelGGL(k_slab_reduce_link, dim3((unsigned)(total + cdiv(link.C, SR_THREADS / 64))), dim3(SR_THREADS), 0, st, L.j[0], L.j[1], L.j[2], L.j[3], L.F, link);
     TCVN_LAUNCH_CHECK();
     return 0;
 }
@@ -375,3 +369,21 @@ int unpack_wgrads(const UnpackDesc* d_descs, int n, hipStream_t st) {
 }
 
 }  // namespace tcvn
+
+#ifdef TCVN_DEBUG_KNOBS
+// Validation build: the slab reducer alone, on the caller's device buffers (tests/test_slab_reduce_gpu.py).  n <= 4 jobs; link_C > 0
+// adds a BatchNorm backward link to the launch.
+extern "C" int tcvn_debug_slab_reduce(int n, const float* const* slab, const int* nslab, const long long* count, const long long* stride,
+                                      float* const* dst, int link_C, int link_nblk, const double* part, const double* bstat,
+                                      long long link_count, float eps, const float* gamma, float* dgamma, float* dbeta, float* dslope, float* P,
+                                      float* Q, int accumulate_pq, void* stream) {
+    using namespace tcvn;
+    if (n < 0 || n > 4) return -1;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    SlabJob jobs[4] = {};
+    for (int i = 0; i < n; ++i) jobs[i] = slab_job(slab[i], nslab[i], count[i], dst[i], stride[i]);
+    if (link_C <= 0) return slab_reduce4(jobs, n, st);
+    const BnBwdLinkArgs la{part, link_nblk, link_C, bstat, (long)link_count, eps, gamma, dgamma, dbeta, dslope, P, Q, accumulate_pq};
+    return slab_reduce4_link(jobs, n, la, st);
+}
+#endif

@@ -16,6 +16,7 @@
 //   TCVN_NO_FWD1_FUSE       1x1 forward: k_act_bf16 + the NT GEMM instead of the fused kernel
 //   TCVN_NO_BWD1_FUSE       1x1 forward and backward: the unfused kernels
 //   TCVN_NO_LF              the BatchNorm link kernels instead of link-free statistics
+//   TCVN_LINK_LAUNCH        dense layers' backward: the norm2 link as a launch of its own instead of riding in the 3x3 weight gradient
 //   TCVN_DENSE_STEM, TCVN_SPARSE_STEM_TRAIN, TCVN_NO_STEM_SKIP, TCVN_POOL0_BWD_FLAT, TCVN_STEM_FWD_V1    stem variants
 #ifdef TCVN_DEBUG_KNOBS
 #define TCVN_KNOB_SET(name) (getenv(name) != nullptr)

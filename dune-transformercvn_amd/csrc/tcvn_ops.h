@@ -149,7 +149,17 @@ int conv3x3_dgrad_tile_nblk(const ConvDgradArgs& a);
 int conv3x3_dgrad_tile(const ConvDgradArgs& a, hipStream_t st);
 
 // one reduction job: dst[i] += sum_{s < nslab} slab[s*stride + i], i < count
-struct SlabJob { const float* slab; float* dst; int nslab; long count, stride; int ny, per_y; int v4; };   // v4: 16-B loads (count, stride multiples of 4, 16-B aligned)
+// (k_slab_reduce, elementwise_bwd.hip: a workgroup owns 32 columns, the sum of every element runs in an order fixed by nslab alone, no atomics)
+struct SlabJob { const float* slab; float* dst; int nslab; long count, stride; int v4, dv4; };   // v4 / dv4: slab rows / dst take 16-B accesses
+// Reduce the backward partials of one BatchNorm, emit parameter gradients and the (P, Q) coefficients of its input.
+struct BnBwdLinkArgs {
+    const double* part; int nblk; int C;
+    const double* bstat;                 // (mean, biased var) of the BN input channels
+    long count; float eps;
+    const float* gamma;
+    float *dgamma, *dbeta, *dslope;      // accumulated
+    float *P, *Q; int accumulate_pq;
+};
 // dWk[n][k] += sum_m eff(m, n) * a(m, k)   (a = the forward A operand, regenerated), dbias[n] += sum_m eff(m, n)
 struct ConvWgradArgs {
     int mode;
@@ -160,6 +170,8 @@ struct ConvWgradArgs {
     int nfast;        // 1: dWk is laid out [k][32] (out-channel fastest) and the padded-tile kernel must be used (bf16 3x3)
     SlabJob* deferred;   // optional [2] (padded-tile kernel): its slab reductions (weights, bias) are returned as jobs instead of being launched --
                          // the caller folds them into a later reduction launch; the slab must stay untouched until then
+    BnBwdLinkArgs link;  // optional (padded-tile kernel; set when link.part != nullptr): a BatchNorm backward link that neither reads nor feeds
+                         // this convolution rides in the launch (bn_link.h) -- the workgroups with one tile fewer than the others run it
 };
 int conv_wgrad(const ConvWgradArgs& a, hipStream_t st);
 bool gemm_tn_f32_ok(const ConvWgradArgs& a);        // gemm_tn_f32.hip: fp32 1x1 weight gradient over an already activated operand (transitions, parity mode)
@@ -185,15 +197,6 @@ bool conv3x3_wgrad_f32_ok(const ConvWgradArgs& a);
 int conv3x3_wgrad_f32(const ConvWgradArgs& a, hipStream_t st);
 int conv3x3_wgrad_tile(const ConvWgradArgs& a, hipStream_t st);
 
-// Reduce the backward partials of one BatchNorm, emit parameter gradients and the (P, Q) coefficients of its input.
-struct BnBwdLinkArgs {
-    const double* part; int nblk; int C;
-    const double* bstat;                 // (mean, biased var) of the BN input channels
-    long count; float eps;
-    const float* gamma;
-    float *dgamma, *dbeta, *dslope;      // accumulated
-    float *P, *Q; int accumulate_pq;
-};
 int bn_bwd_link(const BnBwdLinkArgs& a, hipStream_t st);
 int slab_reduce4_link(const SlabJob* jobs, int n, const BnBwdLinkArgs& link, hipStream_t st);   // up to four slab reductions + one link in ONE launch
 
