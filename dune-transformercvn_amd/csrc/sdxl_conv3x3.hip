@@ -618,7 +618,7 @@ int launch_c64(const SConv& g, const void* In, const void* W, const float* bias,
 // ---------------------------------------------------------------------------------------------------------------------
 // Weight gradient: dW[n][tap*64 + c] = sum over positions p of In[p + shift(tap)][c] * dOut[p][n].
 // The contraction runs over pixels, i.e. over the ROW index of both pixel-major LDS images, so both MFMA operands are read
-// transposed with ds_read_b64_tr_b16 (lane roles as in conv3x3_tile.hip, checked by tools/micro/tr_read_test.hip): per
+// transposed with ds_read_b64_tr_b16 (lane roles as in conv3x3_wgrad_tile.hip, checked by tools/micro/tr_read_test.hip): per
 // 16-position k-step (half a tile row) a wave reads one dOut fragment and nine shifted In fragments.  A wave owns one
 // (32 c x 32 n) quarter of all nine taps for the whole launch (144 accumulator registers); the workgroup's partial
 // gradient leaves as one slab in the kernel layout [n][576], summed by k_slab_reduce.  Pixel rows are 128 B, 16-B chunks

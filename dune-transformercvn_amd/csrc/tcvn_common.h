@@ -10,7 +10,7 @@
 // compare kernel variants).  The default library reads no environment variable: TCVN_KNOB_SET folds to false and the compiler removes
 // the code behind it.  Every switch is set by some test:
 //   TCVN_DISABLE_TILE       generic kernels instead of the bf16 tile / GEMM paths
-//   TCVN_FWD_STRIP          3x3 forward: the strip kernel instead of the pair / ring kernels
+//   TCVN_FWD_STRIP          3x3 forward: the strip kernel (compiled in this build only) instead of the pair kernel
 //   TCVN_DGRAD3_ANY_SIZE    3x3 data gradient: the consecutive-tile kernel at any size
 //   TCVN_NO_ACT_FUSE        3x3: the materialised activation instead of the in-LDS one
 //   TCVN_NO_FWD1_FUSE       1x1 forward: k_act_bf16 + the NT GEMM instead of the fused kernel

@@ -39,13 +39,13 @@ struct ConvFwdArgs {
                                      // leaving as a partial row in `part`
 };
 int conv_fwd(const ConvFwdArgs& a, hipStream_t st);
-enum Conv3x3Fwd { CONV3X3_FWD_NONE = 0, CONV3X3_FWD_STRIP, CONV3X3_FWD_RING, CONV3X3_FWD_PAIR };
+enum Conv3x3Fwd { CONV3X3_FWD_NONE = 0, CONV3X3_FWD_STRIP, CONV3X3_FWD_PAIR };      // STRIP: validation build with TCVN_FWD_STRIP only
 Conv3x3Fwd conv3x3_fwd_kernel(const ConvFwdArgs& a);   // the bf16 padded-tile kernel conv_fwd(a) runs (NONE: another path); only PAIR honours act_fused / lf / isum_out / keep_out
 bool conv3x3_act_fusable(const ConvFwdArgs& a);       // true when both the forward kernel conv_fwd(a) would run and the weight-gradient tile kernel of the
                                                       // same layer can take the raw map (ConvFwdArgs::act_fused)
 int conv_fwd_grid(int M);            // number of M-blocks of the generic kernels for M rows (<= 512)
 int conv_fwd_nblk(const ConvFwdArgs& a);   // grid.x (== rows of `part`) conv_fwd will use for these arguments (<= 512)
-// bf16 3x3 fast path on padded LDS tiles (conv3x3_tile.hip)
+// bf16 3x3 fast path on padded LDS tiles (conv3x3_fwd_tile.hip; its gradients: conv3x3_wgrad_tile.hip, conv3x3_dgrad_tile.hip)
 bool conv3x3_tile_ok(const ConvFwdArgs& a);
 int conv3x3_tile_nblk(const ConvFwdArgs& a);
 int conv3x3_fwd_tile(const ConvFwdArgs& a, hipStream_t st);

@@ -1,4 +1,4 @@
-"""The dense layers' norm2 backward link riding in the 3x3 weight-gradient launch (csrc/conv3x3_tile.hip, bn_link.h) against the same
+"""The dense layers' norm2 backward link riding in the 3x3 weight-gradient launch (k_conv3x3_wgrad_bf16 in csrc/conv3x3_wgrad_tile.hip, bn_link.h) against the same
 link as a launch of its own (TCVN_LINK_LAUNCH on the validation build), and run-to-run reproducibility of the dense layers' gradients.
 
 Golden case tutorial_b2p4, bf16, train mode, dropout 0.1; both sides run on the validation build, one child process each.  The rider

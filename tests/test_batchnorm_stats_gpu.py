@@ -10,9 +10,9 @@ bn_lf.h), bf16 with the link kernels (TCVN_NO_LF on the validation build, ONE ch
 Gates (all from the arithmetic; u = 2^-24):
   * (mean, E[x^2]) rows: |mean - ref| <= 1e-9 s + W 2^-25 / n and |E2 - ref| <= 1e-9 s^2 + W 2^-17 / n (s = sqrt(ref E2)): the fixed-point
     resolution of one lf_add times the W = 1024 workgroups that add per channel at most (grid caps: 768 in fwd1x1_fused_nblk,
-    fwd1x1_fused.hip:439; 256 in tile_grid, conv3x3_tile.hip:1687).  PLUS one rounding step that bound leaves out: the producers sum a
+    fwd1x1_fused.hip:439; 256 in tile_grid, tile3x3.h).  PLUS one rounding step that bound leaves out: the producers sum a
     lane's values in fp32 before they widen to double -- the fused 1x1 kernels four rows per 64-row tile and workgroup
-    (fwd1x1_fused.hip:195-201, :387-393), the 3x3 pair kernel the 16 positions of one epilogue (conv3x3_tile.hip:484-502) -- which costs
+    (fwd1x1_fused.hip:195-201, :387-393), the 3x3 pair kernel the 16 positions of one epilogue (epilogue_impl of k_conv3x3_fwd_pair_bf16, conv3x3_fwd_tile.hip) -- which costs
     at most (L - 1) u mean|x| on the mean and L u E2 on E2 for an fp32 chain of L values.  The other producers (_chains):
       - k_pool0 / k_pool0_vec64 (elementwise.hip:145, :405), k_rows_bn_fwd (rows.hip:69), the generic k_conv_fwd (StatAcc is double for
         both types, conv_tile.h:160-161) and k_conv3x3_fwd_f32 (conv3x3_f32.hip:279) widen every value to double first: L = 1, no term;

@@ -270,9 +270,9 @@ result = dict(out=out, taps=taps, grads=grads)
 
 
 def test_bf16_fallback_variants_match_default_variants():
-    """The strip forward kernel (TCVN_FWD_STRIP: used when a map is wider than the 512-row LDS ring allows) and the flat pool0
-    backward (TCVN_POOL0_BWD_FLAT) against the default ring / tiled variants in a separate process: same arithmetic, different
-    staging, so the forward must agree to bf16-rounding level."""
+    """The strip forward kernel (TCVN_FWD_STRIP: compiled in the validation build only, an independent second implementation -- every
+    map the tile path admits runs the pair kernel) and the flat pool0 backward (TCVN_POOL0_BWD_FLAT) against the default pair /
+    tiled variants in a separate process: same arithmetic, different staging, so the forward must agree to bf16-rounding level."""
     import subprocess, sys, os
     cfg, over, batch, g = _mid_case()
     cfg = train_cfg(over)
