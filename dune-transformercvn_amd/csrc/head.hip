@@ -827,7 +827,7 @@ extern "C" int tcvn_linear_backward(const float* dy, int64_t lddy, const float* 
     if (!dy || !x || !weight || rows <= 0 || n_out <= 0 || n_in <= 0) return -1;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     int rc;
-    if (dweight && (rc = linear_bwd_dw(dy, lddy, x, ldx, dweight, dbias, rows, n_out, n_in, st))) return rc;
+    if ((dweight || dbias) && (rc = linear_bwd_dw(dy, lddy, x, ldx, dweight, dbias, rows, n_out, n_in, st))) return rc;
     if (dx && (rc = linear_bwd_dx(dy, lddy, weight, dx, lddx, rows, n_out, n_in, 0, st))) return rc;
     return 0;
 }

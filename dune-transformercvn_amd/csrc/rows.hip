@@ -184,9 +184,10 @@ __global__ __launch_bounds__(256) void k_colsum_acc(const float* dY, long lddy, 
 
 int linear_bwd_dw(const float* dY, long lddy, const float* X, long ldx, float* dW, float* db, int R, int N, int K, hipStream_t st) {
     if (R <= 0) return 0;
-    SgemmArgs a{dY, 1, lddy, X, 1, ldx, dW, (long)K, N, K, R, nullptr, 1.f, 1};
-    int rc = sgemm(a, st);
-    if (rc) return rc;
+    if (dW) {
+        SgemmArgs a{dY, 1, lddy, X, 1, ldx, dW, (long)K, N, K, R, nullptr, 1.f, 1};
+        if (int rc = sgemm(a, st)) return rc;
+    }
     if (db) {
         hipLaunchKernelGGL(k_colsum_acc, dim3(cdiv(N, 16)), dim3(256), 0, st, dY, lddy, R, N, db);
         TCVN_LAUNCH_CHECK();

@@ -25,7 +25,7 @@ static inline int linear_bwd_dx(const float* dY, long lddy, const float* W, floa
     SgemmArgs a{dY, lddy, 1, W, 1, (long)K, dX, lddx, R, K, N, nullptr, 1.f, accumulate};
     return sgemm(a, st);
 }
-// dW += dY^T X ; db += colsum(dY)
+// dW += dY^T X ; db += colsum(dY)      (dW or db may be null: that one is skipped)
 int linear_bwd_dw(const float* dY, long lddy, const float* X, long ldx, float* dW, float* db, int R, int N, int K, hipStream_t st);
 
 struct RowsBnArgs {

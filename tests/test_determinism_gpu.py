@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from golden_utils import load_case, train_cfg
+from head_utils import head_batch, head_engine, head_train_step
 from oracle import tcvn_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -65,55 +66,7 @@ def test_bf16_dense_layer_weight_gradients_are_bit_reproducible():
         assert not diff, f"repetition {rep}: {len(diff)} of {len(keys)} weight gradients differ, e.g. {diff[:3]}"
 
 
-# ---- head (token path) ---------------------------------------------------------------------------------------------------------------
-def head_engine(seed, hidden=128, heads=8, layers=2, in_dim=40, dec_dims=(32, 16), norm_first=False, dropout=0.1, bn=True, prelu=True):
-    """A bound HeadEngine with random parameters (BatchNorm weights near one, running variances positive) -> (engine, data, grads)."""
-    from transformercvn.hip.engine import HeadEngine
-    from transformercvn.hip import _lib
-    dec_dims = list(dec_dims)
-    eng = HeadEngine(hidden, heads, layers, in_dim, 4, 5, dec_dims, dec_dims[-1] if dec_dims else hidden, True, norm_first, dropout,
-                     2.0, 0.5, bn, prelu)
-    g = torch.Generator().manual_seed(seed)
-    data, grads = {}, {}
-    for name, numel, kind in eng.slots():
-        if kind == _lib.SLOT_COUNTER:
-            continue
-        t = torch.randn(numel, generator=g) * 0.1
-        if "norm" in name and name.endswith(("weight", "running_var")):
-            t = 1.0 + t.abs()
-        data[name] = t.cuda()
-        if kind == _lib.SLOT_PARAM:
-            grads[name] = torch.zeros(numel, device="cuda")
-    eng.bind(data, grads)
-    return eng, data, grads
-
-
-def head_batch(seed, counts, P, in_dim):
-    """rows [B + nP, in_dim], tok_row [B, 1 + P], event targets [B], prong targets [B, P] (-1 on padding) for the prong counts."""
-    from transformercvn.network.layers.packed_data import token_rows
-    g = torch.Generator().manual_seed(seed)
-    B, nP = len(counts), sum(counts)
-    mask = torch.arange(P).view(1, P) < torch.tensor(counts).view(B, 1)
-    rows = torch.randn(B + nP, in_dim, generator=g).cuda()
-    et = torch.randint(0, 4, (B,), generator=g).cuda()
-    pt = torch.where(mask, torch.randint(0, 5, (B, P), generator=g), torch.tensor(-1)).to(torch.int8).cuda()
-    return rows, token_rows(mask.cuda(), B), et, pt, nP
-
-
-def head_train_step(eng, grads, rows, tok_row, et, pt, nP, seed):
-    """One forward + loss + backward from zeroed gradients -> {name: tensor} of everything the step computes."""
-    for v in grads.values():
-        v.zero_()
-    B, S = tok_row.shape
-    ev, pr = eng.forward(rows, tok_row, B, S - 1, nP, True, seed)
-    losses, accs, d_ev, d_pr = eng.loss(ev, pr, et, pt)
-    d_rows = eng.backward(rows, tok_row, d_ev, d_pr)
-    torch.cuda.synchronize()
-    out = {"event_logits": ev, "prong_logits": pr, "losses": losses, "d_rows": d_rows}
-    out.update({"grad:" + k: v.clone() for k, v in grads.items()})
-    return out
-
-
+# ---- head (token path): engine, batch and step come from head_utils.py --------------------------------------------------------------
 @pytest.mark.parametrize("path", ["fused", "post_norm", "pre_norm"])
 def test_head_step_is_bit_reproducible(path):
     """rows.hip, encoder.hip, encoder_fused.hip and head.hip contain no atomic operation and the dropout masks are a function of

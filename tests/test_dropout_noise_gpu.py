@@ -8,14 +8,13 @@ distribution is comparable.  The kernels use stateless counter-based masks recom
   * the noise factor recovered from the scattered pixel map is N(0,1)*std;
   * replaying those masks / that noise in the CPU oracle reproduces the GPU logits within the 1e-3 gate and the gradients
     within the fp32 band -- which can only hold if forward and backward apply the same masks at every site."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
 
 from oracle import tcvn_oracle as O
 from golden_utils import load_case, rel_err
+from head_utils import head_site_id, head_site_keep, keep
 from model_utils import build_trainer, to_device
 from test_oracle_golden import is_noise_grad
 
@@ -25,20 +24,11 @@ EV = "network.prong_embedding.event_pixel_embedding"
 PR = "network.prong_embedding.prong_pixel_embedding"
 
 
-def keep(kind, p, seed, sid, rows, cols):
-    from transformercvn.hip._lib import lib, check
-    out = torch.empty(rows, cols, device="cuda")
-    check(lib.tcvn_dropout_keep(kind, float(p), C.c_uint64(seed), C.c_uint32(sid), rows, cols, C.c_void_p(out.data_ptr()),
-                                C.c_void_p(torch.cuda.current_stream().cuda_stream)), "dropout_keep")
-    return out
-
-
 def _provider(cfg, rt, B, P):
     """site -> keep-scale tensor in the oracle's layout, from the kernels' own generators."""
     p = cfg.dropout
     g = cfg.densenet_growth_rate
     seeds = rt.last_seeds
-    lp = "network.encoder.encoder.layers."
 
     def fn(site, shape):
         if ":dense" in site:                                      # [n, g, H, W]  <- [pixels, g]
@@ -49,16 +39,8 @@ def _provider(cfg, rt, B, P):
             return m.view(n, H, W, g).permute(0, 3, 1, 2).cpu()
         if site.endswith(":out"):
             return keep(0, p, seeds["event" if site.startswith(EV) else "prong"], 0x4000, shape[0], shape[1]).cpu()
-        if site.endswith("combined_embedding"):
-            return keep(0, p, seeds["head"], 0x5000, shape[0], shape[1]).cpu()
-        if site.startswith(lp):
-            l = int(site[len(lp):].split(":")[0])
-            kind = site.split(":")[1]
-            sid = 0x6000 + 8 * l + {"attn": 0, "sa": 1, "ffn_act": 2, "ffn": 3}[kind]
-            n = int(np.prod(shape))
-            return keep(0, p, seeds["head"], sid, n // shape[-1], shape[-1]).view(shape).cpu()
-        if site.startswith("decoder."):
-            return keep(0, p, seeds["head"], 0x7000 + int(site.split(".")[1]), shape[0], shape[1]).cpu()
+        if head_site_id(site) is not None:                        # token path: combined embedding, encoder layers, prong decoder
+            return head_site_keep(site, shape, p, seeds["head"])
         raise KeyError(site)
     return fn
 

@@ -122,3 +122,62 @@ def test_amp_grad_scaler_flow_on_the_arena_views():
     scaler.update()
     torch.cuda.synchronize()
     assert (rt.flat_param != before).float().mean().item() > 0.9 and torch.isfinite(rt.flat_param).all()
+
+
+def test_adamw_and_sumsq_against_the_float64_formula_on_a_second_grid_trip():
+    """n = 2048 * 256 + 77: the AdamW grid (at most 2048 workgroups of 256) takes a second trip of its grid-stride loop for the last 77
+    elements.  Steps 1, 2 and 1000 (the bias corrections), frozen elements scattered through the arena, clip active and inactive,
+    against the update written out in float64 from the float32 inputs and the float32-rounded hyper-parameters the kernel receives.
+    Bound: p, m and v each pass through at most ten float32 roundings (2^-24 relative each, 6e-7 in the worst case): relative L2 1e-6.
+    tcvn_grad_sumsq: one partial and 1024 partials hold the same double sum to 1e-12; out is that sum rounded to float."""
+    import numpy as np
+    from transformercvn.hip._lib import lib, check
+    n = 2048 * 256 + 77
+    gen = torch.Generator().manual_seed(11)
+    p = torch.randn(n, generator=gen).cuda()
+    m, v = torch.zeros(n, device="cuda"), torch.zeros(n, device="cuda")
+    wd = torch.where(torch.rand(n, generator=gen) < 0.5, torch.tensor(0.0213), torch.tensor(0.0))
+    frozen = torch.rand(n, generator=gen) < 0.05
+    frozen[-77:] = torch.arange(77) % 5 == 0                     # some of the second trip's elements too
+    wd[frozen] = -1.0
+    wd = wd.cuda()
+    f32 = lambda x: float(np.float32(x))
+    lr, b1, b2, eps, clip = f32(3e-3), f32(0.9), f32(0.999), f32(1e-8), 5.0
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    ss = torch.zeros(1, device="cuda")
+    p64, m64, v64 = p.double().cpu(), m.double().cpu(), v.double().cpu()
+    fz = frozen
+    for step, scale in ((1, 10.0), (2, 1e-4), (1000, 10.0), (1000, 1e-4)):       # |g| = scale * sqrt(n): clipped at 10, not at 1e-4
+        g = (torch.randn(n, generator=gen) * scale).cuda()
+        g64 = g.double().cpu()
+        want_ss = (g64 * g64).sum().item()
+        sums = {}
+        for n_partials in (1, 1024):
+            partials = torch.full((1024,), float("nan"), dtype=torch.float64, device="cuda")
+            check(lib.tcvn_grad_sumsq(_ptr(g), n, _ptr(partials), n_partials, _ptr(ss), st), "sumsq")
+            torch.cuda.synchronize()
+            assert torch.isnan(partials[n_partials:]).all()             # no partial beyond the ones asked for
+            sums[n_partials] = partials[:n_partials].cpu().sum().item()
+            assert abs(sums[n_partials] - want_ss) <= 1e-12 * want_ss, (n_partials, sums[n_partials], want_ss)
+            assert abs(ss.item() - want_ss) <= 2.0 ** -24 * want_ss * 1.01, (ss.item(), want_ss)
+        assert abs(sums[1] - sums[1024]) <= 1e-12 * want_ss
+        before = (p.clone(), m.clone(), v.clone())
+        check(lib.tcvn_adamw_step(_ptr(p), _ptr(g), _ptr(m), _ptr(v), _ptr(wd), n, lr, b1, b2, eps, step, _ptr(ss), clip, st), "adamw")
+        torch.cuda.synchronize()
+        coef = min(1.0, clip / (f32(ss.item()) ** 0.5 + 1e-6))
+        assert (coef < 1.0) == (scale == 10.0)
+        bc1, bc2 = 1.0 - b1 ** step, 1.0 - b2 ** step
+        gc = g64 * coef
+        w64 = wd.double().cpu()
+        p_new = p64 * (1.0 - lr * w64)
+        m_new = b1 * m64 + (1.0 - b1) * gc
+        v_new = b2 * v64 + (1.0 - b2) * gc * gc
+        p_new = p_new - (lr / bc1) * m_new / (v_new.sqrt() / bc2 ** 0.5 + eps)
+        p64, m64, v64 = torch.where(fz, p64, p_new), torch.where(fz, m64, m_new), torch.where(fz, v64, v_new)
+        for name, mine, ref, old in (("p", p, p64, before[0]), ("m", m, m64, before[1]), ("v", v, v64, before[2])):
+            err = ((mine.double().cpu() - ref).norm() / ref.norm()).item()
+            print(f"adamw step {step} scale {scale}: {name} rel L2 {err:.2e}")
+            assert err <= 1e-6, (step, scale, name, err)
+            assert torch.equal(mine[fz.cuda()].view(torch.int32), old[fz.cuda()].view(torch.int32)), (step, name)
+        # carry the float32 state forward: the next step's reference starts from what the kernel holds (errors do not compound)
+        p64, m64, v64 = p.double().cpu(), m.double().cpu(), v.double().cpu()
