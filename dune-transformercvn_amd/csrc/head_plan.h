@@ -33,6 +33,12 @@ struct HeadStep {
 enum class EncPath { FUSED, POST_NORM, PRE_NORM };
 struct DecIn { const float* x; float* dx; int w; };         // input rows of a decoder layer, where their gradient goes, and their width
 
+// Workspace offsets handed out in order, each rounded up to 256 bytes
+struct Bump {
+    long off = 0;
+    long take(long bytes) { long o = off; off += round_up(bytes, 256); return o; }
+};
+
 struct HeadPlan {
     tcvn_head_cfg cfg;
     std::vector<Slot> slots;
@@ -74,3 +80,10 @@ struct HeadPlan {
 };
 
 }  // namespace tcvn
+
+// The handle of the C ABI (head.hip: plan, stages, loss, backward; head_explain.hip: the explanation scans)
+struct tcvn_head {
+    tcvn::HeadPlan plan;
+    int last_np = 0, last_b = 0, last_p = -1;      // shape of the last forward / encode: what tcvn_head_attention may export
+    explicit tcvn_head(const tcvn_head_cfg& c) : plan(c) {}
+};

@@ -1,6 +1,6 @@
 // Coarse-to-fine occlusion maps (forward only): which variants of one level are refined, which tiles of a level were evaluated, which
 // cells of the finest grid hold a hit, and the final map painted from the levels' stored heat values.  The variant list of a refined
-// level itself is built in occlude.hip (k_occ_count_kept in front of the unchanged k_occ_compact / k_occ_build).
+// level itself is built in occlude.hip (k_occ_count with the parent level's keep_map in front of the same list and build kernels).
 // The only atomic is an integer atomicMax on the bit pattern of a non-negative float: every result is deterministic.
 #include "../../include/tcvn_hip.h"
 #include "tcvn_common.h"

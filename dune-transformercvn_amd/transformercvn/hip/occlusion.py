@@ -112,31 +112,37 @@ def parse_target(target, B: int, Ce: int):
     return _lib.OCC_TARGET_EVENT, classes
 
 
+def _compared_rows(ev: Tensor, pr: Tensor, var_ev: Tensor, var_pr: Tensor, index: Tensor, target, what: str):
+    """What heatmap and curve_and_auc prepare alike: the base logits ev [B, Ce] / pr [B, P, Cp], the variants' var_ev [V, Ce] / var_pr
+    [V, P, Cp] and index [V, 4] -> (B, P, Ce, Cp, V, TCVN_OCC_TARGET_*, None or the int32 [B] classes on the device).  ValueError for a
+    bad target, then the GPU-only guard, then dtype, contiguity, device and shapes."""
+    B, Ce = ev.shape
+    P, Cp = pr.shape[1], pr.shape[2]
+    mode, classes = parse_target(target, B, Ce)
+    _gpu_only(ev, what)
+    assert all(t.dtype == torch.float32 and t.is_contiguous() and t.device == ev.device for t in (ev, pr, var_ev, var_pr))
+    assert index.dtype == torch.int32 and index.is_contiguous() and index.device == ev.device and index.shape[1] == 4
+    V = index.shape[0]
+    assert var_ev.shape == (V, Ce) and var_pr.shape == (V, P, Cp)
+    if classes is not None:
+        classes = classes.to(ev.device, torch.int32).contiguous()
+    return B, P, Ce, Cp, V, mode, classes
+
+
 def heatmap(result: OcclusionResult, target: Union[str, int, Tensor] = "event") -> Tensor:
     """float32 [B, 1 + P, Ht, Wt]: softmax(base)[c] - softmax(occluded)[c] at every variant's position, exactly 0 at tiles without
     hits and at padded prong slots.  target "event": c = each event's predicted event class, from the event logits; an int or a [B]
     integer tensor names the class instead.  target "prong": for s >= 1, c = the predicted class of prong slot s - 1, from the prong
     logits of that slot (how much this region of the prong's map supports the prong's own label); row s = 0 is 0."""
-    ev, pr = result.event_logits, result.prong_logits
-    B, Ce = ev.shape
-    P, Cp = pr.shape[1], pr.shape[2]
-    mode, classes = parse_target(target, B, Ce)
-    _gpu_only(ev, "the occlusion heat map")
-    Ht, Wt = result.grid
-    tensors = [ev, pr, result.occluded_event_logits, result.occluded_prong_logits]
-    assert all(t.dtype == torch.float32 and t.is_contiguous() and t.device == ev.device for t in tensors)
-    index = result.index
-    assert index.dtype == torch.int32 and index.is_contiguous() and index.device == ev.device and index.shape[1] == 4
-    V = index.shape[0]
-    assert result.occluded_event_logits.shape == (V, Ce) and result.occluded_prong_logits.shape == (V, P, Cp)
-    if classes is not None:
-        classes = classes.to(ev.device, torch.int32).contiguous()
+    rows = (result.event_logits, result.prong_logits, result.occluded_event_logits, result.occluded_prong_logits, result.index)
+    B, P, Ce, Cp, V, mode, classes = _compared_rows(*rows, target, "the occlusion heat map")
+    dev, (Ht, Wt) = rows[0].device, result.grid
     if mode == _lib.OCC_TARGET_PRONG and P == 0:
-        return torch.zeros(B, 1, Ht, Wt, device=ev.device)
-    out = torch.empty(B, 1 + P, Ht, Wt, device=ev.device)
-    with torch.cuda.device(ev.device):
-        _lib.check(_lib.lib.tcvn_occlusion_heatmap(_vp(ev), _vp(pr), _vp(tensors[2]), _vp(tensors[3]), _vp(index), V, B, P, Ce, Cp, Ht, Wt,
-                                                   mode, _vp(classes), ptr(out), _stream()), "occlusion_heatmap")
+        return torch.zeros(B, 1, Ht, Wt, device=dev)
+    out = torch.empty(B, 1 + P, Ht, Wt, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib.tcvn_occlusion_heatmap(*map(_vp, rows), V, B, P, Ce, Cp, Ht, Wt, mode, _vp(classes), ptr(out), _stream()),
+                   "occlusion_heatmap")
     return out
 
 
@@ -317,24 +323,14 @@ class OcclusionCurves:
 
 def curve_and_auc(result: OcclusionCurves, target: Union[str, int, Tensor] = "event") -> Tuple[Tensor, Tensor]:
     """tcvn_occlusion_curve -> (curve [B, 1 + P, steps + 1], auc [B, 1 + P]), see OcclusionCurves.curve / .auc."""
-    ev, pr = result.event_logits, result.prong_logits
-    B, Ce = ev.shape
-    P, Cp = pr.shape[1], pr.shape[2]
-    mode, classes = parse_target(target, B, Ce)
-    _gpu_only(ev, "the deletion / insertion curve")
-    tensors = [ev, pr, result.step_event_logits, result.step_prong_logits]
-    assert all(t.dtype == torch.float32 and t.is_contiguous() and t.device == ev.device for t in tensors)
-    index = result.index
-    assert index.dtype == torch.int32 and index.is_contiguous() and index.device == ev.device and index.shape[1] == 4
-    V, K = index.shape[0], result.steps
-    assert result.step_event_logits.shape == (V, Ce) and result.step_prong_logits.shape == (V, P, Cp)
-    if classes is not None:
-        classes = classes.to(ev.device, torch.int32).contiguous()
-    curve = torch.empty(B, 1 + P, K + 1, device=ev.device)
-    auc = torch.empty(B, 1 + P, device=ev.device)
-    with torch.cuda.device(ev.device):
-        _lib.check(_lib.lib.tcvn_occlusion_curve(_vp(ev), _vp(pr), _vp(tensors[2]), _vp(tensors[3]), _vp(index), V, B, P, Ce, Cp, K, mode,
-                                                 _vp(classes), ptr(curve), ptr(auc), _stream()), "occlusion_curve")
+    rows = (result.event_logits, result.prong_logits, result.step_event_logits, result.step_prong_logits, result.index)
+    B, P, Ce, Cp, V, mode, classes = _compared_rows(*rows, target, "the deletion / insertion curve")
+    dev, K = rows[0].device, result.steps
+    curve = torch.empty(B, 1 + P, K + 1, device=dev)
+    auc = torch.empty(B, 1 + P, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib.tcvn_occlusion_curve(*map(_vp, rows), V, B, P, Ce, Cp, K, mode, _vp(classes), ptr(curve), ptr(auc),
+                                                 _stream()), "occlusion_curve")
     return curve, auc
 
 

@@ -111,3 +111,88 @@ def heat_reference(result, target="event"):
             d = torch.softmax(ev[b], 0)[c] - torch.softmax(oev[v], 0)[c]
         out[b, s, ty, tx] = d
     return out
+
+
+# ---- the variant lists themselves (test_occlusion_lists_gpu.py) -------------------------------------------------------------------------
+def list_reference(coords, n_img, shape, tile, img_bs, max_pass, keep_map=None, curve=None):
+    """What tcvn_occlusion_variants / _refine_variants (keep_map uint8 [B, S, parent Ht, parent Wt]) / _curve_variants (curve =
+    (relevance float32 [B, S, Ht, Wt], steps, mode)) return for one COO list, by the rules alone: a variant's hit list is its image's
+    rows, in original order, filtered by the variant's predicate; voff, bounds, V and nh are prefix sums of the row counts; the ranking
+    is sorted(occupied tiles, key=(-relevance with -0.0 as +0.0, tile index)).
+    -> dict: header [V, unsorted, bad, nh]; bounds (every word of the host buffer behind the header: bounds[k] = first row of pass k,
+    the end of the last pass, zero behind it); vimg int32 [V]; index int32 [V, 4]; rows: per variant the positions in `coords` of its
+    hits (meaningful for a list with neither flag set); rank int32 [B, S, Ht, Wt] (curves only; -1 where nothing is ranked)."""
+    c = coords.cpu().long().reshape(-1, 3)
+    bs = img_bs.cpu().long().reshape(n_img, 2)
+    (H, W), (th, tw) = shape, tile
+    Ht, Wt = grid_of(shape, tile)
+    T = Ht * Wt
+    img, y, x = c[:, 0], c[:, 1], c[:, 2]
+    unsorted = bool((img[:-1] > img[1:]).any())
+    inside = (img >= 0) & (img < n_img) & (y >= 0) & (y < H) & (x >= 0) & (x < W)
+    cell = (y // th) * Wt + x // tw                                   # read only where `inside`
+    admitted = inside.clone()                                          # the hits that make their tile a variant
+    if keep_map is not None:
+        km = keep_map.cpu()
+        b, s = bs[img.clamp(0, n_img - 1)].unbind(1)
+        py, px = y // (2 * th), x // (2 * tw)
+        named = inside & (b >= 0) & (b < km.shape[0]) & (s >= 0) & (s < km.shape[1]) & (py < km.shape[2]) & (px < km.shape[3])
+        admitted = torch.zeros_like(inside)
+        admitted[named] = km[b[named], s[named], py[named], px[named]] != 0
+    of_image = [((img == i) & inside).nonzero().flatten() for i in range(n_img)]      # original order
+    occupied = [sorted(set(cell[admitted & (img == i)].tolist())) for i in range(n_img)]
+    variants = []                                                      # (image, two index words, the kept positions)
+    out = {}
+    if curve is None:
+        total = n_img * T
+        for i in range(n_img):
+            for t in occupied[i]:
+                variants.append((i, t // Wt, t % Wt, of_image[i][cell[of_image[i]] != t]))
+    else:
+        relevance, steps, mode = curve
+        rel = relevance.cpu()
+        total = n_img * (steps + 1)
+        rank = torch.full(tuple(rel.shape), -1, dtype=torch.int32)
+        for i in range(n_img):
+            b, s = bs[i].tolist()
+            if not (0 <= b < rel.shape[0] and 0 <= s < rel.shape[1]) or not occupied[i]:
+                continue
+            flat = rel[b, s].reshape(-1)
+            order = sorted(occupied[i], key=lambda t: (-(float(flat[t]) + 0.0), t))      # x + 0.0 turns -0.0 into +0.0
+            rk = torch.full((T,), -1, dtype=torch.long)
+            rk[torch.tensor(order)] = torch.arange(len(order))
+            rank[b, s] = rk.reshape(Ht, Wt).int()
+            mine = of_image[i]
+            for k in range(steps + 1):
+                m = (k * len(order) + steps - 1) // steps
+                top = rk[cell[mine]] < m
+                variants.append((i, k, m, mine[top if mode == 1 else ~top]))           # mode 1: insertion
+        out["rank"] = rank
+    V = len(variants)
+    voff = [0]
+    for v in variants:
+        voff.append(voff[-1] + int(v[3].numel()))
+    nb = -(-total // max_pass)
+    bounds = [0] * (nb + 1)
+    for k in range(-(-V // max_pass)):
+        bounds[k] = voff[k * max_pass]
+    bounds[-(-V // max_pass)] = voff[V]
+    out.update(header=[V, int(unsorted), int(bool((~inside).any())), voff[V]], bounds=bounds,
+               vimg=torch.tensor([v[0] for v in variants], dtype=torch.int32),
+               index=torch.tensor([[*bs[v[0]].tolist(), v[1], v[2]] for v in variants], dtype=torch.int32).reshape(V, 4),
+               rows=[v[3] for v in variants])
+    return out
+
+
+def pass_reference(ref, coords, values, first, count):
+    """The rows tcvn_occlusion_build_pass / _curve_build_pass write for variants first .. first + count - 1 of list_reference's `ref`:
+    (out_coords int32 [n, 3] = (variant - first, y, x), out_values [n, C])."""
+    c, v = coords.cpu(), values.cpu()
+    oc, ov = [], []
+    for j in range(count):
+        at = ref["rows"][first + j]
+        rows = c[at].clone()
+        rows[:, 0] = j
+        oc.append(rows)
+        ov.append(v[at])
+    return torch.cat(oc).reshape(-1, 3), torch.cat(ov).reshape(-1, v.shape[1])
