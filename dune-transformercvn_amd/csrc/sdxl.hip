@@ -12,6 +12,7 @@
 // x + to_out(to_v(groupnorm(x))); to_q / to_k keep their slots and receive zero gradients.
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/tcvn_hip.h"
@@ -21,11 +22,16 @@
 
 using namespace tcvn;
 
+static_assert(SCONV_GENERIC == TCVN_SCONV_GENERIC && SCONV_C64 == TCVN_SCONV_C64 && SCONV_G == TCVN_SCONV_G && SCONV_S2 == TCVN_SCONV_S2 &&
+              SCONV_IN == TCVN_SCONV_IN, "tcvn_sdxl_conv_kernels returns SConvKernel values under the C names");
+
 namespace {
 constexpr float kGnEps = 1e-6f;
 enum { OP_CONV = 0, OP_GN = 1 };
 struct SBuf { int H, W, C; };
-struct SOp { int kind, in, out, res, w, b, ks, stride, pad, act, conv_id, gn_id, final_f32; };
+// stats_gn (CONV): the GroupNorm (gn_id) whose statistics this convolution's output feeds, or -1;  stats_given (GN): the producing
+// convolution delivers this GroupNorm's statistics, so it runs no statistics pass of its own
+struct SOp { int kind, in, out, res, w, b, ks, stride, pad, act, conv_id, gn_id, final_f32, stats_gn, stats_given; };
 struct Bump {
     long off = 0;
     long take(long bytes) { long o = off; off += round_up(bytes, 256); return o; }
@@ -34,6 +40,21 @@ struct SLayout {
     std::vector<long> act, grad;            // per buffer (act[0] = image); grad[0] unused
     std::vector<long> wk, wkt, gwk;         // per conv
     long stats, bstats, zero_begin, zero_end, slab, total;
+};
+// a descriptor table on the device; its rows hold workspace addresses, so it is rebuilt when the workspace moves
+struct DevTable {
+    char* d = nullptr; size_t cap = 0; const char* ws = nullptr; long total = 0; int n = 0;
+    std::vector<char> host;                 // source of the asynchronous copy
+    bool stale(const char* ws_, long total_) const { return ws != ws_ || total != total_; }
+    template <typename D>
+    int upload(const std::vector<D>& rows, const char* ws_, long total_, hipStream_t st) {
+        const size_t bytes = rows.size() * sizeof(D);
+        if (bytes > cap) { if (d) TCVN_CHECK(hipFree(d)); d = nullptr; cap = 0; TCVN_CHECK(hipMalloc(&d, bytes)); cap = bytes; }
+        host.assign(reinterpret_cast<const char*>(rows.data()), reinterpret_cast<const char*>(rows.data()) + bytes);
+        TCVN_CHECK(hipMemcpyAsync(d, host.data(), bytes, hipMemcpyHostToDevice, st));
+        n = (int)rows.size(); ws = ws_; total = total_;
+        return 0;
+    }
 };
 }  // namespace
 
@@ -44,46 +65,56 @@ struct tcvn_sdxl {
     std::vector<float*> data, grad;
     std::vector<SBuf> bufs;
     std::vector<SOp> ops;
+    std::vector<std::pair<std::string, int>> taps;                 // tcvn_sdxl_tap: name -> buffer, recorded as the tape is built
     int n_conv = 0, n_gn = 0;
     bool bound = false;
     int last_n = 0;
     const int32_t* last_coords = nullptr; long last_nnz = 0;       // COO list of the last forward (conv_in weight gradient)
-    char* d_desc = nullptr; size_t desc_cap = 0; char* desc_ws = nullptr; long desc_total = 0; int n_pack = 0;
-    char* d_undesc = nullptr; char* undesc_ws = nullptr; long undesc_total = 0; int n_unpack = 0;
-    std::vector<char> h_desc, h_undesc;
+    DevTable pack, unpack;
 
     explicit tcvn_sdxl(const tcvn_sdxl_cfg& c);
-    ~tcvn_sdxl() { if (d_desc) (void)hipFree(d_desc); if (d_undesc) (void)hipFree(d_undesc); }
-    int slot(const std::string& name, long numel) { slots.push_back({name, numel, TCVN_SLOT_PARAM}); return (int)slots.size() - 1; }
+    ~tcvn_sdxl() { if (pack.d) (void)hipFree(pack.d); if (unpack.d) (void)hipFree(unpack.d); }
+    // slots `p.weight`, `p.bias` (the bias slot follows the weight slot) -> the weight slot
+    int wb(const std::string& p, long w_numel, long b_numel) {
+        slots.push_back({p + ".weight", w_numel, TCVN_SLOT_PARAM});
+        slots.push_back({p + ".bias", b_numel, TCVN_SLOT_PARAM});
+        return (int)slots.size() - 2;
+    }
     int new_buf(int H, int W, int C) { bufs.push_back({H, W, C}); return (int)bufs.size() - 1; }
-    int conv(const std::string& p, int in, int cout, int ks, int stride, int pad, int res, int Ho, int Wo, bool linear_keys = false);
-    int gn(const std::string& p, int in, int act);
+    // the one op constructor of each kind; w >= 0: slots reserved earlier (registration order differs from execution order)
+    int conv(const std::string& p, int in, int cout, int ks, int stride, int pad, int res, int w = -1);
+    int gn(const std::string& p, int in, int act, int w = -1);
     int resnet(const std::string& p, int in, int cout);
     void layout(int n, bool bwd, SLayout& L) const;
     int Kp(const SOp& o) const { return (int)round_up((long)o.ks * o.ks * bufs[o.in].C, 32); }
     int Kpt(const SOp& o) const { return (int)round_up((long)o.ks * o.ks * bufs[o.out].C, 32); }
     SConv geom(const SOp& o, int n) const;
+    SConv bwd_geom(const SOp& o, int n, char* ws, const SLayout& L, const int32_t* hits, long nnz) const;
+    GnArgs gn_args(const SOp& o, int n, char* ws, const SLayout& L) const;
+    SConvFwd fwd_call(const SOp& o, int n, char* ws, const SLayout& L, float* out, long out_ld) const;
+    SConvDgrad dgrad_call(const SOp& o, const SConv& g, char* ws, const SLayout& L, const char* dO, char* dI, int accumulate) const;
+    SConvWgrad wgrad_call(const SOp& o, const SConv& g, char* ws, const SLayout& L, const char* dO) const;
     int forward(int n, const int32_t* coords, const float* values, long nnz, int log_pixels, float noise_std, float* out, long out_ld,
                 char* ws, long ws_bytes, int train, uint64_t seed, hipStream_t st);
     int backward(int n, const float* d_out, long d_out_ld, char* ws, long ws_bytes, hipStream_t st);
 };
 
-int tcvn_sdxl::conv(const std::string& p, int in, int cout, int ks, int stride, int pad, int res, int Ho, int Wo, bool linear_keys) {
+int tcvn_sdxl::conv(const std::string& p, int in, int cout, int ks, int stride, int pad, int res, int w) {
     SOp o{};
-    o.kind = OP_CONV; o.in = in; o.res = res; o.ks = ks; o.stride = stride; o.pad = pad; o.conv_id = n_conv++;
-    const int cin = bufs[in].C;
-    o.w = slot(p + ".weight", (long)cout * cin * ks * ks);
-    o.b = slot(p + ".bias", cout);
-    (void)linear_keys;
-    o.out = new_buf(Ho, Wo, cout);
+    o.kind = OP_CONV; o.in = in; o.res = res; o.ks = ks; o.stride = stride; o.pad = pad; o.conv_id = n_conv++; o.stats_gn = -1;
+    o.w = w >= 0 ? w : wb(p, (long)cout * bufs[in].C * ks * ks, cout);
+    o.b = o.w + 1;
+    // taps beyond the map read zero: behind a stride-2 convolution (pad 0) that is the row and column of diffusers' F.pad(0,1,0,1)
+    const int far = stride == 2 ? 1 : pad;
+    o.out = new_buf((bufs[in].H + pad + far - ks) / stride + 1, (bufs[in].W + pad + far - ks) / stride + 1, cout);
     ops.push_back(o);
     return o.out;
 }
-int tcvn_sdxl::gn(const std::string& p, int in, int act) {
+int tcvn_sdxl::gn(const std::string& p, int in, int act, int w) {
     SOp o{};
     o.kind = OP_GN; o.in = in; o.res = -1; o.act = act; o.gn_id = n_gn++;
-    o.w = slot(p + ".weight", bufs[in].C);
-    o.b = slot(p + ".bias", bufs[in].C);
+    o.w = w >= 0 ? w : wb(p, bufs[in].C, bufs[in].C);
+    o.b = o.w + 1;
     o.out = new_buf(bufs[in].H, bufs[in].W, bufs[in].C);
     ops.push_back(o);
     return o.out;
@@ -91,21 +122,14 @@ int tcvn_sdxl::gn(const std::string& p, int in, int act) {
 // ResnetBlock2D: x + conv2(silu(gn2(conv1(silu(gn1(x)))))), x through a 1x1 conv_shortcut when the width changes.
 // Slot order = module registration order: norm1, conv1, norm2, conv2, conv_shortcut.
 int tcvn_sdxl::resnet(const std::string& p, int in, int cout) {
-    const int H = bufs[in].H, W = bufs[in].W, cin = bufs[in].C;
     const int a1 = gn(p + ".norm1", in, 1);
-    const int h1 = conv(p + ".conv1", a1, cout, 3, 1, 1, -1, H, W);
+    const int h1 = conv(p + ".conv1", a1, cout, 3, 1, 1, -1);
     const int a2 = gn(p + ".norm2", h1, 1);
-    // conv2 is registered before conv_shortcut, but the shortcut's output is conv2's residual: emit the op first, fix the slots after
-    if (cin == cout) return conv(p + ".conv2", a2, cout, 3, 1, 1, in, H, W);
-    const size_t s0 = slots.size();
-    const int w2 = slot(p + ".conv2.weight", (long)cout * cout * 9), b2 = slot(p + ".conv2.bias", cout);
-    const int sc = conv(p + ".conv_shortcut", in, cout, 1, 1, 0, -1, H, W);
-    (void)s0;
-    SOp o{};
-    o.kind = OP_CONV; o.in = a2; o.res = sc; o.ks = 3; o.stride = 1; o.pad = 1; o.conv_id = n_conv++; o.w = w2; o.b = b2;
-    o.out = new_buf(H, W, cout);
-    ops.push_back(o);
-    return o.out;
+    if (bufs[in].C == cout) return conv(p + ".conv2", a2, cout, 3, 1, 1, in);
+    // conv2 is registered before conv_shortcut but runs after it (the shortcut's output is its residual): reserve its slots first
+    const int w2 = wb(p + ".conv2", (long)cout * cout * 9, cout);
+    const int sc = conv(p + ".conv_shortcut", in, cout, 1, 1, 0, -1);
+    return conv(p + ".conv2", a2, cout, 3, 1, 1, sc, w2);
 }
 
 tcvn_sdxl::tcvn_sdxl(const tcvn_sdxl_cfg& c) : cfg(c) {
@@ -116,39 +140,39 @@ tcvn_sdxl::tcvn_sdxl(const tcvn_sdxl_cfg& c) : cfg(c) {
     chans.push_back(cfg.out_dim);
     const std::string e = "encoder";
     int h = new_buf(cfg.H, cfg.W, cfg.in_ch);                                     // buffer 0: the scattered pixel map
-    h = conv(e + ".conv_in", h, chans[0], 3, 1, 1, -1, cfg.H, cfg.W);
+    taps.push_back({"img", h});
+    h = conv(e + ".conv_in", h, chans[0], 3, 1, 1, -1);
+    taps.push_back({"conv_in", h});
     for (size_t i = 0; i < chans.size(); ++i) {
         const std::string p = e + ".down_blocks." + std::to_string(i);
         for (int j = 0; j < 2; ++j) h = resnet(p + ".resnets." + std::to_string(j), h, chans[i]);
-        if (i + 1 != chans.size()) {                                              // F.pad(0,1,0,1) + 3x3 stride 2, padding 0
-            const int Ho = (bufs[h].H + 1 - 3) / 2 + 1, Wo = (bufs[h].W + 1 - 3) / 2 + 1;
-            h = conv(p + ".downsamplers.0.conv", h, chans[i], 3, 2, 0, -1, Ho, Wo);
-        }
+        taps.push_back({"block" + std::to_string(i), h});                         // in front of the block's down-sampler
+        if (i + 1 != chans.size()) h = conv(p + ".downsamplers.0.conv", h, chans[i], 3, 2, 0, -1);      // F.pad(0,1,0,1) + 3x3 stride 2, padding 0
     }
     const int C = chans.back();
     // mid block.  Registration order in diffusers: attentions, then resnets; execution: resnet0, attention, resnet1.
-    const std::string m = e + ".mid_block";
-    const int s_gn_w = slot(m + ".attentions.0.group_norm.weight", C), s_gn_b = slot(m + ".attentions.0.group_norm.bias", C);
-    slot(m + ".attentions.0.to_q.weight", (long)C * C); slot(m + ".attentions.0.to_q.bias", C);
-    slot(m + ".attentions.0.to_k.weight", (long)C * C); slot(m + ".attentions.0.to_k.bias", C);
-    const int s_v_w = slot(m + ".attentions.0.to_v.weight", (long)C * C), s_v_b = slot(m + ".attentions.0.to_v.bias", C);
-    const int s_o_w = slot(m + ".attentions.0.to_out.0.weight", (long)C * C), s_o_b = slot(m + ".attentions.0.to_out.0.bias", C);
+    const std::string m = e + ".mid_block", at = m + ".attentions.0";
+    const int s_gn = wb(at + ".group_norm", C, C);
+    wb(at + ".to_q", (long)C * C, C);
+    wb(at + ".to_k", (long)C * C, C);
+    const int s_v = wb(at + ".to_v", (long)C * C, C), s_o = wb(at + ".to_out.0", (long)C * C, C);
     h = resnet(m + ".resnets.0", h, C);
-    {
-        const int H = bufs[h].H, W = bufs[h].W;
-        SOp g{}; g.kind = OP_GN; g.in = h; g.res = -1; g.act = 0; g.gn_id = n_gn++; g.w = s_gn_w; g.b = s_gn_b; g.out = new_buf(H, W, C);
-        ops.push_back(g);
-        SOp v{}; v.kind = OP_CONV; v.in = g.out; v.res = -1; v.ks = 1; v.stride = 1; v.pad = 0; v.conv_id = n_conv++; v.w = s_v_w; v.b = s_v_b;
-        v.out = new_buf(H, W, C); ops.push_back(v);
-        SOp o{}; o.kind = OP_CONV; o.in = v.out; o.res = h; o.ks = 1; o.stride = 1; o.pad = 0; o.conv_id = n_conv++; o.w = s_o_w; o.b = s_o_b;
-        o.out = new_buf(H, W, C); ops.push_back(o);
-        h = o.out;
-    }
+    const int t = gn(at + ".group_norm", h, 0, s_gn);                             // one token: x + to_out(to_v(gn(x)))
+    const int v = conv(at + ".to_v", t, C, 1, 1, 0, -1, s_v);
+    h = conv(at + ".to_out.0", v, C, 1, 1, 0, h, s_o);
     h = resnet(m + ".resnets.1", h, C);
-    const int a = gn(e + ".conv_norm_out", h, 1);
-    h = conv(e + ".conv_out", a, cfg.out_dim, 3, 1, 1, -1, bufs[a].H, bufs[a].W);
-    h = conv("output_layer.1", h, cfg.out_dim, 1, 1, 0, -1, bufs[h].H, bufs[h].W);
+    taps.push_back({"mid", h});
+    h = conv(e + ".conv_out", gn(e + ".conv_norm_out", h, 1), cfg.out_dim, 3, 1, 1, -1);
+    h = conv("output_layer.1", h, cfg.out_dim, 1, 1, 0, -1);
     ops.back().final_f32 = 1;
+    // a buffer read by exactly one GroupNorm and produced by a convolution gets its statistics from that convolution
+    for (auto& q : ops) {
+        if (q.kind != OP_GN) continue;
+        int readers = 0;
+        for (const auto& o : ops) readers += o.kind == OP_GN && o.in == q.in;
+        for (auto& o : ops)
+            if (o.kind == OP_CONV && o.out == q.in && !o.final_f32 && readers == 1) { o.stats_gn = q.gn_id; q.stats_given = 1; }
+    }
     data.assign(slots.size(), nullptr);
     grad.assign(slots.size(), nullptr);
 }
@@ -184,6 +208,35 @@ SConv tcvn_sdxl::geom(const SOp& o, int n) const {
     g.Kp = Kp(o); g.Kpt = Kpt(o);
     return g;
 }
+// backward geometry: plus the weight-gradient slab and, for conv_in, the hit list of the forward
+SConv tcvn_sdxl::bwd_geom(const SOp& o, int n, char* ws, const SLayout& L, const int32_t* hits, long nnz) const {
+    SConv g = geom(o, n);
+    g.slab = reinterpret_cast<float*>(ws + L.slab); g.slab_bytes = kSconvSlabBytes;
+    if (o.in == 0) { g.hits = hits; g.nnz = nnz; }
+    return g;
+}
+GnArgs tcvn_sdxl::gn_args(const SOp& o, int n, char* ws, const SLayout& L) const {
+    return GnArgs{cfg.mode, ws + L.act[o.in], bufs[o.in].C, n, bufs[o.in].H * bufs[o.in].W, bufs[o.in].C, data[o.w], data[o.b], kGnEps, o.act,
+                  reinterpret_cast<double*>(ws + L.stats) + (long)o.gn_id * n * 2};
+}
+// the last convolution writes the caller's fp32 output, every other one its activation buffer
+SConvFwd tcvn_sdxl::fwd_call(const SOp& o, int n, char* ws, const SLayout& L, float* out, long out_ld) const {
+    SConvFwd c{};
+    c.g = geom(o, n);
+    if (o.stats_gn >= 0) c.g.stats = reinterpret_cast<double*>(ws + L.stats) + (long)o.stats_gn * n * 2;
+    c.In = ws + L.act[o.in]; c.Wk = ws + L.wk[o.conv_id]; c.bias = data[o.b];
+    if (o.res >= 0) { c.Res = ws + L.act[o.res]; c.ldres = bufs[o.res].C; }
+    c.Out = o.final_f32 ? reinterpret_cast<void*>(out) : reinterpret_cast<void*>(ws + L.act[o.out]);
+    c.ldo = o.final_f32 ? out_ld : c.g.Cout;
+    c.out_f32 = o.final_f32;
+    return c;
+}
+SConvDgrad tcvn_sdxl::dgrad_call(const SOp& o, const SConv& g, char* ws, const SLayout& L, const char* dO, char* dI, int accumulate) const {
+    return SConvDgrad{g, dO, g.Cout, ws + L.wkt[o.conv_id], dI, g.Cin, accumulate};
+}
+SConvWgrad tcvn_sdxl::wgrad_call(const SOp& o, const SConv& g, char* ws, const SLayout& L, const char* dO) const {
+    return SConvWgrad{g, ws + L.act[o.in], dO, g.Cout, reinterpret_cast<float*>(ws + L.gwk[o.conv_id]), grad[o.b]};
+}
 
 int tcvn_sdxl::forward(int n, const int32_t* coords, const float* values, long nnz, int log_pixels, float noise_std, float* out,
                        long out_ld, char* ws, long ws_bytes, int train, uint64_t seed, hipStream_t st) {
@@ -198,7 +251,7 @@ int tcvn_sdxl::forward(int n, const int32_t* coords, const float* values, long n
     layout(n, train != 0, L);
     if (ws_bytes < L.total) { fprintf(stderr, "tcvn: sdxl workspace too small (%ld < %ld)\n", ws_bytes, L.total); return -12; }
     int rc;
-    if (desc_ws != ws || desc_total != L.total) {                       // weight packing descriptors depend on the workspace address
+    if (pack.stale(ws, L.total)) {                                      // weight packing descriptors depend on the workspace address
         std::vector<PackDesc> pd;
         for (const auto& o : ops)
             if (o.kind == OP_CONV) {
@@ -206,40 +259,21 @@ int tcvn_sdxl::forward(int n, const int32_t* coords, const float* values, long n
                 pd.push_back(PackDesc{data[o.w], ws + L.wk[o.conv_id], cout, cin, o.ks * o.ks, Kp(o), 0, 0});
                 if (o.in != 0) pd.push_back(PackDesc{data[o.w], ws + L.wkt[o.conv_id], cout, cin, o.ks * o.ks, Kpt(o), 1, 0});
             }
-        n_pack = (int)pd.size();
-        const size_t bytes = pd.size() * sizeof(PackDesc);
-        if (bytes > desc_cap) { if (d_desc) TCVN_CHECK(hipFree(d_desc)); TCVN_CHECK(hipMalloc(&d_desc, bytes)); desc_cap = bytes; }
-        h_desc.assign(reinterpret_cast<char*>(pd.data()), reinterpret_cast<char*>(pd.data()) + bytes);
-        TCVN_CHECK(hipMemcpyAsync(d_desc, h_desc.data(), bytes, hipMemcpyHostToDevice, st));
-        desc_ws = ws; desc_total = L.total;
+        if ((rc = pack.upload(pd, ws, L.total, st))) return rc;
     }
-    if ((rc = pack_weights(reinterpret_cast<const PackDesc*>(d_desc), n_pack, cfg.mode, st))) return rc;
+    if ((rc = pack_weights(reinterpret_cast<const PackDesc*>(pack.d), pack.n, cfg.mode, st))) return rc;
     TCVN_CHECK(hipMemsetAsync(ws + L.act[0], 0, (size_t)n * cfg.H * cfg.W * cfg.in_ch * esz, st));
     TCVN_CHECK(hipMemsetAsync(ws + L.stats, 0, (size_t)n_gn * n * 16, st));
     {
         ScatterArgs a{cfg.mode, coords, values, nnz, n, ws + L.act[0], cfg.H, cfg.W, cfg.in_ch, log_pixels, train ? noise_std : 0.f, seed};
         if ((rc = scatter_pixels(a, st))) return rc;
     }
-    // a buffer consumed by exactly one GroupNorm and produced by a convolution gets its statistics from that convolution's epilogue
-    std::vector<int> gn_of(bufs.size(), -1), conv_made(bufs.size(), 0);
-    for (const auto& o : ops) {
-        if (o.kind == OP_GN) gn_of[o.in] = gn_of[o.in] == -1 ? o.gn_id : -2;
-        else if (!o.final_f32) conv_made[o.out] = 1;
-    }
     for (const auto& o : ops) {
         if (o.kind == OP_GN) {
-            GnArgs a{cfg.mode, ws + L.act[o.in], bufs[o.in].C, n, bufs[o.in].H * bufs[o.in].W, bufs[o.in].C, data[o.w], data[o.b], kGnEps, o.act,
-                     reinterpret_cast<double*>(ws + L.stats) + (long)o.gn_id * n * 2};
-            if (!(gn_of[o.in] >= 0 && conv_made[o.in]) && (rc = gn_stats(a, st))) return rc;
+            const GnArgs a = gn_args(o, n, ws, L);
+            if (!o.stats_given && (rc = gn_stats(a, st))) return rc;
             if ((rc = gn_act(a, ws + L.act[o.out], bufs[o.out].C, st))) return rc;
-        } else {
-            SConv g = geom(o, n);
-            if (!o.final_f32 && gn_of[o.out] >= 0) g.stats = reinterpret_cast<double*>(ws + L.stats) + (long)gn_of[o.out] * n * 2;
-            void* dst = o.final_f32 ? reinterpret_cast<void*>(out) : reinterpret_cast<void*>(ws + L.act[o.out]);
-            const long ldo = o.final_f32 ? out_ld : g.Cout;
-            if ((rc = sconv_fwd(g, ws + L.act[o.in], ws + L.wk[o.conv_id], data[o.b], o.res >= 0 ? ws + L.act[o.res] : nullptr,
-                                o.res >= 0 ? bufs[o.res].C : 0, dst, ldo, o.final_f32, st))) return rc;
-        }
+        } else if ((rc = sconv_fwd(fwd_call(o, n, ws, L, out, out_ld), st))) return rc;
     }
     last_n = n; last_coords = coords; last_nnz = nnz;
     return 0;
@@ -255,17 +289,13 @@ int tcvn_sdxl::backward(int n, const float* d_out, long d_out_ld, char* ws, long
     layout(n, true, L);
     if (ws_bytes < L.total) return -12;
     int rc;
-    if (undesc_ws != ws || undesc_total != L.total) {
+    if (unpack.stale(ws, L.total)) {
         std::vector<UnpackDesc> ud;
         for (const auto& o : ops)
             if (o.kind == OP_CONV)
                 ud.push_back(UnpackDesc{reinterpret_cast<const float*>(ws + L.gwk[o.conv_id]), grad[o.w], bufs[o.out].C, bufs[o.in].C,
                                         o.ks * o.ks, Kp(o), 0});
-        n_unpack = (int)ud.size();
-        if (!d_undesc) TCVN_CHECK(hipMalloc(&d_undesc, ud.size() * sizeof(UnpackDesc)));
-        h_undesc.assign(reinterpret_cast<char*>(ud.data()), reinterpret_cast<char*>(ud.data()) + ud.size() * sizeof(UnpackDesc));
-        TCVN_CHECK(hipMemcpyAsync(d_undesc, h_undesc.data(), h_undesc.size(), hipMemcpyHostToDevice, st));
-        undesc_ws = ws; undesc_total = L.total;
+        if ((rc = unpack.upload(ud, ws, L.total, st))) return rc;
     }
     // zero: backward GroupNorm sums and the kernel-layout weight gradients (forward statistics sit in front of them and stay)
     TCVN_CHECK(hipMemsetAsync(ws + L.bstats, 0, (size_t)(L.zero_end - L.bstats), st));
@@ -282,21 +312,17 @@ int tcvn_sdxl::backward(int n, const float* d_out, long d_out_ld, char* ws, long
         const SOp& o = ops[oi];
         if (!written[o.out]) { fprintf(stderr, "tcvn: sdxl backward: gradient of buffer %d never produced\n", o.out); return -15; }
         const char* dO = ws + goff[o.out];
-        const long rows_in = (long)n * bufs[o.in].H * bufs[o.in].W;
         if (o.kind == OP_GN) {
-            GnArgs a{cfg.mode, ws + L.act[o.in], bufs[o.in].C, n, bufs[o.in].H * bufs[o.in].W, bufs[o.in].C, data[o.w], data[o.b], kGnEps, o.act,
-                     reinterpret_cast<double*>(ws + L.stats) + (long)o.gn_id * n * 2};
+            const GnArgs a = gn_args(o, n, ws, L);
             double* bs = reinterpret_cast<double*>(ws + L.bstats) + (long)o.gn_id * n * 2;
             if ((rc = gn_bwd_reduce(a, dO, bufs[o.out].C, bs, grad[o.w], grad[o.b], st))) return rc;
             if ((rc = gn_bwd_apply(a, dO, bufs[o.out].C, bs, ws + goff[o.in], bufs[o.in].C, written[o.in], st))) return rc;
             written[o.in] = 1;
         } else {
-            SConv g = geom(o, n);
-            g.slab = reinterpret_cast<float*>(ws + L.slab); g.slab_bytes = kSconvSlabBytes;
-            if (o.in == 0) { g.hits = last_coords; g.nnz = last_nnz; }
-            if ((rc = sconv_wgrad(g, ws + L.act[o.in], dO, g.Cout, reinterpret_cast<float*>(ws + L.gwk[o.conv_id]), grad[o.b], st))) return rc;
+            const SConv g = bwd_geom(o, n, ws, L, last_coords, last_nnz);
+            if ((rc = sconv_wgrad(wgrad_call(o, g, ws, L, dO), st))) return rc;
             if (o.in != 0) {
-                if ((rc = sconv_dgrad(g, dO, g.Cout, ws + L.wkt[o.conv_id], ws + goff[o.in], g.Cin, written[o.in], st))) return rc;
+                if ((rc = sconv_dgrad(dgrad_call(o, g, ws, L, dO, ws + goff[o.in], written[o.in]), st))) return rc;
                 written[o.in] = 1;
             }
             if (o.res >= 0) {                                            // out = conv(...) + res: the residual receives dOut as is
@@ -307,9 +333,8 @@ int tcvn_sdxl::backward(int n, const float* d_out, long d_out_ld, char* ws, long
                 written[o.res] = 1;
             }
         }
-        (void)rows_in;
     }
-    return unpack_wgrads(reinterpret_cast<const UnpackDesc*>(d_undesc), n_unpack, st);
+    return unpack_wgrads(reinterpret_cast<const UnpackDesc*>(unpack.d), unpack.n, st);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -339,7 +364,7 @@ int tcvn_sdxl_bind(tcvn_sdxl* p, void* const* d, void* const* g) {
         p->grad[i] = g ? reinterpret_cast<float*>(g[i]) : nullptr;
         if (p->data[i] == nullptr) { fprintf(stderr, "tcvn: slot %s unbound\n", p->slots[i].name.c_str()); return -10; }
     }
-    p->bound = true; p->desc_ws = nullptr; p->undesc_ws = nullptr;
+    p->bound = true; p->pack.ws = nullptr; p->unpack.ws = nullptr;
     return 0;
 }
 int64_t tcvn_sdxl_workspace_bytes(const tcvn_sdxl* p, int n_img, int with_backward) {
@@ -355,45 +380,35 @@ int tcvn_sdxl_forward(tcvn_sdxl* p, int n_img, const int32_t* coords, const floa
 int tcvn_sdxl_backward(tcvn_sdxl* p, int n_img, const float* d_out, int64_t d_out_ld, void* ws, int64_t ws_bytes, void* stream) {
     return p->backward(n_img, d_out, d_out_ld, reinterpret_cast<char*>(ws), ws_bytes, reinterpret_cast<hipStream_t>(stream));
 }
-/* tap: "conv_in", "block<i>" (output of down block i before its downsampler), "mid" -> byte offset + NHWC shape */
+/* tap: "img", "conv_in", "block<i>" (output of down block i before its downsampler), "mid" -> byte offset + NHWC shape */
 int tcvn_sdxl_tap(const tcvn_sdxl* p, int n_img, const char* name, int64_t* byte_off, int* n, int* h, int* w, int* c, int* ld,
                   int* elem_bytes) {
-    SLayout L;
-    p->layout(n_img, false, L);
-    const std::string s(name);
-    int buf = -1;
-    int convs = 0, target = -1;
-    if (s == "conv_in") buf = p->ops[0].out;
-    else if (s == "img") buf = 0;
-    else {
-        // walk the tape: down block i ends at the input of its stride-2 conv (or, for the last block, at the first mid-block GN)
-        std::vector<int> block_end;
-        for (const auto& o : p->ops)
-            if (o.kind == OP_CONV && o.stride == 2) block_end.push_back(o.in);
-        (void)convs; (void)target;
-        if (s.rfind("block", 0) == 0) {
-            const int i = atoi(s.c_str() + 5);
-            const int nb = p->cfg.num_blocks * p->cfg.repeat + 1;
-            if (i < 0 || i >= nb) return -1;
-            if (i < (int)block_end.size()) buf = block_end[i];
-            else {                                   // last block: two resnets after the last downsampler
-                int seen = 0;
-                for (size_t k = 0; k < p->ops.size(); ++k)
-                    if (p->ops[k].kind == OP_CONV && p->ops[k].stride == 2 && ++seen == (int)block_end.size()) {
-                        int resn = 0;
-                        for (size_t q = k + 1; q < p->ops.size(); ++q)
-                            if (p->ops[q].kind == OP_CONV && p->ops[q].ks == 3 && p->ops[q].res >= 0 && ++resn == 2) { buf = p->ops[q].out; break; }
-                        break;
-                    }
-            }
-        } else if (s == "mid") {
-            for (const auto& o : p->ops)
-                if (o.kind == OP_GN && o.act == 1) buf = o.in;      // the last SiLU GroupNorm is conv_norm_out: its input is the mid block's output
+    for (const auto& t : p->taps)
+        if (t.first == name) {
+            SLayout L;
+            p->layout(n_img, false, L);
+            const SBuf& b = p->bufs[t.second];
+            *byte_off = L.act[t.second]; *n = n_img; *h = b.H; *w = b.W; *c = b.C; *ld = b.C; *elem_bytes = p->esz;
+            return 0;
         }
-    }
-    if (buf < 0 || L.act[buf] < 0) return -1;
-    *byte_off = L.act[buf]; *n = n_img; *h = p->bufs[buf].H; *w = p->bufs[buf].W; *c = p->bufs[buf].C; *ld = p->bufs[buf].C;
-    *elem_bytes = p->esz;
+    return -1;
+}
+int tcvn_sdxl_num_convs(const tcvn_sdxl* p) { return p->n_conv; }
+/* The choosers' answers for one convolution of a training step.  Operand addresses enter the choice through their alignment only, so
+ * any 256-byte aligned workspace base stands for the caller's; no HIP call is made. */
+int tcvn_sdxl_conv_kernels(const tcvn_sdxl* p, int n_img, int conv_index, int* fwd, int* dgrad, int* wgrad) {
+    if (conv_index < 0 || conv_index >= p->n_conv || n_img <= 0) return -1;
+    const SOp* o = nullptr;
+    for (const auto& q : p->ops)
+        if (q.kind == OP_CONV && q.conv_id == conv_index) o = &q;
+    SLayout L;
+    p->layout(n_img, true, L);
+    char* ws = reinterpret_cast<char*>(uintptr_t(1) << 20);
+    static const int32_t some_hit[3] = {0, 0, 0};
+    const SConv g = p->bwd_geom(*o, n_img, ws, L, some_hit, 1);
+    *fwd = sconv_fwd_kernel(p->fwd_call(*o, n_img, ws, L, reinterpret_cast<float*>(ws), g.Cout));
+    *dgrad = o->in == 0 ? -1 : sconv_dgrad_kernel(p->dgrad_call(*o, g, ws, L, ws + L.grad[o->out], ws + L.grad[o->in], 0));
+    *wgrad = sconv_wgrad_kernel(p->wgrad_call(*o, g, ws, L, ws + L.grad[o->out]));
     return 0;
 }
 

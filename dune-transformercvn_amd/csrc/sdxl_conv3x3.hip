@@ -577,40 +577,38 @@ __global__ __launch_bounds__(512, 1) void k_sconv3_s2_dgrad(const D2Args g) {
     }
 }
 
+bool packed(const TileMap& m) { return m.px > 1 || m.py > 1; }
+int grid256(int ntiles) { return ntiles < 256 ? ntiles : 256; }        // one persistent workgroup per CU
+
+// SCONV_G forward (flip = 0) and, on the transposed pack with the channel roles exchanged, data gradient (flip = 1)
 int launch_g(const SConv& g, const void* In, int cin, const void* W, int cout, const float* bias, const void* Res, void* Out, int flip,
-             double* stats, hipStream_t st) {
+             hipStream_t st) {
     CGArgs a{};
     a.In = reinterpret_cast<const bf16*>(In); a.W = reinterpret_cast<const bf16*>(W); a.bias = bias;
     a.Res = reinterpret_cast<const bf16*>(Res); a.Out = reinterpret_cast<bf16*>(Out);
     a.n = g.n; a.H = g.Hin; a.W_ = g.Win; a.flip = flip; a.cin = cin; a.cout = cout; a.nc = cin / 64;
     a.map = make_map(g.n, g.Hin, g.Win); a.ntiles = a.map.ntiles();
-    a.stats = (a.map.px == 1 && a.map.py == 1) ? stats : nullptr;
+    a.stats = (flip || packed(a.map)) ? nullptr : g.stats;
     static bool attr = false;
-    if (!attr) {
-        TCVN_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_sconv3_g), hipFuncAttributeMaxDynamicSharedMemorySize, (int)C64_SMEM));
-        attr = true;
-    }
-    const int grid = a.ntiles < 256 ? a.ntiles : 256;
-    hipLaunchKernelGGL(k_sconv3_g, dim3(grid, cout / 64), dim3(512), C64_SMEM, st, a);
+    int rc;
+    if ((rc = allow_lds(reinterpret_cast<const void*>(k_sconv3_g), (int)C64_SMEM, attr))) return rc;
+    hipLaunchKernelGGL(k_sconv3_g, dim3(grid256(a.ntiles), cout / 64), dim3(512), C64_SMEM, st, a);
     TCVN_LAUNCH_CHECK();
     return 0;
 }
 
-int launch_c64(const SConv& g, const void* In, const void* W, const float* bias, const void* Res, void* Out, int flip, double* stats,
-               hipStream_t st) {
+// SCONV_C64, same two roles
+int launch_c64(const SConv& g, const void* In, const void* W, const float* bias, const void* Res, void* Out, int flip, hipStream_t st) {
     C64Args a{};
-    a.stats = stats;
+    a.stats = flip ? nullptr : g.stats;
     a.In = reinterpret_cast<const bf16*>(In); a.W = reinterpret_cast<const bf16*>(W); a.bias = bias;
     a.Res = reinterpret_cast<const bf16*>(Res); a.Out = reinterpret_cast<bf16*>(Out);
     a.n = g.n; a.H = g.Hin; a.W_ = g.Win; a.flip = flip;
     a.tiles_x = (g.Win + TW - 1) / TW; a.tiles_y = (g.Hin + TH - 1) / TH; a.ntiles = g.n * a.tiles_x * a.tiles_y;
     static bool attr = false;
-    if (!attr) {
-        TCVN_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_sconv3_c64), hipFuncAttributeMaxDynamicSharedMemorySize, (int)C64_SMEM));
-        attr = true;
-    }
-    const int grid = a.ntiles < 256 ? a.ntiles : 256;
-    hipLaunchKernelGGL(k_sconv3_c64, dim3(grid), dim3(512), C64_SMEM, st, a);
+    int rc;
+    if ((rc = allow_lds(reinterpret_cast<const void*>(k_sconv3_c64), (int)C64_SMEM, attr))) return rc;
+    hipLaunchKernelGGL(k_sconv3_c64, dim3(grid256(a.ntiles)), dim3(512), C64_SMEM, st, a);
     TCVN_LAUNCH_CHECK();
     return 0;
 }
@@ -809,50 +807,6 @@ __global__ __launch_bounds__(256, 2) void k_sconv3_c64_wgrad(const W64Args g) {
     }
 }
 
-bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-bool geom_ok(const SConv& g) {
-    return conv3x3_tile_enabled() && g.mode == MODE_BF16 && g.ks == 3 && g.stride == 1 && g.pad == 1 && g.Cin == 64 && g.Cout == 64 && g.lda == 64 &&
-           g.Ho == g.Hin && g.Wo == g.Win && g.Kp == 576 && g.Kpt == 576 && (long)g.n * g.Hin * g.Win < (1L << 31) / 64;
-}
-
-}  // namespace
-
-namespace {
-bool geom_g_ok(const SConv& g) {
-    return conv3x3_tile_enabled() && g.mode == MODE_BF16 && g.ks == 3 && g.stride == 1 && g.pad == 1 && g.Cin % 64 == 0 && g.Cout % 64 == 0 &&
-           g.Cin <= 512 && g.Cout <= 512 && g.lda == g.Cin && g.Ho == g.Hin && g.Wo == g.Win && g.Kp == 9 * g.Cin && g.Kpt == 9 * g.Cout &&
-           !(g.Cin == 64 && g.Cout == 64);
-}
-}  // namespace
-bool sconv3_g_fwd_ok(const SConv& g, const void* In, const void* Wk, const void* Res, long ldres, const void* Out, long ldo, int out_f32) {
-    return geom_g_ok(g) && !out_f32 && ldo == g.Cout && (Res == nullptr || ldres == g.Cout) && al16(In) && al16(Wk) && al16(Res) && al16(Out);
-}
-bool sconv3_g_fuses_stats(const SConv& g) { const TileMap m = make_map(g.n, g.Hin, g.Win); return m.px == 1 && m.py == 1; }
-int sconv3_g_fwd(const SConv& g, const void* In, const void* Wk, const float* bias, const void* Res, void* Out, double* stats, hipStream_t st) {
-    return launch_g(g, In, g.Cin, Wk, g.Cout, bias, Res, Out, 0, stats, st);
-}
-bool sconv3_g_dgrad_ok(const SConv& g, const void* dOut, long lddo, const void* Wt, const void* dIn, long lddi) {
-    return geom_g_ok(g) && lddo == g.Cout && lddi == g.Cin && al16(dOut) && al16(Wt) && al16(dIn);
-}
-int sconv3_g_dgrad(const SConv& g, const void* dOut, const void* Wt, void* dIn, int accumulate, hipStream_t st) {
-    return launch_g(g, dOut, g.Cout, Wt, g.Cin, nullptr, accumulate ? dIn : nullptr, dIn, 1, nullptr, st);
-}
-
-bool sconv3_c64_fwd_ok(const SConv& g, const void* In, const void* Wk, const void* Res, long ldres, const void* Out, long ldo, int out_f32) {
-    return geom_ok(g) && !out_f32 && ldo == 64 && (Res == nullptr || ldres == 64) && al16(In) && al16(Wk) && al16(Res) && al16(Out);
-}
-int sconv3_c64_fwd(const SConv& g, const void* In, const void* Wk, const float* bias, const void* Res, void* Out, double* stats, hipStream_t st) {
-    return launch_c64(g, In, Wk, bias, Res, Out, 0, stats, st);
-}
-bool sconv3_c64_dgrad_ok(const SConv& g, const void* dOut, long lddo, const void* Wt, const void* dIn, long lddi) {
-    return geom_ok(g) && lddo == 64 && lddi == 64 && al16(dOut) && al16(Wt) && al16(dIn);
-}
-int sconv3_c64_dgrad(const SConv& g, const void* dOut, const void* Wt, void* dIn, int accumulate, hipStream_t st) {
-    return launch_c64(g, dOut, Wt, nullptr, accumulate ? dIn : nullptr, dIn, 1, nullptr, st);
-}
-
-namespace {
 // dWk[(n0 + n)*Kp + tap*Cin + c0 + c] += sum_x slab[x][sub][n][tap*64 + c]
 __global__ __launch_bounds__(256) void k_sub_reduce(const float* __restrict__ slab, int nx, int nsub, int ncc, int cin, float* __restrict__ dWk) {
     const int sub = blockIdx.y;
@@ -876,134 +830,110 @@ __global__ __launch_bounds__(256) void k_sub_reduce(const float* __restrict__ sl
     const int c0 = 64 * (sub % ncc), n0 = 64 * (sub / ncc);
     dWk[(long)(n0 + n) * (9 * cin) + tap * cin + c0 + c] += s0 + s1;
 }
-}  // namespace
 
-bool sconv3_g_wgrad_ok(const SConv& g, const void* In, const void* dOut, long lddo) {
-    return geom_g_ok(g) && lddo == g.Cout && al16(In) && al16(dOut) && g.slab != nullptr && g.slab_bytes >= kSconvSlabBytes;
-}
-int sconv3_g_wgrad(const SConv& g, const void* In, const void* dOut, float* dWk, float* dbias, hipStream_t st) {
-    W64Args a{};
-    a.In = reinterpret_cast<const bf16*>(In); a.dOut = reinterpret_cast<const bf16*>(dOut);
-    a.n = g.n; a.H = g.Hin; a.W_ = g.Win; a.cin = g.Cin; a.cout = g.Cout; a.Hi = g.Hin; a.Wi = g.Win;
-    a.map = make_map(g.n, g.Hin, g.Win); a.tiles_x = a.map.tiles_x; a.tiles_y = a.map.tiles_y; a.ntiles = a.map.ntiles();
-    const int ncc = g.Cin / 64, nsub = ncc * (g.Cout / 64);
-    int gx = 512 / nsub;                                           // slab holds 512 sub-block partials; two workgroups per CU
-    if (gx > a.ntiles) gx = a.ntiles;
-    if (gx < 1) gx = 1;
-    // bias gradient from the kernel's own dOut tiles (round 5; before: a separate column-sum pass over dOut, 73 launches and ~8 GB of reads per step):
-    // one row of cout sums per x-workgroup, behind the 512 weight sub-block slabs (gx * cout <= 512 * 64 floats)
-    a.slab = g.slab; a.bslab = dbias != nullptr ? g.slab + 512L * 64 * 576 : nullptr;
-    static bool attr = false;
-    if (!attr) {
-        TCVN_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_sconv3_c64_wgrad<1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)WG_SMEM));
-        attr = true;
-    }
-    if (a.map.px > 1 || a.map.py > 1) {
-        static bool attr2 = false;
-        if (!attr2) {
-            TCVN_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_sconv3_c64_wgrad<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)WG_SMEM));
-            attr2 = true;
-        }
-        hipLaunchKernelGGL((k_sconv3_c64_wgrad<1, true>), dim3(gx, nsub), dim3(256), WG_SMEM, st, a);
-    } else {
-        hipLaunchKernelGGL((k_sconv3_c64_wgrad<1, false>), dim3(gx, nsub), dim3(256), WG_SMEM, st, a);
-    }
-    TCVN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_sub_reduce, dim3((64 * 576 + 255) / 256, nsub), dim3(256), 0, st, a.slab, gx, nsub, ncc, g.Cin, dWk);
-    TCVN_LAUNCH_CHECK();
-    if (dbias != nullptr) return slab_reduce(a.bslab, gx, g.Cout, dbias, st);
-    return 0;
-}
-
-namespace {
-bool geom_s2_ok(const SConv& g) {
-    return conv3x3_tile_enabled() && g.mode == MODE_BF16 && g.ks == 3 && g.stride == 2 && g.pad == 0 && g.Cin % 64 == 0 && g.Cout % 64 == 0 &&
-           g.Cin <= 512 && g.Cout <= 512 && g.lda == g.Cin && g.Ho == (g.Hin - 2) / 2 + 1 && g.Wo == (g.Win - 2) / 2 + 1 &&
-           g.Kp == 9 * g.Cin && g.Kpt == 9 * g.Cout;
-}
-}  // namespace
-bool sconv3_s2_fwd_ok(const SConv& g, const void* In, const void* Wk, const void* Res, const void* Out, long ldo, int out_f32) {
-    return geom_s2_ok(g) && Res == nullptr && !out_f32 && ldo == g.Cout && al16(In) && al16(Wk) && al16(Out);
-}
-int sconv3_s2_fwd(const SConv& g, const void* In, const void* Wk, const float* bias, void* Out, double* stats, hipStream_t st) {
+int launch_s2_fwd(const SConvFwd& c, hipStream_t st) {
+    const SConv& g = c.g;
     S2Args a{};
-    a.stats = stats;
-    a.In = reinterpret_cast<const bf16*>(In); a.W = reinterpret_cast<const bf16*>(Wk); a.bias = bias; a.Out = reinterpret_cast<bf16*>(Out);
+    a.stats = g.stats;
+    a.In = reinterpret_cast<const bf16*>(c.In); a.W = reinterpret_cast<const bf16*>(c.Wk); a.bias = c.bias; a.Out = reinterpret_cast<bf16*>(c.Out);
     a.n = g.n; a.Hi = g.Hin; a.Wi = g.Win; a.Ho = g.Ho; a.Wo = g.Wo; a.cin = g.Cin; a.cout = g.Cout; a.nc = g.Cin / 64;
     a.tiles_x = (g.Wo + TW - 1) / TW; a.tiles_y = (g.Ho + 1) / 2; a.ntiles = g.n * a.tiles_x * a.tiles_y;
     static bool attr = false;
-    if (!attr) {
-        TCVN_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_sconv3_s2_fwd), hipFuncAttributeMaxDynamicSharedMemorySize, (int)S2_SMEM));
-        attr = true;
-    }
-    const int grid = a.ntiles < 256 ? a.ntiles : 256;
-    hipLaunchKernelGGL(k_sconv3_s2_fwd, dim3(grid, g.Cout / 64), dim3(256), S2_SMEM, st, a);
+    int rc;
+    if ((rc = allow_lds(reinterpret_cast<const void*>(k_sconv3_s2_fwd), (int)S2_SMEM, attr))) return rc;
+    hipLaunchKernelGGL(k_sconv3_s2_fwd, dim3(grid256(a.ntiles), g.Cout / 64), dim3(256), S2_SMEM, st, a);
     TCVN_LAUNCH_CHECK();
     return 0;
 }
-bool sconv3_s2_dgrad_ok(const SConv& g, const void* dOut, long lddo, const void* Wt, const void* dIn, long lddi) {
-    return geom_s2_ok(g) && g.Cout == 64 && lddo == 64 && lddi == g.Cin && al16(dOut) && al16(Wt) && al16(dIn);
-}
-int sconv3_s2_dgrad(const SConv& g, const void* dOut, const void* Wt, void* dIn, int accumulate, hipStream_t st) {
+int launch_s2_dgrad(const SConvDgrad& c, hipStream_t st) {
+    const SConv& g = c.g;
     D2Args a{};
-    a.dOut = reinterpret_cast<const bf16*>(dOut); a.Wt = reinterpret_cast<const bf16*>(Wt); a.dIn = reinterpret_cast<bf16*>(dIn);
-    a.n = g.n; a.Hi = g.Hin; a.Wi = g.Win; a.Ho = g.Ho; a.Wo = g.Wo; a.cin = g.Cin; a.accumulate = accumulate;
+    a.dOut = reinterpret_cast<const bf16*>(c.dOut); a.Wt = reinterpret_cast<const bf16*>(c.Wt); a.dIn = reinterpret_cast<bf16*>(c.dIn);
+    a.n = g.n; a.Hi = g.Hin; a.Wi = g.Win; a.Ho = g.Ho; a.Wo = g.Wo; a.cin = g.Cin; a.accumulate = c.accumulate;
     // half-resolution positions (Y, X) cover input pixels (2Y + py, 2X + px): Y up to ceil(Hi / 2) - 1
     const int hy = (g.Hin + 1) / 2, hx = (g.Win + 1) / 2;
     a.tiles_x = (hx + TW - 1) / TW; a.tiles_y = (hy + 3) / 4; a.ntiles = g.n * a.tiles_x * a.tiles_y;
     static bool attr = false;
-    if (!attr) {
-        TCVN_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_sconv3_s2_dgrad), hipFuncAttributeMaxDynamicSharedMemorySize, (int)D2_SMEM));
-        attr = true;
-    }
-    const int grid = a.ntiles < 256 ? a.ntiles : 256;
-    hipLaunchKernelGGL(k_sconv3_s2_dgrad, dim3(grid, g.Cin / 64), dim3(512), D2_SMEM, st, a);
+    int rc;
+    if ((rc = allow_lds(reinterpret_cast<const void*>(k_sconv3_s2_dgrad), (int)D2_SMEM, attr))) return rc;
+    hipLaunchKernelGGL(k_sconv3_s2_dgrad, dim3(grid256(a.ntiles), g.Cin / 64), dim3(512), D2_SMEM, st, a);
     TCVN_LAUNCH_CHECK();
-    return 0;
-}
-bool sconv3_s2_wgrad_ok(const SConv& g, const void* In, const void* dOut, long lddo) {
-    return geom_s2_ok(g) && lddo == g.Cout && al16(In) && al16(dOut) && g.slab != nullptr && g.slab_bytes >= kSconvSlabBytes;
-}
-int sconv3_s2_wgrad(const SConv& g, const void* In, const void* dOut, float* dWk, float* dbias, hipStream_t st) {
-    W64Args a{};
-    a.In = reinterpret_cast<const bf16*>(In); a.dOut = reinterpret_cast<const bf16*>(dOut);
-    a.n = g.n; a.H = g.Ho; a.W_ = g.Wo; a.Hi = g.Hin; a.Wi = g.Win; a.cin = g.Cin; a.cout = g.Cout;
-    a.tiles_x = (g.Wo + TW - 1) / TW; a.tiles_y = (g.Ho + 1) / 2; a.ntiles = g.n * a.tiles_x * a.tiles_y;
-    const int ncc = g.Cin / 64, nsub = ncc * (g.Cout / 64);
-    int gx = 512 / nsub;
-    if (gx > a.ntiles) gx = a.ntiles;
-    if (gx < 1) gx = 1;
-    a.slab = g.slab; a.bslab = dbias != nullptr ? g.slab + 512L * 64 * 576 : nullptr;
-    hipLaunchKernelGGL((k_sconv3_c64_wgrad<2, false>), dim3(gx, nsub), dim3(256), (size_t)(5 * 65 * 128 + 2 * TW * 128), st, a);
-    TCVN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_sub_reduce, dim3((64 * 576 + 255) / 256, nsub), dim3(256), 0, st, a.slab, gx, nsub, ncc, g.Cin, dWk);
-    TCVN_LAUNCH_CHECK();
-    if (dbias != nullptr) return slab_reduce(a.bslab, gx, g.Cout, dbias, st);
     return 0;
 }
 
-bool sconv3_c64_wgrad_ok(const SConv& g, const void* In, const void* dOut, long lddo) {
-    return geom_ok(g) && lddo == 64 && al16(In) && al16(dOut) && g.slab != nullptr &&
-           g.slab_bytes >= kSconvSlabBytes;
-}
-int sconv3_c64_wgrad(const SConv& g, const void* In, const void* dOut, float* dWk, float* dbias, hipStream_t st) {
+// The weight gradient of all three families is k_sconv3_c64_wgrad over 64 x 64 channel sub-blocks (blockIdx.y, c chunk fastest).  SCONV_G
+// walks the packed TileMap; SCONV_C64 (always one sub-block) and SCONV_S2 tile every image on its own.
+W64Args wgrad_args(SConvKernel k, const SConvWgrad& c) {
+    const SConv& g = c.g;
     W64Args a{};
-    a.In = reinterpret_cast<const bf16*>(In); a.dOut = reinterpret_cast<const bf16*>(dOut);
-    a.n = g.n; a.H = g.Hin; a.W_ = g.Win; a.cin = 64; a.cout = 64; a.Hi = g.Hin; a.Wi = g.Win;
-    a.tiles_x = (g.Win + TW - 1) / TW; a.tiles_y = (g.Hin + TH - 1) / TH; a.ntiles = g.n * a.tiles_x * a.tiles_y;
-    const int grid = a.ntiles < 512 ? (a.ntiles < 256 ? a.ntiles : 256) : 512;
-    a.slab = g.slab; a.bslab = g.slab + (long)grid * 64 * 576;
-    static bool attr = false;
-    if (!attr) {
-        TCVN_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_sconv3_c64_wgrad<1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)WG_SMEM));
-        attr = true;
+    a.In = reinterpret_cast<const bf16*>(c.In); a.dOut = reinterpret_cast<const bf16*>(c.dOut); a.slab = g.slab;
+    a.n = g.n; a.H = g.Ho; a.W_ = g.Wo; a.Hi = g.Hin; a.Wi = g.Win; a.cin = g.Cin; a.cout = g.Cout;
+    if (k == SCONV_G) {
+        a.map = make_map(g.n, g.Hin, g.Win); a.tiles_x = a.map.tiles_x; a.tiles_y = a.map.tiles_y; a.ntiles = a.map.ntiles();
+    } else {
+        a.tiles_x = (g.Wo + TW - 1) / TW; a.tiles_y = k == SCONV_S2 ? (g.Ho + 1) / 2 : (g.Ho + TH - 1) / TH; a.ntiles = g.n * a.tiles_x * a.tiles_y;
     }
-    hipLaunchKernelGGL((k_sconv3_c64_wgrad<1, false>), dim3(grid), dim3(256), WG_SMEM, st, a);
+    return a;
+}
+
+}  // namespace
+
+bool sconv3_packs(const SConv& g) { return packed(make_map(g.n, g.Hin, g.Win)); }
+
+int sconv3_fwd(SConvKernel k, const SConvFwd& c, hipStream_t st) {
+    const SConv& g = c.g;
+    switch (k) {
+    case SCONV_C64: return launch_c64(g, c.In, c.Wk, c.bias, c.Res, c.Out, 0, st);
+    case SCONV_G: return launch_g(g, c.In, g.Cin, c.Wk, g.Cout, c.bias, c.Res, c.Out, 0, st);
+    case SCONV_S2: return launch_s2_fwd(c, st);
+    default: return -2;
+    }
+}
+int sconv3_dgrad(SConvKernel k, const SConvDgrad& c, hipStream_t st) {
+    const SConv& g = c.g;
+    const void* acc = c.accumulate ? c.dIn : nullptr;              // accumulation = the gradient so far as the residual operand
+    switch (k) {
+    case SCONV_C64: return launch_c64(g, c.dOut, c.Wt, nullptr, acc, c.dIn, 1, st);
+    case SCONV_G: return launch_g(g, c.dOut, g.Cout, c.Wt, g.Cin, nullptr, acc, c.dIn, 1, st);
+    case SCONV_S2: return launch_s2_dgrad(c, st);
+    default: return -2;
+    }
+}
+int sconv3_wgrad(SConvKernel k, const SConvWgrad& c, hipStream_t st) {
+    const SConv& g = c.g;
+    W64Args a = wgrad_args(k, c);
+    static bool attr = false, attr_pack = false;
+    int rc;
+    if (k == SCONV_C64) {
+        // one slab per workgroup, two workgroups per CU; the bias rows sit behind the slabs in use
+        const int grid = a.ntiles < 512 ? grid256(a.ntiles) : 512;
+        a.bslab = g.slab + (long)grid * 64 * 576;
+        if ((rc = allow_lds(reinterpret_cast<const void*>(k_sconv3_c64_wgrad<1, false>), (int)WG_SMEM, attr))) return rc;
+        hipLaunchKernelGGL((k_sconv3_c64_wgrad<1, false>), dim3(grid), dim3(256), WG_SMEM, st, a);
+        TCVN_LAUNCH_CHECK();
+        SlabJob none{};
+        return slab_reduce2(slab_job(a.slab, grid, 64L * 576, c.dWk, 0), c.dbias ? slab_job(a.bslab, grid, 64, c.dbias, 0) : none, st);
+    }
+    const int ncc = g.Cin / 64, nsub = ncc * (g.Cout / 64);
+    int gx = 512 / nsub;                                           // slab holds 512 sub-block partials; two workgroups per CU
+    if (gx > a.ntiles) gx = a.ntiles;
+    if (gx < 1) gx = 1;
+    // bias gradient from the kernel's own dOut tiles: one row of cout sums per x-workgroup, behind the 512 weight sub-block slabs
+    // (gx * cout <= 512 * 64 floats)
+    a.bslab = c.dbias != nullptr ? g.slab + 512L * 64 * 576 : nullptr;
+    if (k == SCONV_S2) {
+        hipLaunchKernelGGL((k_sconv3_c64_wgrad<2, false>), dim3(gx, nsub), dim3(256), (size_t)(5 * 65 * 128 + 2 * TW * 128), st, a);
+    } else if (packed(a.map)) {
+        if ((rc = allow_lds(reinterpret_cast<const void*>(k_sconv3_c64_wgrad<1, true>), (int)WG_SMEM, attr_pack))) return rc;
+        hipLaunchKernelGGL((k_sconv3_c64_wgrad<1, true>), dim3(gx, nsub), dim3(256), WG_SMEM, st, a);
+    } else {
+        if ((rc = allow_lds(reinterpret_cast<const void*>(k_sconv3_c64_wgrad<1, false>), (int)WG_SMEM, attr))) return rc;
+        hipLaunchKernelGGL((k_sconv3_c64_wgrad<1, false>), dim3(gx, nsub), dim3(256), WG_SMEM, st, a);
+    }
     TCVN_LAUNCH_CHECK();
-    SlabJob none{};
-    SlabJob jw = slab_job(a.slab, grid, 64L * 576, dWk, 0);
-    SlabJob jb = dbias ? slab_job(a.bslab, grid, 64, dbias, 0) : none;
-    return slab_reduce2(jw, jb, st);
+    hipLaunchKernelGGL(k_sub_reduce, dim3((64 * 576 + 255) / 256, nsub), dim3(256), 0, st, a.slab, gx, nsub, ncc, g.Cin, c.dWk);
+    TCVN_LAUNCH_CHECK();
+    return c.dbias != nullptr ? slab_reduce(a.bslab, gx, g.Cout, c.dbias, st) : 0;
 }
 
 }  // namespace tcvn

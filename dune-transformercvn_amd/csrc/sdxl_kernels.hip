@@ -5,6 +5,8 @@
 // two-phase reduction (per-image fp64 sums, then the normalising pass).  The convolution operands are plain tensors: the
 // normalised + activated input of every convolution is materialised once by gn_act (it is read by the forward AND the
 // weight-gradient GEMM), residual adds and biases are epilogues.
+// Also here, behind the kernels: which kernel family a convolution runs (sconv_fwd_kernel / sconv_dgrad_kernel / sconv_wgrad_kernel;
+// the tile families' kernels are in sdxl_conv3x3.hip and sdxl_stem.hip) and the three entry points that switch over the answer.
 #include "conv_tile.h"
 #include "prof.h"
 #include "sdxl_ops.h"
@@ -676,31 +678,42 @@ __global__ void k_add_into(T* dst, long ldd, const T* src, long lds, long rows, 
 
 int grid_for(int M) { const int t = cdiv(M, BM); return t < 1024 ? t : 1024; }
 
+// launch(Elem<float>{}) or launch(Elem<bf16>{}), then the launch check: the one place a launcher turns `mode` into the element type
+template <typename T> struct Elem { using type = T; };
+template <typename F> int launch_by_mode(int mode, F&& launch) {
+    if (mode == MODE_F32) launch(Elem<float>{});
+    else launch(Elem<bf16>{});
+    TCVN_LAUNCH_CHECK();
+    return 0;
+}
+
 template <typename T>
-int fwd_t(const SConv& g, const void* In, const void* Wk, const float* bias, const void* Res, long ldres, void* Out, long ldo,
-          int out_f32, hipStream_t st) {
+int fwd_t(const SConvFwd& c, hipStream_t st) {
+    const SConv& g = c.g;
     const int M = g.n * g.Ho * g.Wo, K = g.ks * g.ks * g.Cin;
-    const T* in = reinterpret_cast<const T*>(In); const T* wk = reinterpret_cast<const T*>(Wk); const T* res = reinterpret_cast<const T*>(Res);
+    const T* in = reinterpret_cast<const T*>(c.In); const T* wk = reinterpret_cast<const T*>(c.Wk); const T* res = reinterpret_cast<const T*>(c.Res);
     const int gx = grid_for(M);
-    if (g.Cout <= 32) hipLaunchKernelGGL((k_sconv_fwd<T, 32>), dim3(gx, 1), dim3(NT), 0, st, g, in, wk, bias, res, ldres, Out, ldo, out_f32, M, K);
-    else if (g.Cout <= 64) hipLaunchKernelGGL((k_sconv_fwd<T, 64>), dim3(gx, 1), dim3(NT), 0, st, g, in, wk, bias, res, ldres, Out, ldo, out_f32, M, K);
-    else hipLaunchKernelGGL((k_sconv_fwd<T, 128>), dim3(gx, cdiv(g.Cout, 128)), dim3(NT), 0, st, g, in, wk, bias, res, ldres, Out, ldo, out_f32, M, K);
+    if (g.Cout <= 32) hipLaunchKernelGGL((k_sconv_fwd<T, 32>), dim3(gx, 1), dim3(NT), 0, st, g, in, wk, c.bias, res, c.ldres, c.Out, c.ldo, c.out_f32, M, K);
+    else if (g.Cout <= 64) hipLaunchKernelGGL((k_sconv_fwd<T, 64>), dim3(gx, 1), dim3(NT), 0, st, g, in, wk, c.bias, res, c.ldres, c.Out, c.ldo, c.out_f32, M, K);
+    else hipLaunchKernelGGL((k_sconv_fwd<T, 128>), dim3(gx, cdiv(g.Cout, 128)), dim3(NT), 0, st, g, in, wk, c.bias, res, c.ldres, c.Out, c.ldo, c.out_f32, M, K);
     TCVN_LAUNCH_CHECK();
     return 0;
 }
 template <typename T>
-int dgrad_t(const SConv& g, const void* dOut, long lddo, const void* Wt, void* dIn, long lddi, int accumulate, hipStream_t st) {
+int dgrad_t(const SConvDgrad& c, hipStream_t st) {
+    const SConv& g = c.g;
     const int M = g.n * g.Hin * g.Win, K = g.ks * g.ks * g.Cout;
-    const T* d = reinterpret_cast<const T*>(dOut); const T* wt = reinterpret_cast<const T*>(Wt); T* o = reinterpret_cast<T*>(dIn);
+    const T* d = reinterpret_cast<const T*>(c.dOut); const T* wt = reinterpret_cast<const T*>(c.Wt); T* o = reinterpret_cast<T*>(c.dIn);
     const int gx = grid_for(M);
-    if (g.Cin <= 32) hipLaunchKernelGGL((k_sconv_dgrad<T, 32>), dim3(gx, 1), dim3(NT), 0, st, g, d, lddo, wt, o, lddi, accumulate, M, K);
-    else if (g.Cin <= 64) hipLaunchKernelGGL((k_sconv_dgrad<T, 64>), dim3(gx, 1), dim3(NT), 0, st, g, d, lddo, wt, o, lddi, accumulate, M, K);
-    else hipLaunchKernelGGL((k_sconv_dgrad<T, 128>), dim3(gx, cdiv(g.Cin, 128)), dim3(NT), 0, st, g, d, lddo, wt, o, lddi, accumulate, M, K);
+    if (g.Cin <= 32) hipLaunchKernelGGL((k_sconv_dgrad<T, 32>), dim3(gx, 1), dim3(NT), 0, st, g, d, c.lddo, wt, o, c.lddi, c.accumulate, M, K);
+    else if (g.Cin <= 64) hipLaunchKernelGGL((k_sconv_dgrad<T, 64>), dim3(gx, 1), dim3(NT), 0, st, g, d, c.lddo, wt, o, c.lddi, c.accumulate, M, K);
+    else hipLaunchKernelGGL((k_sconv_dgrad<T, 128>), dim3(gx, cdiv(g.Cin, 128)), dim3(NT), 0, st, g, d, c.lddo, wt, o, c.lddi, c.accumulate, M, K);
     TCVN_LAUNCH_CHECK();
     return 0;
 }
 template <typename T>
-int wgrad_t(const SConv& g, const void* In, const void* dOut, long lddo, float* dWk, float* dbias, hipStream_t st) {
+int wgrad_t(const SConvWgrad& c, hipStream_t st) {
+    const SConv& g = c.g;
     const int M = g.n * g.Ho * g.Wo, K = g.ks * g.ks * g.Cin;
     const int jt = cdiv(g.Kp, BJ);
     const int BIv = g.Cout <= 32 ? 32 : g.Cout <= 64 ? 64 : 128;
@@ -712,10 +725,10 @@ int wgrad_t(const SConv& g, const void* In, const void* dOut, long lddo, float* 
     const int rows = (int)round_up(cdiv(M, split), BK);
     split = cdiv(M, rows);
     const dim3 grid(jt, it, split);
-    const T* in = reinterpret_cast<const T*>(In); const T* d = reinterpret_cast<const T*>(dOut);
-    if (BIv == 32) hipLaunchKernelGGL((k_sconv_wgrad<T, 32>), grid, dim3(NT), 0, st, g, in, d, lddo, dWk, dbias, M, K, rows);
-    else if (BIv == 64) hipLaunchKernelGGL((k_sconv_wgrad<T, 64>), grid, dim3(NT), 0, st, g, in, d, lddo, dWk, dbias, M, K, rows);
-    else hipLaunchKernelGGL((k_sconv_wgrad<T, 128>), grid, dim3(NT), 0, st, g, in, d, lddo, dWk, dbias, M, K, rows);
+    const T* in = reinterpret_cast<const T*>(c.In); const T* d = reinterpret_cast<const T*>(c.dOut);
+    if (BIv == 32) hipLaunchKernelGGL((k_sconv_wgrad<T, 32>), grid, dim3(NT), 0, st, g, in, d, c.lddo, c.dWk, c.dbias, M, K, rows);
+    else if (BIv == 64) hipLaunchKernelGGL((k_sconv_wgrad<T, 64>), grid, dim3(NT), 0, st, g, in, d, c.lddo, c.dWk, c.dbias, M, K, rows);
+    else hipLaunchKernelGGL((k_sconv_wgrad<T, 128>), grid, dim3(NT), 0, st, g, in, d, c.lddo, c.dWk, c.dbias, M, K, rows);
     TCVN_LAUNCH_CHECK();
     return 0;
 }
@@ -725,61 +738,115 @@ const char* label(char* buf, size_t cap, const char* what, const SConv& g) {
     return buf;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Kernel choice: which geometries each tile family serves (its kernels are in sdxl_conv3x3.hip / sdxl_stem.hip) ...
+// ---------------------------------------------------------------------------------------------------------------------
+bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+bool geom_c64_ok(const SConv& g) {
+    return conv3x3_tile_enabled() && g.mode == MODE_BF16 && g.ks == 3 && g.stride == 1 && g.pad == 1 && g.Cin == 64 && g.Cout == 64 && g.lda == 64 &&
+           g.Ho == g.Hin && g.Wo == g.Win && g.Kp == 576 && g.Kpt == 576 && (long)g.n * g.Hin * g.Win < (1L << 31) / 64;
+}
+bool geom_g_ok(const SConv& g) {
+    return conv3x3_tile_enabled() && g.mode == MODE_BF16 && g.ks == 3 && g.stride == 1 && g.pad == 1 && g.Cin % 64 == 0 && g.Cout % 64 == 0 &&
+           g.Cin <= 512 && g.Cout <= 512 && g.lda == g.Cin && g.Ho == g.Hin && g.Wo == g.Win && g.Kp == 9 * g.Cin && g.Kpt == 9 * g.Cout &&
+           !(g.Cin == 64 && g.Cout == 64);
+}
+bool geom_s2_ok(const SConv& g) {
+    return conv3x3_tile_enabled() && g.mode == MODE_BF16 && g.ks == 3 && g.stride == 2 && g.pad == 0 && g.Cin % 64 == 0 && g.Cout % 64 == 0 &&
+           g.Cin <= 512 && g.Cout <= 512 && g.lda == g.Cin && g.Ho == (g.Hin - 2) / 2 + 1 && g.Wo == (g.Win - 2) / 2 + 1 &&
+           g.Kp == 9 * g.Cin && g.Kpt == 9 * g.Cout;
+}
+bool geom_in_ok(const SConv& g) {
+    return conv3x3_tile_enabled() && g.mode == MODE_BF16 && g.ks == 3 && g.stride == 1 && g.pad == 1 && g.Cin == 3 && g.Cout == 64 && g.lda == 3 &&
+           g.Ho == g.Hin && g.Wo == g.Win && g.Kp == 32;
+}
+bool has_slab(const SConv& g) { return g.slab != nullptr && g.slab_bytes >= kSconvSlabBytes; }
+
 }  // namespace
 
-int sconv_fwd(const SConv& g, const void* In, const void* Wk, const float* bias, const void* Res, long ldres, void* Out, long ldo,
-              int out_f32, hipStream_t st) {
+// ... and, per direction, the operands it needs: dense rows, 16-B aligned bases, bf16 output.  First match wins.
+SConvKernel sconv_fwd_kernel(const SConvFwd& c, bool* fuses_stats) {
+    const SConv& g = c.g;
+    SConvKernel k = SCONV_GENERIC;
+    if (geom_c64_ok(g) && !c.out_f32 && c.ldo == 64 && (c.Res == nullptr || c.ldres == 64) && al16(c.In) && al16(c.Wk) && al16(c.Res) && al16(c.Out))
+        k = SCONV_C64;
+    else if (geom_in_ok(g) && c.Res == nullptr && !c.out_f32 && c.ldo == 64 && al16(c.Wk) && al16(c.Out) && c.In != nullptr) k = SCONV_IN;
+    else if (geom_g_ok(g) && !c.out_f32 && c.ldo == g.Cout && (c.Res == nullptr || c.ldres == g.Cout) && al16(c.In) && al16(c.Wk) && al16(c.Res) &&
+             al16(c.Out))
+        k = SCONV_G;
+    else if (geom_s2_ok(g) && c.Res == nullptr && !c.out_f32 && c.ldo == g.Cout && al16(c.In) && al16(c.Wk) && al16(c.Out)) k = SCONV_S2;
+    // every tile kernel adds its stored values to g.stats in its epilogue, except SCONV_G on packed maps (several images per tile)
+    if (fuses_stats) *fuses_stats = k != SCONV_GENERIC && !(k == SCONV_G && sconv3_packs(g));
+    return k;
+}
+SConvKernel sconv_dgrad_kernel(const SConvDgrad& c) {
+    const SConv& g = c.g;
+    if (geom_c64_ok(g) && c.lddo == 64 && c.lddi == 64 && al16(c.dOut) && al16(c.Wt) && al16(c.dIn)) return SCONV_C64;
+    if (geom_g_ok(g) && c.lddo == g.Cout && c.lddi == g.Cin && al16(c.dOut) && al16(c.Wt) && al16(c.dIn)) return SCONV_G;
+    if (geom_s2_ok(g) && g.Cout == 64 && c.lddo == 64 && c.lddi == g.Cin && al16(c.dOut) && al16(c.Wt) && al16(c.dIn)) return SCONV_S2;
+    return SCONV_GENERIC;
+}
+SConvKernel sconv_wgrad_kernel(const SConvWgrad& c) {
+    const SConv& g = c.g;
+    if (geom_c64_ok(g) && c.lddo == 64 && al16(c.In) && al16(c.dOut) && has_slab(g)) return SCONV_C64;
+    if (geom_in_ok(g) && g.hits != nullptr && c.lddo == 64 && al16(c.dOut)) return SCONV_IN;
+    if (geom_g_ok(g) && c.lddo == g.Cout && al16(c.In) && al16(c.dOut) && has_slab(g)) return SCONV_G;
+    if (geom_s2_ok(g) && c.lddo == g.Cout && al16(c.In) && al16(c.dOut) && has_slab(g)) return SCONV_S2;
+    return SCONV_GENERIC;
+}
+
+int sconv_fwd(const SConvFwd& c, hipStream_t st) {
+    const SConv& g = c.g;
     if (g.n <= 0) return 0;
     if (g.Kp % BK != 0 || g.Kp < g.ks * g.ks * g.Cin) return -2;
     const double M = (double)g.n * g.Ho * g.Wo, es = g.mode == MODE_F32 ? 4.0 : 2.0;
     char nm[96];
     ProfScope ps(label(nm, sizeof(nm), "fwd", g), 2.0 * M * g.Cout * g.ks * g.ks * g.Cin,
-                 es * ((double)g.n * g.Hin * g.Win * g.Cin + M * g.Cout * (Res ? 2.0 : 1.0)), st);
-    // g.stats: the consumer GroupNorm's statistics.  The tile kernels accumulate them in their epilogue; any other path is followed by
-    // the stand-alone statistics pass, so the caller never runs one for a convolution it handed `stats` to.
+                 es * ((double)g.n * g.Hin * g.Win * g.Cin + M * g.Cout * (c.Res ? 2.0 : 1.0)), st);
+    // g.stats: the consumer GroupNorm's statistics.  A kernel that does not accumulate them in its epilogue is followed by the
+    // stand-alone statistics pass, so the caller never runs one for a convolution it handed `stats` to.
     int rc;
-    bool fused = true;
-    if (sconv3_c64_fwd_ok(g, In, Wk, Res, ldres, Out, ldo, out_f32)) rc = sconv3_c64_fwd(g, In, Wk, bias, Res, Out, g.stats, st);
-    else if (sconv_in_fwd_ok(g, In, Wk, Res, Out, ldo, out_f32)) rc = sconv_in_fwd(g, In, Wk, bias, Out, g.stats, st);
-    else if (sconv3_g_fwd_ok(g, In, Wk, Res, ldres, Out, ldo, out_f32)) {
-        fused = sconv3_g_fuses_stats(g);
-        rc = sconv3_g_fwd(g, In, Wk, bias, Res, Out, g.stats, st);
-    } else if (sconv3_s2_fwd_ok(g, In, Wk, Res, Out, ldo, out_f32)) rc = sconv3_s2_fwd(g, In, Wk, bias, Out, g.stats, st);
-    else {
-        fused = false;
-        rc = g.mode == MODE_F32 ? fwd_t<float>(g, In, Wk, bias, Res, ldres, Out, ldo, out_f32, st)
-                                : fwd_t<bf16>(g, In, Wk, bias, Res, ldres, Out, ldo, out_f32, st);
+    bool fused;
+    const SConvKernel k = sconv_fwd_kernel(c, &fused);
+    switch (k) {
+    case SCONV_C64: case SCONV_G: case SCONV_S2: rc = sconv3_fwd(k, c, st); break;
+    case SCONV_IN: rc = sconv_in_fwd(c, st); break;
+    default: rc = g.mode == MODE_F32 ? fwd_t<float>(c, st) : fwd_t<bf16>(c, st);
     }
     if (rc == 0 && g.stats != nullptr && !fused) {
-        GnArgs ga{g.mode, Out, ldo, g.n, g.Ho * g.Wo, g.Cout, nullptr, nullptr, 0.f, 0, g.stats};
+        GnArgs ga{g.mode, c.Out, c.ldo, g.n, g.Ho * g.Wo, g.Cout, nullptr, nullptr, 0.f, 0, g.stats};
         rc = gn_stats(ga, st);
     }
     return rc;
 }
-int sconv_dgrad(const SConv& g, const void* dOut, long lddo, const void* Wt, void* dIn, long lddi, int accumulate, hipStream_t st) {
+int sconv_dgrad(const SConvDgrad& c, hipStream_t st) {
+    const SConv& g = c.g;
     if (g.n <= 0) return 0;
     if (g.Kpt % BK != 0 || g.Kpt < g.ks * g.ks * g.Cout) return -2;
     const double Mi = (double)g.n * g.Hin * g.Win, es = g.mode == MODE_F32 ? 4.0 : 2.0;
     char nm[96];
     ProfScope ps(label(nm, sizeof(nm), "dgrad", g), 2.0 * (double)g.n * g.Ho * g.Wo * g.Cout * g.ks * g.ks * g.Cin,
                  es * ((double)g.n * g.Ho * g.Wo * g.Cout + Mi * g.Cin), st);
-    if (sconv3_c64_dgrad_ok(g, dOut, lddo, Wt, dIn, lddi)) return sconv3_c64_dgrad(g, dOut, Wt, dIn, accumulate, st);
-    if (sconv3_g_dgrad_ok(g, dOut, lddo, Wt, dIn, lddi)) return sconv3_g_dgrad(g, dOut, Wt, dIn, accumulate, st);
-    if (sconv3_s2_dgrad_ok(g, dOut, lddo, Wt, dIn, lddi)) return sconv3_s2_dgrad(g, dOut, Wt, dIn, accumulate, st);
-    return g.mode == MODE_F32 ? dgrad_t<float>(g, dOut, lddo, Wt, dIn, lddi, accumulate, st)
-                              : dgrad_t<bf16>(g, dOut, lddo, Wt, dIn, lddi, accumulate, st);
+    const SConvKernel k = sconv_dgrad_kernel(c);
+    switch (k) {
+    case SCONV_C64: case SCONV_G: case SCONV_S2: return sconv3_dgrad(k, c, st);
+    default: return g.mode == MODE_F32 ? dgrad_t<float>(c, st) : dgrad_t<bf16>(c, st);
+    }
 }
-int sconv_wgrad(const SConv& g, const void* In, const void* dOut, long lddo, float* dWk, float* dbias, hipStream_t st) {
+int sconv_wgrad(const SConvWgrad& c, hipStream_t st) {
+    const SConv& g = c.g;
     if (g.n <= 0) return 0;
     const double M = (double)g.n * g.Ho * g.Wo, es = g.mode == MODE_F32 ? 4.0 : 2.0;
     char nm[96];
     ProfScope ps(label(nm, sizeof(nm), "wgrad", g), 2.0 * M * g.Cout * g.ks * g.ks * g.Cin,
                  es * ((double)g.n * g.Hin * g.Win * g.Cin + M * g.Cout), st);
-    if (sconv3_c64_wgrad_ok(g, In, dOut, lddo)) return sconv3_c64_wgrad(g, In, dOut, dWk, dbias, st);
-    if (sconv_in_wgrad_ok(g, dOut, lddo)) return sconv_in_wgrad(g, In, dOut, dWk, dbias, st);
-    if (sconv3_g_wgrad_ok(g, In, dOut, lddo)) return sconv3_g_wgrad(g, In, dOut, dWk, dbias, st);
-    if (sconv3_s2_wgrad_ok(g, In, dOut, lddo)) return sconv3_s2_wgrad(g, In, dOut, dWk, dbias, st);
-    return g.mode == MODE_F32 ? wgrad_t<float>(g, In, dOut, lddo, dWk, dbias, st) : wgrad_t<bf16>(g, In, dOut, lddo, dWk, dbias, st);
+    const SConvKernel k = sconv_wgrad_kernel(c);
+    switch (k) {
+    case SCONV_C64: case SCONV_G: case SCONV_S2: return sconv3_wgrad(k, c, st);
+    case SCONV_IN: return sconv_in_wgrad(c, st);
+    default: return g.mode == MODE_F32 ? wgrad_t<float>(c, st) : wgrad_t<bf16>(c, st);
+    }
 }
 
 namespace {
@@ -792,10 +859,7 @@ bool gn_dense(const GnArgs& a) {
 int gn_stats(const GnArgs& a, hipStream_t st) {
     if (a.n <= 0) return 0;
     const dim3 grid(cdiv((long)a.HW * a.C, GN_CHUNK), a.n);
-    if (a.mode == MODE_F32) hipLaunchKernelGGL(k_gn_stats<float>, grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(k_gn_stats<bf16>, grid, dim3(256), 0, st, a);
-    TCVN_LAUNCH_CHECK();
-    return 0;
+    return launch_by_mode(a.mode, [&](auto e) { hipLaunchKernelGGL(k_gn_stats<typename decltype(e)::type>, grid, dim3(256), 0, st, a); });
 }
 int gn_act(const GnArgs& a, void* Out, long ldo, hipStream_t st) {
     if (a.n <= 0) return 0;
@@ -803,86 +867,61 @@ int gn_act(const GnArgs& a, void* Out, long ldo, hipStream_t st) {
     int gx = cdiv(per / 8 + 1, 256);
     if (gx > 2048) gx = 2048;
     const dim3 grid(gx, a.n);
-    if (gn_dense(a) && ldo == a.C) {
-        const size_t smem = 2 * (size_t)a.C * sizeof(float);
-        if (a.mode == MODE_F32) hipLaunchKernelGGL(k_gn_act_v<float>, grid, dim3(256), smem, st, a, reinterpret_cast<float*>(Out));
-        else hipLaunchKernelGGL(k_gn_act_v<bf16>, grid, dim3(256), smem, st, a, reinterpret_cast<bf16*>(Out));
-        TCVN_LAUNCH_CHECK();
-        return 0;
-    }
-    if (a.mode == MODE_F32) hipLaunchKernelGGL(k_gn_act<float>, grid, dim3(256), 0, st, a, reinterpret_cast<float*>(Out), ldo);
-    else hipLaunchKernelGGL(k_gn_act<bf16>, grid, dim3(256), 0, st, a, reinterpret_cast<bf16*>(Out), ldo);
-    TCVN_LAUNCH_CHECK();
-    return 0;
+    const bool dense = gn_dense(a) && ldo == a.C;
+    return launch_by_mode(a.mode, [&](auto e) {
+        using T = typename decltype(e)::type;
+        if (dense) hipLaunchKernelGGL(k_gn_act_v<T>, grid, dim3(256), 2 * (size_t)a.C * sizeof(float), st, a, reinterpret_cast<T*>(Out));
+        else hipLaunchKernelGGL(k_gn_act<T>, grid, dim3(256), 0, st, a, reinterpret_cast<T*>(Out), ldo);
+    });
 }
 int gn_bwd_reduce(const GnArgs& a, const void* dA, long ldda, double* bsum, float* dgamma, float* dbeta, hipStream_t st) {
     if (a.n <= 0) return 0;
     int rows = GN_CHUNK / a.C;
     if (rows < 1) rows = 1;
-    const dim3 grid(cdiv(a.HW, rows), a.n);
+    const bool dense = gn_dense(a) && ldda == a.C && 256 % (a.C / 8) == 0;
+    // dense: few workgroups per image, as every workgroup ends with 2C global atomics on the same dgamma / dbeta words
+    int gxv = cdiv(a.HW, 4096);
+    const int cap = a.n >= 64 ? 8 : a.n >= 8 ? 32 : 128;
+    if (gxv > cap) gxv = cap;
+    const dim3 grid(dense ? gxv : cdiv(a.HW, rows), a.n);
     const size_t smem = 2 * (size_t)a.C * sizeof(float);
-    if (gn_dense(a) && ldda == a.C && 256 % (a.C / 8) == 0) {
-        // few workgroups per image: every workgroup ends with 2C global atomics on the same dgamma / dbeta words
-        int gxv = cdiv(a.HW, 4096);
-        const int cap = a.n >= 64 ? 8 : a.n >= 8 ? 32 : 128;
-        if (gxv > cap) gxv = cap;
-        const dim3 grid(gxv, a.n);
-        if (a.mode == MODE_F32)
-            hipLaunchKernelGGL(k_gn_bwd_reduce_v<float>, grid, dim3(256), smem, st, a, reinterpret_cast<const float*>(dA), bsum, dgamma, dbeta, rows);
-        else
-            hipLaunchKernelGGL(k_gn_bwd_reduce_v<bf16>, grid, dim3(256), smem, st, a, reinterpret_cast<const bf16*>(dA), bsum, dgamma, dbeta, rows);
-        TCVN_LAUNCH_CHECK();
-        return 0;
-    }
-    if (a.mode == MODE_F32)
-        hipLaunchKernelGGL(k_gn_bwd_reduce<float>, grid, dim3(256), smem, st, a, reinterpret_cast<const float*>(dA), ldda, bsum, dgamma, dbeta, rows);
-    else
-        hipLaunchKernelGGL(k_gn_bwd_reduce<bf16>, grid, dim3(256), smem, st, a, reinterpret_cast<const bf16*>(dA), ldda, bsum, dgamma, dbeta, rows);
-    TCVN_LAUNCH_CHECK();
-    return 0;
+    return launch_by_mode(a.mode, [&](auto e) {
+        using T = typename decltype(e)::type;
+        const T* d = reinterpret_cast<const T*>(dA);
+        if (dense) hipLaunchKernelGGL(k_gn_bwd_reduce_v<T>, grid, dim3(256), smem, st, a, d, bsum, dgamma, dbeta, rows);
+        else hipLaunchKernelGGL(k_gn_bwd_reduce<T>, grid, dim3(256), smem, st, a, d, ldda, bsum, dgamma, dbeta, rows);
+    });
 }
 int gn_bwd_apply(const GnArgs& a, const void* dA, long ldda, const double* bsum, void* dX, long lddx, int accumulate, hipStream_t st) {
     if (a.n <= 0) return 0;
     const long per = (long)a.HW * a.C;
-    int gx = cdiv(per, 256 * 4);
+    const bool dense = gn_dense(a) && ldda == a.C && lddx == a.C;
+    int gx = dense ? cdiv(per / 8, 256 * 2) : cdiv(per, 256 * 4);
     if (gx > 2048) gx = 2048;
     if (gx < 1) gx = 1;
     const dim3 grid(gx, a.n);
-    if (gn_dense(a) && ldda == a.C && lddx == a.C) {
-        int gv = cdiv(per / 8, 256 * 2);
-        if (gv > 2048) gv = 2048;
-        if (gv < 1) gv = 1;
-        const size_t smem = 2 * (size_t)a.C * sizeof(float);
-        if (a.mode == MODE_F32)
-            hipLaunchKernelGGL(k_gn_bwd_apply_v<float>, dim3(gv, a.n), dim3(256), smem, st, a, reinterpret_cast<const float*>(dA), bsum, reinterpret_cast<float*>(dX), accumulate);
-        else
-            hipLaunchKernelGGL(k_gn_bwd_apply_v<bf16>, dim3(gv, a.n), dim3(256), smem, st, a, reinterpret_cast<const bf16*>(dA), bsum, reinterpret_cast<bf16*>(dX), accumulate);
-        TCVN_LAUNCH_CHECK();
-        return 0;
-    }
-    if (a.mode == MODE_F32)
-        hipLaunchKernelGGL(k_gn_bwd_apply<float>, grid, dim3(256), 0, st, a, reinterpret_cast<const float*>(dA), ldda, bsum, reinterpret_cast<float*>(dX), lddx, accumulate);
-    else
-        hipLaunchKernelGGL(k_gn_bwd_apply<bf16>, grid, dim3(256), 0, st, a, reinterpret_cast<const bf16*>(dA), ldda, bsum, reinterpret_cast<bf16*>(dX), lddx, accumulate);
-    TCVN_LAUNCH_CHECK();
-    return 0;
+    return launch_by_mode(a.mode, [&](auto e) {
+        using T = typename decltype(e)::type;
+        const T* d = reinterpret_cast<const T*>(dA); T* dx = reinterpret_cast<T*>(dX);
+        if (dense) hipLaunchKernelGGL(k_gn_bwd_apply_v<T>, grid, dim3(256), 2 * (size_t)a.C * sizeof(float), st, a, d, bsum, dx, accumulate);
+        else hipLaunchKernelGGL(k_gn_bwd_apply<T>, grid, dim3(256), 0, st, a, d, ldda, bsum, dx, lddx, accumulate);
+    });
 }
 int cast_f32_to(int mode, const float* src, long lds, void* dst, long ldd, long rows, int cols, hipStream_t st) {
     if (rows <= 0) return 0;
     const int gx = cdiv(rows * cols, 256);
-    if (mode == MODE_F32) hipLaunchKernelGGL(k_cast_f32_to<float>, dim3(gx), dim3(256), 0, st, src, lds, reinterpret_cast<float*>(dst), ldd, rows, cols);
-    else hipLaunchKernelGGL(k_cast_f32_to<bf16>, dim3(gx), dim3(256), 0, st, src, lds, reinterpret_cast<bf16*>(dst), ldd, rows, cols);
-    TCVN_LAUNCH_CHECK();
-    return 0;
+    return launch_by_mode(mode, [&](auto e) {
+        using T = typename decltype(e)::type;
+        hipLaunchKernelGGL(k_cast_f32_to<T>, dim3(gx), dim3(256), 0, st, src, lds, reinterpret_cast<T*>(dst), ldd, rows, cols);
+    });
 }
 int add_into(int mode, void* dst, long ldd, const void* src, long lds, long rows, int cols, hipStream_t st) {
     if (rows <= 0) return 0;
-    const long tot = rows * cols;
-    const int gx = cdiv(tot, 256);
-    if (mode == MODE_F32) hipLaunchKernelGGL(k_add_into<float>, dim3(gx), dim3(256), 0, st, reinterpret_cast<float*>(dst), ldd, reinterpret_cast<const float*>(src), lds, rows, cols);
-    else hipLaunchKernelGGL(k_add_into<bf16>, dim3(gx), dim3(256), 0, st, reinterpret_cast<bf16*>(dst), ldd, reinterpret_cast<const bf16*>(src), lds, rows, cols);
-    TCVN_LAUNCH_CHECK();
-    return 0;
+    const int gx = cdiv(rows * cols, 256);
+    return launch_by_mode(mode, [&](auto e) {
+        using T = typename decltype(e)::type;
+        hipLaunchKernelGGL(k_add_into<T>, dim3(gx), dim3(256), 0, st, reinterpret_cast<T*>(dst), ldd, reinterpret_cast<const T*>(src), lds, rows, cols);
+    });
 }
 
 }  // namespace tcvn

@@ -1,7 +1,16 @@
-// Launch interface of the SDXL-style embedder kernels (sdxl_kernels.hip): general NHWC convolutions as implicit GEMMs
-// (any kernel size / stride / top-left padding, forward, data gradient, weight gradient) and GroupNorm(1 group) + SiLU.
+// Launch interface of the SDXL-style embedder kernels: general NHWC convolutions (any kernel size / stride / top-left padding;
+// forward, data gradient, weight gradient) and GroupNorm(1 group) + SiLU.
 // Reference call sites: transformercvn/network/layers/sdxl_net.py:27-34,41-42 (diffusers.models.vae.Encoder, see
 // oracle/sdxl_oracle.py for the restated block definitions).
+//
+// A convolution is ONE call record per direction (SConvFwd / SConvDgrad / SConvWgrad: the geometry plus that direction's operands
+// and row strides) and runs on one of five kernel families, chosen by sconv_{fwd,dgrad,wgrad}_kernel and nowhere else:
+//   SCONV_GENERIC  implicit GEMM, any geometry, fp32 and bf16                                          (sdxl_kernels.hip)
+//   SCONV_C64      bf16 3x3 / stride 1 / pad 1, 64 -> 64: halo patch in LDS, weights in registers      (sdxl_conv3x3.hip)
+//   SCONV_G        bf16 3x3 / stride 1 / pad 1, channels multiples of 64 up to 512: chunked patch      (sdxl_conv3x3.hip)
+//   SCONV_S2       bf16 3x3 / stride 2 / pad 0 down-samplers, channels multiples of 64                 (sdxl_conv3x3.hip)
+//   SCONV_IN       bf16 conv_in 3 -> 64: gather-MFMA forward, weight gradient from the hit list        (sdxl_stem.hip)
+// sconv_fwd / sconv_dgrad / sconv_wgrad are a switch over that answer.
 #pragma once
 #include "tcvn_common.h"
 
@@ -22,40 +31,31 @@ struct SConv {
 };
 constexpr long kSconvSlabBytes = 512L * (64 * 576 + 64) * 4;     // what the 64 -> 64 weight-gradient kernel asks for
 
-int sconv_fwd(const SConv& g, const void* In, const void* Wk, const float* bias, const void* Res, long ldres, void* Out, long ldo,
-              int out_f32, hipStream_t st);
+struct SConvFwd { SConv g; const void* In; const void* Wk; const float* bias; const void* Res; long ldres; void* Out; long ldo; int out_f32; };
 // dIn[(img,y,x)][c] (+)= sum_{ky,kx,n} dOut[img][(y+pad-ky)/stride][(x+pad-kx)/stride][n] * W[n][c][ky][kx]  (exact divisions only)
-int sconv_dgrad(const SConv& g, const void* dOut, long lddo, const void* Wt, void* dIn, long lddi, int accumulate, hipStream_t st);
+struct SConvDgrad { SConv g; const void* dOut; long lddo; const void* Wt; void* dIn; long lddi; int accumulate; };
 // dWk[n][k] += sum_m dOut[m][n] * a(m, k) (fp32, kernel layout [Cout][Kp]);  dbias[n] += sum_m dOut[m][n]
-int sconv_wgrad(const SConv& g, const void* In, const void* dOut, long lddo, float* dWk, float* dbias, hipStream_t st);
+struct SConvWgrad { SConv g; const void* In; const void* dOut; long lddo; float* dWk; float* dbias; };
 
-// bf16 fast paths for 3x3 / stride 1 / pad 1, 64 -> 64 channels (sdxl_conv3x3.hip): halo patch in LDS, weights in registers
-bool sconv3_c64_fwd_ok(const SConv& g, const void* In, const void* Wk, const void* Res, long ldres, const void* Out, long ldo, int out_f32);
-int sconv3_c64_fwd(const SConv& g, const void* In, const void* Wk, const float* bias, const void* Res, void* Out, double* stats, hipStream_t st);
-bool sconv3_c64_dgrad_ok(const SConv& g, const void* dOut, long lddo, const void* Wt, const void* dIn, long lddi);
-int sconv3_c64_dgrad(const SConv& g, const void* dOut, const void* Wt, void* dIn, int accumulate, hipStream_t st);
-// general width (channels multiples of 64, <= 512): chunked patch, weight fragments streamed from L2
-bool sconv3_g_fwd_ok(const SConv& g, const void* In, const void* Wk, const void* Res, long ldres, const void* Out, long ldo, int out_f32);
-bool sconv3_g_fuses_stats(const SConv& g);
-int sconv3_g_fwd(const SConv& g, const void* In, const void* Wk, const float* bias, const void* Res, void* Out, double* stats, hipStream_t st);
-bool sconv3_g_dgrad_ok(const SConv& g, const void* dOut, long lddo, const void* Wt, const void* dIn, long lddi);
-int sconv3_g_dgrad(const SConv& g, const void* dOut, const void* Wt, void* dIn, int accumulate, hipStream_t st);
-bool sconv3_g_wgrad_ok(const SConv& g, const void* In, const void* dOut, long lddo);
-int sconv3_g_wgrad(const SConv& g, const void* In, const void* dOut, float* dWk, float* dbias, hipStream_t st);
-// 3x3 / stride 2 / pad 0 down-samplers (zeros beyond the map), channels multiples of 64
-bool sconv3_s2_fwd_ok(const SConv& g, const void* In, const void* Wk, const void* Res, const void* Out, long ldo, int out_f32);
-int sconv3_s2_fwd(const SConv& g, const void* In, const void* Wk, const float* bias, void* Out, double* stats, hipStream_t st);
-bool sconv3_s2_dgrad_ok(const SConv& g, const void* dOut, long lddo, const void* Wt, const void* dIn, long lddi);
-int sconv3_s2_dgrad(const SConv& g, const void* dOut, const void* Wt, void* dIn, int accumulate, hipStream_t st);
-bool sconv3_s2_wgrad_ok(const SConv& g, const void* In, const void* dOut, long lddo);
-int sconv3_s2_wgrad(const SConv& g, const void* In, const void* dOut, float* dWk, float* dbias, hipStream_t st);
-// conv_in (3 -> 64, sdxl_stem.hip): gather-MFMA forward, weight gradient from the hit list
-bool sconv_in_fwd_ok(const SConv& g, const void* In, const void* Wk, const void* Res, const void* Out, long ldo, int out_f32);
-int sconv_in_fwd(const SConv& g, const void* In, const void* Wk, const float* bias, void* Out, double* stats, hipStream_t st);
-bool sconv_in_wgrad_ok(const SConv& g, const void* dOut, long lddo);
-int sconv_in_wgrad(const SConv& g, const void* In, const void* dOut, float* dWk, float* dbias, hipStream_t st);
-bool sconv3_c64_wgrad_ok(const SConv& g, const void* In, const void* dOut, long lddo);
-int sconv3_c64_wgrad(const SConv& g, const void* In, const void* dOut, float* dWk, float* dbias, hipStream_t st);
+enum SConvKernel { SCONV_GENERIC, SCONV_C64, SCONV_G, SCONV_S2, SCONV_IN };
+// The ONE place per direction that chooses the kernel (every tile family goes through conv3x3_tile_enabled()).  fuses_stats: whether
+// the chosen kernel accumulates g.stats in its epilogue; after any other kernel sconv_fwd runs the stand-alone statistics pass.
+SConvKernel sconv_fwd_kernel(const SConvFwd& c, bool* fuses_stats = nullptr);
+SConvKernel sconv_dgrad_kernel(const SConvDgrad& c);
+SConvKernel sconv_wgrad_kernel(const SConvWgrad& c);
+
+int sconv_fwd(const SConvFwd& c, hipStream_t st);
+int sconv_dgrad(const SConvDgrad& c, hipStream_t st);
+int sconv_wgrad(const SConvWgrad& c, hipStream_t st);
+
+// behind the switch: the tile families of sdxl_conv3x3.hip (k = SCONV_C64 / SCONV_G / SCONV_S2) and of sdxl_stem.hip (SCONV_IN)
+int sconv3_fwd(SConvKernel k, const SConvFwd& c, hipStream_t st);
+int sconv3_dgrad(SConvKernel k, const SConvDgrad& c, hipStream_t st);
+int sconv3_wgrad(SConvKernel k, const SConvWgrad& c, hipStream_t st);
+int sconv_in_fwd(const SConvFwd& c, hipStream_t st);
+int sconv_in_wgrad(const SConvWgrad& c, hipStream_t st);
+// whether SCONV_G packs several maps of this size into one tile (TileMap); a packed tile cannot accumulate per-image statistics
+bool sconv3_packs(const SConv& g);
 
 // GroupNorm with ONE group (statistics over C*H*W of each image) followed by SiLU (act = 1) or nothing (act = 0).
 // stats: [n][2] doubles (sum, sum of squares), zeroed by the caller before gn_stats.

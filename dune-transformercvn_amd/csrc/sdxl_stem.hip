@@ -182,52 +182,39 @@ __global__ __launch_bounds__(256) void k_colsum64_bf16(const bf16* __restrict__ 
     }
 }
 
-bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-bool in_geom_ok(const SConv& g) {
-    return conv3x3_tile_enabled() && g.mode == MODE_BF16 && g.ks == 3 && g.stride == 1 && g.pad == 1 && g.Cin == 3 && g.Cout == 64 && g.lda == 3 &&
-           g.Ho == g.Hin && g.Wo == g.Win && g.Kp == 32;
-}
-
 }  // namespace
 
-bool sconv_in_fwd_ok(const SConv& g, const void* In, const void* Wk, const void* Res, const void* Out, long ldo, int out_f32) {
-    return in_geom_ok(g) && Res == nullptr && !out_f32 && ldo == 64 && al16(Wk) && al16(Out) && In != nullptr;
-}
-int sconv_in_fwd(const SConv& g, const void* In, const void* Wk, const float* bias, void* Out, double* stats, hipStream_t st) {
+int sconv_in_fwd(const SConvFwd& c, hipStream_t st) {
+    const SConv& g = c.g;
     InFwdArgs a{};
-    a.stats = stats;
-    a.img = reinterpret_cast<const bf16*>(In); a.W = reinterpret_cast<const bf16*>(Wk); a.bias = bias; a.Out = reinterpret_cast<bf16*>(Out);
+    a.stats = g.stats;
+    a.img = reinterpret_cast<const bf16*>(c.In); a.W = reinterpret_cast<const bf16*>(c.Wk); a.bias = c.bias; a.Out = reinterpret_cast<bf16*>(c.Out);
     a.n = g.n; a.H = g.Hin; a.W_ = g.Win;
     a.tiles_x = (g.Win + TW - 1) / TW; a.tiles_y = (g.Hin + TH - 1) / TH; a.ntiles = g.n * a.tiles_x * a.tiles_y;
     constexpr size_t smem = TH * TW * CP * 4 + (PH * PW * 3 + 8) * 2 + 16;
     static bool attr = false;
-    if (!attr) {
-        TCVN_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_sconv_in_fwd), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        attr = true;
-    }
+    int rc;
+    if ((rc = allow_lds(reinterpret_cast<const void*>(k_sconv_in_fwd), (int)smem, attr))) return rc;
     const int grid = a.ntiles < 512 ? a.ntiles : 512;
     hipLaunchKernelGGL(k_sconv_in_fwd, dim3(grid), dim3(256), smem, st, a);
     TCVN_LAUNCH_CHECK();
     return 0;
 }
 
-bool sconv_in_wgrad_ok(const SConv& g, const void* dOut, long lddo) {
-    return in_geom_ok(g) && g.hits != nullptr && lddo == 64 && al16(dOut);
-}
-int sconv_in_wgrad(const SConv& g, const void* In, const void* dOut, float* dWk, float* dbias, hipStream_t st) {
-    InWgradArgs a{g.hits, g.nnz, reinterpret_cast<const bf16*>(In), reinterpret_cast<const bf16*>(dOut), dWk, g.n, g.Hin, g.Win, g.Kp};
+int sconv_in_wgrad(const SConvWgrad& c, hipStream_t st) {
+    const SConv& g = c.g;
+    InWgradArgs a{g.hits, g.nnz, reinterpret_cast<const bf16*>(c.In), reinterpret_cast<const bf16*>(c.dOut), c.dWk, g.n, g.Hin, g.Win, g.Kp};
     if (g.nnz > 0) {
         long nb = (g.nnz + 63) / 64;                              // about 16 hits per wave
         if (nb > 256) nb = 256;
         hipLaunchKernelGGL(k_sconv_in_wgrad_sparse, dim3((int)nb), dim3(256), 0, st, a);
         TCVN_LAUNCH_CHECK();
     }
-    if (dbias != nullptr) {
+    if (c.dbias != nullptr) {
         const long rows = (long)g.n * g.Hin * g.Win;
         long nb = (rows + 32 * 64 - 1) / (32 * 64);
         if (nb > 1024) nb = 1024;
-        hipLaunchKernelGGL(k_colsum64_bf16, dim3((int)nb), dim3(256), 0, st, reinterpret_cast<const bf16*>(dOut), rows, dbias);
+        hipLaunchKernelGGL(k_colsum64_bf16, dim3((int)nb), dim3(256), 0, st, reinterpret_cast<const bf16*>(c.dOut), rows, c.dbias);
         TCVN_LAUNCH_CHECK();
     }
     return 0;

@@ -50,6 +50,14 @@ bool conv3x3_tile_ok(const ConvFwdArgs& a);
 int conv3x3_tile_nblk(const ConvFwdArgs& a);
 int conv3x3_fwd_tile(const ConvFwdArgs& a, hipStream_t st);
 bool conv3x3_tile_enabled();                         // false when TCVN_DISABLE_TILE is set
+// a tile kernel's dynamic LDS exceeds the 64 KB default: raised once per kernel
+inline int allow_lds(const void* kernel, int bytes, bool& done) {
+    if (!done) {
+        TCVN_CHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+        done = true;
+    }
+    return 0;
+}
 
 // ---------------------------------------------------------------------------------------------------------
 // BatchNorm plumbing

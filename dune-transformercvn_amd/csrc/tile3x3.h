@@ -151,14 +151,5 @@ inline int tile_grid2(long ntiles) {           // two workgroups per CU
 
 inline PadGeom geom_of(int M, int H, int W) { return PadGeom(M / (H * W), H, W); }      // n_img is recovered from M = n*H*W
 
-// the kernels' dynamic LDS exceeds the 64 KB default: raised once per kernel
-inline int allow_lds(const void* kernel, int bytes, bool& done) {
-    if (!done) {
-        TCVN_CHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-        done = true;
-    }
-    return 0;
-}
-
 }  // namespace t3
 }  // namespace tcvn

@@ -32,6 +32,7 @@ OCC_GROUP_EVENT, OCC_GROUP_MAP = 0, 1          # TCVN_OCC_GROUP_*: whose largest
 OCC_MAX_LEVELS = 16                 # TCVN_OCC_MAX_LEVELS: levels of one coarse-to-fine occlusion scan
 CURVE_MAX_STEPS, CURVE_MAX_TILES = 64, 4096    # TCVN_CURVE_MAX_*: steps of a deletion / insertion curve, tiles per map it can rank
 CURVE_DELETION, CURVE_INSERTION = 0, 1         # TCVN_CURVE_*: which hits a curve variant keeps
+SCONV_KERNELS = ("generic", "c64", "g", "s2", "in")    # TCVN_SCONV_*: kernel families of the SDXL embedder's convolutions
 
 
 class DenseNetCfg(C.Structure):
@@ -89,6 +90,8 @@ def _load():
     sig("tcvn_sdxl_forward", i32, vp, i32, vp, vp, i64, i32, f32, vp, i64, vp, i64, i32, u64, vp)
     sig("tcvn_sdxl_backward", i32, vp, i32, vp, i64, vp, i64, vp)
     sig("tcvn_sdxl_tap", i32, vp, i32, C.c_char_p, P(i64), P(i32), P(i32), P(i32), P(i32), P(i32), P(i32))
+    sig("tcvn_sdxl_num_convs", i32, vp)
+    sig("tcvn_sdxl_conv_kernels", i32, vp, i32, i32, P(i32), P(i32), P(i32))
     sig("tcvn_head_create", i32, P(HeadCfg), P(vp))
     sig("tcvn_head_destroy", None, vp)
     sig("tcvn_head_num_slots", i32, vp)
@@ -159,7 +162,7 @@ EXPORTS = [
     "tcvn_grad_sumsq", "tcvn_adamw_step", "tcvn_backward_overlap", "tcvn_profile_enable", "tcvn_profile_filter", "tcvn_profile_reset", "tcvn_profile_count", "tcvn_profile_get",
     "tcvn_focal_loss", "tcvn_dropout_keep", "tcvn_head_set_fused_encoder", "tcvn_head_embed", "tcvn_head_encode", "tcvn_head_decode", "tcvn_linear_forward",
     "tcvn_rows_bn_prelu_forward", "tcvn_linear_backward", "tcvn_rows_bn_prelu_backward", "tcvn_sdxl_create", "tcvn_sdxl_destroy", "tcvn_sdxl_num_slots", "tcvn_sdxl_slot", "tcvn_sdxl_bind",
-    "tcvn_sdxl_workspace_bytes", "tcvn_sdxl_forward", "tcvn_sdxl_backward", "tcvn_sdxl_tap",
+    "tcvn_sdxl_workspace_bytes", "tcvn_sdxl_forward", "tcvn_sdxl_backward", "tcvn_sdxl_tap", "tcvn_sdxl_num_convs", "tcvn_sdxl_conv_kernels",
     "tcvn_version", "tcvn_densenet_create", "tcvn_densenet_destroy", "tcvn_densenet_num_slots", "tcvn_densenet_slot",
     "tcvn_densenet_bind", "tcvn_densenet_workspace_bytes", "tcvn_densenet_forward", "tcvn_densenet_backward",
     "tcvn_densenet_tap", "tcvn_densenet_num_blocks", "tcvn_densenet_backward_blocks", "tcvn_head_create", "tcvn_head_destroy", "tcvn_head_num_slots", "tcvn_head_slot", "tcvn_head_bind",

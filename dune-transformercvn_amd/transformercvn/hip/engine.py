@@ -258,6 +258,16 @@ class SdxlEngine(_EmbedderEngine):
         self.out_dim = out_dim
         check(lib.tcvn_sdxl_create(C.byref(cfg), C.byref(self.handle)), "sdxl_create")
 
+    def conv_kernels(self, n_img: int) -> List[Tuple[str, Optional[str], str]]:
+        """tcvn_sdxl_conv_kernels: per convolution of the tape, the kernel family (_lib.SCONV_KERNELS) that a training step on n_img
+        maps runs forward, for the data gradient (None for conv_in, which has none) and for the weight gradient.  No GPU call."""
+        out = []
+        f, d, w = C.c_int(), C.c_int(), C.c_int()
+        for i in range(lib.tcvn_sdxl_num_convs(self.handle)):
+            check(lib.tcvn_sdxl_conv_kernels(self.handle, n_img, i, C.byref(f), C.byref(d), C.byref(w)), "sdxl_conv_kernels")
+            out.append(tuple(None if v.value < 0 else _lib.SCONV_KERNELS[v.value] for v in (f, d, w)))
+        return out
+
 
 class HeadEngine(_Plan):
     """Combined embedding + transformer encoder + decoders + focal loss (tcvn_head_* in include/tcvn_hip.h)."""

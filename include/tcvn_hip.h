@@ -125,6 +125,12 @@ int tcvn_sdxl_backward(tcvn_sdxl* p, int n_img, const float* d_out, int64_t d_ou
 /* taps: "img", "conv_in", "block<i>" (output of down block i in front of its downsampler), "mid" */
 int tcvn_sdxl_tap(const tcvn_sdxl* p, int n_img, const char* name, int64_t* byte_off, int* n, int* h, int* w, int* c, int* ld,
                   int* elem_bytes);
+/* Which kernel family convolution `conv_index` (tape order, 0 .. tcvn_sdxl_num_convs - 1) of a training step on n_img maps runs in each
+ * direction: TCVN_SCONV_*; *dgrad = -1 for conv_in, which has no data gradient.  Assumes a workspace at a 256-byte aligned address
+ * with the weight-gradient slab and a hit list present.  Makes no GPU call. */
+enum { TCVN_SCONV_GENERIC = 0, TCVN_SCONV_C64 = 1, TCVN_SCONV_G = 2, TCVN_SCONV_S2 = 3, TCVN_SCONV_IN = 4 };
+int tcvn_sdxl_num_convs(const tcvn_sdxl* p);
+int tcvn_sdxl_conv_kernels(const tcvn_sdxl* p, int n_img, int conv_index, int* fwd, int* dgrad, int* wgrad);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Token path: combined embedding, transformer encoder, decoders, focal loss
