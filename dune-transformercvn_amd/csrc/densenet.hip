@@ -727,10 +727,41 @@ int DenseNetPlan::tap(int n, const char* name, long* off, int* tn, int* th, int*
     }
     // output block: the rows its BatchNorm1d normalises (Linear output, fp32) and, after a train-mode forward, the (mean, 1 / sqrt(var + eps)) rows it saved
     if (s == "output_linear") { *off = L.Z; *th = 1; *tw = 1; *tc = *tld = cfg.out_dim; *tes = 4; return 0; }
-    if (s == "raw:grad1") {      // after a backward pass: the gradient accumulator of block 1's concat buffer (what reaches the stem)
+    // after a backward pass (read-only offsets into the backward layout)
+    if (s.rfind("raw:grad", 0) == 0) {      // the gradient accumulator of block b's concat buffer ("raw:grad1": what reaches the stem)
+        const int b = atoi(s.c_str() + 8) - 1;
+        if (b < 0 || b >= (int)blocks.size()) return -1;
         Layout Lb;
         layout(n, true, Lb);
-        *off = Lb.G[0]; *th = blocks[0].H; *tw = blocks[0].W; *tc = blocks[0].Ctot; *tld = blocks[0].ld; return 0;
+        *off = Lb.G[b]; *th = blocks[b].H; *tw = blocks[b].W; *tc = blocks[b].Ctot; *tld = blocks[b].ld; return 0;
+    }
+    if (s.rfind("raw:pq", 0) == 0) {        // the [2][ld] fp32 (P, Q) rows of block b's channels
+        const int b = atoi(s.c_str() + 6) - 1;
+        if (b < 0 || b >= (int)blocks.size()) return -1;
+        Layout Lb;
+        layout(n, true, Lb);
+        *tn = *th = *tw = 1; *off = Lb.pqD[b]; *tc = *tld = 2 * blocks[b].ld; *tes = 4; return 0;
+    }
+    if (s == "raw:dcondense") {             // fp32 [n][Cf]: the gradient with respect to "condense" (what the head pooling backward spreads over the last block)
+        Layout Lb;
+        layout(n, true, Lb);
+        *off = Lb.dF; *th = 1; *tw = 1; *tc = *tld = Cf; *tes = 4; return 0;
+    }
+    if (s.rfind("raw:du", 0) == 0) {        // "raw:du<b>": the bottleneck-sized scratch DU in block b's geometry -- every dense layer overwrites it, so
+        const int b = atoi(s.c_str() + 6) - 1;      // it holds the 3x3 data gradient of the layer that ran last (layer 0 of the lowest block run)
+        if (b < 0 || b >= (int)blocks.size()) return -1;
+        Layout Lb;
+        layout(n, true, Lb);
+        *off = Lb.du; *th = blocks[b].H; *tw = blocks[b].W; *tc = *tld = cfg.bn_size * cfg.growth; return 0;
+    }
+    if (s.rfind("raw:ey", 0) == 0) {        // "raw:ey<b>.<l>": the eff rows [pixels][32] of the layer's 3x3 output gradient; the buffer exists in bf16 mode with growth 32,
+        int b = 0, l = 0;                   // and only the consecutive-tile data-gradient kernel fills it (the caller knows which kernel ran)
+        if (sscanf(s.c_str(), "raw:ey%d.%d", &b, &l) != 2) return -1;
+        b -= 1;
+        Layout Lb;
+        layout(n, true, Lb);
+        if (b < 0 || b >= (int)blocks.size() || l < 0 || l >= blocks[b].L || Lb.EY3[b].empty()) return -1;
+        *off = Lb.EY3[b][l]; *th = blocks[b].H; *tw = blocks[b].W; *tc = *tld = 32; return 0;
     }
     if (s == "raw:head_stat") { *tn = *th = *tw = 1; *off = L.head_stat; *tc = *tld = 2 * cfg.out_dim; *tes = 4; return 0; }
     if (s.rfind("dense", 0) == 0) {

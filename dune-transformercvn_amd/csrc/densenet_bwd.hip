@@ -24,6 +24,50 @@ void tcvn::set_backward_overlap(int on) { g_backward_overlap = on; }
 // dst == nullptr switches the tap off (tests/test_backward_link_rider_gpu.py).
 static struct { int block, layer; float* dst; } g_pq_tap = {0, 0, nullptr};
 extern "C" void tcvn_debug_pq_tap(int block, int layer, float* dst) { g_pq_tap = {block, layer, dst}; }
+// Validation build: snapshots of the backward state around dense layer (block, layer), or around the block's transition / the head
+// (layer == -1), for tests/test_densenet_layers_float64_gpu.py.  The buffers involved are reused layer after layer, so armed layers are
+// copied device to device on the backward's stream into a caller-owned buffer: in front of the first launch G[block] and the block's
+// (P, Q) rows; behind the last launch G[block] and (P, Q) again, DU, (PY, QY) and the layer's eff rows EY3 (where the layout has them).
+// Sections in that order, each starting at a multiple of 256 bytes (tcvn_debug_layer_snapshot_report gives the total); a buffer that is
+// too small is refused.  The report also says which 3x3 data-gradient kernel ran (Conv3x3Dgrad), whether the fused 1x1 backward ran and
+// whether the data-gradient kernel filled EY3.  The backward-overlap side stream must be off (the default).
+struct LayerSnap { int block, layer; char* dst; long cap, bytes; int dgrad_kernel, fused1, ey_valid; };
+static std::vector<LayerSnap> g_snaps;
+static struct { int dgrad_kernel, fused1, ey_valid; } g_snap_path = {0, 0, 0};
+extern "C" void tcvn_debug_layer_snapshot_clear(void) { g_snaps.clear(); }
+extern "C" int tcvn_debug_layer_snapshot(int block, int layer, void* dst, int64_t cap) {
+    if (!dst || cap <= 0) return -1;
+    g_snaps.push_back(LayerSnap{block, layer, reinterpret_cast<char*>(dst), (long)cap, 0, 0, 0, 0});
+    return (int)g_snaps.size() - 1;
+}
+extern "C" int tcvn_debug_layer_snapshot_report(int i, int* dgrad_kernel, int* fused1, int* ey_valid, int64_t* bytes) {
+    if (i < 0 || i >= (int)g_snaps.size()) return -1;
+    *dgrad_kernel = g_snaps[i].dgrad_kernel; *fused1 = g_snaps[i].fused1; *ey_valid = g_snaps[i].ey_valid; *bytes = g_snaps[i].bytes;
+    return 0;
+}
+static int layer_snapshot(const DenseNetPlan& pl, const Step& s, int bi, int l, bool after) {
+    for (LayerSnap& sn : g_snaps) {
+        if (sn.block != bi || sn.layer != l) continue;
+        const BlockGeom& bg = pl.blocks[bi];
+        const int mid = pl.cfg.bn_size * pl.cfg.growth;
+        const long M = (long)s.n * bg.H * bg.W;
+        const long gb = round_up(M * bg.ld * pl.esz, 256), pb = round_up((long)bg.ld * 8, 256), db = round_up(M * mid * pl.esz, 256),
+                   yb = round_up((long)mid * 8, 256), eb = round_up(M * 32 * pl.esz, 256);
+        const bool ey = l >= 0 && !s.L.EY3[bi].empty();
+        sn.bytes = 2 * (gb + pb) + db + yb + (ey ? eb : 0);
+        if (sn.bytes > sn.cap) { fprintf(stderr, "tcvn: layer snapshot buffer too small (%ld < %ld)\n", sn.cap, sn.bytes); return -18; }
+        char* d = sn.dst + (after ? gb + pb : 0);
+        TCVN_CHECK(hipMemcpyAsync(d, s.ws + s.L.G[bi], (size_t)(M * bg.ld * pl.esz), hipMemcpyDeviceToDevice, s.st));
+        TCVN_CHECK(hipMemcpyAsync(d + gb, s.ws + s.L.pqD[bi], (size_t)bg.ld * 8, hipMemcpyDeviceToDevice, s.st));
+        if (!after || l < 0) continue;
+        d = sn.dst + 2 * (gb + pb);
+        TCVN_CHECK(hipMemcpyAsync(d, s.ws + s.L.du, (size_t)(M * mid * pl.esz), hipMemcpyDeviceToDevice, s.st));
+        TCVN_CHECK(hipMemcpyAsync(d + db, s.ws + s.L.pqY, (size_t)mid * 8, hipMemcpyDeviceToDevice, s.st));
+        if (ey) TCVN_CHECK(hipMemcpyAsync(d + db + yb, s.ws + s.L.EY3[bi][l], (size_t)(M * 32 * pl.esz), hipMemcpyDeviceToDevice, s.st));
+        sn.dgrad_kernel = g_snap_path.dgrad_kernel; sn.fused1 = g_snap_path.fused1; sn.ey_valid = g_snap_path.ey_valid;
+    }
+    return 0;
+}
 #endif
 
 namespace {
@@ -183,9 +227,22 @@ int DenseNetPlan::backward(int n, const float* d_out, long d_out_ld, char* ws, l
         if ((rc = bwd_output(s, d_out, d_out_ld))) return rc;
     }
     for (int bi = bi_hi; bi >= bi_lo; --bi) {
+#ifdef TCVN_DEBUG_KNOBS
+        if ((rc = layer_snapshot(*this, s, bi, -1, false))) return rc;
+#endif
         if ((rc = bwd_transition(s, bi))) return rc;
-        for (int l = blocks[bi].L - 1; l >= 0; --l)
+#ifdef TCVN_DEBUG_KNOBS
+        if ((rc = layer_snapshot(*this, s, bi, -1, true))) return rc;
+#endif
+        for (int l = blocks[bi].L - 1; l >= 0; --l) {
+#ifdef TCVN_DEBUG_KNOBS
+            if ((rc = layer_snapshot(*this, s, bi, l, false))) return rc;
+#endif
             if ((rc = bwd_layer(s, bi, l))) return rc;
+#ifdef TCVN_DEBUG_KNOBS
+            if ((rc = layer_snapshot(*this, s, bi, l, true))) return rc;
+#endif
+        }
     }
     if ((rc = drain(s))) return rc;                // the stem weight gradient uses the slab; k_unpack reads every weight gradient
     if (last_part && (rc = bwd_stem(s))) return rc;
@@ -310,6 +367,9 @@ int DenseNetPlan::bwd_layer(Step& s, int bi, int l) const {
         d.Wfrag = wk_frag(s.ws, L, ls.w2, 1); d.zeros = s.ws + L.zeros;
         ey_valid = fast3x3 && !L.EY3[bi].empty() && conv3x3_dgrad_kernel(d) == CONV3X3_DGRAD_CONSEC;      // the kernel that fills ey_out
         if (ey_valid) d.ey_out = s.ws + L.EY3[bi][l];
+#ifdef TCVN_DEBUG_KNOBS
+        g_snap_path.dgrad_kernel = (int)conv3x3_dgrad_kernel(d); g_snap_path.ey_valid = ey_valid ? 1 : 0;
+#endif
         d.nblk = conv_dgrad_nblk(d);
         if ((rc = conv_dgrad(d, st))) return rc;
         link2 = BnBwdLinkArgs{s.part, d.nblk, ls.n2.C, reinterpret_cast<const double*>(s.ws + L.bstatY[bi][l]), M, kEps, data[ls.n2.w],
@@ -324,6 +384,9 @@ int DenseNetPlan::bwd_layer(Step& s, int bi, int l) const {
     // per layer on the main stream and the TN GEMM competing on the side stream.
     Bwd1x1Args fa{};
     const bool fuse1 = bwd1x1_fill(bi, l, M, s.ws, L, fa);       // (the same function the forward asked before it dropped the activated copy)
+#ifdef TCVN_DEBUG_KNOBS
+    g_snap_path.fused1 = fuse1 ? 1 : 0;
+#endif
     SlabJob w3jobs[2] = {};        // the 3x3 weight gradient's slab reductions, folded into the fused kernel's reduction launch (same stream only)
     bool w3_deferred = false;
     {   // conv2 (3x3) weight gradient: beside the rest of this layer's data-gradient chain

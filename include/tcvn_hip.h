@@ -87,6 +87,10 @@ int tcvn_densenet_backward_blocks(tcvn_densenet* p, int n_img, const float* d_ou
  * "output_linear" (the fp32 rows the output block's BatchNorm1d normalises), in bf16 mode also the materialised operands
  * "xa<b>.<l>" / "ya<b>.<l>", and the raw regions "raw:wk","raw:tabs","raw:bstat<b>" (b = 0: norm0),"raw:ystat<b>.<l>","raw:head_stat",
  * "raw:isumy<b>.<l>" (exists only where the last forward derived norm2 link-free);
+ * after a backward pass also "raw:grad<b>" (gradient accumulator of block b's concat buffer), "raw:pq<b>" (its [2][ld] fp32 (P, Q) rows),
+ * "raw:du<b>" (the 3x3 data-gradient scratch in block b's geometry: it holds the layer that ran last) and "raw:ey<b>.<l>" (the eff rows
+ * [pixels][32] of a layer's 3x3 output gradient, bf16 mode with growth 32; filled only by the consecutive-tile data-gradient kernel)
+ * and "raw:dcondense" (fp32 [n][C]: the gradient with respect to "condense");
  * returns the byte offset into the workspace and the logical NHWC shape + channel stride + element size. */
 int tcvn_densenet_tap(const tcvn_densenet* p, int n_img, const char* name, int64_t* byte_off, int* n, int* h, int* w,
                       int* c, int* ld, int* elem_bytes);

@@ -184,7 +184,9 @@ def test_densenet_bf16_close_to_fp32_oracle(name, training):
 @pytest.mark.parametrize("name", ["mid"])
 def test_bf16_tile_kernels_match_generic_kernels(name, monkeypatch):
     """The padded-tile 3x3 kernels against the generic implicit-GEMM kernels (TCVN_DISABLE_TILE=1 on the -DTCVN_DEBUG_KNOBS build, separate process) on
-    identical bf16 inputs: same products, different summation order only."""
+    identical bf16 inputs: same products, different summation order only.  This compares two bf16 variants with each other through all
+    layers, so it guards drift through depth; the kernels themselves -- both variants, each against float64 on its own stored inputs,
+    element by element -- are guarded by test_densenet_layers_float64_gpu.py."""
     import subprocess, sys, os, json
     cfg, over, batch, g = _mid_case() if name == "mid" else load_case(name)
     cfg = train_cfg(over)
@@ -384,7 +386,11 @@ result = dict(out=out, taps=taps, grads=grads)
 @pytest.mark.parametrize("name", ["small_b3", "mid", "tutorial_b2p4"])
 def test_densenet_bf16_backward_tracks_fp64_oracle(name):
     """Every bf16 gradient tensor must point the same way as the fp64 oracle gradient (cosine) and have its size: a tiling /
-    layout bug in any of the bf16 kernels shows up as a cosine far from 1, bf16 rounding does not."""
+    layout bug in any of the bf16 kernels shows up as a cosine far from 1, bf16 rounding does not.  A whole-network bound: it guards drift
+    through depth and every backward kernel at once, loosely (for the layers between a block's first and last it is, with the variant
+    tests, still the only guard of the 1x1 backward and the links); test_densenet_layers_float64_gpu.py holds the forward kernels of every
+    layer, the 3x3 weight gradient of every layer and the whole backward of each block's first and last layer, transition and head to
+    float64 per element."""
     cfg, over, batch, g = _mid_case() if name == "mid" else load_case(name)
     cfg = train_cfg(over)
     sd = O.fill_state(cfg, int(g["weight_seed"]))

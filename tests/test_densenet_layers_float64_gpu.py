@@ -1,0 +1,579 @@
+"""Kernels of the HIP DenseNet, each against a float64 recomputation from its OWN stored inputs, element by element: every forward kernel, the
+3x3 data- and weight-gradient kernels and the transition data gradient.  Needs an MI355X.
+
+The whole-network tests (test_densenet_gpu.py) compare with an oracle through all layers, so their bounds must leave room for bf16 drift
+(3e-2 on dense1, 5e-2 on the embedding) -- room enough for a kernel that is wrong on a few pixels or channels.  Here each operation is
+recomputed in float64 (densenet_layer_reference.py) from the maps the engine stored (tap()), its (scale, shift) tables (raw:tabs) and the
+bound fp32 parameters, so no drift accumulates and the gate of every element comes from the arithmetic alone (that module's docstring;
+test_densenet_layer_reference_cpu.py shows that the listed defects leave these gates).  No element is excluded.
+
+Operations: pool0 (where the conv0 map exists), every dense layer's 1x1 and 3x3 (with the dropout keep scale of tcvn_dropout_keep kind 1,
+stream 64 b + l + 1), the materialised operands xa / ya where a build stores them, every transition, the head pooling, the output Linear.
+Builds: the product library in bf16 train mode (fused 1x1 on the raw buffer, activation inside the 3x3 pair kernel), bf16 eval mode
+(norm2 + PReLU2 in the 1x1 epilogue, stored ya) and fp32 mode; the validation library without the fusions (act_bf16 + NT GEMM, stored
+xa / ya) and with the generic kernels (TCVN_DISABLE_TILE), one child process each for all cases.  Each run asserts from the taps and the
+launch labels that it went through the kernels it is meant to cover.
+
+Backward.  The backward pass reuses its scratch buffers layer after layer, so what can be read back without a hook is what stays: G and
+(P, Q) of every layer's own slice (final once the layer has run: raw:grad<b>, raw:pq<b>), the eff rows the consecutive-tile kernel stores
+per layer (raw:ey<b>.<l>), the parameter gradients, and DU of the layer that ran last (raw:du<b>).  The backward is issued block by block
+(backward_part), and compared are:
+  * 3x3 data gradient: DU = sc2 dA prelu'(u2) of the FIRST layer of every block, element by element (its slice starts at c_off = the
+    block's first width, its keep stream is 64 b + 1), and the stored eff rows of every layer;
+  * 3x3 weight and bias gradient of EVERY layer, from the eff rows recomputed from the final (G, P, Q) slices (or the stored rows) and
+    the activated bottleneck map (or the stored ya);
+  * transition data gradient and head pooling backward, the first writers of a block's accumulator: the last layer's slice of G[b]
+    receives nothing but their contribution, so it is compared as the contribution alone -- for a transition exactly zero at the pixels
+    of an odd edge that no 2x2 window covers (the head's input is raw:dcondense).
+Builds: product (the kernel choice at these sizes), TCVN_DGRAD3_ANY_SIZE (the consecutive-tile data gradient with its eff rows feeding
+the weight gradient; the odd-width case, whose slices are not 16-byte aligned, stays on the two-workgroup kernel), TCVN_DISABLE_TILE,
+fp32.  With one image the output block's train-mode BatchNorm1d passes no gradient: every reference is exactly zero there, and so must
+the kernels' results be.
+The layers' transient state -- DU of any layer, (PY, QY), G[:, :cin] and (P, Q) in front of a layer's update -- is read through the snapshot
+hook of the validation build (tcvn_debug_layer_snapshot, densenet_bwd.hip), armed in one backward for the first and the last layer of
+every block and for its transition or the head (test_first_and_last_layer_backward_...): eff rows, DU, norm2's link (dgamma2, dbeta2,
+dslope2, PY, QY), db1, dW1, the read-add-write of G[:, :cin], norm1's link (dgamma1, dbeta1, dslope1, P / Q[:cin] +=), everything else of
+G, P, Q bit-unchanged; for the block's first writer G and (P, Q) over all channels as the contribution alone, the transition's weight and
+bias gradient and its norm's parameter gradients.  Builds: validation library without knobs (the product kernel choice; also in fp32
+mode), TCVN_DGRAD3_ANY_SIZE, the unfused build (eff_materialize, TN and NT GEMMs on stored operands) and TCVN_DISABLE_TILE.  The hook's
+report (which 3x3 data-gradient kernel ran, whether the fused 1x1 backward ran, whether the eff rows were stored) and the launch labels
+are asserted per build."""
+import ctypes as C
+import functools
+
+import pytest
+import torch
+
+import densenet_layer_reference as R
+from oracle import tcvn_oracle as O
+from test_densenet_gpu import _conv0_activity, _engine
+
+pytestmark = pytest.mark.gpu
+
+F32, BF16 = 0, 1
+SEED = 11
+
+
+def _all_maps(batch):
+    """One COO list over the event map and the prong maps of a synthetic batch with one event: image 0 = the event map."""
+    pc = batch[5].clone()
+    pc[:, 0] += 1
+    return torch.cat([batch[2], pc]).contiguous(), torch.cat([batch[3], batch[6]]).contiguous(), 1 + int(batch[7].sum())
+
+
+def _case(name):
+    """-> cfg, coords, values, n_img"""
+    base = dict(pixel_noise_std=0.0, num_encoder_layers=2)
+    if name in ("wide", "wide-dropout"):      # block 1 as wide as production's: conv0 20 x 140, block 1 9 x 69 (odd in front of the transition), block 2 4 x 34
+        cfg = O.tutorial_config(pixel_shape=(40, 280), densenet_structure=[3, 2], dropout=0.1 if name == "wide-dropout" else 0.0, **base)
+        b = O.synthetic_batch([3], 47, cfg, prong_hits=(20, 400))
+        return cfg, b[5], b[6], 3
+    if name == "odd":                         # cin = 250 .. 538: cin % 8 == 2, two to five 128-column slices, cin > 512 at the last layer
+        cfg = O.tutorial_config(initial_pixel_dim=250, densenet_structure=[10], pixel_shape=(56, 40), dropout=0.0, **base)
+        return (cfg,) + _all_maps(O.synthetic_batch([2], 41, cfg, event_hits=(60, 200), prong_hits=(20, 120)))
+    cfg = O.tutorial_config(pixel_shape=(104, 72), densenet_structure=[3, 3, 2], dropout=0.0, **base)      # block 1 26 x 18 ... block 3 6 x 4
+    if name == "narrow-one":                  # one image: the last block has fewer padded positions than one 128-position tile
+        b = O.synthetic_batch([1], 53, cfg, prong_hits=(60, 200))
+        return cfg, b[5], b[6], 1
+    assert name == "narrow"
+    return (cfg,) + _all_maps(O.synthetic_batch([2], 41, cfg))
+
+
+CASES = ["wide", "wide-dropout", "narrow", "narrow-one", "odd"]
+
+
+def _geometry(cfg):
+    """Per block (H, W, first cin), from the config alone (the runs assert the tapped maps have these sizes)."""
+    H, W = ((s - 1) // 2 + 1 for s in cfg.pixel_shape)
+    H, W = (H - 3) // 2 + 1, (W - 3) // 2 + 1
+    out, ch = [], cfg.initial_pixel_dim
+    for layers in cfg.densenet_structure:
+        out.append((H, W, ch))
+        ch = (ch + layers * cfg.densenet_growth_rate) // 2
+        H, W = H // 2, W // 2
+    return out
+
+
+def _keep(p, seed, sid, rows, cols):
+    from transformercvn.hip._lib import lib, check
+    out = torch.empty(rows, cols, device="cuda")
+    check(lib.tcvn_dropout_keep(1, float(p), C.c_uint64(seed), C.c_uint32(sid), rows, cols, C.c_void_p(out.data_ptr()),
+                                C.c_void_p(torch.cuda.current_stream().cuda_stream)), "dropout_keep")
+    return out
+
+
+def _exists(eng, name):
+    """Does the plan have this tap?  Only the plan's own "no such tap" answer (code -1 of tcvn_densenet_tap) means no; any other error
+    -- a HIP error among them -- is raised."""
+    try:
+        eng.tap(name)
+    except RuntimeError as err:
+        if str(err) != f"libtcvn_hip: tap {name} failed with code -1":
+            raise
+        return False
+    return True
+
+
+def _tap(eng, name):
+    return eng.tap(name).detach().double().cpu() if _exists(eng, name) else None
+
+
+def _run(case, mode, train):
+    """One forward of the case on a fresh engine, the float64 recomputation of every operation, the comparison -> report (plain data: it
+    also travels from a child process)."""
+    from transformercvn.hip import _lib
+    cfg, coords, values, n_img = _case(case)
+    sd = O.fill_state(cfg, 19)
+    eng, data, _ = _engine(cfg, sd, mode=mode)
+    out = torch.empty(n_img, eng.out_dim, device="cuda")
+    _lib.lib.tcvn_profile_filter(None); _lib.lib.tcvn_profile_reset(); _lib.lib.tcvn_profile_enable(1)
+    eng.forward(coords.cuda(), values.cuda(), n_img, out, train=train, seed=SEED)
+    torch.cuda.synchronize()
+    _lib.lib.tcvn_profile_enable(0)
+    labels = [r[0] for r in _lib.profile_records()]
+    _lib.lib.tcvn_profile_reset()
+
+    geo = _geometry(cfg)
+    g = cfg.densenet_growth_rate
+    P = {k: v.detach().double().cpu() for k, v in data.items()}
+    stored, paths, keeps = {}, [], {}
+    for b, layers in enumerate(cfg.densenet_structure):
+        stored[f"dense{b + 1}"] = _tap(eng, f"dense{b + 1}")
+        assert tuple(stored[f"dense{b + 1}"].shape[1:3]) == geo[b][:2], (stored[f"dense{b + 1}"].shape, geo[b])
+        for l in range(layers):
+            for nm in (f"bottleneck{b + 1}.{l}", f"xa{b + 1}.{l}", f"ya{b + 1}.{l}"):
+                t = _tap(eng, nm)
+                if t is not None:
+                    stored[nm] = t
+            paths.append((b, l, geo[b][2] + l * g, f"xa{b + 1}.{l}" in stored, f"ya{b + 1}.{l}" in stored, f"bottleneck{b + 1}.{l}" in stored,
+                          _exists(eng, f"raw:isumy{b + 1}.{l}")))
+            if train and cfg.dropout > 0:
+                H, W, _ = geo[b]
+                keeps[(b, l)] = _keep(cfg.dropout, SEED, 64 * b + l + 1, n_img * H * W, g).double().cpu().reshape(n_img, H, W, g)
+    stored["condense"] = _tap(eng, "condense").reshape(n_img, -1)
+    stored["output_linear"] = _tap(eng, "output_linear").reshape(n_img, -1)
+    c0 = _tap(eng, "conv0")
+    if c0 is not None:                        # a row no hit reaches is the stored-precision bias row, whether or not the stem wrote it
+        act = _conv0_activity(coords, n_img, c0.shape[1], c0.shape[2])
+        bias_row = P["features.conv0.bias"]
+        c0 = torch.where(act[..., None], c0, (R.bf16(bias_row) if mode == BF16 else bias_row).expand_as(c0))
+    tabs = _tap(eng, "raw:tabs").flatten()
+    checks, _ = R.run_forward(cfg, P, mode == BF16, train, c0, keeps or None, stored=stored, tabs=tabs)
+    figures = []
+    for c in checks:
+        worst, bad, where = c.ratio(R.stored_counterpart(c, stored))
+        figures.append((c.name, c.kernel, worst, bad, c.ref.numel(), where))
+    pp = [n_img * (H + 2) * (W + 2) for H, W, _ in geo]
+    return dict(figures=figures, labels=labels, paths=paths, padded=pp, geometry=geo, conv0=c0 is not None,
+                dropped=sum(int((k == 0).sum()) for k in keeps.values()))
+
+
+def _run_backward(case, mode, generic=False):
+    """Train-mode forward, then the backward block by block (last block first); after each block the 3x3 data gradient of its first layer
+    and the stored eff rows of all its layers against float64 -> report."""
+    from transformercvn.hip import _lib
+    cfg, coords, values, n_img = _case(case)
+    sd = O.fill_state(cfg, 19)
+    eng, data, grads = _engine(cfg, sd, mode=mode, with_grad=True)
+    out = torch.empty(n_img, eng.out_dim, device="cuda")
+    eng.forward(coords.cuda(), values.cuda(), n_img, out, train=True, seed=SEED)
+    d_out = torch.randn(n_img, eng.out_dim, generator=torch.Generator().manual_seed(5)).cuda()
+    geo, g, rnd = _geometry(cfg), cfg.densenet_growth_rate, mode == BF16
+    P = {k: v.detach().double().cpu() for k, v in data.items()}
+    tabd = R.tables_from_tabs(cfg, _tap(eng, "raw:tabs").flatten())
+    for b, layers in enumerate(cfg.densenet_structure):           # the eff-row buffers start as NaN: a kernel that fills one leaves none
+        for l in range(layers):
+            if _exists(eng, f"raw:ey{b + 1}.{l}"):
+                eng.tap(f"raw:ey{b + 1}.{l}").fill_(float("nan"))
+    _lib.lib.tcvn_profile_filter(None); _lib.lib.tcvn_profile_reset(); _lib.lib.tcvn_profile_enable(1)
+    figures, ey_filled = [], []
+    for b in reversed(range(len(cfg.densenet_structure))):
+        eng.backward_part(d_out, b)
+        torch.cuda.synchronize()
+        H, W, c0 = geo[b]
+        G, X, pq = _tap(eng, f"raw:grad{b + 1}"), _tap(eng, f"dense{b + 1}"), _tap(eng, f"raw:pq{b + 1}").flatten()
+        Pr, Qr = pq[:pq.numel() // 2], pq[pq.numel() // 2:]
+        for l in range(cfg.densenet_structure[b]):
+            p = f"features.dense{b + 1}.layers.{l}"
+            c_off = c0 + l * g
+            keep = _keep(cfg.dropout, SEED, 64 * b + l + 1, n_img * H * W, g).double().cpu().reshape(n_img, H, W, g) if cfg.dropout > 0 else None
+            ey = _tap(eng, f"raw:ey{b + 1}.{l}")
+            if ey is not None and bool(torch.isnan(ey).all()):
+                ey = None                                          # untouched: another kernel ran
+            ey_filled.append(ey is not None)
+            # ---- 3x3 weight and bias gradient: every layer (the parameter gradients are the layer's own)
+            c_sl = slice(c_off, c_off + g)
+            fe, taue, e, de = R.eff_rows(G[..., c_sl], X[..., c_sl], Pr[c_sl], Qr[c_sl], keep, rnd)
+            if ey is not None:
+                e, de = ey, torch.zeros_like(ey)
+            sc2, sh2 = tabd[p + ".output_block.norm2"]
+            _, _, a2, da2 = R.activation(_tap(eng, f"bottleneck{b + 1}.{l}"), sc2, sh2, P[p + ".output_block.relu2.weight"], rnd)
+            ya = _tap(eng, f"ya{b + 1}.{l}")
+            if ya is not None:                                      # the materialised operand (checked by the forward test)
+                a2, da2 = ya, torch.zeros_like(ya)
+            (dW, dWd), (db, dbd) = R.conv3x3_wgrad(e, de, a2, da2, rnd, bias_terms=(fe, taue) if generic else None)
+            for nm, ref, dl in ((".output_block.conv2.weight", dW, dWd), (".output_block.conv2.bias", db, dbd)):
+                c = R.Check(p + nm, "wgrad3x3", ref, dl, False)
+                worst, bad, where = c.ratio(grads[p + nm].detach().double().cpu().reshape(ref.shape))
+                figures.append((c.name, c.kernel, worst, bad, ref.numel(), where, 0, float(ref.abs().max())))
+            if l == 0:
+                checks = R.dgrad3_layer(f"dense{b + 1}.{l}", G, X, Pr, Qr, keep, _tap(eng, f"bottleneck{b + 1}.{l}"), sc2, sh2,
+                                        P[p + ".output_block.relu2.weight"], P[p + ".output_block.conv2.weight"], rnd, c_off, ey)
+                got = [ey, _tap(eng, f"raw:du{b + 1}")] if ey is not None else [_tap(eng, f"raw:du{b + 1}")]
+            elif ey is not None:
+                checks, got = [R.Check(f"dense{b + 1}.{l}:ey", "eff rows", fe, taue, rnd)], [ey]
+            else:
+                continue
+            for c, t in zip(checks, got):
+                worst, bad, where = c.ratio(t)
+                figures.append((c.name, c.kernel, worst, bad, c.ref.numel(), where, 0 if c.kink is None else int(c.kink.sum()),
+                                float(c.ref.abs().max())))
+    # ---- transition data gradients: the first writer of a block's accumulator.  The last layer's slice of G[b] receives nothing else, so
+    # there the stored values are the transition's contribution alone (and exactly zero at the pixels no 2x2 window covers)
+    for b in range(len(cfg.densenet_structure) - 1):
+        t = f"features.transition{b + 1}"
+        x, Gb = _tap(eng, f"dense{b + 1}"), _tap(eng, f"raw:grad{b + 1}")
+        C = x.shape[-1]
+        pq = _tap(eng, f"raw:pq{b + 2}").flatten()
+        sc, sh = tabd[t + ".norm"]
+        DU, d, kink = R.transition_dgrad(_tap(eng, f"raw:grad{b + 2}"), _tap(eng, f"dense{b + 2}"), pq[:pq.numel() // 2], pq[pq.numel() // 2:], x,
+                                         sc, sh, P[t + ".relu.weight"], P[t + ".conv.weight"].reshape(C // 2, C), rnd, C - g)
+        c = R.Check(f"transition{b + 1}:grad[{C - g}:{C}]", "transition dgrad", DU, d, rnd, kink)
+        worst, bad, where = c.ratio(Gb[..., C - g:])
+        H, W = x.shape[1:3]
+        uncovered = int(H % 2) * W + int(W % 2) * H - int(H % 2) * int(W % 2)
+        figures.append((c.name, c.kernel, worst, bad, DU.numel(), where, int(kink.sum()), float(DU.abs().max()), uncovered))
+    # ---- head pooling backward: the first writer of the last block's accumulator, compared on the last layer's slice as above
+    nb = len(cfg.densenet_structure)
+    x, Gb = _tap(eng, f"dense{nb}"), _tap(eng, f"raw:grad{nb}")
+    C = x.shape[-1]
+    sc, sh = tabd["features.final_norm"]
+    Gr, d, kink = R.head_pool_backward(_tap(eng, "raw:dcondense").reshape(n_img, C), x, sc, sh, P["features.final_relu.weight"], C - g)
+    c = R.Check(f"head:grad[{C - g}:{C}]", "head pooling backward", Gr, d, rnd, kink)
+    worst, bad, where = c.ratio(Gb[..., C - g:])
+    figures.append((c.name, c.kernel, worst, bad, Gr.numel(), where, int(kink.sum()), float(Gr.abs().max())))
+    _lib.lib.tcvn_profile_enable(0)
+    labels = [r[0] for r in _lib.profile_records()]
+    _lib.lib.tcvn_profile_reset()
+    return dict(figures=figures, labels=labels, ey_filled=ey_filled, geometry=geo)
+
+
+def _ru(v):
+    return -(-v // 256) * 256
+
+
+def _run_layers_backward(case, mode):
+    """Validation build only: one backward with the snapshot hook (tcvn_debug_layer_snapshot, densenet_bwd.hip) armed for the first and the
+    last layer of every block; every kernel of those layers against float64 on the state the layer found: eff rows (where stored), DU,
+    norm2's link (dgamma2, dbeta2, dslope2, PY, QY), db1, dW1, the read-add-write of G[:, :cin], norm1's link (dgamma1, dbeta1, dslope1,
+    P / Q[:cin] +=); the rest of G and (P, Q) must be bit-unchanged.  -> report."""
+    from transformercvn.hip import _lib
+    lib = _lib.lib
+    lib.tcvn_debug_layer_snapshot.restype = C.c_int
+    lib.tcvn_debug_layer_snapshot.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int64]
+    lib.tcvn_debug_layer_snapshot_clear.restype = None
+    lib.tcvn_debug_layer_snapshot_report.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int64)]
+    cfg, coords, values, n_img = _case(case)
+    sd = O.fill_state(cfg, 19)
+    eng, data, grads = _engine(cfg, sd, mode=mode, with_grad=True)
+    out = torch.empty(n_img, eng.out_dim, device="cuda")
+    eng.forward(coords.cuda(), values.cuda(), n_img, out, train=True, seed=SEED)
+    d_out = torch.randn(n_img, eng.out_dim, generator=torch.Generator().manual_seed(5)).cuda()
+    geo, g, rnd = _geometry(cfg), cfg.densenet_growth_rate, mode == BF16
+    mid, esz, dt = cfg.densenet_batch_norm_size * g, (2 if rnd else 4), (torch.bfloat16 if rnd else torch.float32)
+    P = {k: v.detach().double().cpu() for k, v in data.items()}
+    tabd = R.tables_from_tabs(cfg, _tap(eng, "raw:tabs").flatten())
+    has_ey = rnd and g == 32
+    armed = []
+    lib.tcvn_debug_layer_snapshot_clear()
+    for b, layers in enumerate(cfg.densenet_structure):
+        H, W, _ = geo[b]
+        M, ld = n_img * H * W, eng.tap(f"raw:pq{b + 1}").numel() // 2
+        sizes = [_ru(M * ld * esz), _ru(ld * 8)] * 2 + [_ru(M * mid * esz), _ru(mid * 8)] + ([_ru(M * 32 * esz)] if has_ey else [])
+        for l in [-1] + sorted({0, layers - 1}):                         # -1: the block's transition, or the head
+            buf = torch.zeros(sum(sizes), dtype=torch.uint8, device="cuda")
+            idx = lib.tcvn_debug_layer_snapshot(b, l, buf.data_ptr(), buf.numel())
+            armed.append((b, l, idx, buf, sizes, M, ld))
+    _lib.lib.tcvn_profile_filter(None); _lib.lib.tcvn_profile_reset(); _lib.lib.tcvn_profile_enable(1)
+    try:
+        eng.backward(d_out)
+        torch.cuda.synchronize()
+    finally:
+        _lib.lib.tcvn_profile_enable(0)
+    labels = [r[0] for r in _lib.profile_records()]
+    _lib.lib.tcvn_profile_reset()
+    gr = {k: v.detach().double().cpu() for k, v in grads.items()}
+    figures, reports = [], []
+
+    def compare(name, kernel, ref, delta, got, rnd_store, kink=None):
+        c = R.Check(name, kernel, ref, delta, rnd_store, kink)
+        worst, bad, where = c.ratio(got.reshape(ref.shape))
+        figures.append((name, kernel, worst, bad, ref.numel(), where, 0 if kink is None else int(kink.sum()), float(ref.abs().max())))
+
+    for b, l, idx, buf, sizes, M, ld in armed:
+        kern, fused, eyv, nbytes = C.c_int(), C.c_int(), C.c_int(), C.c_int64()
+        assert lib.tcvn_debug_layer_snapshot_report(idx, C.byref(kern), C.byref(fused), C.byref(eyv), C.byref(nbytes)) == 0
+        assert nbytes.value == buf.numel() - (0 if l >= 0 or not has_ey else sizes[-1]), (nbytes.value, buf.numel())      # (no eff rows around a transition)
+        H, W, c0 = geo[b]
+        cin = c0 + l * g
+        if l >= 0:
+            reports.append((b, l, cin, kern.value, fused.value, eyv.value))
+        offs = [sum(sizes[:i]) for i in range(len(sizes))]
+        raw = buf.cpu()
+        sec = lambda i, nbytes_, d: raw[offs[i]: offs[i] + nbytes_].view(d).double()
+        Gmap = lambda i: sec(i, M * ld * esz, dt).reshape(n_img, H, W, ld)
+        G0, G1 = Gmap(0), Gmap(2)
+        pq0, pq1 = sec(1, ld * 8, torch.float32), sec(3, ld * 8, torch.float32)
+        DU = sec(4, M * mid * esz, dt).reshape(n_img, H, W, mid)
+        pqy = sec(5, mid * 8, torch.float32)
+        ey = sec(6, M * 32 * esz, dt).reshape(n_img, H, W, 32) if has_ey and eyv.value else None
+        X = _tap(eng, f"dense{b + 1}")
+        Ct = X.shape[-1]
+        if l < 0:
+            # ---- the first writer of G[b] and of its (P, Q): the stored state behind it is its contribution alone
+            last = b == len(cfg.densenet_structure) - 1
+            bs = _tap(eng, f"raw:bstat{b + 1}").flatten()[:2 * ld].view(ld, 2)[:Ct]
+            if last:
+                norm, relu, kind = "features.final_norm", "features.final_relu", "head pooling backward"
+                sc, sh = tabd[norm]
+                Gr, sums, gates = R.head_backward(_tap(eng, "raw:dcondense").reshape(n_img, Ct), X, sc, sh, P[relu + ".weight"])
+            else:
+                t = f"features.transition{b + 1}"
+                norm, relu, kind = t + ".norm", t + ".relu", "transition backward"
+                sc, sh = tabd[norm]
+                pqn = _tap(eng, f"raw:pq{b + 2}").flatten()
+                o, sums, gates = R.transition_backward(_tap(eng, f"raw:grad{b + 2}"), _tap(eng, f"dense{b + 2}"), pqn[:pqn.numel() // 2],
+                                                       pqn[pqn.numel() // 2:], X, sc, sh, P[relu + ".weight"],
+                                                       P[t + ".conv.weight"].reshape(Ct // 2, Ct), rnd)
+                Gr = o["G"]
+                compare(t + ".conv.bias", kind, o["db"][0], o["db"][1], gr[t + ".conv.bias"], False)
+                compare(t + ".conv.weight", kind, o["dW"][0], o["dW"][1], gr[t + ".conv.weight"], False)
+            compare(f"block{b + 1}:G after its first writer", kind, Gr[0], Gr[1], G1[..., :Ct], rnd, Gr[2])
+            lk = R.bn_link(sums, gates, bs[:, 0], bs[:, 1], P[norm + ".weight"], M)
+            for q, k in (("dgamma", norm + ".weight"), ("dbeta", norm + ".bias"), ("dslope", relu + ".weight")):
+                compare(k, kind + " link", lk[q][0], lk[q][1], gr[k], False)
+            for q, i0 in (("P", 0), ("Q", ld)):
+                compare(f"block{b + 1}:{q} after its first writer", kind + " link", lk[q][0], lk[q][1], pq1[i0: i0 + Ct], False)
+            continue
+        p = f"features.dense{b + 1}.layers.{l}"
+        nm = f"dense{b + 1}.{l}"
+        y = _tap(eng, f"bottleneck{b + 1}.{l}")
+        keep = _keep(cfg.dropout, SEED, 64 * b + l + 1, M, g).double().cpu().reshape(n_img, H, W, g) if cfg.dropout > 0 else None
+        n2, n1 = p + ".output_block.norm2", p + ".bottleneck_block.norm1"
+        sc2, sh2 = tabd[n2]
+        sl2 = P[p + ".output_block.relu2.weight"]
+        cs = slice(cin, cin + g)
+        # ---- 3x3 data gradient -> DU
+        f, tau, e, de = R.eff_rows(G0[..., cs], X[..., cs], pq0[:ld][cs], pq0[ld:][cs], keep, rnd)
+        if ey is not None:
+            compare(nm + ":ey", "eff rows", f, tau, ey, rnd)
+            e, de = ey, torch.zeros_like(ey)
+        dA, ddA = R.conv3x3_dgrad(e, de, P[p + ".output_block.conv2.weight"], rnd)
+        ref, dl, kink = R.prelu_bn_backward(dA, ddA, y, sc2, sh2, sl2)
+        compare(nm + ":du", "dgrad3x3", ref, dl, DU, rnd, kink)
+        # ---- norm2's link
+        ys = _tap(eng, f"raw:ystat{b + 1}.{l}").flatten()[:2 * mid].view(mid, 2)
+        _, _, _, sums, gates = R.bn_sums(dA, ddA, y, sc2, sh2, sl2)
+        lk = R.bn_link(sums, gates, ys[:, 0], ys[:, 1], P[n2 + ".weight"], M)
+        for q, k in (("dgamma", n2 + ".weight"), ("dbeta", n2 + ".bias"), ("dslope", p + ".output_block.relu2.weight")):
+            compare(k, "norm2 link", lk[q][0], lk[q][1], gr[k], False)
+        compare(nm + ":PY", "norm2 link", lk["P"][0], lk["P"][1], pqy[:mid], False)
+        compare(nm + ":QY", "norm2 link", lk["Q"][0], lk["Q"][1], pqy[mid:], False)
+        # ---- 1x1 backward from the STORED DU and (PY, QY)
+        xin = X[..., :cin]
+        sc1, sh1 = tabd[n1]
+        sl1 = P[p + ".bottleneck_block.relu1.weight"]
+        _, _, a1, da1 = R.activation(xin, sc1, sh1, sl1, rnd)
+        xa = _tap(eng, f"xa{b + 1}.{l}")
+        if xa is not None:
+            a1, da1 = xa, torch.zeros_like(xa)
+        o1, sums1, gates1 = R.conv1x1_backward(DU, y, pqy[:mid], pqy[mid:], a1, da1, P[p + ".bottleneck_block.conv1.weight"].reshape(mid, cin),
+                                               G0[..., :cin], xin, sc1, sh1, sl1, rnd)
+        kind = "1x1 backward (fused)" if fused.value else "1x1 backward (GEMMs)" if xa is not None else "1x1 backward (generic)"
+        compare(p + ".bottleneck_block.conv1.bias", kind, o1["db1"][0], o1["db1"][1], gr[p + ".bottleneck_block.conv1.bias"], False)
+        compare(p + ".bottleneck_block.conv1.weight", kind, o1["dW1"][0], o1["dW1"][1], gr[p + ".bottleneck_block.conv1.weight"], False)
+        compare(nm + f":G[0:{cin}]", kind, o1["G"][0], o1["G"][1], G1[..., :cin], rnd, o1["G"][2])
+        Ct = X.shape[-1]                                               # (the columns behind Ctot are padding nobody initialises)
+        same = bool(torch.equal(G1[..., cin:Ct], G0[..., cin:Ct])) and bool(torch.equal(pq1[:ld][cin:Ct], pq0[:ld][cin:Ct])) and \
+            bool(torch.equal(pq1[ld:][cin:Ct], pq0[ld:][cin:Ct]))
+        figures.append((nm + ":rest of G, P, Q unchanged", "untouched", 0.0 if same else float("inf"), 0 if same else 1, 1, [], 0, 1.0))
+        # ---- norm1's link
+        bs = _tap(eng, f"raw:bstat{b + 1}").flatten()[:2 * ld].view(ld, 2)[:cin]
+        lk = R.bn_link(sums1, gates1, bs[:, 0], bs[:, 1], P[n1 + ".weight"], M)
+        for q, k in (("dgamma", n1 + ".weight"), ("dbeta", n1 + ".bias"), ("dslope", p + ".bottleneck_block.relu1.weight")):
+            compare(k, "norm1 link", lk[q][0], lk[q][1], gr[k], False)
+        for q, i0 in (("P", 0), ("Q", ld)):
+            inc, d_inc = lk[q]
+            compare(nm + f":{q}[0:{cin}]", "norm1 link", pq0[i0: i0 + cin] + inc, d_inc + 0.5 * R.ulp(inc.abs() + d_inc, 24), pq1[i0: i0 + cin], False)
+    lib.tcvn_debug_layer_snapshot_clear()
+    return dict(figures=figures, labels=labels, reports=reports)
+
+
+BUILDS = {"validation": {}, "consec": dict(TCVN_DGRAD3_ANY_SIZE="1"), "unfused": dict(TCVN_NO_FWD1_FUSE="1", TCVN_NO_BWD1_FUSE="1", TCVN_NO_ACT_FUSE="1"), "generic": dict(TCVN_DISABLE_TILE="1")}
+
+
+@functools.lru_cache(maxsize=None)
+def _child_reports(build):
+    """All cases of one validation-build knob set in ONE child process (knobs are read once per process)."""
+    from variant_utils import run_on_debug_build
+    fwd, bwd = build in ("unfused", "generic"), build in ("consec", "generic")
+    modes = "(T.BF16, T.F32)" if build == "validation" else "(T.BF16,)"
+    return run_on_debug_build("import test_densenet_layers_float64_gpu as T\n"
+                              f"result = dict((c, (T._run(c, T.BF16, True) if {fwd} else None,\n"
+                              f"                       T._run_backward(c, T.BF16, {build == 'generic'}) if {bwd} else None,\n"
+                              f"                       dict((m, T._run_layers_backward(c, m)) for m in {modes}))) for c in T.CASES)\n",
+                              BUILDS[build])
+
+
+@functools.lru_cache(maxsize=None)
+def _report(case, build):
+    if build in BUILDS:
+        return _child_reports(build)[case][0]
+    return _run(case, F32 if build == "fp32" else BF16, build != "bf16-eval")
+
+
+@functools.lru_cache(maxsize=None)
+def _backward_report(case, build):
+    if build in BUILDS:
+        return _child_reports(build)[case][1]
+    return _run_backward(case, F32 if build == "fp32" else BF16)
+
+
+def _count(labels, what):
+    return sum(what in k for k in labels)
+
+
+@pytest.mark.parametrize("build", ["bf16", "bf16-eval", "fp32", "unfused", "generic"])
+@pytest.mark.parametrize("case", CASES)
+def test_every_forward_kernel_matches_float64_on_its_own_stored_input(case, build):
+    rep = _report(case, build)
+    cfg, _, _, n_img = _case(case)
+    worst = {}
+    for name, kernel, w, bad, numel, where in rep["figures"]:
+        if not w <= worst.get(kernel, (-1.0, ""))[0]:
+            worst[kernel] = (w, name)
+    print(case, build, "worst |error| / gate per kernel:", {k: (round(v, 4), nm) for k, (v, nm) in sorted(worst.items())},
+          "elements", sum(f[4] for f in rep["figures"]))
+    bad = [f for f in rep["figures"] if f[3] or not f[2] <= 1.0]
+    assert not bad, bad[:8]
+
+    # ---- the case is what it is there for
+    geo, pp = rep["geometry"], rep["padded"]
+    layers = sum(cfg.densenet_structure)
+    if case.startswith("wide"):
+        assert geo[0][:2] == (9, 69) and 128 < 2 * (69 + 2) and pp[0] % 128 != 0 and (pp[0] // n_img) % 128 != 0      # tiles straddle images
+        assert geo[0][0] % 2 == 1 and geo[0][1] % 2 == 1                                                          # floor-pooling remainder
+    if case == "wide-dropout" and build != "bf16-eval":
+        assert rep["dropped"] > 0
+    if case == "narrow-one":
+        assert pp[-1] < 128
+    if case.startswith("narrow"):
+        assert geo[-1][:2] == (6, 4)
+    if case == "odd":
+        assert [p[2] % 8 for p in rep["paths"]] == [2] * 10 and rep["paths"][-1][2] > 512
+    # ---- every operation was compared
+    n_ops = 2 * layers + len(cfg.densenet_structure) - 1 + 2 + int(rep["conv0"]) + sum(p[3] + (p[4] and p[5]) for p in rep["paths"])
+    assert len(rep["figures"]) == n_ops, (len(rep["figures"]), n_ops)
+    # ---- the run went through the kernels it is meant to cover
+    labels = rep["labels"]
+    wide1 = [p[2] > 512 for p in rep["paths"]]                     # fwd1x1_fused_ok rejects K > 512: NT GEMM on the materialised operand
+    xa, ya, y, lf2 = ([p[i] for p in rep["paths"]] for i in (3, 4, 5, 6))
+    if build == "bf16":
+        assert rep["conv0"] and xa == wide1 and not any(ya) and all(y) and lf2 == [not w for w in wide1], rep["paths"]
+        assert _count(labels, "k_fwd1x1_fused_bf16") == layers - sum(wide1) and _count(labels, "k_gemm_nt_bf16<fwd1x1>") == sum(wide1), labels
+        assert _count(labels, "k_conv3x3_fwd_bf16") == layers and not _count(labels, "k_conv_fwd<bf16,2"), labels
+    elif build == "bf16-eval":
+        assert all(ya) and not any(y) and not any(lf2), rep["paths"]      # the activated map is the 1x1's only output
+        assert _count(labels, "k_conv3x3_fwd_bf16") == layers, labels
+    elif build == "fp32":
+        assert not any(xa) and not any(ya) and all(y) and not any(lf2), rep["paths"]
+        assert not _count(labels, "bf16"), labels
+    elif build == "unfused":
+        assert all(xa) and all(ya) and all(y), rep["paths"]
+        assert not _count(labels, "k_fwd1x1_fused_bf16") and _count(labels, "k_gemm_nt_bf16<fwd1x1>") == layers, labels
+        assert _count(labels, "k_gemm_nt_bf16<fwdtrans>") == len(cfg.densenet_structure) - 1, labels
+    elif build == "generic":
+        assert not _count(labels, "k_conv3x3_fwd_bf16") and _count(labels, "k_conv_fwd<bf16") >= layers, labels
+
+
+@pytest.mark.parametrize("build", ["bf16", "consec", "generic", "fp32"])
+@pytest.mark.parametrize("case", CASES)
+def test_backward_kernels_match_float64_on_their_own_stored_inputs(case, build):
+    rep = _backward_report(case, build)
+    cfg, _, _, n_img = _case(case)
+    nb, layers = len(cfg.densenet_structure), sum(cfg.densenet_structure)
+    worst = {}
+    for name, kernel, w, bad, numel, where, kinks, amax, *_ in rep["figures"]:
+        if not w <= worst.get(kernel, (-1.0, ""))[0]:
+            worst[kernel] = (w, name)
+    print(case, build, "worst |error| / gate per kernel:", {k: (round(v, 4), nm) for k, (v, nm) in sorted(worst.items())},
+          "elements at a PReLU kink (left out):", sum(f[6] for f in rep["figures"]), "of", sum(f[4] for f in rep["figures"] if f[1] in ("dgrad3x3", "transition dgrad", "head pooling backward")))
+    bad = [f for f in rep["figures"] if f[3] or not f[2] <= 1.0]
+    assert not bad, bad[:8]
+    assert len([f for f in rep["figures"] if f[1] == "wgrad3x3"]) == 2 * layers
+    if build in ("bf16", "consec"):
+        assert _count(rep["labels"], "k_conv3x3_wgrad_bf16") == layers, rep["labels"]
+    assert len([f for f in rep["figures"] if f[1] == "head pooling backward"]) == 1
+    tr = [f for f in rep["figures"] if f[1] == "transition dgrad"]
+    assert len(tr) == nb - 1
+    if case.startswith("wide"):
+        assert tr[0][8] == 9 + 69 - 1, tr[0]                            # the odd 9 x 69 map: a row and a column no window covers
+    if build in ("bf16", "consec"):
+        assert _count(rep["labels"], "k_gemm_nt_bf16<dgradtrans>") == nb - 1, rep["labels"]
+    du = [f for f in rep["figures"] if f[1] == "dgrad3x3"]
+    assert len(du) == nb, du                                           # one first layer per block
+    if n_img == 1:      # the output block's train-mode BatchNorm1d over ONE row passes no gradient: every reference is exactly 0, and so must the kernels' be
+        assert all(f[7] == 0 and f[2] == 0 for f in rep["figures"]), rep["figures"]
+    else:
+        assert all(f[7] > 0 for f in rep["figures"]), [f for f in rep["figures"] if not f[7] > 0]
+    labels, filled = rep["labels"], rep["ey_filled"]
+    aligned = cfg.initial_pixel_dim % 8 == 0                           # the LDS-DMA kernels need 16-byte aligned slices
+    if build == "consec":
+        assert filled == [aligned] * layers, filled                    # the consecutive-tile kernel ran (it alone stores the eff rows)
+        assert len([f for f in rep["figures"] if f[1] == "eff rows"]) == (layers if aligned else 0)
+    else:
+        assert not any(filled), filled
+    if build in ("bf16", "consec"):
+        assert _count(labels, "k_conv3x3_dgrad_bf16") == layers and not _count(labels, "k_conv_dgrad<bf16,2"), labels
+    elif build == "generic":
+        assert _count(labels, "k_conv_dgrad<bf16,2") == layers and not _count(labels, "k_conv3x3_dgrad_bf16"), labels
+        assert _count(labels, "k_conv_wgrad<bf16,2") == layers and not _count(labels, "k_conv3x3_wgrad_bf16"), labels
+    else:
+        assert not _count(labels, "bf16"), labels
+        assert _count(labels, "k_conv3x3_dgrad_f32") + _count(labels, "k_conv_dgrad<float,2") == layers, labels
+
+
+@pytest.mark.parametrize("build", ["validation", "validation-fp32", "consec", "unfused", "generic"])
+@pytest.mark.parametrize("case", CASES)
+def test_first_and_last_layer_backward_match_float64_on_the_state_they_found(case, build):
+    """The snapshot hook of the validation build, armed for the first and the last layer of every block (_run_layers_backward)."""
+    child, mode = ("validation", F32) if build == "validation-fp32" else (build, BF16)
+    rep = _child_reports(child)[case][2][mode]
+    cfg, _, _, n_img = _case(case)
+    worst = {}
+    for name, kernel, w, bad, numel, where, kinks, amax in rep["figures"]:
+        if not w <= worst.get(kernel, (-1.0, ""))[0]:
+            worst[kernel] = (w, name)
+    print(case, build, "worst |error| / gate per kernel:", {k: (round(v, 4), nm) for k, (v, nm) in sorted(worst.items())},
+          "elements at a PReLU kink (left out):", sum(f[6] for f in rep["figures"]), "layers (block, layer, cin, dgrad kernel, fused 1x1, eff rows):", rep["reports"])
+    bad = [f for f in rep["figures"] if f[3] or not f[2] <= 1.0]
+    assert not bad, [f[:5] for f in bad[:12]]
+    armed = sum(len({0, L - 1}) for L in cfg.densenet_structure)
+    assert len(rep["reports"]) == armed and [r[:2] for r in rep["reports"]] == [(b, l) for b, L in enumerate(cfg.densenet_structure) for l in sorted({0, L - 1})]
+    labels = rep["labels"]
+    layers = sum(cfg.densenet_structure)
+    aligned = cfg.initial_pixel_dim % 8 == 0
+    TWO_WG, PIPELINED, CONSEC = 1, 2, 3                                # Conv3x3Dgrad (tcvn_ops.h)
+    for b, l, cin, kern, fused, eyv in rep["reports"]:
+        if build in ("validation", "unfused"):
+            assert kern == (PIPELINED if aligned else TWO_WG) and not eyv, rep["reports"]      # the product choice at these sizes
+        elif build == "consec":
+            assert kern == (CONSEC if aligned else TWO_WG) and eyv == int(aligned), rep["reports"]
+        else:
+            assert kern == 0 and not eyv, rep["reports"]
+        assert fused == int(build in ("validation", "consec")), rep["reports"]
+    if build == "unfused":
+        assert _count(labels, "k_gemm_tn_bf16<conv1>") == layers and _count(labels, "k_gemm_nt_bf16<dgrad1x1>") == layers, labels
+        assert not _count(labels, "k_bwd1x1_fused_bf16"), labels
+    if build in ("validation", "consec"):
+        assert _count(labels, "k_bwd1x1_fused_bf16") == layers, labels
