@@ -289,6 +289,7 @@ int DenseNetPlan::bind(void* const* d, void* const* g) {
     bound = true;
     desc_ws = nullptr;   // device descriptor tables are rebuilt on the next forward
     undesc_ws = nullptr;
+    last_ws = nullptr;   // ... and nothing packed from the old bindings is resumed from
     return 0;
 }
 
@@ -432,34 +433,46 @@ LfLink DenseNetPlan::lf_link(const Step& s, const BnSlots& bn, const long long* 
     return k;
 }
 
+// draw (eval pass only): Monte-Carlo dropout, the dropout sites draw from `seed` and nothing else changes.  resume (with draw): the call
+// starts at dense block 1, layer 0, on what the last eval-kind forward of the same inputs left in this workspace -- no dropout site lies
+// in front of the first 3x3 convolution, and the eval layout gives the stem's channels of D[0], the packed weights (wk) and the BatchNorm
+// tables (tabs) regions that no later launch of an eval pass writes (link() returns at once, lf_link needs lf_on).
 int DenseNetPlan::forward(int n, const int32_t* coords, const float* values, long nnz, int log_pixels, float noise_std,
-                          float* out, long out_ld, char* ws, long ws_bytes, int train, uint64_t seed, hipStream_t st) {
+                          float* out, long out_ld, char* ws, long ws_bytes, int train, uint64_t seed, hipStream_t st, bool draw, bool resume) {
     if (!bound) return -11;
     if (n <= 0) return 0;
     Layout L;
     layout(n, train != 0, L);
     if (ws_bytes < L.total) { fprintf(stderr, "tcvn: densenet workspace too small (%ld < %ld)\n", ws_bytes, L.total); return -12; }
+    if (resume && !(last_ws == ws && last_eval && last_n == n && last_coords == coords && last_nnz == nnz && last_values == values &&
+                    last_value_mode == log_pixels)) {
+        fprintf(stderr, "tcvn: densenet forward_mc cannot resume: the last call on this workspace was not an eval-mode forward of these inputs\n");
+        return -18;
+    }
     int rc;
-    if ((rc = upload_descs(ws, L, st))) return rc;
-    // weights -> kernel layout (fp32 -> T); eval: all BN tables from the running statistics in one launch
-    if ((rc = pack_weights(reinterpret_cast<const PackDesc*>(d_desc), n_pack, cfg.mode, st))) return rc;
-    if (!train && (rc = bn_eval_tables(reinterpret_cast<const BnEvalDesc*>(d_desc + n_pack * sizeof(PackDesc)), n_bneval, kEps, st))) return rc;
+    if (!resume) {
+        last_ws = nullptr;       // until this call has come through
+        if ((rc = upload_descs(ws, L, st))) return rc;
+        // weights -> kernel layout (fp32 -> T); eval: all BN tables from the running statistics in one launch
+        if ((rc = pack_weights(reinterpret_cast<const PackDesc*>(d_desc), n_pack, cfg.mode, st))) return rc;
+        if (!train && (rc = bn_eval_tables(reinterpret_cast<const BnEvalDesc*>(d_desc + n_pack * sizeof(PackDesc)), n_bneval, kEps, st))) return rc;
+    }
     // Round 5, link-free BatchNorm statistics (bn_lf.h): the fused 1x1 kernels and the 3x3 pair kernel ADD their per-workgroup sums to
     // fixed-point accumulators and derive their input BatchNorm's table in their own prologue -- no k_bn_link launch between them (120 of
     // the 132 per step and embedder).  TCVN_NO_LF (validation build): the link kernels of rounds 1-4.
     static const bool no_lf = TCVN_KNOB_SET("TCVN_NO_LF");
     const bool lf_on = train && !no_lf && cfg.mode == MODE_BF16 && L.isum_bytes > 0;
     TCVN_CHECK(hipMemsetAsync(ws + L.zeros, 0, 1024 + (lf_on ? L.isum_bytes : 0), st));
-    const Step s{ws, L, st, n, train != 0, seed, reinterpret_cast<double*>(ws + L.part), lf_on, false, 0, false};
-    FreshStats fr{};                  // statistics of the newest channels of the block being built
-    if ((rc = fwd_stem(s, coords, values, nnz, log_pixels, noise_std, fr))) return rc;
+    const Step s{ws, L, st, n, train != 0, seed, reinterpret_cast<double*>(ws + L.part), lf_on, false, 0, false, draw && !train};
+    FreshStats fr{};                  // statistics of the newest channels of the block being built (read by train-mode links only)
+    if (!resume && (rc = fwd_stem(s, coords, values, nnz, log_pixels, noise_std, fr))) return rc;
     for (int bi = 0; bi < (int)blocks.size(); ++bi) {
         for (int l = 0; l < blocks[bi].L; ++l)
             if ((rc = fwd_layer(s, bi, l, fr))) return rc;
         if ((rc = fwd_transition(s, bi, fr))) return rc;
     }
     if ((rc = fwd_output(s, out, out_ld))) return rc;
-    last_seed = seed; last_n = n; last_coords = coords; last_nnz = nnz;
+    last_seed = seed; last_n = n; last_coords = coords; last_nnz = nnz; last_ws = ws; last_eval = !train;
     return 0;
 }
 
@@ -629,7 +642,7 @@ int DenseNetPlan::fwd_layer(const Step& s, int bi, int l, FreshStats& fr) {
         a.Aact = s.ws + L.YA[bi][l];
     }
     a.part = s.train ? s.part : nullptr;
-    a.drop_p = s.train ? cfg.dropout : 0.f; a.seed = s.seed; a.stream_id = (uint32_t)(bi * 64 + l + 1);
+    a.drop_p = s.drop_p(cfg.dropout); a.seed = s.seed; a.stream_id = (uint32_t)(bi * 64 + l + 1);
     a.nblk = conv_fwd_nblk(a);
     if (p.lf2) {
         if (!a.act_fused) { fprintf(stderr, "tcvn: link-free norm2 without the in-LDS activation\n"); return -17; }
@@ -690,7 +703,7 @@ int DenseNetPlan::fwd_output(const Step& s, float* out, long out_ld) const {
     r.X = Z; r.ldx = cfg.out_dim; r.R = s.n; r.C = cfg.out_dim; r.gamma = data[nl.w]; r.beta = data[nl.b]; r.slope = data[s_al];
     r.running_mean = data[nl.rm]; r.running_var = data[nl.rv]; r.Y = out; r.ldy = out_ld;
     r.save_mean = hs; r.save_rstd = hs + cfg.out_dim; r.train = s.train; r.eps = kEps; r.momentum = kMom;
-    r.drop_p = s.train ? cfg.dropout : 0.f; r.seed = s.seed; r.stream_id = 0x4000u;
+    r.drop_p = s.drop_p(cfg.dropout); r.seed = s.seed; r.stream_id = 0x4000u;
     return rows_bn_fwd(r, s.st);
 }
 
@@ -832,6 +845,11 @@ int tcvn_densenet_forward(tcvn_densenet* p, int n_img, const int32_t* coords, co
                           void* stream) {
     return p->plan.forward(n_img, coords, values, nnz, log_pixels, noise_std, out, out_ld, reinterpret_cast<char*>(ws), ws_bytes,
                            train, seed, reinterpret_cast<hipStream_t>(stream));
+}
+int tcvn_densenet_forward_mc(tcvn_densenet* p, int n_img, const int32_t* coords, const float* values, int64_t nnz, int log_pixels,
+                             float* out, int64_t out_ld, void* ws, int64_t ws_bytes, uint64_t seed, int resume, void* stream) {
+    return p->plan.forward(n_img, coords, values, nnz, log_pixels, 0.f, out, out_ld, reinterpret_cast<char*>(ws), ws_bytes, 0, seed,
+                           reinterpret_cast<hipStream_t>(stream), true, resume != 0);
 }
 int tcvn_densenet_backward(tcvn_densenet* p, int n_img, const float* d_out, int64_t d_out_ld, void* ws, int64_t ws_bytes,
                            void* stream) {

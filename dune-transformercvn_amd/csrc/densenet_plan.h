@@ -63,7 +63,10 @@ struct Step {                  // values shared by the pieces of one forward or 
     char* ws; const Layout& L; hipStream_t st; int n; bool train; uint64_t seed;
     double* part; bool lf_on;  // statistics partials (Layout::part forward, Layout::bpart backward); forward: link-free BatchNorm statistics (bn_lf.h)
     bool side_on; int seq; bool side_busy;      // backward: weight gradients on the side stream; parity of the EY buffer / tail half (reset by drain);
-};                                              // work on the side stream that `st` has not waited for
+                                                // work on the side stream that `st` has not waited for
+    bool draw = false;         // forward, train == false: the dropout sites draw their masks (Monte-Carlo dropout); everything else is the eval pass
+    float drop_p(float cfg_p) const { return train || draw ? cfg_p : 0.f; }      // the effective dropout probability of this call
+};
 
 bool backward_overlap_enabled();
 void set_backward_overlap(int on);
@@ -87,6 +90,8 @@ struct DenseNetPlan {
     uint64_t last_seed = 0; int last_n = 0;
     const int32_t* last_coords = nullptr; long last_nnz = 0;     // COO list of the last forward (sparse stem weight gradient)
     const float* last_values = nullptr; int last_value_mode = 0; float last_noise = 0.f;
+    const char* last_ws = nullptr; bool last_eval = false;       // workspace of the last forward, and whether it ran on running statistics: what a
+                                                                 // Monte-Carlo dropout sample may resume from (null: nothing)
     std::vector<std::vector<LayerPath>> path;    // [block][layer] of the last forward
     StemPath stem_path;
     bool sparse_stem_possible() const;   // plan-level condition (bf16, 3 -> 64 channels); the hit count decides per call
@@ -110,7 +115,7 @@ struct DenseNetPlan {
     int bind(void* const* d, void* const* g);
     int upload_descs(char* ws, const Layout& L, hipStream_t st);
     int forward(int n, const int32_t* coords, const float* values, long nnz, int log_pixels, float noise_std, float* out,
-                long out_ld, char* ws, long ws_bytes, int train, uint64_t seed, hipStream_t st);
+                long out_ld, char* ws, long ws_bytes, int train, uint64_t seed, hipStream_t st, bool draw = false, bool resume = false);
     int backward(int n, const float* d_out, long d_out_ld, char* ws, long ws_bytes, hipStream_t st, int bi_hi = -1, int bi_lo = 0);
     // the pieces of forward and of backward, each in launch order
     int fwd_stem(const Step& s, const int32_t* coords, const float* values, long nnz, int log_pixels, float noise_std, FreshStats& fr);

@@ -141,12 +141,13 @@ void HeadPlan::layout(int B, int P, int nP, HLayout& L) const {
 }
 
 // ---- the step: what check() was, plus every size constant the drivers derive from (B, P, nP) ---------------------------------
-int HeadPlan::step(int B, int P, int nP, void* ws, long ws_bytes, int train, uint64_t seed, hipStream_t st, HeadStep& s) const {
+int HeadPlan::step(int B, int P, int nP, void* ws, long ws_bytes, int train, uint64_t seed, hipStream_t st, HeadStep& s, bool draw) const {
     if (!bound) return -11;
     if (cfg.dec_out_in != dec_width) { fprintf(stderr, "tcvn: prong decoder width mismatch (reference would fail too)\n"); return -21; }
     if (B <= 0 || P < 0 || nP < 0 || 1 + P > 64) return -1;          // attention kernel: sequences up to 64 tokens
     s.B = B; s.P = P; s.nP = nP; s.S = 1 + P; s.T = s.S * B; s.R = B + nP; s.TP = P * B;
-    s.ws = reinterpret_cast<char*>(ws); s.train = train; s.seed = seed; s.dp = train ? cfg.dropout : 0.f; s.st = st;
+    s.ws = reinterpret_cast<char*>(ws); s.train = train; s.seed = seed; s.draw = draw && !train; s.st = st;
+    s.dp = train || s.draw ? cfg.dropout : 0.f;
     layout(B, P, nP, s.L);
     return ws_bytes < s.L.total ? -12 : 0;
 }
@@ -286,9 +287,9 @@ int HeadPlan::decode(const HeadStep& s, float* ev_logits, float* pr_logits) cons
 }
 
 int HeadPlan::forward(int B, int P, int nP, const float* rows, const int32_t* tok_row, float* ev_logits, float* pr_logits,
-                      void* ws, long ws_bytes, int train, uint64_t seed, hipStream_t st) {
+                      void* ws, long ws_bytes, int train, uint64_t seed, hipStream_t st, bool draw) {
     HeadStep s;
-    if (int rc = step(B, P, nP, ws, ws_bytes, train, seed, st, s)) return rc;
+    if (int rc = step(B, P, nP, ws, ws_bytes, train, seed, st, s, draw)) return rc;
     if (int rc = embed(s, rows, tok_row)) return rc;
     if (int rc = encode(s, tok_row)) return rc;
     if (int rc = decode(s, ev_logits, pr_logits)) return rc;
@@ -474,6 +475,12 @@ int tcvn_head_forward(tcvn_head* p, int batch, int max_prongs, int n_prongs, con
     return p->plan.forward(batch, max_prongs, n_prongs, rows, tok_row, event_logits, prong_logits, ws, ws_bytes, train, seed,
                            reinterpret_cast<hipStream_t>(stream));
 }
+int tcvn_head_forward_mc(tcvn_head* p, int batch, int max_prongs, int n_prongs, const float* rows, const int32_t* tok_row,
+                         float* event_logits, float* prong_logits, void* ws, int64_t ws_bytes, uint64_t seed, void* stream) {
+    p->last_np = n_prongs; p->last_b = batch; p->last_p = max_prongs;
+    return p->plan.forward(batch, max_prongs, n_prongs, rows, tok_row, event_logits, prong_logits, ws, ws_bytes, 0, seed,
+                           reinterpret_cast<hipStream_t>(stream), true);
+}
 /* stage entry points (forward only): see include/tcvn_hip.h */
 int tcvn_head_embed(tcvn_head* p, int batch, int max_prongs, int n_prongs, const float* rows, const int32_t* tok_row, float* tokens,
                     void* ws, int64_t ws_bytes, int train, uint64_t seed, void* stream) {
@@ -525,20 +532,37 @@ extern "C" int tcvn_linear_forward(const float* x, int64_t ldx, const float* wei
     if (rows == 0) return 0;
     return linear_fwd(x, ldx, weight, bias, y, ldy, rows, n_out, n_in, reinterpret_cast<hipStream_t>(stream));
 }
-extern "C" int tcvn_rows_bn_prelu_forward(const float* x, int64_t ldx, int rows, int channels, const float* gamma, const float* beta,
-                                          const float* slope, float* running_mean, float* running_var, float* y, int64_t ldy,
-                                          float* save_mean_rstd, int train, float drop_p, uint64_t seed, uint32_t stream_id,
-                                          void* stream) {
+// train: batch statistics and their running-stat update; draw: dropout is applied (a training call draws, an eval call does not, the
+// Monte-Carlo dropout call runs on running statistics and draws).  save_mean_rstd may be NULL only where the caller says so (mc: an
+// eval pass saves nothing)
+static int rows_bn_prelu_forward(const float* x, int64_t ldx, int rows, int channels, const float* gamma, const float* beta,
+                                 const float* slope, float* running_mean, float* running_var, float* y, int64_t ldy,
+                                 float* save_mean_rstd, int train, bool draw, float drop_p, uint64_t seed, uint32_t stream_id, void* stream,
+                                 bool need_save = true) {
     const bool no_norm = !gamma && !beta && !running_mean && !running_var;      // LinearBlock without BatchNorm1d (norm = Identity)
     if (!x || !y || rows <= 0 || channels <= 0) return -1;
-    if (!no_norm && (!gamma || !beta || !running_mean || !running_var || !save_mean_rstd)) return -1;
+    if (!no_norm && (!gamma || !beta || !running_mean || !running_var || (need_save && !save_mean_rstd))) return -1;
     RowsBnArgs r{};
     r.no_norm = no_norm ? 1 : 0;
     r.X = x; r.ldx = ldx; r.R = rows; r.C = channels; r.gamma = gamma; r.beta = beta; r.slope = slope;      // slope NULL: ReLU
     r.running_mean = running_mean; r.running_var = running_var; r.Y = y; r.ldy = ldy;
     r.save_mean = save_mean_rstd; r.save_rstd = save_mean_rstd ? save_mean_rstd + channels : nullptr; r.train = train; r.eps = kEps; r.momentum = kMom;
-    r.drop_p = train ? drop_p : 0.f; r.seed = seed; r.stream_id = stream_id;
+    r.drop_p = draw ? drop_p : 0.f; r.seed = seed; r.stream_id = stream_id;
     return rows_bn_fwd(r, reinterpret_cast<hipStream_t>(stream));
+}
+extern "C" int tcvn_rows_bn_prelu_forward(const float* x, int64_t ldx, int rows, int channels, const float* gamma, const float* beta,
+                                          const float* slope, float* running_mean, float* running_var, float* y, int64_t ldy,
+                                          float* save_mean_rstd, int train, float drop_p, uint64_t seed, uint32_t stream_id,
+                                          void* stream) {
+    return rows_bn_prelu_forward(x, ldx, rows, channels, gamma, beta, slope, running_mean, running_var, y, ldy, save_mean_rstd, train,
+                                 train != 0, drop_p, seed, stream_id, stream);
+}
+extern "C" int tcvn_rows_bn_prelu_forward_mc(const float* x, int64_t ldx, int rows, int channels, const float* gamma, const float* beta,
+                                             const float* slope, const float* running_mean, const float* running_var, float* y,
+                                             int64_t ldy, float drop_p, uint64_t seed, uint32_t stream_id, void* stream) {
+    if (!(drop_p >= 0.f && drop_p < 1.f)) { fprintf(stderr, "tcvn: rows_bn_prelu_forward_mc: drop_p %g outside [0, 1)\n", (double)drop_p); return -1; }
+    return rows_bn_prelu_forward(x, ldx, rows, channels, gamma, beta, slope, const_cast<float*>(running_mean),
+                                 const_cast<float*>(running_var), y, ldy, nullptr, 0, true, drop_p, seed, stream_id, stream, false);
 }
 
 // Backward of the two row operators (smart-feature MLP, layers/prong_feature_embedding.py:36-78: the only LinearBlocks outside the head plan)

@@ -27,7 +27,8 @@ struct HLayout {
 struct HeadStep {
     int B, P, nP, S, T, R, TP;       // S = 1 + P tokens a sequence, T = S * B token rows, R = B + nP embedding rows, TP = P * B prong rows
     char* ws; HLayout L;
-    int train; uint64_t seed; float dp; hipStream_t st;      // dp: the effective dropout probability (0 in eval mode)
+    int train; uint64_t seed; float dp; hipStream_t st;      // dp: the effective dropout probability (0 in eval mode, unless the call draws)
+    bool draw = false;               // train == 0: the dropout sites draw their masks (Monte-Carlo dropout); everything else is the eval pass
     float* F(long off) const { return reinterpret_cast<float*>(ws + off); }
 };
 enum class EncPath { FUSED, POST_NORM, PRE_NORM };
@@ -56,7 +57,7 @@ struct HeadPlan {
     HBn add_bn(const std::string& p, int c);
     int bind(void* const* d, void* const* g);
     void layout(int B, int P, int nP, HLayout& L) const;
-    int step(int B, int P, int nP, void* ws, long ws_bytes, int train, uint64_t seed, hipStream_t st, HeadStep& s) const;
+    int step(int B, int P, int nP, void* ws, long ws_bytes, int train, uint64_t seed, hipStream_t st, HeadStep& s, bool draw = false) const;
     EncPath enc_path(int S) const;
     // launch arguments that forward and backward must agree on
     EncLayerW enc_w(int l) const;  EncLayerBuf enc_buf(const HeadStep& s, int l) const;
@@ -68,7 +69,7 @@ struct HeadPlan {
         encode_pre(const HeadStep& s, const int32_t* tok_row) const;
     int decode(const HeadStep& s, float* ev_logits, float* pr_logits) const;
     int forward(int B, int P, int nP, const float* rows, const int32_t* tok_row, float* ev_logits, float* pr_logits, void* ws,
-                long ws_bytes, int train, uint64_t seed, hipStream_t st);
+                long ws_bytes, int train, uint64_t seed, hipStream_t st, bool draw = false);
     int loss(int B, int P, const float* ev_logits, const float* pr_logits, const int64_t* et, const int8_t* pt, float* losses,
              float* accs, float* dEv, float* dPr, hipStream_t st);
     int backward(int B, int P, int nP, const float* rows, const int32_t* tok_row, const float* dEv, const float* dPr, float* d_rows,

@@ -58,7 +58,7 @@ __global__ __launch_bounds__(256) void k_rows_bn_fwd(const RowsBnArgs a) {
         const float sl = a.slope ? a.slope[c] : 0.f;
         for (int r = rg; r < a.R; r += 16) {
             float z = prelu(a.X[(long)r * a.ldx + c], sl);
-            if (a.train && a.drop_p > 0.f) z *= drop_scale(a.drop_p, a.seed, a.stream_id, (uint64_t)r * a.C + c);
+            if (a.drop_p > 0.f) z *= drop_scale(a.drop_p, a.seed, a.stream_id, (uint64_t)r * a.C + c);
             a.Y[(long)r * a.ldy + c] = z;
         }
         return;
@@ -97,7 +97,7 @@ __global__ __launch_bounds__(256) void k_rows_bn_fwd(const RowsBnArgs a) {
     for (int r = rg; r < a.R; r += 16) {
         const float u = (a.X[(long)r * a.ldx + c] - mean) * rstd * g + b;
         float z = prelu(u, sl);
-        if (a.train && a.drop_p > 0.f) z *= drop_scale(a.drop_p, a.seed, a.stream_id, (uint64_t)r * a.C + c);
+        if (a.drop_p > 0.f) z *= drop_scale(a.drop_p, a.seed, a.stream_id, (uint64_t)r * a.C + c);
         a.Y[(long)r * a.ldy + c] = z;
     }
 }

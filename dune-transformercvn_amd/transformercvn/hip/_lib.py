@@ -32,6 +32,7 @@ OCC_GROUP_EVENT, OCC_GROUP_MAP = 0, 1          # TCVN_OCC_GROUP_*: whose largest
 OCC_MAX_LEVELS = 16                 # TCVN_OCC_MAX_LEVELS: levels of one coarse-to-fine occlusion scan
 CURVE_MAX_STEPS, CURVE_MAX_TILES = 64, 4096    # TCVN_CURVE_MAX_*: steps of a deletion / insertion curve, tiles per map it can rank
 CURVE_DELETION, CURVE_INSERTION = 0, 1         # TCVN_CURVE_*: which hits a curve variant keeps
+MC_MAX_CLASSES = 256                # TCVN_MC_MAX_CLASSES: the widest logit row tcvn_mc_dropout_stats takes
 SCONV_KERNELS = ("generic", "c64", "g", "s2", "in")    # TCVN_SCONV_*: kernel families of the SDXL embedder's convolutions
 
 
@@ -132,6 +133,10 @@ def _load():
     sig("tcvn_occlusion_curve", i32, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp)
     sig("tcvn_linear_forward", i32, vp, i64, vp, vp, vp, i64, i32, i32, i32, vp)
     sig("tcvn_rows_bn_prelu_forward", i32, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp, i32, f32, u64, C.c_uint32, vp)
+    sig("tcvn_densenet_forward_mc", i32, vp, i32, vp, vp, i64, i32, vp, i64, vp, i64, u64, i32, vp)
+    sig("tcvn_head_forward_mc", i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, i64, u64, vp)
+    sig("tcvn_rows_bn_prelu_forward_mc", i32, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, i64, f32, u64, C.c_uint32, vp)
+    sig("tcvn_mc_dropout_stats", i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp)
     sig("tcvn_linear_backward", i32, vp, i64, vp, i64, vp, vp, i64, vp, vp, i32, i32, i32, vp)
     sig("tcvn_rows_bn_prelu_backward", i32, vp, i64, vp, i64, i32, i32, vp, vp, vp, vp, vp, i64, vp, vp, vp, f32, u64, C.c_uint32, vp)
     sig("tcvn_focal_loss", i32, vp, vp, i32, i32, f32, f32, vp, vp, vp)
@@ -173,6 +178,7 @@ EXPORTS = [
     "tcvn_occlusion_select", "tcvn_occlusion_refine_variants", "tcvn_occlusion_mark", "tcvn_occlusion_occupancy", "tcvn_occlusion_paint",
     "tcvn_occlusion_curve_workspace_bytes", "tcvn_occlusion_curve_variants", "tcvn_occlusion_curve_build_pass", "tcvn_occlusion_curve",
     "tcvn_head_shapley_workspace_bytes", "tcvn_head_shapley_count", "tcvn_head_shapley",
+    "tcvn_densenet_forward_mc", "tcvn_head_forward_mc", "tcvn_rows_bn_prelu_forward_mc", "tcvn_mc_dropout_stats",
 ]
 
 lib = _load()

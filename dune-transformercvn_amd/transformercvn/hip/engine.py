@@ -244,6 +244,21 @@ class DenseNetEngine(_EmbedderEngine):
         return pre
 
 
+    def forward_mc(self, coords: torch.Tensor, values: torch.Tensor, n_img: int, out: torch.Tensor, seed: int, resume: bool = False,
+                   log_pixels=False):
+        """tcvn_densenet_forward_mc: one Monte-Carlo dropout sample -- the eval forward with the dropout masks of `seed` drawn -- in the
+        step workspace.  resume: start behind the stem, on what the last eval-mode forward() / forward_mc() of the same coords / values
+        tensors left there (the library refuses anything else)."""
+        assert coords.dtype == torch.int32 and coords.is_contiguous() and values.dtype == torch.float32 and values.is_contiguous()
+        self._check_out(out, n_img)
+        ws = self.workspace(self.workspace_bytes(n_img, False), coords.device)
+        check(lib.tcvn_densenet_forward_mc(self.handle, n_img, _ptr(coords), _ptr(values), coords.shape[0], int(log_pixels), _ptr(out),
+                                           out.stride(0), _ptr(ws), ws.numel(), C.c_uint64(seed), int(resume), _stream_ptr()),
+              "densenet_forward_mc")
+        self._n = n_img
+        self._inputs = (coords, values)
+
+
 class SdxlEngine(_EmbedderEngine):
     """SDXL-style embedder plan (tcvn_sdxl_* in include/tcvn_hip.h; parity unpinned, see oracle/sdxl_oracle.py)."""
     _prefix = "sdxl"
@@ -293,6 +308,7 @@ class HeadEngine(_Plan):
         self._shape = (0, 0, 0)
         self._last = (0, -1)                 # (batch, max_prongs) of the last forward / encode on self._ws: what attention() exports
         self._loo_ws = self._occ_ws = self._shap_ws = None      # scratch workspaces (_scratch) of leave_one_out(), occlusion_pass(), shapley()
+        self._mc_ws = None                   # ... and of forward_mc()
 
     def forward(self, rows: torch.Tensor, tok_row: torch.Tensor, batch: int, max_prongs: int, n_prongs: int, train: bool,
                 seed: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -306,6 +322,18 @@ class HeadEngine(_Plan):
         check(lib.tcvn_head_forward(self.handle, batch, max_prongs, n_prongs, _ptr(rows), _ptr(tok_row), _ptr(ev), _ptr(pr),
                                     _ptr(ws), ws.numel(), int(train), C.c_uint64(seed), _stream_ptr()), "head_forward")
         return ev, pr
+
+    def forward_mc(self, rows: torch.Tensor, tok_row: torch.Tensor, batch: int, max_prongs: int, n_prongs: int, seed: int,
+                   ev: torch.Tensor, pr: torch.Tensor):
+        """tcvn_head_forward_mc: one Monte-Carlo dropout sample of the token path -> ev [batch, Ce], pr [batch, max_prongs, Cp]
+        (contiguous, the caller's).  Workspace of its own, as leave_one_out has: attention() still exports the last forward()."""
+        self._check_rows(rows, batch + n_prongs)
+        self._check_tok_row(tok_row, batch, 1 + max_prongs)
+        assert ev.dtype == torch.float32 and ev.is_contiguous() and ev.shape == (batch, self.cfg.event_classes)
+        assert pr.dtype == torch.float32 and pr.is_contiguous() and pr.shape == (batch, max_prongs, self.cfg.prong_classes)
+        ws = self._scratch("_mc_ws", lib.tcvn_head_workspace_bytes(self.handle, batch, max_prongs, n_prongs), rows.device)
+        check(lib.tcvn_head_forward_mc(self.handle, batch, max_prongs, n_prongs, _ptr(rows), _ptr(tok_row), _ptr(ev), _ptr(pr),
+                                       _ptr(ws), ws.numel(), C.c_uint64(seed), _stream_ptr()), "head_forward_mc")
 
     def _stage_ws(self, batch: int, max_prongs: int, n_prongs: int, device):
         return self.workspace(lib.tcvn_head_workspace_bytes(self.handle, batch, max_prongs, n_prongs), device)
@@ -450,6 +478,27 @@ class HeadEngine(_Plan):
         check(lib.tcvn_head_backward(self.handle, batch, max_prongs, n_prongs, _ptr(rows), _ptr(tok_row), _ptr(d_ev), _ptr(d_pr),
                                      _ptr(d_rows), _ptr(ws), ws.numel(), _stream_ptr()), "head_backward")
         return d_rows
+
+
+def mc_stats(sample_logits: torch.Tensor, valid: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    """tcvn_mc_dropout_stats: sample_logits [T, R, C] fp32 (valid [R] int32: rows < 0 become NaN) -> mean_prob, std_prob, votes [R, C]
+    and entropy, expected_entropy, mutual_info [R] by name."""
+    gpu_only(sample_logits, "the Monte-Carlo dropout statistics")
+    assert sample_logits.dtype == torch.float32 and sample_logits.is_contiguous() and sample_logits.dim() == 3
+    T, R, Cn = sample_logits.shape
+    dev = sample_logits.device
+    if T < 1 or Cn < 1:
+        raise ValueError(f"mc_stats: needs at least one sample and one class, got {T} samples of {Cn} classes")
+    if valid is not None:
+        assert valid.dtype == torch.int32 and valid.is_contiguous() and valid.shape == (R,) and valid.device == dev
+    out = {k: torch.empty(R, Cn, device=dev) for k in ("mean_prob", "std_prob", "votes")}
+    out.update({k: torch.empty(R, device=dev) for k in ("entropy", "expected_entropy", "mutual_info")})
+    if R == 0:                                  # a batch without prong slots: nothing to summarise
+        return out
+    check(lib.tcvn_mc_dropout_stats(_ptr(sample_logits), _ptr(valid), T, R, Cn, _ptr(out["mean_prob"]), _ptr(out["std_prob"]),
+                                    _ptr(out["entropy"]), _ptr(out["expected_entropy"]), _ptr(out["mutual_info"]), _ptr(out["votes"]),
+                                    _stream_ptr()), "mc_dropout_stats")
+    return out
 
 
 class _FocalRows(torch.autograd.Function):

@@ -57,7 +57,13 @@ class FeatureMLP:
         self.blocks = list(blocks)
         self.saved = []
 
-    def forward(self, x: Tensor, training: bool, seed: int) -> Tensor:
+    def forward(self, x: Tensor, training: bool, seed: int, draw: bool = False) -> Tensor:
+        """draw (eval only): Monte-Carlo dropout -- running statistics, untouched, with every block's dropout mask of `seed` drawn
+        (tcvn_rows_bn_prelu_forward_mc); nothing is kept for a backward."""
+        if draw:
+            if training:
+                raise ValueError("FeatureMLP.forward: draw is the eval pass with dropout drawn; training draws anyway")
+            return self._forward_mc(x, seed)
         self.saved = []
         for i, blk in enumerate(self.blocks):
             x = x.detach().float().contiguous()
@@ -75,6 +81,19 @@ class FeatureMLP:
             if training and norm is not None:
                 norm.num_batches_tracked += 1
             self.saved.append((x, z, stat, p, seed, 0x4800 + i))
+            x = y
+        return x
+
+    def _forward_mc(self, x: Tensor, seed: int) -> Tensor:
+        for i, blk in enumerate(self.blocks):
+            z = linear(x, blk.linear.weight, blk.linear.bias)
+            rows, ch = z.shape
+            y = torch.empty_like(z)
+            norm, slope = _norm_of(blk.norm), getattr(blk.activation, "weight", None)
+            check(lib.tcvn_rows_bn_prelu_forward_mc(_p(z), z.stride(0), rows, ch, _p(norm.weight if norm else None),
+                                                    _p(norm.bias if norm else None), _p(slope), _p(norm.running_mean if norm else None),
+                                                    _p(norm.running_var if norm else None), _p(y), y.stride(0), float(blk.dropout.p),
+                                                    C.c_uint64(seed), C.c_uint32(0x4800 + i), _st()), "rows_bn_prelu_forward_mc")
             x = y
         return x
 

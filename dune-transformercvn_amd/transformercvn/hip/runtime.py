@@ -14,8 +14,8 @@ from typing import Dict, List, NamedTuple, Optional, Tuple
 import torch
 from torch import Tensor, nn
 
-from . import _lib, attention, occlusion
-from .engine import DenseNetEngine, HeadEngine
+from . import _lib, attention, occlusion, uncertainty
+from .engine import DenseNetEngine, HeadEngine, mc_stats
 from .native import gpu_only
 from .pixels import SparsePixels
 from ..network.layers.packed_data import token_rows
@@ -425,6 +425,56 @@ class HipRuntime:
             relevance = occlusion.relevance_map(relevance)
             scan = self._scan(maps, features, extra, event_px, event_mask, prong_px, prong_mask, counts)
             return scan.curves(relevance, tile, steps, mode, max_pass)
+
+    # ---------------------------------------------------------------------------------------------------------------
+    # predictive uncertainty (forward only): Monte-Carlo dropout
+    # ---------------------------------------------------------------------------------------------------------------
+    def forward_mc_dropout(self, features: Tensor, extra: Tensor, event_px: SparsePixels, event_mask: Tensor, prong_px: SparsePixels,
+                           prong_mask: Tensor, counts: Optional[Tuple[int, int]] = None, samples: int = 32, seed: int = 0,
+                           reuse_stem: bool = True) -> "uncertainty.McDropout":
+        """Eval-mode forward() plus `samples` Monte-Carlo dropout samples of the whole model (eval statistics, dropout drawn: both
+        embedders, the smart-feature MLP and the token path) and their statistics -> uncertainty.McDropout.  One forward() for the step
+        counter; the head's forward workspace is left as forward() wrote it.  reuse_stem: every sample starts behind the embedders' stems,
+        on what forward() left in their workspaces (no dropout site lies in front of the first 3x3 convolution: same bits, less work)."""
+        samples, seed = uncertainty.check_args(samples, seed)
+        if self.network.training:
+            raise RuntimeError("mc_dropout samples an eval-mode prediction: call network.eval() first")
+        for eng in (self.ev_engine, self.pr_engine):
+            if not hasattr(eng, "forward_mc"):
+                raise NotImplementedError("mc_dropout: the SDXL embedder has no dropout site, so it has no Monte-Carlo dropout mode; "
+                                          "only the DenseNet network can be sampled")
+        with torch.no_grad():
+            ev, pr = self.forward(features, extra, event_px, event_mask, prong_px, prong_mask, counts)
+            last = self._last_forward
+            B, P, n_prongs = last.B, last.P, last.n_prongs
+            dev = ev.device
+            pe = self.network.prong_embedding
+            feat, pix = pe.feature_embedding_dim, pe.pixel_embedding_dim
+            fin = None
+            if self.smart_features:                 # the MLP's input rows, as _input_rows builds them
+                i1, i2 = prong_mask.to(dev).nonzero(as_tuple=True)
+                fin = torch.cat((features.to(dev)[i1, i2], extra.to(dev)[i1]), dim=1)
+            sample_ev = torch.empty(samples, *ev.shape, device=dev)
+            sample_pr = torch.empty(samples, *pr.shape, device=dev)
+            seeds = torch.tensor([uncertainty.sample_seeds(seed, t) for t in range(samples)], dtype=torch.int64).view(samples, 4)
+            main = torch.cuda.current_stream(dev)
+            side = self._side if self.overlap_embedders else main
+            for t, (s_ev, s_pr, s_head, s_mlp) in enumerate(seeds.tolist()):
+                rows = last.rows.clone()            # the position columns (and zero feature columns) stay; the embedders' are rewritten
+                if fin is not None:
+                    rows[B:, :feat] = self._mlp().forward(fin, False, s_mlp, draw=True)
+                side.wait_stream(main)
+                with torch.cuda.stream(side):       # the event embedder underneath the prong embedder, as in _input_rows
+                    self.ev_engine.forward_mc(event_px.coords, event_px.values, B, rows[:B, :feat + pix], s_ev, reuse_stem,
+                                              event_px.value_mode)
+                self.pr_engine.forward_mc(prong_px.coords, prong_px.values, n_prongs, rows[B:, feat:feat + pix], s_pr, reuse_stem,
+                                          prong_px.value_mode)
+                main.wait_stream(side)
+                self.head.forward_mc(rows, last.tok_row, B, P, n_prongs, s_head, sample_ev[t], sample_pr[t])
+            event = uncertainty.McStats.from_rows(mc_stats(sample_ev), (B,))
+            valid = last.tok_row[:, 1:].contiguous().view(-1)
+            prong = uncertainty.McStats.from_rows(mc_stats(sample_pr.view(samples, B * P, pr.shape[2]), valid), (B, P))
+            return uncertainty.McDropout(ev, pr, sample_ev, sample_pr, seeds.to(dev), event, prong)
 
     def _backward(self, st: dict, d_ev: Tensor, d_pr: Tensor):
         """Backward of the fused step in the order the gradient segments become final -- token path, event embedder (side

@@ -233,3 +233,23 @@ class NeutrinoBaseNetwork(nn.Module):
         event_pixels, prong_pixels = _as_sparse(event_pixels), _as_sparse(prong_pixels)
         return self.hip_runtime().forward_occlusion_curves(features, extra, event_pixels, event_mask, prong_pixels, prong_mask, counts,
                                                            relevance, tile, steps, mode, maps, max_maps_per_pass)
+
+    # ---- how sure is a prediction (eager only; forward only, no autograd graph) -------------------------------------------------------
+    @torch.jit.unused
+    def mc_dropout(self, features: Tensor, extra: Tensor, event_pixels: Tensor, event_mask: Tensor, prong_pixels: Tensor,
+                   prong_mask: Tensor, counts: Optional[Tuple[int, int]] = None, samples: int = 32, seed: int = 0,
+                   reuse_stem: bool = True):
+        """Eval mode only -> transformercvn.hip.uncertainty.McDropout: Monte-Carlo dropout through the whole model.  The prediction of
+        forward(), then `samples` runs in which BatchNorm stays on its running statistics (and the pixels get no noise) while every
+        dropout layer draws a mask from `seed` (0..2^63-1), and per event / per prong slot the mean and standard deviation of the class
+        probabilities, the predictive entropy, the expected entropy, their difference (the mutual information between prediction and
+        weights) and the arg-max votes.  Parameters, buffers and running statistics are not touched; one forward() for the step counter.
+        reuse_stem=False recomputes the embedders' stems for every sample (same bits).  The SDXL embedder has no dropout site:
+        NotImplementedError."""
+        from transformercvn.hip import uncertainty
+        uncertainty.check_args(samples, seed)
+        if self.training:
+            raise RuntimeError("mc_dropout samples an eval-mode prediction: call .eval() first")
+        event_pixels, prong_pixels = _as_sparse(event_pixels), _as_sparse(prong_pixels)
+        return self.hip_runtime().forward_mc_dropout(features, extra, event_pixels, event_mask, prong_pixels, prong_mask, counts,
+                                                     samples, seed, reuse_stem)

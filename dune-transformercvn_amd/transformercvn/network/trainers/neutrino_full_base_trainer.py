@@ -227,6 +227,19 @@ class NeutrinoFullBaseTrainer(NeutrinoBase, ABC):
                                                                    prong_coords, prong_values, prong_mask), None, relevance, tile,
                                              steps, mode, maps, max_maps_per_pass)
 
+    def mc_dropout(self, features: Tensor, extra: Tensor, event_coords: Tensor, event_values: Tensor, event_mask: Tensor,
+                   prong_coords: Tensor, prong_values: Tensor, prong_mask: Tensor, samples: int = 32, seed: int = 0,
+                   reuse_stem: bool = True):
+        """Eval mode only -> McDropout (transformercvn.hip.uncertainty): how sure the model is of this prediction, by Monte-Carlo
+        dropout through the whole model; see NeutrinoBaseNetwork.mc_dropout.  Bad keywords raise ValueError and train mode RuntimeError
+        before any device work."""
+        from transformercvn.hip import uncertainty
+        uncertainty.check_args(samples, seed)
+        if self.training:
+            raise RuntimeError("mc_dropout samples an eval-mode prediction: call .eval() first")
+        return self.network.mc_dropout(*self._network_inputs(features, extra, event_coords, event_values, event_mask, prong_coords,
+                                                             prong_values, prong_mask), None, samples, seed, reuse_stem)
+
     def shared_step(self, batch):
         (features, extra, ev_c, ev_v, ev_m, pr_c, pr_v, pr_m, ev_t, pr_t) = batch[:10]
         counts = batch[10] if len(batch) > 10 else None               # optional host-side (max_prongs, n_prongs): avoids syncs

@@ -395,6 +395,44 @@ int tcvn_occlusion_curve(const float* event_logits, const float* prong_logits, c
                          int event_classes, int prong_classes, int steps, int target, const int32_t* classes, float* curve, float* auc,
                          void* stream);
 
+/* Predictive uncertainty: Monte-Carlo dropout (forward only; nothing here changes a parameter, a buffer or a running statistic).
+ * A third run mode beside "train" and "eval": EVAL statistics, dropout DRAWN.  An _mc forward is the train = 0 forward of the same
+ * plan (BatchNorm on running statistics, no pixel noise, no statistics partials, no keep-flag output, no running-stat update, the same
+ * kernel choices) except that every dropout site applies the mask of (seed, stream id, element) with the plan's dropout probability --
+ * the masks tcvn_dropout_keep reports.  It counts as an eval-mode forward for what follows: taps work, tcvn_head_attention may export
+ * it, a backward is not defined after it.  With dropout = 0 it is the eval forward, bit for bit.
+ *   densenet_forward_mc   workspace: tcvn_densenet_workspace_bytes(p, n_img, 0).  resume = 0: a whole forward.  resume != 0: starts at
+ *               dense block 1, layer 0, on what the last forward left in `workspace` (no dropout site lies in front of the first 3x3
+ *               convolution; the stem's output channels, the packed weights and the BatchNorm tables are written by no later launch of
+ *               an eval pass).  Accepted only if the plan's last forward ran on this workspace with train = 0 (plain or _mc) and the
+ *               same n_img, coords, values, nnz and log_pixels, and no tcvn_densenet_bind came between; otherwise one "tcvn:" line,
+ *               non-zero, no launch.  The caller must not have changed the bound parameters or the hit list in between.
+ *   head_forward_mc       tcvn_head_forward in this mode, on either encoder path.
+ *   rows_bn_prelu_forward_mc   tcvn_rows_bn_prelu_forward on running statistics (never written) with dropout drop_p in [0, 1) drawn.
+ *   mc_dropout_stats      sample_logits [n_samples, rows, classes] fp32 -> per row, with p_t = softmax(sample t) in double precision
+ *               (max-subtracted), natural logarithms and 0 ln 0 = 0:
+ *                 mean_prob[c] = 1/T sum_t p_t[c];  std_prob[c] = sqrt(sum_t (p_t[c] - mean_prob[c])^2 / (T - 1)), 0 at T = 1;
+ *                 entropy = -sum_c mean_prob[c] ln mean_prob[c];  expected_entropy = 1/T sum_t H(p_t);
+ *                 mutual_info = max(entropy - expected_entropy, 0);  votes[c] = the share of samples whose arg max is c (ties: the
+ *                 lowest class).
+ *               mean_prob, std_prob, votes [rows, classes]; entropy, expected_entropy, mutual_info [rows].  valid [rows] int32 or NULL:
+ *               rows with valid[r] < 0 (padded prong slots) are NaN in every output.  One wave per row, its lanes stride over the
+ *               samples; sums in a fixed order without atomics (two runs agree bit for bit), rounded to fp32 once.
+ *               Argument errors (NULL other than valid, n_samples < 1, classes outside 1..TCVN_MC_MAX_CLASSES) return non-zero before
+ *               any launch and print one "tcvn:" line. */
+#define TCVN_MC_MAX_CLASSES 256
+int tcvn_densenet_forward_mc(tcvn_densenet* p, int n_img, const int32_t* coords, const float* values, int64_t nnz, int log_pixels,
+                             float* out, int64_t out_ld, void* workspace, int64_t workspace_bytes, uint64_t seed, int resume,
+                             void* stream);
+int tcvn_head_forward_mc(tcvn_head* p, int batch, int max_prongs, int n_prongs, const float* rows, const int32_t* tok_row,
+                         float* event_logits, float* prong_logits, void* workspace, int64_t workspace_bytes, uint64_t seed,
+                         void* stream);
+int tcvn_rows_bn_prelu_forward_mc(const float* x, int64_t ldx, int rows, int channels, const float* gamma, const float* beta,
+                                  const float* slope, const float* running_mean, const float* running_var, float* y, int64_t ldy,
+                                  float drop_p, uint64_t seed, uint32_t stream_id, void* stream);
+int tcvn_mc_dropout_stats(const float* sample_logits, const int32_t* valid, int n_samples, int rows, int classes, float* mean_prob,
+                          float* std_prob, float* entropy, float* expected_entropy, float* mutual_info, float* votes, void* stream);
+
 /* Row operators behind the holder modules' own forward() (forward only, fp32):
  *   y = x W^T + b (torch.nn.Linear layout; bias may be NULL)                      -- layers/prong_decoder.py:15-16
  *   y = dropout(prelu(batchnorm1d(x)))  with batch statistics + running-stat update when train != 0, running statistics

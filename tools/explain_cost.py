@@ -6,8 +6,10 @@ them occlusion_refine(tile=(64, 64), levels=4) -- the same 8x8 grid, coarse to f
 occlusion_curves(steps=10) on the 16x16 heat map is timed with its V = 11 x maps (the 16x16 scan that gives the heat map is not in it).
 prong_shapley() is timed with its default keywords and with max_exact=12, beside leave_one_prong_out: the whole call (forward() included)
 and the coalition scan alone on the same tokens, with the number of coalitions and of encoder passes.
+mc_dropout() is timed at samples = 8 and 32, with and without reuse_stem: the whole call (forward() and the statistics included) and,
+from it and the forward() line, what one sample costs beside one forward().
 
-    python tools/explain_cost.py [--batch 32 --reps 15 --occ-reps 3 --shap-reps 5 --precision bf16 --keep 0.25]
+    python tools/explain_cost.py [--batch 32 --reps 15 --occ-reps 3 --shap-reps 5 --mc-reps 3 --precision bf16 --keep 0.25]
 """
 import argparse
 import json
@@ -31,6 +33,7 @@ def main():
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--occ-reps", type=int, default=3, help="repetitions of each occlusion_maps line (0: skip them)")
     ap.add_argument("--shap-reps", type=int, default=5, help="repetitions of each prong_shapley line (0: skip them)")
+    ap.add_argument("--mc-reps", type=int, default=3, help="repetitions of each mc_dropout line (0: skip them)")
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--keep", type=float, nargs="*", default=[0.25], help="keep of each occlusion_refine line (none: skip them)")
     args = ap.parse_args()
@@ -118,6 +121,14 @@ def main():
             "coalitions": J, "exact_events": int(res.exact.sum()), "sampled_events": int((~res.exact).sum()),
             "passes": -(-J // _lib.SHAP_MAX_PASS), "max_pass": _lib.SHAP_MAX_PASS, "reps": args.shap_reps, "ms": ms(ts), "scan_ms": ms(scan),
             "scan_us_per_coalition": round(1e3 * statistics.median(scan) / J, 3)}
+    fwd = out["forward_ms"]["median"]
+    for samples in (8, 32) if args.mc_reps > 0 else ():
+        for reuse in (True, False):
+            res, ts = timed(lambda: model.mc_dropout(*inputs[:8], samples=samples, reuse_stem=reuse), args.mc_reps)
+            per = (statistics.median(ts) - fwd) / samples
+            out[f"mc_dropout_samples{samples}" + ("" if reuse else "_no_reuse_stem")] = {
+                "samples": res.samples, "reps": args.mc_reps, "ms": ms(ts), "ms_per_sample": round(per, 3),
+                "sample_over_forward": round(per / fwd, 3)}
     cfg = rt.head.cfg
     out["weights_bytes"] = cfg.n_layers * args.batch * cfg.heads * (1 + width) ** 2 * 4
     print(json.dumps(out))
