@@ -6,7 +6,7 @@
 // 1x1 backward kernel (bwd1x1_fused.hip) rebuilds the same activation from x on its side.
 // One workgroup = one 64-pixel tile, all 128 output channels (a wave owns 32 of them: its weight fragments for the whole K extent stay in
 // registers).  K <= 256 (dense blocks 1-2): one or two resident chunks, three to four workgroups per CU; 256 < K <= 512 (k_fwd1x1_wide_bf16):
-// the chunks stream through a two-slot ring, two workgroups per CU.  Arithmetic and summation orders are those of k_gemm_nt_bf16<EPI_FWD>
+// the chunks stream through a three-slot ring (two in flight), two workgroups per CU.  Arithmetic and summation orders are those of k_gemm_nt_bf16<EPI_FWD>
 // on the materialised operand: identical Y.  OACT (eval mode): norm2 + PReLU2 of the consumer in the epilogue.
 #include "tcvn_ops.h"
 #include "prof.h"
@@ -232,13 +232,29 @@ __global__ __launch_bounds__(256, 3) void k_fwd1x1_fused_bf16(const Fwd1x1Args g
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // Wide layers (256 < K <= 512: the deep half of dense block 3, blocks 4-5): the K extent does not fit LDS next to a second workgroup, so its
-// 128-channel chunks stream through a two-slot ring -- chunk kc + 1 (or the next tile's first chunk) is requested before chunk kc is
-// activated and multiplied.  Same arithmetic and summation order as above (k ascending); all 32 weight fragments of a wave in registers.
+// 128-channel chunks stream through a three-slot ring.  A workgroup's chunks form one sequence q = 0, 1, 2, ... that runs across its tiles
+// (after a tile's last chunk come the next tile's chunks 0 and 1); chunk q lives in slot q % 3, and chunk q + 2 is requested at the top of
+// chunk q, so two 16 KB chunks travel while one is activated and multiplied.  Same arithmetic and summation order as above (k ascending);
+// all 32 weight fragments of a wave in registers.
+//
+// Vector-memory queue of a wave (it retires in issue order; every request is ROWS / 16 = 4 DMAs per thread, unconditionally):
+//   top of chunk q, before the wait:   R(q)  [S]  R(q+1)  [S]        S = the 4 Y stores of a FULL tile's epilogue, present where the epilogue
+//                                                                    lies between the two requests (q is chunk 1) or after both (q is chunk 0)
+//   the wait leaves R(q+1) in flight:  vmcnt(4), which retires an S between the two requests as well (it is a whole chunk old);
+//                                      vmcnt(8) at chunk 0 of every tile but the workgroup's first, where S is younger than R(q+1);
+//                                      vmcnt(0) where R(q+1) does not exist (the last chunk of the launch for this workgroup).
+//   Only a full tile is followed by another chunk (the partial tile is the launch's last), so S is exactly 4 where it is counted.
+// Slot reuse: R(q+2) overwrites slot (q + 2) % 3 = (q - 1) % 3, whose readers are chunk q - 1's MFMA loop (and before it the in-place
+// activation).  A wave has its fragments in registers before it issues the MFMAs and reaches the next barrier, so for every slot the barrier
+// that frees it is the one at the top of the chunk that follows its reader: slot 0 (q = 3n) is free after the top barrier of chunk 3n + 1,
+// slot 1 after that of 3n + 2, slot 2 after that of 3n + 3 -- exactly where the request into it is issued.  The landed data of chunk q are read
+// after that same top barrier, which every wave passes only after its own counted wait.
 // ---------------------------------------------------------------------------------------------------------------------------------
 struct WideCfg {
-    static constexpr int OFF_C = 2 * TILE;
+    static constexpr int NSLOT = 3;
+    static constexpr int OFF_C = NSLOT * TILE;
     static constexpr int OFF_TAB = OFF_C + ROWS * CLD * 2;
-    static constexpr int SMEM = OFF_TAB + 3 * 512 * 4;             // 56 320 B: two workgroups per CU
+    static constexpr int SMEM = OFF_TAB + 3 * 512 * 4;             // 72 704 B: two workgroups per CU
 };
 
 template <bool OACT>
@@ -267,6 +283,7 @@ __global__ __launch_bounds__(256, 2) void k_fwd1x1_wide_bf16(const Fwd1x1Args g)
         }
         tab[i] = tsc; tab[512 + i] = tsh; tab[1024 + i] = ok ? g.sl[i] : 0.f;
     }
+    __syncthreads();                                                       // the table is in LDS: the tile loop has bare barriers only
     bf16x8_t bw[KS];
     {
         const bf16* __restrict__ Wf = reinterpret_cast<const bf16*>(g.Wfrag) + (((long)(tid >> 6) * ksteps) * 64 + (tid & 63)) * 8;
@@ -303,11 +320,25 @@ __global__ __launch_bounds__(256, 2) void k_fwd1x1_wide_bf16(const Fwd1x1Args g)
         }
     };
 
-    long mt = blockIdx.x;
+    // the request sequence (all wave-uniform): r_mt / r_kc / r_slot name the next chunk to ask for, inflight counts requests not yet waited for
+    long r_mt = blockIdx.x;
+    int r_kc = 0, r_slot = 0, inflight = 0;
+    auto request_next = [&]() {
+        if (r_mt >= mtiles) return;
+        request(r_mt, r_kc, r_slot);
+        ++inflight;
+        if (++r_kc == nkc) { r_kc = 0; r_mt += gridDim.x; }
+        r_slot = r_slot == WideCfg::NSLOT - 1 ? 0 : r_slot + 1;
+    };
+    // every load of the prologue (weight fragments, bias) has returned before the first request: told to the compiler with its own wait
+    // instruction (vmcnt(0); it cannot see into an asm), or it would wait for them inside the loop with a vmcnt(0) that drains the ring
+    __builtin_amdgcn_s_waitcnt(0x0F70);
+    request_next();
+    request_next();
     int slot = 0;
-    if (mt < mtiles) request(mt, 0, 0);
-    for (; mt < mtiles; mt += gridDim.x) {
+    for (long mt = blockIdx.x; mt < mtiles; mt += gridDim.x) {
         const long m0 = mt * ROWS;
+        const bool first = mt == (long)blockIdx.x;
         int t_o = tid;
         asm volatile("" : "+v"(t_o));
         const int c8 = t_o & 15, c_r0 = t_o >> 4;
@@ -323,29 +354,47 @@ __global__ __launch_bounds__(256, 2) void k_fwd1x1_wide_bf16(const Fwd1x1Args g)
 #pragma unroll
         for (int kc = 0; kc < 4; ++kc) {
             if (kc < nkc) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __syncthreads();                                           // chunk kc has landed; the other slot's readers (previous chunk's MFMAs) are done
-                if (kc + 1 < nkc) request(mt, kc + 1, slot ^ 1);
-                else if (mt + gridDim.x < mtiles) request(mt + gridDim.x, 0, slot ^ 1);
+                // this chunk has landed, the newest request stays in flight (the counts: see the head of this section)
+                if (inflight < 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                else if (kc == 0 && !first) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+                else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+                asm volatile("s_barrier" ::: "memory");                    // every wave's part of the chunk; the previous chunk's readers are done
+                --inflight;
+                request_next();                                            // two chunks ahead, into the previous chunk's slot
                 // ---- activate chunk kc in place
                 const int col = kc * 128 + c8 * 8;
                 if (col < K) {
                     const float* tp = tab + col;
-                    const float4 s0 = *reinterpret_cast<const float4*>(tp), s1 = *reinterpret_cast<const float4*>(tp + 4);
-                    const float4 h0 = *reinterpret_cast<const float4*>(tp + 512), h1 = *reinterpret_cast<const float4*>(tp + 516);
-                    const float4 l0 = *reinterpret_cast<const float4*>(tp + 1024), l1 = *reinterpret_cast<const float4*>(tp + 1028);
+                    // f32x4, not float4: an LDS read of the struct type carries no type-based alias information, and before such a read the
+                    // compiler waits for every LDS-DMA in flight (s_waitcnt vmcnt(0)) -- which drained the request just issued
+                    const f32x4 s0 = *reinterpret_cast<const f32x4*>(tp), s1 = *reinterpret_cast<const f32x4*>(tp + 4);
+                    const f32x4 h0 = *reinterpret_cast<const f32x4*>(tp + 512), h1 = *reinterpret_cast<const f32x4*>(tp + 516);
+                    const f32x4 l0 = *reinterpret_cast<const f32x4*>(tp + 1024), l1 = *reinterpret_cast<const f32x4*>(tp + 1028);
                     const float sc[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
                     const float sh[8] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
                     const float sl[8] = {l0.x, l0.y, l0.z, l0.w, l1.x, l1.y, l1.z, l1.w};
                     const int nrem = K - col;
+                    // eight live channels (every piece but the one that straddles K): no per-element guard, which compiles to a branch each
+                    if (nrem >= 8) {
 #pragma unroll
-                    for (int i = 0; i < ROWS / 16; ++i) {
-                        u16x8* p = reinterpret_cast<u16x8*>(smem + slot * TILE + e_off + i * 4096);
-                        const u16x8 v = *p;
-                        u16x8 o;
+                        for (int i = 0; i < ROWS / 16; ++i) {
+                            u16x8* p = reinterpret_cast<u16x8*>(smem + slot * TILE + e_off + i * 4096);
+                            const u16x8 v = *p;
+                            u16x8 o;
 #pragma unroll
-                        for (int j = 0; j < 8; ++j) o[j] = j < nrem ? f2bf(prelu(fmaf(bf2f(v[j]), sc[j], sh[j]), sl[j])) : (bf16)0;
-                        *p = o;
+                            for (int j = 0; j < 8; ++j) o[j] = f2bf(prelu(fmaf(bf2f(v[j]), sc[j], sh[j]), sl[j]));
+                            *p = o;
+                        }
+                    } else {
+#pragma unroll
+                        for (int i = 0; i < ROWS / 16; ++i) {
+                            u16x8* p = reinterpret_cast<u16x8*>(smem + slot * TILE + e_off + i * 4096);
+                            const u16x8 v = *p;
+                            u16x8 o;
+#pragma unroll
+                            for (int j = 0; j < 8; ++j) o[j] = j < nrem ? f2bf(prelu(fmaf(bf2f(v[j]), sc[j], sh[j]), sl[j])) : (bf16)0;
+                            *p = o;
+                        }
                     }
                 }
                 asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // bare barrier: a __syncthreads() would drain the request just issued
@@ -353,19 +402,19 @@ __global__ __launch_bounds__(256, 2) void k_fwd1x1_wide_bf16(const Fwd1x1Args g)
                 auto afrag = [&](int ks, int i) {
                     return *reinterpret_cast<const bf16x8_t*>(smem + slot * TILE + a_base + i * 8192 + (w4 ^ (ks << 5)));
                 };
+                // all eight k-steps, unconditionally: beyond ksteps the weight fragments are zero and the chunk holds zeros (zero line, or
+                // nrem above), so those steps add +0 to an accumulator that cannot be -0 -- the same bits, without a branch per step
                 bf16x8_t a0 = afrag(0, 0), a1 = afrag(0, 1);
 #pragma unroll
                 for (int ks = 0; ks < 8; ++ks) {
-                    if (kc * 8 + ks < ksteps) {
-                        bf16x8_t b0 = a0, b1 = a1;
-                        if (ks + 1 < 8 && kc * 8 + ks + 1 < ksteps) { b0 = afrag(ks + 1, 0); b1 = afrag(ks + 1, 1); }
-                        acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, bw[kc * 8 + ks], acc[0], 0, 0, 0);
-                        acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, bw[kc * 8 + ks], acc[1], 0, 0, 0);
-                        a0 = b0; a1 = b1;
-                    }
+                    bf16x8_t b0 = a0, b1 = a1;
+                    if (ks + 1 < 8) { b0 = afrag(ks + 1, 0); b1 = afrag(ks + 1, 1); }
+                    acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, bw[kc * 8 + ks], acc[0], 0, 0, 0);
+                    acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, bw[kc * 8 + ks], acc[1], 0, 0, 0);
+                    a0 = b0; a1 = b1;
                     __builtin_amdgcn_sched_barrier(0);
                 }
-                slot ^= 1;
+                slot = slot == WideCfg::NSLOT - 1 ? 0 : slot + 1;
             }
         }
         {
@@ -383,20 +432,25 @@ __global__ __launch_bounds__(256, 2) void k_fwd1x1_wide_bf16(const Fwd1x1Args g)
         {
             const bf16* crow = Cs + c_r0 * CLD + c8 * 8;
             bf16* yb = reinterpret_cast<bf16*>(g.Out) + (m0 + c_r0) * 128 + c8 * 8;
+            auto row = [&](int i) {
+                const u16x8 o = *reinterpret_cast<const u16x8*>(crow + i * 16 * CLD);
 #pragma unroll
-            for (int i = 0; i < ROWS / 16; ++i) {
-                if (m0 + c_r0 + 16 * i < g.M) {
-                    const u16x8 o = *reinterpret_cast<const u16x8*>(crow + i * 16 * CLD);
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const float x = bf2f(o[j]);
-                        st1[j] += x; st2[j] += x * x;
-                    }
-                    *reinterpret_cast<u16x8*>(yb + (long)i * 16 * 128) = o;
+                for (int j = 0; j < 8; ++j) {
+                    const float x = bf2f(o[j]);
+                    st1[j] += x; st2[j] += x * x;
                 }
+                *reinterpret_cast<u16x8*>(yb + (long)i * 16 * 128) = o;
+            };
+            if (m0 + ROWS <= g.M) {                                        // full tile: exactly four stores per thread, the count the ring's waits rely on
+#pragma unroll
+                for (int i = 0; i < ROWS / 16; ++i) row(i);
+            } else {                                                       // the launch's last, partial tile: no chunk follows it in this workgroup
+#pragma unroll
+                for (int i = 0; i < ROWS / 16; ++i)
+                    if (m0 + c_r0 + 16 * i < g.M) row(i);
             }
         }
-        // (the next tile's C tile is written three barriers from here)
+        // (the next tile's C tile is written after the barriers of its chunks)
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (g.part == nullptr && g.isum_out == nullptr) return;
