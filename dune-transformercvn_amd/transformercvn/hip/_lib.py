@@ -32,6 +32,8 @@ OCC_GROUP_EVENT, OCC_GROUP_MAP = 0, 1          # TCVN_OCC_GROUP_*: whose largest
 OCC_MAX_LEVELS = 16                 # TCVN_OCC_MAX_LEVELS: levels of one coarse-to-fine occlusion scan
 CURVE_MAX_STEPS, CURVE_MAX_TILES = 64, 4096    # TCVN_CURVE_MAX_*: steps of a deletion / insertion curve, tiles per map it can rank
 CURVE_DELETION, CURVE_INSERTION = 0, 1         # TCVN_CURVE_*: which hits a curve variant keeps
+DET_MAX_EFFECTS = 64                # TCVN_DET_MAX_EFFECTS: settings of one detector-effect scan
+DET_SCOPE_EVENT, DET_SCOPE_MAP = 0, 1          # TCVN_DET_SCOPE_*: an effect hits every map of an event, or one map at a time
 MC_MAX_CLASSES = 256                # TCVN_MC_MAX_CLASSES: the widest logit row tcvn_mc_dropout_stats takes
 SCONV_KERNELS = ("generic", "c64", "g", "s2", "in")    # TCVN_SCONV_*: kernel families of the SDXL embedder's convolutions
 
@@ -53,6 +55,12 @@ class HeadCfg(C.Structure):
                 ("dec_out_in", C.c_int), ("gelu", C.c_int), ("norm_first", C.c_int), ("dropout_modules", C.c_int),
                 ("dropout", C.c_float), ("gamma", C.c_float), ("event_weight", C.c_float),
                 ("no_linear_bn", C.c_int), ("linear_relu", C.c_int)]
+
+
+class DetectorEffectC(C.Structure):
+    """struct tcvn_detector_effect"""
+    _fields_ = [("scale", C.c_float), ("threshold", C.c_float), ("drop", C.c_float), ("dead_y0", C.c_int32), ("dead_y1", C.c_int32),
+                ("dead_x0", C.c_int32), ("dead_x1", C.c_int32), ("shift_y", C.c_int32), ("shift_x", C.c_int32), ("seed", C.c_uint64)]
 
 
 def _load():
@@ -131,6 +139,10 @@ def _load():
     sig("tcvn_occlusion_curve_build_pass", i32, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, i64, i32, i32, vp, vp, i64,
         vp)
     sig("tcvn_occlusion_curve", i32, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp)
+    sig("tcvn_detector_workspace_bytes", i64, i32, i32, i32)
+    sig("tcvn_detector_variants", i32, vp, i64, i32, i32, i32, i32, vp, vp, P(DetectorEffectC), i32, i32, vp, vp, vp, i64, P(i64), i64, vp)
+    sig("tcvn_detector_build_pass", i32, vp, vp, i64, i32, i32, i32, i32, vp, i32, i32, vp, vp, i64, i32, i32, vp, vp, i64, vp)
+    sig("tcvn_detector_response", i32, vp, vp, vp, vp, vp, i64, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp)
     sig("tcvn_linear_forward", i32, vp, i64, vp, vp, vp, i64, i32, i32, i32, vp)
     sig("tcvn_rows_bn_prelu_forward", i32, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp, i32, f32, u64, C.c_uint32, vp)
     sig("tcvn_densenet_forward_mc", i32, vp, i32, vp, vp, i64, i32, vp, i64, vp, i64, u64, i32, vp)
@@ -179,6 +191,7 @@ EXPORTS = [
     "tcvn_occlusion_curve_workspace_bytes", "tcvn_occlusion_curve_variants", "tcvn_occlusion_curve_build_pass", "tcvn_occlusion_curve",
     "tcvn_head_shapley_workspace_bytes", "tcvn_head_shapley_count", "tcvn_head_shapley",
     "tcvn_densenet_forward_mc", "tcvn_head_forward_mc", "tcvn_rows_bn_prelu_forward_mc", "tcvn_mc_dropout_stats",
+    "tcvn_detector_workspace_bytes", "tcvn_detector_variants", "tcvn_detector_build_pass", "tcvn_detector_response",
 ]
 
 lib = _load()

@@ -193,6 +193,43 @@ class _EmbedderEngine(_Plan):
         check(fn(_ptr(coords), _ptr(values), coords.shape[0], values.shape[1], *plan.geometry, _ptr(plan.vimg), _ptr(plan.ws),
                  plan.ws.numel(), first, count, _ptr(out_coords), _ptr(out_values), out_coords.shape[0], _stream_ptr()), what)
 
+    # ---- detector-effect scan: the variants transform the hits (hip/detector.py); passes and embedder forward are the occlusion scan's -----
+    def detector_variants(self, coords: torch.Tensor, values: torch.Tensor, n_img: int, shape: Tuple[int, int], img_bs: torch.Tensor,
+                          max_pass: int, effects) -> Tuple[VariantPlan, bool, bool]:
+        """tcvn_detector_variants: one variant per (map of this list that holds a hit, effect) -- effects: a ctypes array of
+        _lib.DetectorEffectC -- with index [V, 4] = (b, s, k, surviving hits).  Same results as occlusion_variants(); the plan serves
+        detector_build.  One synchronisation."""
+        assert coords.dtype == torch.int32 and coords.is_contiguous() and img_bs.dtype == torch.int32 and img_bs.shape == (n_img, 2)
+        assert values.dtype == torch.float32 and values.is_contiguous() and values.shape[0] == coords.shape[0]
+        assert values.device == coords.device and img_bs.device == coords.device
+        (H, W), K = shape, len(effects)
+        need = lib.tcvn_detector_workspace_bytes(n_img, K, max_pass)
+        if need < 0:
+            raise RuntimeError(f"libtcvn_hip: detector_variants: the workspace query rejects {n_img} maps under {K} effects")
+        dev, rows = coords.device, n_img * K
+        img_bs = img_bs.contiguous()
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        vimg = torch.empty(rows, dtype=torch.int32, device=dev)
+        index = torch.empty(rows, 4, dtype=torch.int32, device=dev)
+        words = 4 + -(-rows // max_pass) + 1
+        host = (C.c_int64 * words)()
+        check(lib.tcvn_detector_variants(_ptr(coords), coords.shape[0], n_img, H, W, values.shape[1], _ptr(values), _ptr(img_bs), effects, K,
+                                         max_pass, _ptr(vimg), _ptr(index), _ptr(ws), ws.numel(), host, words, _stream_ptr()),
+              "detector_variants")
+        V = int(host[0])
+        bounds = [int(host[4 + k]) for k in range(-(-V // max_pass) + 1)]
+        return VariantPlan(V, bounds, vimg[:V], index[:V], ws, (n_img, H, W, img_bs, K, max_pass)), bool(host[1]), bool(host[2])
+
+    def detector_build(self, plan: VariantPlan, coords: torch.Tensor, values: torch.Tensor, first: int, count: int,
+                       out_coords: torch.Tensor, out_values: torch.Tensor):
+        """tcvn_detector_build_pass: the transformed hit lists of variants first .. first + count - 1 of a plan of detector_variants()."""
+        assert out_coords.dtype == torch.int32 and out_coords.is_contiguous() and out_values.is_contiguous()
+        assert out_values.dtype == torch.float32 and out_values.shape == (out_coords.shape[0], values.shape[1])
+        n_img, H, W, img_bs, K, max_pass = plan.geometry
+        check(lib.tcvn_detector_build_pass(_ptr(coords), _ptr(values), coords.shape[0], values.shape[1], n_img, H, W, _ptr(img_bs), K,
+                                           max_pass, _ptr(plan.vimg), _ptr(plan.ws), plan.ws.numel(), first, count, _ptr(out_coords),
+                                           _ptr(out_values), out_coords.shape[0], _stream_ptr()), "detector_build_pass")
+
     def occlusion_forward(self, coords: torch.Tensor, values: torch.Tensor, nnz: int, n_img: int, out: torch.Tensor, log_pixels: int = 0):
         """The plan's eval forward over one pass of variant maps (the first nnz rows of coords / values; nnz = 0: empty maps), in a
         workspace of its own: what the last forward() left for backward() and tap() stays as it is."""
@@ -309,6 +346,7 @@ class HeadEngine(_Plan):
         self._last = (0, -1)                 # (batch, max_prongs) of the last forward / encode on self._ws: what attention() exports
         self._loo_ws = self._occ_ws = self._shap_ws = None      # scratch workspaces (_scratch) of leave_one_out(), occlusion_pass(), shapley()
         self._mc_ws = None                   # ... and of forward_mc()
+        self._det_ws = None                  # ... and of forward_aside()
 
     def forward(self, rows: torch.Tensor, tok_row: torch.Tensor, batch: int, max_prongs: int, n_prongs: int, train: bool,
                 seed: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -334,6 +372,19 @@ class HeadEngine(_Plan):
         ws = self._scratch("_mc_ws", lib.tcvn_head_workspace_bytes(self.handle, batch, max_prongs, n_prongs), rows.device)
         check(lib.tcvn_head_forward_mc(self.handle, batch, max_prongs, n_prongs, _ptr(rows), _ptr(tok_row), _ptr(ev), _ptr(pr),
                                        _ptr(ws), ws.numel(), C.c_uint64(seed), _stream_ptr()), "head_forward_mc")
+
+    def forward_aside(self, rows: torch.Tensor, tok_row: torch.Tensor, batch: int, max_prongs: int, n_prongs: int, ev: torch.Tensor,
+                      pr: torch.Tensor):
+        """tcvn_head_forward in eval mode on other input rows of the batch layout of the last forward() -> ev [batch, Ce], pr [batch,
+        max_prongs, Cp] (contiguous, the caller's).  Workspace of its own, and neither _shape nor _last moves: attention() still
+        exports the last forward()."""
+        self._check_rows(rows, batch + n_prongs)
+        self._check_tok_row(tok_row, batch, 1 + max_prongs)
+        assert ev.dtype == torch.float32 and ev.is_contiguous() and ev.shape == (batch, self.cfg.event_classes)
+        assert pr.dtype == torch.float32 and pr.is_contiguous() and pr.shape == (batch, max_prongs, self.cfg.prong_classes)
+        ws = self._scratch("_det_ws", lib.tcvn_head_workspace_bytes(self.handle, batch, max_prongs, n_prongs), rows.device)
+        check(lib.tcvn_head_forward(self.handle, batch, max_prongs, n_prongs, _ptr(rows), _ptr(tok_row), _ptr(ev), _ptr(pr),
+                                    _ptr(ws), ws.numel(), 0, C.c_uint64(0), _stream_ptr()), "head_forward")
 
     def _stage_ws(self, batch: int, max_prongs: int, n_prongs: int, device):
         return self.workspace(lib.tcvn_head_workspace_bytes(self.handle, batch, max_prongs, n_prongs), device)

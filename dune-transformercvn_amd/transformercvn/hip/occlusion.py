@@ -360,13 +360,17 @@ class VariantPlan:
     geometry: Tuple[int, ...]       # (n_img, H, W, th, tw, [steps, mode,] max_pass) the list was made for: the build call repeats them
 
 
-def plan_variants(lst: HitList, shape: Tuple[int, int], tile: Tuple[int, int], max_pass: int, keep_map: Optional[Tensor] = None,
-                  curve: Optional[tuple] = None) -> Tuple[HitList, VariantPlan]:
+def plan_variants(lst: HitList, shape: Tuple[int, int], tile: Optional[Tuple[int, int]], max_pass: int,
+                  keep_map: Optional[Tensor] = None, curve: Optional[tuple] = None,
+                  detector: Optional[tuple] = None) -> Tuple[HitList, VariantPlan]:
     """The variant list of one hit list (one host read-back): every tile that holds a hit, or (keep_map) the children of the selected
     tiles of the level above, or (curve = (relevance, steps, mode, rank), see the engine's occlusion_curve_variants) the steps of a
-    deletion / insertion curve.  -> (the list the plan is for, the plan): `lst` itself, or a cleaned copy if the engine found it unsorted
-    or with hits outside the maps -- the caller keeps that one for the later levels."""
+    deletion / insertion curve, or (detector = (effects,), see the engine's detector_variants; no tile) the maps under detector
+    effects.  -> (the list the plan is for, the plan): `lst` itself, or a cleaned copy if the engine found it unsorted or with hits
+    outside the maps -- the caller keeps that one for the later levels."""
     def variants(hits):
+        if detector is not None:
+            return hits.engine.detector_variants(hits.coords, hits.values, hits.n_img, shape, hits.img_bs, max_pass, *detector)
         if curve is not None:
             return hits.engine.occlusion_curve_variants(hits.coords, hits.n_img, shape, tile, hits.img_bs, max_pass, *curve)
         if keep_map is None:
@@ -395,7 +399,7 @@ class Scan:
                  event_px, prong_px, prong_mask: Tensor, maps: str):
         self.head, self.shape, self.last, self.ev, self.pr = head, tuple(pixel_shape), last, event_logits, prong_logits
         B, dev = last.B, last.rows.device
-        self.tokens = head.embed(last.rows, last.tok_row, B, last.P, last.n_prongs, False, 0)
+        self._tokens: Optional[Tensor] = None
         self.lists: List[HitList] = []
         if maps in ("all", "event"):
             bs = torch.stack((torch.arange(B, device=dev), torch.zeros(B, dtype=torch.int64, device=dev)), 1).to(torch.int32)
@@ -406,6 +410,15 @@ class Scan:
             # a prong's pixel embedding sits behind its feature embedding; the event embedder is wider by exactly those columns
             self.lists.append(HitList(pr_engine, prong_px.coords.to(dev), prong_px.values.to(dev), prong_px.value_mode, last.n_prongs, bs,
                                       B, ev_engine.out_dim - pr_engine.out_dim))
+
+    @property
+    def tokens(self) -> Tensor:
+        """The tokens [B, 1 + P, hidden] of the forward being explained, rebuilt from its rows when a token path first asks for them
+        (a whole-event detector scan never does)."""
+        if self._tokens is None:
+            last = self.last
+            self._tokens = self.head.embed(last.rows, last.tok_row, last.B, last.P, last.n_prongs, False, 0)
+        return self._tokens
 
     def level(self, tile: Tuple[int, int], max_pass: int, keep_map: Optional[Tensor] = None,
               budget: Optional[int] = None) -> Optional[OcclusionResult]:
@@ -440,14 +453,25 @@ class Scan:
         """The variants of one list, pass by pass, through its embedder and the token path -> (index [V, 4], occluded_event_logits
         [V, Ce], occluded_prong_logits [V, P, Cp]) in the embedder's image order.  The embedder writes [col0, col0 + engine.out_dim)
         of its maps' rows.  build: the engine call that writes a pass's hit lists from `plan` (default: occlusion_build)."""
-        engine, head, last = lst.engine, self.head, self.last
-        build = build or engine.occlusion_build
+        head, last = self.head, self.last
         dev = last.rows.device
-        V, bounds, vimg, index = plan.V, plan.bounds, plan.vimg, plan.index
+        V, vimg, index = plan.V, plan.vimg, plan.index
         occ_ev = torch.empty(V, head.cfg.event_classes, device=dev)
         occ_pr = torch.empty(V, self.tokens.shape[1] - 1, head.cfg.prong_classes, device=dev)
+        for first, n, emb in self._embeddings(lst, plan, max_pass, build):
+            head.occlusion_pass(last.rows, self.tokens, last.tok_row, last.n_prongs, vimg[first:first + n], index[first:first + n],
+                                lst.row_base, emb, lst.col0, occ_ev[first:first + n], occ_pr[first:first + n])
+        return index, occ_ev, occ_pr
+
+    def _embeddings(self, lst: HitList, plan: VariantPlan, max_pass: int, build=None):
+        """The variants of one list through its embedder, pass by pass: yields (first, n, emb [n, engine.out_dim]) for variants first ..
+        first + n - 1.  emb is one buffer, rewritten by the next pass.  build: see _passes."""
+        engine = lst.engine
+        build = build or engine.occlusion_build
+        dev = self.last.rows.device
+        V, bounds = plan.V, plan.bounds
         if V == 0:
-            return index, occ_ev, occ_pr
+            return
         cap = max(1, max(bounds[k + 1] - bounds[k] for k in range(len(bounds) - 1)))
         out_coords = torch.empty(cap, 3, dtype=torch.int32, device=dev)
         out_values = torch.empty(cap, lst.values.shape[1], dtype=torch.float32, device=dev)
@@ -459,9 +483,7 @@ class Scan:
             if nnz > 0:
                 build(plan, lst.coords, lst.values, first, n, out_coords, out_values)
             engine.occlusion_forward(out_coords, out_values, nnz, n, emb[:n], lst.value_mode)
-            head.occlusion_pass(last.rows, self.tokens, last.tok_row, last.n_prongs, vimg[first:first + n], index[first:first + n],
-                                lst.row_base, emb[:n], lst.col0, occ_ev[first:first + n], occ_pr[first:first + n])
-        return index, occ_ev, occ_pr
+            yield first, n, emb[:n]
 
     def curves(self, relevance: Tensor, tile: Tuple[int, int], steps: int, mode: str, max_pass: int) -> "OcclusionCurves":
         """Deletion / insertion curves of relevance float32 [B, 1 + P, Ht, Wt] on the grid of `tile`: the tiles of every scanned map

@@ -14,10 +14,10 @@ from typing import Dict, List, NamedTuple, Optional, Tuple
 import torch
 from torch import Tensor, nn
 
-from . import _lib, attention, occlusion, uncertainty
+from . import _lib, attention, detector, occlusion, uncertainty
 from .engine import DenseNetEngine, HeadEngine, mc_stats
 from .native import gpu_only
-from .pixels import SparsePixels
+from .pixels import SparsePixels, VALUE_ONE_HOT
 from ..network.layers.packed_data import token_rows
 
 PRECISIONS = {"fp32": _lib.MODE_F32, "f32": _lib.MODE_F32, "32": _lib.MODE_F32, "bf16": _lib.MODE_BF16, "16": _lib.MODE_BF16}
@@ -320,7 +320,7 @@ class HipRuntime:
             return (hidden, self.head.attention(tok)) if return_attention else hidden
 
     # ---------------------------------------------------------------------------------------------------------------
-    # explaining a prediction (forward only): attention maps, the leave-one-prong-out scan, occlusion maps
+    # explaining a prediction (forward only): attention maps, the leave-one-prong-out scan, occlusion maps, detector-effect scans
     # ---------------------------------------------------------------------------------------------------------------
     def forward_with_attention(self, features: Tensor, extra: Tensor, event_px: SparsePixels, event_mask: Tensor, prong_px: SparsePixels,
                                prong_mask: Tensor, counts: Optional[Tuple[int, int]] = None) -> Tuple[Tensor, Tensor, Tensor]:
@@ -425,6 +425,19 @@ class HipRuntime:
             relevance = occlusion.relevance_map(relevance)
             scan = self._scan(maps, features, extra, event_px, event_mask, prong_px, prong_mask, counts)
             return scan.curves(relevance, tile, steps, mode, max_pass)
+
+    def forward_detector_scan(self, features: Tensor, extra: Tensor, event_px: SparsePixels, event_mask: Tensor,
+                              prong_px: SparsePixels, prong_mask: Tensor, counts: Optional[Tuple[int, int]] = None, effects=None,
+                              scope: str = "event", maps: str = "all", max_maps_per_pass: int = 256):
+        """Eval-mode forward() plus the detector-effect scan over its pixel maps (detector.scan: every scanned map under every
+        DetectorEffect of `effects`, the whole event at once or one map at a time) -> detector.DetectorScan."""
+        one_hot = VALUE_ONE_HOT in (event_px.value_mode, prong_px.value_mode)
+        effects, scope, maps, max_pass = detector.check_args(effects, scope, maps, max_maps_per_pass, self.pixel_shape, one_hot)
+        if self.network.training:
+            raise RuntimeError("detector_scan varies an eval-mode prediction: call network.eval() first")
+        with torch.no_grad():
+            scan = self._scan(maps, features, extra, event_px, event_mask, prong_px, prong_mask, counts)
+            return detector.scan(scan, effects, scope, max_pass)
 
     # ---------------------------------------------------------------------------------------------------------------
     # predictive uncertainty (forward only): Monte-Carlo dropout

@@ -234,6 +234,27 @@ class NeutrinoBaseNetwork(nn.Module):
         return self.hip_runtime().forward_occlusion_curves(features, extra, event_pixels, event_mask, prong_pixels, prong_mask, counts,
                                                            relevance, tile, steps, mode, maps, max_maps_per_pass)
 
+    # ---- how far a prediction moves under detector effects (eager only; forward only, no autograd graph) -----------------------------
+    @torch.jit.unused
+    def detector_scan(self, features: Tensor, extra: Tensor, event_pixels: Tensor, event_mask: Tensor, prong_pixels: Tensor,
+                      prong_mask: Tensor, counts: Optional[Tuple[int, int]] = None, effects=None, scope: str = "event",
+                      maps: str = "all", max_maps_per_pass: int = 256):
+        """Eval mode only -> transformercvn.hip.detector.DetectorScan: the prediction of forward() and the prediction under each of the
+        1..64 DetectorEffect settings of `effects` (charge scale, hit threshold, dead rows / columns, hit inefficiency, a shifted
+        window; applied per hit as drop, dead, scale, threshold, shift).  scope "event": every scanned map of an event under the same
+        setting at once, varied logits [K, B, ...]; scope "map": one variant per (scanned map that holds a hit, setting), only that
+        map's token replaced, as in occlusion_maps.  result.response() -> class probability, its change and the flipped arg-max;
+        result.summary() -> their mean per setting.  One forward() for the step counter; nothing of the model is touched."""
+        from transformercvn.hip import detector
+        from transformercvn.hip.pixels import VALUE_ONE_HOT
+        one_hot = any(isinstance(px, SparsePixels) and px.value_mode == VALUE_ONE_HOT for px in (event_pixels, prong_pixels))
+        detector.check_args(effects, scope, maps, max_maps_per_pass, self.pixel_shape, one_hot)
+        if self.training:
+            raise RuntimeError("detector_scan varies an eval-mode prediction: call .eval() first")
+        event_pixels, prong_pixels = _as_sparse(event_pixels), _as_sparse(prong_pixels)
+        return self.hip_runtime().forward_detector_scan(features, extra, event_pixels, event_mask, prong_pixels, prong_mask, counts,
+                                                        effects, scope, maps, max_maps_per_pass)
+
     # ---- how sure is a prediction (eager only; forward only, no autograd graph) -------------------------------------------------------
     @torch.jit.unused
     def mc_dropout(self, features: Tensor, extra: Tensor, event_pixels: Tensor, event_mask: Tensor, prong_pixels: Tensor,

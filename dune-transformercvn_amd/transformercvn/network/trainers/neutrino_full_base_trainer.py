@@ -227,6 +227,21 @@ class NeutrinoFullBaseTrainer(NeutrinoBase, ABC):
                                                                    prong_coords, prong_values, prong_mask), None, relevance, tile,
                                              steps, mode, maps, max_maps_per_pass)
 
+    def detector_scan(self, features: Tensor, extra: Tensor, event_coords: Tensor, event_values: Tensor, event_mask: Tensor,
+                      prong_coords: Tensor, prong_values: Tensor, prong_mask: Tensor, effects, scope: str = "event", maps: str = "all",
+                      max_maps_per_pass: int = 256):
+        """Eval mode only -> DetectorScan (transformercvn.hip.detector): how far the prediction moves under each DetectorEffect of
+        `effects`, acting on the hits; see NeutrinoBaseNetwork.detector_scan.  Bad arguments raise ValueError and train mode
+        RuntimeError before any device work."""
+        from transformercvn.hip import detector
+        detector.check_args(effects, scope, maps, max_maps_per_pass, self.training_dataset.pixel_shape,
+                            bool(getattr(self.options, "one_hot_pixels", False)))
+        if self.training:
+            raise RuntimeError("detector_scan varies an eval-mode prediction: call .eval() first")
+        return self.network.detector_scan(*self._network_inputs(features, extra, event_coords, event_values, event_mask,
+                                                                prong_coords, prong_values, prong_mask), None, effects, scope, maps,
+                                          max_maps_per_pass)
+
     def mc_dropout(self, features: Tensor, extra: Tensor, event_coords: Tensor, event_values: Tensor, event_mask: Tensor,
                    prong_coords: Tensor, prong_values: Tensor, prong_mask: Tensor, samples: int = 32, seed: int = 0,
                    reuse_stem: bool = True):

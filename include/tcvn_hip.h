@@ -395,6 +395,61 @@ int tcvn_occlusion_curve(const float* event_logits, const float* prong_logits, c
                          int event_classes, int prong_classes, int steps, int target, const int32_t* classes, float* curve, float* auc,
                          void* stream);
 
+/* Detector-effect scans (forward only, eval arithmetic): how a prediction moves when the hits are not those of the detector the training
+ * sample assumed.  A variant is a map whose hits went through one effect; unlike the occlusion variants it transforms coordinates and
+ * values.  One effect acts on every hit (y, x, v[0..channels)) of the map (b, s) = img_bs[image] in this order -- the detector acts, then
+ * the window moves --:
+ *   1. drop       u = (philox4(y * width + x, b, s, 0x44455453, seed & 0xffffffff, seed >> 32).x >> 8) * 2^-24 (the Philox-4x32-10 of
+ *                 the dropout masks); the hit is removed iff drop > 0 and u < drop.  The draw belongs to the original pixel of the map:
+ *                 two hits on one pixel share it, and neither the hit's position in the list nor the pass enters.
+ *   2. dead       removed iff dead_y0 <= y < dead_y1 or dead_x0 <= x < dead_x1 (original coordinates; the empty range 0, 0 is "none").
+ *   3. scale      v[c] = v[c] * scale, one fp32 multiplication on the raw list value (before the embedder's log_pixels transform).
+ *   4. threshold  only if threshold > 0: every v[c] < threshold becomes 0, and a hit whose channels are all 0 afterwards is removed.
+ *   5. shift      y += shift_y, x += shift_x; a hit that leaves [0, height) x [0, width) is removed.
+ * The hits that survive keep their order (duplicate coordinates: the highest index wins, as in the embedders).
+ *   detector_variants  the hit list of tcvn_occlusion_variants and n_effects effects (host array, copied into the launch arguments: it is
+ *               not read after the call returns) -> rows (image, k), a row being a variant iff its image holds a hit inside the map (a
+ *               variant may be an empty map).  The V variants are ordered by (image, k): vimg [V] the image, index [V, 4] =
+ *               (img_bs[image][0], img_bs[image][1], k, surviving hits); both need room for n_img * n_effects rows.  The surviving hits
+ *               are counted by one thread per hit looping over the effects (integer atomics: deterministic).  host_out (4 +
+ *               ceil(n_img * n_effects / max_pass) + 1 words), the two flags, the pass boundaries and the one synchronisation are
+ *               those of tcvn_occlusion_variants.  The effects are kept in the workspace for the build passes.
+ *   detector_build_pass  the hit lists of variants first .. first + count - 1: out_coords [rows, 3] = (variant's index inside the pass,
+ *               y + shift_y, x + shift_x), out_values [rows, channels] the transformed values.  The count and the build evaluate the
+ *               same device function per hit and effect.  The result goes through the embedder and (one token replaced)
+ *               tcvn_head_occlusion unchanged; the latter reads index[j][0:2] only.
+ *   detector_response  prob = softmax(varied)[c], delta = prob - softmax(base)[c] (double precision, stored as fp32) and flipped uint8 =
+ *               (arg max of the varied row != arg max of the base row); target and classes as in tcvn_occlusion_heatmap.
+ *               TCVN_DET_SCOPE_MAP: varied_event_logits [V, Ce], varied_prong_logits [V, max_prongs, Cp] and index [V, 4] as above;
+ *               outputs [n_effects, batch, 1 + max_prongs], written at (k, b, s) of every variant.  TCVN_DET_SCOPE_EVENT: varied_event_logits
+ *               [n_effects, batch, Ce], varied_prong_logits [n_effects, batch, max_prongs, Cp], index unused; outputs [n_effects, batch]
+ *               with TCVN_OCC_TARGET_EVENT, [n_effects, batch, max_prongs] with TCVN_OCC_TARGET_PRONG: every slot p with
+ *               valid[b * (1 + max_prongs) + 1 + p] >= 0 against its own predicted class.  Every other entry is NaN (flipped 0).  No
+ *               atomics: one thread per entry.
+ * Argument errors (NULL, n_effects outside 1..TCVN_DET_MAX_EFFECTS, an effect with a negative or non-finite scale / threshold, drop
+ * outside [0, 1], a dead range outside 0 <= lo <= hi <= dimension or |shift| > 32767, max_pass outside 1..TCVN_OCC_MAX_PASS, unknown
+ * scope or target, workspace too small) return non-zero before any device call and print one "tcvn:" line. */
+#define TCVN_DET_MAX_EFFECTS 64
+#define TCVN_DET_SCOPE_EVENT 0
+#define TCVN_DET_SCOPE_MAP 1
+typedef struct tcvn_detector_effect {
+    float scale, threshold, drop;
+    int32_t dead_y0, dead_y1, dead_x0, dead_x1, shift_y, shift_x;
+    uint64_t seed;
+} tcvn_detector_effect;
+int64_t tcvn_detector_workspace_bytes(int n_img, int n_effects, int max_pass);
+int tcvn_detector_variants(const int32_t* coords, int64_t nnz, int n_img, int height, int width, int channels, const float* values,
+                           const int32_t* img_bs, const tcvn_detector_effect* effects, int n_effects, int max_pass, int32_t* vimg,
+                           int32_t* index, void* workspace, int64_t workspace_bytes, int64_t* host_out, int64_t host_cap, void* stream);
+int tcvn_detector_build_pass(const int32_t* coords, const float* values, int64_t nnz, int channels, int n_img, int height, int width,
+                             const int32_t* img_bs, int n_effects, int max_pass, const int32_t* vimg, const void* workspace,
+                             int64_t workspace_bytes, int first, int count, int32_t* out_coords, float* out_values, int64_t out_rows,
+                             void* stream);
+int tcvn_detector_response(const float* event_logits, const float* prong_logits, const float* varied_event_logits,
+                           const float* varied_prong_logits, const int32_t* index, int64_t n_variants, const int32_t* valid, int batch,
+                           int max_prongs, int event_classes, int prong_classes, int n_effects, int scope, int target,
+                           const int32_t* classes, float* prob, float* delta, uint8_t* flipped, void* stream);
+
 /* Predictive uncertainty: Monte-Carlo dropout (forward only; nothing here changes a parameter, a buffer or a running statistic).
  * A third run mode beside "train" and "eval": EVAL statistics, dropout DRAWN.  An _mc forward is the train = 0 forward of the same
  * plan (BatchNorm on running statistics, no pixel noise, no statistics partials, no keep-flag output, no running-stat update, the same

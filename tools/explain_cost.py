@@ -8,8 +8,10 @@ prong_shapley() is timed with its default keywords and with max_exact=12, beside
 and the coalition scan alone on the same tokens, with the number of coalitions and of encoder passes.
 mc_dropout() is timed at samples = 8 and 32, with and without reuse_stem: the whole call (forward() and the statistics included) and,
 from it and the forward() line, what one sample costs beside one forward().
+detector_scan() is timed with 8 effects in both scopes: the whole call (forward() included) and, from it and the forward() line, what one
+variant -- one whole-event setting, or one map under one effect -- costs beside one forward().
 
-    python tools/explain_cost.py [--batch 32 --reps 15 --occ-reps 3 --shap-reps 5 --mc-reps 3 --precision bf16 --keep 0.25]
+    python tools/explain_cost.py [--batch 32 --reps 15 --occ-reps 3 --shap-reps 5 --mc-reps 3 --det-reps 3 --precision bf16 --keep 0.25]
 """
 import argparse
 import json
@@ -34,6 +36,7 @@ def main():
     ap.add_argument("--occ-reps", type=int, default=3, help="repetitions of each occlusion_maps line (0: skip them)")
     ap.add_argument("--shap-reps", type=int, default=5, help="repetitions of each prong_shapley line (0: skip them)")
     ap.add_argument("--mc-reps", type=int, default=3, help="repetitions of each mc_dropout line (0: skip them)")
+    ap.add_argument("--det-reps", type=int, default=3, help="repetitions of each detector_scan line (0: skip them)")
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--keep", type=float, nargs="*", default=[0.25], help="keep of each occlusion_refine line (none: skip them)")
     args = ap.parse_args()
@@ -129,6 +132,20 @@ def main():
             out[f"mc_dropout_samples{samples}" + ("" if reuse else "_no_reuse_stem")] = {
                 "samples": res.samples, "reps": args.mc_reps, "ms": ms(ts), "ms_per_sample": round(per, 3),
                 "sample_over_forward": round(per / fwd, 3)}
+    if args.det_reps > 0:
+        from transformercvn.hip.detector import DetectorEffect  # noqa: E402
+        effects = [DetectorEffect(scale=0.95), DetectorEffect(scale=1.05), DetectorEffect(threshold=20.0), DetectorEffect(dead_cols=(120, 136)),
+                   DetectorEffect(dead_rows=(200, 216)), DetectorEffect(drop=0.05, seed=1), DetectorEffect(shift=(0, 4)),
+                   DetectorEffect(scale=0.95, threshold=20.0, drop=0.05, shift=(4, 0), seed=2)]
+        row = {"effects": len(effects), "reps": args.det_reps}
+        for scope in ("event", "map"):
+            res, ts = timed(lambda: model.detector_scan(*inputs[:8], effects=effects, scope=scope), args.det_reps)
+            maps = res.num_variants if scope == "map" else int((res.surviving[0] > 0).sum()) * len(effects)
+            per = (statistics.median(ts) - fwd) / res.num_variants            # a variant: one map (scope map), one whole event (scope event)
+            row[scope] = {"variants": res.num_variants, "perturbed_maps": maps, "ms": ms(ts), "ms_per_variant": round(per, 4),
+                          "variant_over_forward": round(per / fwd, 5),
+                          "us_per_perturbed_map": round(1e3 * (statistics.median(ts) - fwd) / max(1, maps), 2)}
+        out["detector_scan_effects8"] = row
     cfg = rt.head.cfg
     out["weights_bytes"] = cfg.n_layers * args.batch * cfg.heads * (1 + width) ** 2 * 4
     print(json.dumps(out))
