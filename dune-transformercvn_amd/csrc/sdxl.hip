@@ -26,6 +26,10 @@ static_assert(SCONV_GENERIC == TCVN_SCONV_GENERIC && SCONV_C64 == TCVN_SCONV_C64
               SCONV_IN == TCVN_SCONV_IN, "tcvn_sdxl_conv_kernels returns SConvKernel values under the C names");
 
 namespace {
+#ifdef TCVN_DEBUG_KNOBS
+int g_backward_stop = -1;                   // tcvn_debug_sdxl_backward_stop: backward() processes the ops last .. stop only; -1 = all
+int g_forward_stop = -1;                    // tcvn_debug_sdxl_forward_stop: forward() processes the ops 0 .. stop only; -1 = all
+#endif
 constexpr float kGnEps = 1e-6f;
 enum { OP_CONV = 0, OP_GN = 1 };
 struct SBuf { int H, W, C; };
@@ -71,6 +75,10 @@ struct tcvn_sdxl {
     int last_n = 0;
     const int32_t* last_coords = nullptr; long last_nnz = 0;       // COO list of the last forward (conv_in weight gradient)
     DevTable pack, unpack;
+#ifdef TCVN_DEBUG_KNOBS
+    std::vector<long> dbg_goff;                                    // tcvn_debug_sdxl_goff: gradient region and written flag of every buffer
+    std::vector<char> dbg_written;                                 // when the last backward returned
+#endif
 
     explicit tcvn_sdxl(const tcvn_sdxl_cfg& c);
     ~tcvn_sdxl() { if (pack.d) (void)hipFree(pack.d); if (unpack.d) (void)hipFree(unpack.d); }
@@ -269,6 +277,9 @@ int tcvn_sdxl::forward(int n, const int32_t* coords, const float* values, long n
         if ((rc = scatter_pixels(a, st))) return rc;
     }
     for (const auto& o : ops) {
+#ifdef TCVN_DEBUG_KNOBS
+        if (g_forward_stop >= 0 && &o - ops.data() > g_forward_stop) break;
+#endif
         if (o.kind == OP_GN) {
             const GnArgs a = gn_args(o, n, ws, L);
             if (!o.stats_given && (rc = gn_stats(a, st))) return rc;
@@ -309,6 +320,9 @@ int tcvn_sdxl::backward(int n, const float* d_out, long d_out_ld, char* ws, long
     if ((rc = cast_f32_to(cfg.mode, d_out, d_out_ld, ws + goff[last], bufs[last].C, n, bufs[last].C, st))) return rc;
     written[last] = 1;
     for (int oi = (int)ops.size() - 1; oi >= 0; --oi) {
+#ifdef TCVN_DEBUG_KNOBS
+        if (g_backward_stop >= 0 && oi < g_backward_stop) break;
+#endif
         const SOp& o = ops[oi];
         if (!written[o.out]) { fprintf(stderr, "tcvn: sdxl backward: gradient of buffer %d never produced\n", o.out); return -15; }
         const char* dO = ws + goff[o.out];
@@ -334,6 +348,9 @@ int tcvn_sdxl::backward(int n, const float* d_out, long d_out_ld, char* ws, long
             }
         }
     }
+#ifdef TCVN_DEBUG_KNOBS
+    dbg_goff = goff; dbg_written = written;
+#endif
     return unpack_wgrads(reinterpret_cast<const UnpackDesc*>(unpack.d), unpack.n, st);
 }
 
@@ -411,5 +428,73 @@ int tcvn_sdxl_conv_kernels(const tcvn_sdxl* p, int n_img, int conv_index, int* f
     *wgrad = sconv_wgrad_kernel(p->wgrad_call(*o, g, ws, L, ws + L.grad[o->out]));
     return 0;
 }
+int tcvn_sdxl_num_ops(const tcvn_sdxl* p) { return (int)p->ops.size(); }
+/* One op of the tape, in execution order.  Fields that do not apply to the op's kind are -1 (res without a residual; ks, stride, pad,
+ * conv_id, stats_gn and final_f32 of a GroupNorm; act, gn_id and stats_given of a convolution). */
+int tcvn_sdxl_op(const tcvn_sdxl* p, int i, int* fields, int n_fields) {
+    if (i < 0 || i >= (int)p->ops.size() || !fields || n_fields < TCVN_SDXL_OP_FIELDS) return -1;
+    const SOp& o = p->ops[i];
+    const bool cv = o.kind == OP_CONV;
+    fields[TCVN_SDXL_OP_KIND] = o.kind; fields[TCVN_SDXL_OP_IN] = o.in; fields[TCVN_SDXL_OP_OUT] = o.out; fields[TCVN_SDXL_OP_RES] = o.res;
+    fields[TCVN_SDXL_OP_W] = o.w;
+    fields[TCVN_SDXL_OP_KS] = cv ? o.ks : -1; fields[TCVN_SDXL_OP_STRIDE] = cv ? o.stride : -1; fields[TCVN_SDXL_OP_PAD] = cv ? o.pad : -1;
+    fields[TCVN_SDXL_OP_ACT] = cv ? -1 : o.act;
+    fields[TCVN_SDXL_OP_CONV_ID] = cv ? o.conv_id : -1; fields[TCVN_SDXL_OP_GN_ID] = cv ? -1 : o.gn_id;
+    fields[TCVN_SDXL_OP_STATS_GN] = cv ? o.stats_gn : -1; fields[TCVN_SDXL_OP_STATS_GIVEN] = cv ? -1 : o.stats_given;
+    fields[TCVN_SDXL_OP_FINAL_F32] = cv ? o.final_f32 : -1;
+    return 0;
+}
+/* Where a piece of the engine's state lies in a workspace of n_img maps: byte offset, shape (ndim <= 4 extents, row-major, dense) and
+ * element size.  -1: no such region in this layout (the last buffer is the caller's output; conv_in has no transposed pack; gradients,
+ * gwk and bstats exist only with_backward).  No HIP call. */
+int tcvn_sdxl_region(const tcvn_sdxl* p, int n_img, int with_backward, int what, int index, int64_t* byte_off, int64_t* shape, int* ndim,
+                     int* elem_bytes) {
+    if (n_img <= 0 || !byte_off || !shape || !ndim || !elem_bytes) return -1;
+    SLayout L;
+    p->layout(n_img, with_backward != 0, L);
+    long off = -1;
+    auto set = [&](long o, int es, int nd, long a, long b, long c, long d) {
+        off = o; *elem_bytes = es; *ndim = nd; shape[0] = a; shape[1] = b; shape[2] = c; shape[3] = d;
+    };
+    const SOp* cv = nullptr;
+    if (what == TCVN_SDXL_REGION_WK || what == TCVN_SDXL_REGION_WKT || what == TCVN_SDXL_REGION_GWK) {
+        for (const auto& q : p->ops)
+            if (q.kind == OP_CONV && q.conv_id == index) cv = &q;
+        if (!cv) return -1;
+    }
+    switch (what) {
+    case TCVN_SDXL_REGION_ACT: case TCVN_SDXL_REGION_GRAD: {
+        if (index < 0 || index >= (int)p->bufs.size()) return -1;
+        const SBuf& b = p->bufs[index];
+        set(what == TCVN_SDXL_REGION_ACT ? L.act[index] : L.grad[index], p->esz, 4, n_img, b.H, b.W, b.C);
+        break;
+    }
+    case TCVN_SDXL_REGION_WK: set(L.wk[index], p->esz, 2, p->bufs[cv->out].C, p->Kp(*cv), 1, 1); break;
+    case TCVN_SDXL_REGION_WKT: set(L.wkt[index], p->esz, 2, p->bufs[cv->in].C, p->Kpt(*cv), 1, 1); break;
+    case TCVN_SDXL_REGION_GWK: set(L.gwk[index], 4, 2, p->bufs[cv->out].C, p->Kp(*cv), 1, 1); break;
+    case TCVN_SDXL_REGION_STATS: set(L.stats, 8, 3, p->n_gn, n_img, 2, 1); break;
+    case TCVN_SDXL_REGION_BSTATS: set(L.bstats, 8, 3, p->n_gn, n_img, 2, 1); break;
+    default: return -1;
+    }
+    if (off < 0) return -1;
+    *byte_off = off;
+    return 0;
+}
 
 }  // extern "C"
+
+#ifdef TCVN_DEBUG_KNOBS
+// Validation build only.  A process-wide stop point for tcvn_sdxl_backward: it processes the ops last .. op of the tape (op = number of ops:
+// only the cast of d_out), runs the weight-gradient unpack and returns; -1 switches it off.
+extern "C" void tcvn_debug_sdxl_backward_stop(int op) { g_backward_stop = op; }
+// The same for tcvn_sdxl_forward: it scatters the pixels and processes the ops 0 .. op of the tape, so that a test can see what one op wrote
+// outside its own buffer before a later op overwrites it; -1 switches it off.
+extern "C" void tcvn_debug_sdxl_forward_stop(int op) { g_forward_stop = op; }
+// Where buffer `buf`'s gradient lay (byte offset in the workspace; a residual input may have taken over its output's region) and whether it had
+// been written when the last tcvn_sdxl_backward of this plan returned.
+extern "C" int tcvn_debug_sdxl_goff(const tcvn_sdxl* p, int buf, int64_t* off, int* written) {
+    if (buf < 0 || buf >= (int)p->dbg_goff.size()) return -1;
+    *off = p->dbg_goff[buf]; *written = p->dbg_written[buf];
+    return 0;
+}
+#endif

@@ -925,3 +925,23 @@ int add_into(int mode, void* dst, long ldd, const void* src, long lds, long rows
 }
 
 }  // namespace tcvn
+
+#ifdef TCVN_DEBUG_KNOBS
+// validation build only, at the end of the file so that no line of the kernels moves: this file's own silu / dsilu on a list of arguments
+namespace tcvn {
+namespace {
+__global__ void k_silu_probe(const float* __restrict__ u, float* __restrict__ s, float* __restrict__ d, long n) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) { s[i] = silu(u[i]); d[i] = dsilu(u[i]); }
+}
+}  // namespace
+}  // namespace tcvn
+// silu(u[i]) and dsilu(u[i]) as the GroupNorm kernels evaluate them (__expf, v_rcp_f32), for the test that bounds the two intrinsics
+extern "C" int tcvn_debug_sdxl_silu_probe(const float* u, float* silu_out, float* dsilu_out, long n, void* stream) {
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(tcvn::k_silu_probe, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), u, silu_out,
+                       dsilu_out, n);
+    TCVN_LAUNCH_CHECK();
+    return 0;
+}
+#endif

@@ -36,6 +36,9 @@ DET_MAX_EFFECTS = 64                # TCVN_DET_MAX_EFFECTS: settings of one dete
 DET_SCOPE_EVENT, DET_SCOPE_MAP = 0, 1          # TCVN_DET_SCOPE_*: an effect hits every map of an event, or one map at a time
 MC_MAX_CLASSES = 256                # TCVN_MC_MAX_CLASSES: the widest logit row tcvn_mc_dropout_stats takes
 SCONV_KERNELS = ("generic", "c64", "g", "s2", "in")    # TCVN_SCONV_*: kernel families of the SDXL embedder's convolutions
+# TCVN_SDXL_OP_*: the fields of tcvn_sdxl_op, in order;  TCVN_SDXL_REGION_*: what tcvn_sdxl_region locates
+SDXL_OP_FIELDS = ("kind", "in", "out", "res", "w", "ks", "stride", "pad", "act", "conv_id", "gn_id", "stats_gn", "stats_given", "final_f32")
+SDXL_REGIONS = ("act", "grad", "wk", "wkt", "gwk", "stats", "bstats")
 
 
 class DenseNetCfg(C.Structure):
@@ -101,6 +104,9 @@ def _load():
     sig("tcvn_sdxl_tap", i32, vp, i32, C.c_char_p, P(i64), P(i32), P(i32), P(i32), P(i32), P(i32), P(i32))
     sig("tcvn_sdxl_num_convs", i32, vp)
     sig("tcvn_sdxl_conv_kernels", i32, vp, i32, i32, P(i32), P(i32), P(i32))
+    sig("tcvn_sdxl_num_ops", i32, vp)
+    sig("tcvn_sdxl_op", i32, vp, i32, P(i32), i32)
+    sig("tcvn_sdxl_region", i32, vp, i32, i32, i32, i32, P(i64), P(i64), P(i32), P(i32))
     sig("tcvn_head_create", i32, P(HeadCfg), P(vp))
     sig("tcvn_head_destroy", None, vp)
     sig("tcvn_head_num_slots", i32, vp)
@@ -180,6 +186,7 @@ EXPORTS = [
     "tcvn_focal_loss", "tcvn_dropout_keep", "tcvn_head_set_fused_encoder", "tcvn_head_embed", "tcvn_head_encode", "tcvn_head_decode", "tcvn_linear_forward",
     "tcvn_rows_bn_prelu_forward", "tcvn_linear_backward", "tcvn_rows_bn_prelu_backward", "tcvn_sdxl_create", "tcvn_sdxl_destroy", "tcvn_sdxl_num_slots", "tcvn_sdxl_slot", "tcvn_sdxl_bind",
     "tcvn_sdxl_workspace_bytes", "tcvn_sdxl_forward", "tcvn_sdxl_backward", "tcvn_sdxl_tap", "tcvn_sdxl_num_convs", "tcvn_sdxl_conv_kernels",
+    "tcvn_sdxl_num_ops", "tcvn_sdxl_op", "tcvn_sdxl_region",
     "tcvn_version", "tcvn_densenet_create", "tcvn_densenet_destroy", "tcvn_densenet_num_slots", "tcvn_densenet_slot",
     "tcvn_densenet_bind", "tcvn_densenet_workspace_bytes", "tcvn_densenet_forward", "tcvn_densenet_backward",
     "tcvn_densenet_tap", "tcvn_densenet_num_blocks", "tcvn_densenet_backward_blocks", "tcvn_head_create", "tcvn_head_destroy", "tcvn_head_num_slots", "tcvn_head_slot", "tcvn_head_bind",

@@ -320,6 +320,38 @@ class SdxlEngine(_EmbedderEngine):
             out.append(tuple(None if v.value < 0 else _lib.SCONV_KERNELS[v.value] for v in (f, d, w)))
         return out
 
+    def ops(self) -> List[Dict[str, int]]:
+        """tcvn_sdxl_op: the tape in execution order, one dict of _lib.SDXL_OP_FIELDS per op (-1: not a field of that kind).  No GPU call."""
+        nf = len(_lib.SDXL_OP_FIELDS)
+        buf = (C.c_int * nf)()
+        out = []
+        for i in range(lib.tcvn_sdxl_num_ops(self.handle)):
+            check(lib.tcvn_sdxl_op(self.handle, i, buf, nf), "sdxl_op")
+            out.append(dict(zip(_lib.SDXL_OP_FIELDS, buf)))
+        return out
+
+    def region_spec(self, what: str, index: int = 0, n_img: Optional[int] = None, with_backward: bool = True):
+        """tcvn_sdxl_region -> (byte offset, shape, element bytes) or None where the layout has no such region.  No GPU call."""
+        off, shape, nd, es = C.c_int64(), (C.c_int64 * 4)(), C.c_int(), C.c_int()
+        n = self._n if n_img is None else n_img
+        if lib.tcvn_sdxl_region(self.handle, n, int(with_backward), _lib.SDXL_REGIONS.index(what), index, C.byref(off), shape, C.byref(nd),
+                                C.byref(es)) != 0:
+            return None
+        return off.value, tuple(shape[:nd.value]), es.value
+
+    def region(self, what: str, index: int = 0, with_backward: bool = True) -> torch.Tensor:
+        """View of a piece of the last forward's workspace (validation only, as tap()): what in _lib.SDXL_REGIONS.  with_backward must be
+        what the forward ran with (train)."""
+        spec = self.region_spec(what, index, None, with_backward)
+        if spec is None:
+            raise KeyError(f"sdxl region {what}[{index}]")
+        off, shape, es = spec
+        dt = {8: torch.float64, 4: torch.float32}.get(es, torch.bfloat16)
+        numel = 1
+        for s in shape:
+            numel *= s
+        return self._ws[off: off + numel * es].view(dt).view(*shape)
+
 
 class HeadEngine(_Plan):
     """Combined embedding + transformer encoder + decoders + focal loss (tcvn_head_* in include/tcvn_hip.h)."""

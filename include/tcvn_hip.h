@@ -135,6 +135,26 @@ int tcvn_sdxl_tap(const tcvn_sdxl* p, int n_img, const char* name, int64_t* byte
 enum { TCVN_SCONV_GENERIC = 0, TCVN_SCONV_C64 = 1, TCVN_SCONV_G = 2, TCVN_SCONV_S2 = 3, TCVN_SCONV_IN = 4 };
 int tcvn_sdxl_num_convs(const tcvn_sdxl* p);
 int tcvn_sdxl_conv_kernels(const tcvn_sdxl* p, int n_img, int conv_index, int* fwd, int* dgrad, int* wgrad);
+/* The tape, op by op in execution order (validation): fields[TCVN_SDXL_OP_*], n_fields >= TCVN_SDXL_OP_FIELDS.  kind 0 = convolution
+ * (out = conv(in; slot w, bias slot w + 1) [+ res]), 1 = GroupNorm (+ SiLU when act).  in / out / res are buffer indices (0 = the pixel
+ * map), w a slot index, conv_id the row of tcvn_sdxl_conv_kernels, stats_gn the GroupNorm (gn_id) a convolution delivers the statistics
+ * of, stats_given whether a GroupNorm receives them, final_f32 the convolution that writes the caller's fp32 output.  A field that does
+ * not apply to the op's kind is -1.  Makes no GPU call. */
+enum { TCVN_SDXL_OP_KIND = 0, TCVN_SDXL_OP_IN, TCVN_SDXL_OP_OUT, TCVN_SDXL_OP_RES, TCVN_SDXL_OP_W, TCVN_SDXL_OP_KS, TCVN_SDXL_OP_STRIDE,
+       TCVN_SDXL_OP_PAD, TCVN_SDXL_OP_ACT, TCVN_SDXL_OP_CONV_ID, TCVN_SDXL_OP_GN_ID, TCVN_SDXL_OP_STATS_GN, TCVN_SDXL_OP_STATS_GIVEN,
+       TCVN_SDXL_OP_FINAL_F32, TCVN_SDXL_OP_FIELDS };
+int tcvn_sdxl_num_ops(const tcvn_sdxl* p);
+int tcvn_sdxl_op(const tcvn_sdxl* p, int i, int* fields, int n_fields);
+/* Where the engine keeps a piece of its state in a workspace of n_img maps (validation): byte offset, up to four extents (dense,
+ * row-major) and the element size.  ACT / GRAD: buffer `index`, [n, H, W, C] in the mode's element type (GRAD: the nominal gradient
+ * region; a residual input may take over its output's region during a backward).  WK / WKT / GWK: convolution `index` (conv_id), the
+ * packed weights [Cout][Kp], k = tap * Cin + c, the transposed pack [Cin][Kpt], k = tap * Cout + n, and the fp32 kernel-layout weight
+ * gradient [Cout][Kp].  STATS / BSTATS: [n_gn][n][2] doubles, (sum, sum of squares) of every GroupNorm input and the backward sums
+ * (sum gamma dU, sum gamma dU xhat); index ignored.  Returns non-zero where the layout has no such region.  Makes no GPU call. */
+enum { TCVN_SDXL_REGION_ACT = 0, TCVN_SDXL_REGION_GRAD, TCVN_SDXL_REGION_WK, TCVN_SDXL_REGION_WKT, TCVN_SDXL_REGION_GWK,
+       TCVN_SDXL_REGION_STATS, TCVN_SDXL_REGION_BSTATS };
+int tcvn_sdxl_region(const tcvn_sdxl* p, int n_img, int with_backward, int what, int index, int64_t* byte_off, int64_t* shape, int* ndim,
+                     int* elem_bytes);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Token path: combined embedding, transformer encoder, decoders, focal loss

@@ -1,7 +1,8 @@
 """SDXL-style embedder (BASELINE config 4; reference: layers/sdxl_net.py:7-42) on the MI355X against the CPU restatement in
 oracle/sdxl_oracle.py.  PARITY UNPINNED: the arithmetic lives in an un-vendored, un-pinned `diffusers`, so these
 tests establish oracle <-> HIP self-consistency plus the shape facts the reference fixes ([N,3,400,280] -> [N,out] through a
-1x1 final map); they are not reference parity."""
+1x1 final map); they are not reference parity.  Everything here is a relative L2 norm over a whole tensor through the whole chain;
+tests/test_sdxl_ops_float64_gpu.py checks every op of the tape per element on its own stored inputs."""
 import functools
 
 import numpy as np
