@@ -126,6 +126,7 @@ void DenseNetPlan::layout(int n, bool bwd, Layout& L) const {
     Bump b;
     const int mid = cfg.bn_size * cfg.growth;
     L.img = b.take((long)n * cfg.H * cfg.W * cfg.in_ch * esz);
+    L.own = b.take(pixel_owners_bytes((long)n * cfg.H * cfg.W));      // directly behind img: one memset clears the map and the record's bitmaps
     L.c0 = b.take((long)n * Hc * Wc * cfg.init_ch * esz);
     L.D.clear(); L.Y.clear(); L.bstatD.clear(); L.bstatY.clear(); L.YA.clear(); L.XA.clear(); L.XP.clear(); L.KM.clear();
     L.zeros = b.take(1024);
@@ -519,8 +520,9 @@ int DenseNetPlan::fwd_stem(const Step& s, const int32_t* coords, const float* va
         fr.nblk = stem_sparse_pool_grid(sa);
         return 0;
     }
-    TCVN_CHECK(hipMemsetAsync(s.ws + L.img, 0, (size_t)n * cfg.H * cfg.W * cfg.in_ch * esz, s.st));
-    ScatterArgs sc{mode, coords, values, nnz, n, s.ws + L.img, cfg.H, cfg.W, cfg.in_ch, log_pixels, noise, s.seed};
+    TCVN_CHECK(hipMemsetAsync(s.ws + L.img, 0, (size_t)(L.own - L.img + pixel_owners_zero_bytes((long)n * cfg.H * cfg.W)), s.st));
+    ScatterArgs sc{mode, coords, values, nnz, n, s.ws + L.img, cfg.H, cfg.W, cfg.in_ch, log_pixels, noise, s.seed,
+                   PixelOwners{reinterpret_cast<uint32_t*>(s.ws + L.own), (long)n * cfg.H * cfg.W}};
     if ((rc = scatter_pixels(sc, s.st))) return rc;
     ConvFwdArgs a = conv0_args(s);
     stem_path.act_skip = !no_stem_skip && s.train && L.sact >= 0 && stem_fwd_ok(a) && (b0.ld & 7) == 0 && coords != nullptr;
@@ -747,6 +749,14 @@ int DenseNetPlan::tap(int n, const char* name, long* off, int* tn, int* th, int*
         Layout Lb;
         layout(n, true, Lb);
         *off = Lb.G[b]; *th = blocks[b].H; *tw = blocks[b].W; *tc = blocks[b].Ctot; *tld = blocks[b].ld; return 0;
+    }
+    // the stem's own backward state (checked by tests/stem_reference.py): "raw:du0" = DU0 = sc0 prelu0'(u) dz over the conv0 map (with the
+    // activity bitmap on, rows no hit reaches are never stored), "raw:pq0" = BatchNorm0's [2][init_ch] fp32 (P0, Q0) rows
+    if (s == "raw:du0" || s == "raw:pq0") {
+        Layout Lb;
+        layout(n, true, Lb);
+        if (s == "raw:du0") { *off = Lb.du0; *th = Hc; *tw = Wc; *tc = *tld = cfg.init_ch; return 0; }
+        *tn = *th = *tw = 1; *off = Lb.pq0; *tc = *tld = 2 * cfg.init_ch; *tes = 4; return 0;
     }
     if (s.rfind("raw:pq", 0) == 0) {        // the [2][ld] fp32 (P, Q) rows of block b's channels
         const int b = atoi(s.c_str() + 6) - 1;

@@ -516,7 +516,8 @@ int DenseNetPlan::bwd_stem(const Step& s) const {
     if (conv3x3_tile_enabled() && cfg.in_ch <= 3 && cfg.init_ch <= 64 && last_coords != nullptr) {
         // conv0 weight gradient from the hit list (bias gradient is exactly zero in exact arithmetic: BN0 follows)
         StemWgradArgs sa{last_coords, last_nnz, s.ws + L.img, n, cfg.H, cfg.W, cfg.in_ch, e0, Hc, Wc, wk_find(s_w0, 0).Kp,
-                         reinterpret_cast<float*>(s.ws + L.slab), kSlabBytes, mode};
+                         reinterpret_cast<float*>(s.ws + L.slab), kSlabBytes, mode,
+                         PixelOwners{reinterpret_cast<uint32_t*>(s.ws + L.own), (long)n * cfg.H * cfg.W}};
         return stem_wgrad_sparse(sa, gw_of(s, s_w0), s.st);
     }
     ConvWgradArgs w{};

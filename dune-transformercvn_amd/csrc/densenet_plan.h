@@ -33,6 +33,7 @@ struct Layout {
                                          // on the side stream when tcvn_backward_overlap is on)
     long sact;                           // bf16 dense stem: activity bitmap of the conv0 output (stem_mark), -1 when unused
     long sidx;                           // sparse-stem bucket index (stem_sparse.hip), -1 when the plan cannot use it
+    long own;                            // dense stem: duplicate-coordinate record (PixelOwners: scatter_pixels writes it, the hit-list weight gradient reads it)
     std::vector<std::vector<long>> XA;   // activated bf16 copies of the 1x1-conv inputs (per layer, -1 if absent)
     std::vector<long> XP;                // pooled activated transition inputs (-1 if absent)
     // backward

@@ -74,15 +74,18 @@ __global__ void k_bn_eval_tables(const BnEvalDesc* d, float eps) {
 }
 
 // ---- COO pixel list -> dense NHWC map (reference: trainers/neutrino_full_dense_trainer.py:15-24, :46-67) ---------
-// The map must be zero-filled beforehand.  Duplicate coordinates are last-writer-wins like the reference's
-// non-accumulating indexed `+=`.
+// The map must be zero-filled beforehand.  Duplicate coordinates: the reference's non-accumulating indexed `+=` keeps one of the entries;
+// here the one with the highest list index, the whole pixel from that entry (PixelOwners, tcvn_ops.h).  A list without duplicates pays one
+// atomicOr per entry on a cache-resident bitmap and one launch of a single workgroup that returns at once: an entry that finds its pixel's
+// bit set marks the pixel in the `dup` bitmap, sets its owner word to -1 and counts itself.  k_scatter_repair looks at that count and,
+// only when it is nonzero, walks the list twice: the entries of marked pixels raise the owner word with atomicMax to the highest list
+// index (an integer maximum: the same in any order), then the owner writes the whole pixel again.  Slow -- one workgroup over the whole
+// list -- but duplicates are the exception and must be right, not fast.  (Measured and dropped: owner passes over every entry of every
+// list, +0.08 ms per training step; three full-grid repair launches that return at once, +0.06 ms; the repair in k_scatter's last
+// workgroup behind a fence, +0.12 ms: the fence writes the L2 back in every wave.)  The hit-list weight gradient (stem.hip) asks the
+// same record, to count each pixel once.
 template <typename T>
-__global__ void k_scatter(const ScatterArgs a) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= a.nnz) return;
-    const int img = a.coords[i * 3], y = a.coords[i * 3 + 1], x = a.coords[i * 3 + 2];
-    if (img < 0 || img >= a.n_img || y < 0 || y >= a.H || x < 0 || x >= a.W) return;
-    T* o = reinterpret_cast<T*>(a.img) + (((long)img * a.H + y) * a.W + x) * a.Cpix;
+__device__ __forceinline__ void scatter_pixel(const ScatterArgs& a, long i, T* o) {
     if (a.log_pixels == 3) {       // one_hot_pixels (reference :47-52): F.one_hot(values.long(), 256) per value channel, no scaling, no noise
         const int F = a.Cpix / 256;
         for (int f = 0; f < F; ++f) {
@@ -101,6 +104,50 @@ __global__ void k_scatter(const ScatterArgs a) {
             v *= 1.f + a.noise_std * sqrtf(-2.f * logf(u1)) * cospif(2.f * u2);
         }
         o[c] = from_f<T>(v);
+    }
+}
+
+// flat pixel index of list entry i, -1 for an entry outside the maps
+__device__ __forceinline__ long scatter_pixel_index(const ScatterArgs& a, long i) {
+    const int img = a.coords[i * 3], y = a.coords[i * 3 + 1], x = a.coords[i * 3 + 2];
+    if (img < 0 || img >= a.n_img || y < 0 || y >= a.H || x < 0 || x >= a.W) return -1;
+    return ((long)img * a.H + y) * a.W + x;
+}
+
+template <typename T>
+__global__ void k_scatter(const ScatterArgs a) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.nnz) return;
+    const long pix = scatter_pixel_index(a, i);
+    if (pix < 0) return;
+    if (a.o.base != nullptr) {
+        const uint32_t bit = 1u << (pix & 31);
+        if (atomicOr(a.o.seen() + (pix >> 5), bit) & bit) {              // listed before: k_scatter_repair settles which entry stays
+            atomicOr(a.o.dup() + (pix >> 5), bit);
+            a.o.own()[pix] = -1;
+            atomicAdd(a.o.ndup(), 1u);
+        }
+    }
+    scatter_pixel<T>(a, i, reinterpret_cast<T*>(a.img) + pix * a.Cpix);
+}
+
+// one workgroup, behind k_scatter
+template <typename T>
+__global__ __launch_bounds__(1024) void k_scatter_repair(const ScatterArgs a) {
+    if (*a.o.ndup() == 0) return;
+    auto listed_twice = [&](long p) { return (a.o.dup()[p >> 5] >> (p & 31)) & 1u; };
+    for (long j = threadIdx.x; j < a.nnz; j += blockDim.x) {
+        const long p = scatter_pixel_index(a, j);
+        if (p >= 0 && listed_twice(p)) atomicMax(a.o.own() + p, (int)j);
+    }
+    __threadfence();
+    __syncthreads();
+    for (long j = threadIdx.x; j < a.nnz; j += blockDim.x) {
+        const long p = scatter_pixel_index(a, j);
+        if (p < 0 || !listed_twice(p) || __hip_atomic_load(a.o.own() + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != (int)j) continue;
+        T* o = reinterpret_cast<T*>(a.img) + p * a.Cpix;
+        if (a.log_pixels == 3) for (int c = 0; c < a.Cpix; ++c) o[c] = from_f<T>(0.f);       // (the other entries' bins)
+        scatter_pixel<T>(a, j, o);
     }
 }
 
@@ -437,8 +484,13 @@ int bn_eval_tables(const BnEvalDesc* d_descs, int n, float eps, hipStream_t st) 
 
 int scatter_pixels(const ScatterArgs& a, hipStream_t st) {
     if (a.nnz <= 0) return 0;
+    if (a.o.base != nullptr && a.nnz > 0x7fffffffL) return -2;      // the owner words hold 32-bit list indices
     if (a.mode == MODE_F32) hipLaunchKernelGGL(k_scatter<float>, dim3(cdiv(a.nnz, 256)), dim3(256), 0, st, a);
     else hipLaunchKernelGGL(k_scatter<bf16>, dim3(cdiv(a.nnz, 256)), dim3(256), 0, st, a);
+    TCVN_LAUNCH_CHECK();
+    if (a.o.base == nullptr) return 0;
+    if (a.mode == MODE_F32) hipLaunchKernelGGL(k_scatter_repair<float>, dim3(1), dim3(1024), 0, st, a);
+    else hipLaunchKernelGGL(k_scatter_repair<bf16>, dim3(1), dim3(1024), 0, st, a);
     TCVN_LAUNCH_CHECK();
     return 0;
 }

@@ -126,6 +126,7 @@ __global__ __launch_bounds__(256, 2) void k_stem_wgrad_sparse(const StemWgradArg
 #pragma unroll
     for (int t = 0; t < 49; ++t) { acc[t][0] = 0.f; acc[t][1] = 0.f; acc[t][2] = 0.f; }
     const long gw = (long)blockIdx.x * 4 + (tid >> 6), nw = (long)gridDim.x * 4;
+    const bool dups = a.o.base != nullptr && *a.o.ndup() != 0;          // (uniform)
     // the coordinates of the NEXT hit are requested while this one is processed (a hit is a chain of dependent L2 round trips:
     // coordinates -> pixel value / gradient rows; with the first link prefetched a wave pays one per hit instead of two to three)
     int c_im = -1, c_y = 0, c_x = 0;
@@ -136,10 +137,15 @@ __global__ __launch_bounds__(256, 2) void k_stem_wgrad_sparse(const StemWgradArg
         const int x = __builtin_amdgcn_readfirstlane(c_x);
         if (hit + nw < a.nnz) { c_im = a.coords[(hit + nw) * 3]; c_y = a.coords[(hit + nw) * 3 + 1]; c_x = a.coords[(hit + nw) * 3 + 2]; }
         if (im < 0 || im >= a.n_img || y < 0 || y >= a.H || x < 0 || x >= a.W) continue;
-        const T* px = img + (((long)im * a.H + y) * a.W + x) * a.Cpix;
+        const long pix = ((long)im * a.H + y) * a.W + x;
+        const T* px = img + pix * a.Cpix;
+        // a pixel listed k times must enter once: only the entry that owns it (scatter_pixels: the highest index) carries its value, the
+        // others carry zeros -- a select, no branch.  A list without duplicates (dups == 0, the usual case) asks nothing.
+        bool owned = true;
+        if (dups && ((a.o.dup()[pix >> 5] >> (pix & 31)) & 1u)) owned = a.o.own()[pix] == (int)hit;
         float v[3];
 #pragma unroll
-        for (int c = 0; c < 3; ++c) v[c] = c < a.Cpix ? to_f<T>(px[c]) : 0.f;
+        for (int c = 0; c < 3; ++c) v[c] = (c < a.Cpix && owned) ? to_f<T>(px[c]) : 0.f;
         // The taps that see this hit have ky = (y+3) mod 2 (+2, +4, +6) and kx likewise: 9-16 of the 49.  One code copy per parity pair
         // keeps the accumulator indices static AND lets all <= 32 gradient-row loads of the hit be requested before the first use (the
         // tap-by-tap loop with its parity tests waited for every tap's two loads in turn: ~16 L2 round trips per hit).

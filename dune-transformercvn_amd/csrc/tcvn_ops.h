@@ -86,9 +86,25 @@ int bn_eval_tables(const BnEvalDesc* d_descs, int n, float eps, hipStream_t st);
 // ---------------------------------------------------------------------------------------------------------
 // Pixel-map scatter (COO -> dense NHWC), stem pooling, global pooling
 // ---------------------------------------------------------------------------------------------------------
+// Duplicate coordinates of a hit list (include/tcvn_hip.h: the highest list index wins, the whole pixel from one entry).  One region of
+// pixel_owners_bytes(npix): [64 words; word 0 = entries that found their pixel already listed][seen bitmap][dup bitmap: pixels listed
+// more than once][owner i32 per pixel: the highest list index, valid where the dup bit is set].  The first pixel_owners_zero_bytes(npix)
+// must be zero in front of scatter_pixels; the owner words are written before they are read and need no clearing.  base == nullptr: no
+// such handling -- duplicates are then a race between plain stores.
+struct PixelOwners {
+    uint32_t* base = nullptr; long npix = 0;
+    __host__ __device__ long words() const { return (npix + 31) >> 5; }
+    __host__ __device__ uint32_t* ndup() const { return base; }
+    __host__ __device__ uint32_t* seen() const { return base + 64; }
+    __host__ __device__ uint32_t* dup() const { return base + 64 + words(); }
+    __host__ __device__ int* own() const { return reinterpret_cast<int*>(base + 64 + 2 * words()); }
+};
+inline long pixel_owners_zero_bytes(long npix) { return (64 + 2 * ((npix + 31) >> 5)) * 4; }
+inline long pixel_owners_bytes(long npix) { return pixel_owners_zero_bytes(npix) + npix * 4; }
 struct ScatterArgs {
     int mode; const int* coords; const float* values; long nnz; int n_img;
     void* img; int H, W, Cpix; int log_pixels; float noise_std; uint64_t seed;
+    PixelOwners o;
 };
 int scatter_pixels(const ScatterArgs& a, hipStream_t st);
 
@@ -330,6 +346,7 @@ struct StemWgradArgs {
     EffSrc e;                                                                // gradient of the conv0 output [n,Hc,Wc,N]
     int Hc, Wc, Kp; float* slab; long slab_bytes;
     int mode;                                                                // element type of img / G / X (MODE_F32 or MODE_BF16)
+    PixelOwners o;                                                           // scatter_pixels' record: an entry that does not own its pixel adds nothing
 };
 int stem_wgrad_sparse(const StemWgradArgs& a, float* dWk, hipStream_t st);
 // conv0 forward on an NHWC4 LDS patch (bf16, 3 -> 64 channels, 7x7 / 2)

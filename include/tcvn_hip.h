@@ -90,7 +90,9 @@ int tcvn_densenet_backward_blocks(tcvn_densenet* p, int n_img, const float* d_ou
  * after a backward pass also "raw:grad<b>" (gradient accumulator of block b's concat buffer), "raw:pq<b>" (its [2][ld] fp32 (P, Q) rows),
  * "raw:du<b>" (the 3x3 data-gradient scratch in block b's geometry: it holds the layer that ran last) and "raw:ey<b>.<l>" (the eff rows
  * [pixels][32] of a layer's 3x3 output gradient, bf16 mode with growth 32; filled only by the consecutive-tile data-gradient kernel)
- * and "raw:dcondense" (fp32 [n][C]: the gradient with respect to "condense");
+ * and "raw:dcondense" (fp32 [n][C]: the gradient with respect to "condense"), and the stem's own backward state (b = 0): "raw:du0"
+ * (DU0 over the conv0 map, [n][Hc][Wc][init_ch]; with the activity bitmap on, rows no hit reaches are never stored) and "raw:pq0"
+ * (BatchNorm0's [2][init_ch] fp32 (P0, Q0) rows) -- what tests/stem_reference.py checks per element;
  * returns the byte offset into the workspace and the logical NHWC shape + channel stride + element size. */
 int tcvn_densenet_tap(const tcvn_densenet* p, int n_img, const char* name, int64_t* byte_off, int* n, int* h, int* w,
                       int* c, int* ld, int* elem_bytes);

@@ -1,4 +1,6 @@
-"""Float64 reference of the DenseNet embedder's forward and backward operations (behind the stem), one plain function per operation,
+"""Float64 reference of the DenseNet embedder's forward and backward operations behind the stem (the stem itself -- hit list -> map, conv0,
+the sparse pooled output, the stem's backward with its taps raw:du0 / raw:pq0 -- is stem_reference.py, built on this module's formats and
+gate rules; pool0 below starts from the conv0 map that module checks), one plain function per operation,
 each with the |error| a correct kernel may show per element.  No GPU: the functions take an operation's ACTUAL inputs (the maps the engine stored, its
 (scale, shift) tables, the bound fp32 parameters) as float64 NHWC tensors, so nothing drifts between the two sides.  `rnd` switches the
 bf16 roundings on (bf16 mode) or off (fp32 mode; with float64 inputs and the gates ignored it is the exact network, which
@@ -6,8 +8,8 @@ test_densenet_layer_reference_cpu.py pins against the oracle).
 
 Gates (derived, u = 2^-24, R(n) = (1 + u)^n - 1 the compound of n fp32 roundings):
   * Operand the kernel computes itself, f = prelu(sc x + sh): one fma, one multiply by the slope (tile3x3.h:118 act8_apply,
-    fwd1x1_fused.hip:144, elementwise.hip:204 k_act_bf16, conv_tile.h:111 act8) -> tau = R(2) |f|; rounding never changes a sign, so the
-    fp32 evaluation takes the branch of the exact one.  Pooled operand (2x2 floor windows, elementwise.hip:279 / conv_tile.h:133-136):
+    fwd1x1_fused.hip:144, elementwise.hip:258 k_act_bf16, conv_tile.h:111 act8) -> tau = R(2) |f|; rounding never changes a sign, so the
+    fp32 evaluation takes the branch of the exact one.  Pooled operand (2x2 floor windows, elementwise.hip:326 / conv_tile.h:133-136):
     four such terms, four fp32 additions from 0, an exact * 0.25 -> tau = R(6) * 1/4 sum |f_k|.
     bf16 mode: the kernel's rounded operand is bf16(f - tau) or bf16(f + tau); where they differ the operand is uncertain by their
     difference da (one bf16 ulp), else da = 0.  fp32 mode: da = tau.
@@ -18,8 +20,8 @@ Gates (derived, u = 2^-24, R(n) = (1 + u)^n - 1 the compound of n fp32 roundings
           multiplies by the dropout keep scale (:322); the single-wave kernels (:143-146, conv3x3_f32.hip:276-277) do less;
       c = 1 for the output Linear (rows.hip:36-43: one fma chain, alpha * acc + 0).
     Eval mode, norm2 + PReLU2 in the 1x1 epilogue (fwd1x1_fused.hip:185, gemm_nt.hip:221): delta' = max(1, |sl|) |sc| delta + R(2) |f|.
-  * pool0 (elementwise.hip:133-139, :395-400): nine terms, nine additions, * fl(1/9): delta = R(2 + 9 + 2) * 1/9 sum |f_k|.
-    Head pooling (elementwise.hip:167-168): HW terms and additions, one division: delta = R(2 + HW + 1) * 1/HW sum |f_k|.
+  * pool0 (elementwise.hip:180-186, :442-447): nine terms, nine additions, * fl(1/9): delta = R(2 + 9 + 2) * 1/9 sum |f_k|.
+    Head pooling (elementwise.hip:214-215): HW terms and additions, one division: delta = R(2 + HW + 1) * 1/HW sum |f_k|.
   * Store: |hip - ref| <= delta + 1/2 ulp(|ref| + delta), the ulp of bf16 (bf16 mode maps) or fp32.
   * Stored operand (xa, ya): checked itself with delta = tau and the store rule, then used as the exact operand (da = 0).
   * Backward (3x3 data gradient, 3x3 weight and bias gradient, transition data gradient, head pooling): eff_rows, conv3x3_dgrad,

@@ -8,7 +8,7 @@ The number formats, R(n) and the store rule are those of densenet_layer_referenc
 The forward gates follow; the backward operations and their gates are derived in front of conv_dgrad below.
 
 Gates (u = 2^-24, R(n) = (1 + u)^n - 1 the compound of n fp32 roundings; line numbers are those of csrc/ as it stands with this file; the validation-only code sits behind the cited lines):
-  * Weight packs (elementwise.hip:336-365 k_pack): wk[n][tap Cin + c] = wkt[c][tap Cout + n] = bf16(w[n][c][tap]) (f2bf, :360) or w itself
+  * Weight packs (elementwise.hip:383-412 k_pack): wk[n][tap Cin + c] = wkt[c][tap Cout + n] = bf16(w[n][c][tap]) (f2bf, :360) or w itself
     in fp32 mode (:363); every column from taps * inner up to Kp is written 0 (:351-352).  Bit for bit, no gate.
   * Convolution forward.  Operands are stored values, bf16 x bf16 products are exact in fp32, and every kernel is one fp32 accumulation
     chain over the K = ks ks Cin products of an output element (the MFMA is one, whatever its internal order: sdxl_conv3x3.hip:145-154

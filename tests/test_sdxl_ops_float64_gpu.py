@@ -211,7 +211,7 @@ def run_and_check(name, out_dim, mode_name):
             stored[b] = eng.region("act", b, train).cpu().double()
     stats = eng.region("stats", 0, train).cpu()
     P = {k: v.double() for k, v in P32.items()}
-    # buffer 0: the scattered map is values / 255 (elementwise.hip:97, one rounding), stored in the mode's element type
+    # buffer 0: the scattered map is values / 255 (elementwise.hip:100, one rounding), stored in the mode's element type
     img = R.dense_image((n, H, W), coords, values)
     img_chk = R.stored_check("img", "scatter", "-", img, R.R(1) * img.abs(), rnd)
     checks, _ = R.run_forward(ops, names, P, stored[0], rnd, kernels, stored, stats.double())
