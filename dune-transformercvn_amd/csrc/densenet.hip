@@ -513,11 +513,11 @@ int DenseNetPlan::fwd_stem(const Step& s, const int32_t* coords, const float* va
         if (s.train) {
             sa.part = s.part;
             if ((rc = stem_sparse_stats(sa, s.st))) return rc;
-            if ((rc = link(s, n0, stem_sparse_stats_grid(sa), cfg.init_ch, 0, cfg.init_ch, bstat0, M0))) return rc;
+            if ((rc = link(s, n0, stem_sparse_plan(sa, StemPass::Stats).grid, cfg.init_ch, 0, cfg.init_ch, bstat0, M0))) return rc;
         }
         sa.Out = s.ws + L.D[0]; sa.ldo = b0.ld; sa.part = s.train ? s.part : nullptr;
         if ((rc = stem_sparse_pool(sa, s.st))) return rc;
-        fr.nblk = stem_sparse_pool_grid(sa);
+        fr.nblk = stem_sparse_plan(sa, StemPass::Pool).grid;
         return 0;
     }
     TCVN_CHECK(hipMemsetAsync(s.ws + L.img, 0, (size_t)(L.own - L.img + pixel_owners_zero_bytes((long)n * cfg.H * cfg.W)), s.st));

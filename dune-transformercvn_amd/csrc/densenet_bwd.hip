@@ -491,14 +491,14 @@ int DenseNetPlan::bwd_stem(const Step& s) const {
     const EffSrc e{s.ws + L.G[0], b0.ld, s.ws + L.D[0], b0.ld, 0, cfg.init_ch, P, Q, 0.f, 0, 0};
     int rc;
     if (stem_path.sparse) {
-        // stem_sparse.hip: pass 0 = pooling / PReLU0 / BN0 backward sums with the conv0 output rebuilt from the hit list per region;
-        // pass 1 = conv0 weight gradient from the same regions with (P0, Q0) applied.  No conv0-sized tensor is read or written.
+        // stem_sparse.hip: BwdSums = pooling / PReLU0 / BN0 backward sums with the conv0 output rebuilt from the hit list per region;
+        // BwdWgrad = conv0 weight gradient from the same regions with (P0, Q0) applied.  No conv0-sized tensor is read or written.
         StemSparseArgs sa = stem_sparse_args(s, last_coords, last_values, last_nnz, last_value_mode, last_noise);
         sa.e = e; sa.part = s.part;
-        if ((rc = stem_sparse_bwd(sa, 0, s.st))) return rc;
-        if ((rc = bwd_link(s, n0, stem_sparse_bwd_grid(sa), bstat0, M0, P0, Q0, 0, s_a0))) return rc;
+        if ((rc = stem_sparse_bwd(sa, StemPass::BwdSums, s.st))) return rc;
+        if ((rc = bwd_link(s, n0, stem_sparse_plan(sa, StemPass::BwdSums).grid, bstat0, M0, P0, Q0, 0, s_a0))) return rc;
         sa.P0 = P0; sa.Q0 = Q0; sa.slab = reinterpret_cast<float*>(s.ws + L.slab); sa.slab_bytes = kSlabBytes; sa.dWk = gw_of(s, s_w0);
-        return stem_sparse_bwd(sa, 1, s.st);
+        return stem_sparse_bwd(sa, StemPass::BwdWgrad, s.st);
     }
     const Tab t = tab(s.ws, L, n0);
     Pool0BwdArgs a{mode, s.ws + L.c0, n, Hc, Wc, cfg.init_ch, t.sc, t.sh, data[s_a0], e, b0.H, b0.W, s.ws + L.du0, s.part,

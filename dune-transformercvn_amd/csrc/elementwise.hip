@@ -109,8 +109,8 @@ __device__ __forceinline__ void scatter_pixel(const ScatterArgs& a, long i, T* o
 
 // flat pixel index of list entry i, -1 for an entry outside the maps
 __device__ __forceinline__ long scatter_pixel_index(const ScatterArgs& a, long i) {
-    const int img = a.coords[i * 3], y = a.coords[i * 3 + 1], x = a.coords[i * 3 + 2];
-    if (img < 0 || img >= a.n_img || y < 0 || y >= a.H || x < 0 || x >= a.W) return -1;
+    int img, y, x;
+    if (!hit_in_map(a.coords, i, a.n_img, a.H, a.W, img, y, x)) return -1;
     return ((long)img * a.H + y) * a.W + x;
 }
 

@@ -1,9 +1,14 @@
 // Stem-specific bf16 kernels (conv0 7x7/2 + BN0 + PReLU0 + AvgPool 3/2; reference layers/dense_net.py:112-121):
-//   * k_pool0_bwd_vec   : pooling + PReLU + BatchNorm backward over the conv0 output, 16 B per thread
+//   * k_stem_mark        : activity bitmap of the conv0 output (which positions a hit reaches) + the shared row of the others
+//   * k_pool0_bwd_vec    : pooling + PReLU + BatchNorm backward over the conv0 output, 16 B per thread (any channel count)
+//   * k_pool0_bwd_tile   : the same for 64 channels on 8 x 32 tiles with the pooled gradient staged in LDS; positions no hit reaches read one shared row
 //   * k_stem_wgrad_sparse: conv0 weight gradient from the COO hit list -- the pixel maps are mostly empty, so
 //         dW0[n][ky][kx][c] = sum_hits v[hit][c] * eff0[(y+3-ky)/2, (x+3-kx)/2][n]
 //     touches ~12 output pixels per hit instead of contracting 147 taps for every one of the 28 000 output pixels
 //     (~1.7 GFLOP instead of 135 GFLOP per 288 maps).
+//   * k_stem_fwd2_bf16   : conv0 forward as an implicit GEMM on an NHWC4 LDS patch (+ BatchNorm0 statistics); k_stem_fwd_bf16, its
+//     first version, exists in the validation build only
+// The sparse-aware stem, which needs neither the dense map nor the conv0 output, is stem_sparse.hip.
 #include <cstdlib>
 #include <type_traits>
 #include "tcvn_ops.h"
@@ -18,9 +23,8 @@ __global__ void k_stem_mark(const int* __restrict__ coords, long nnz, int n_img,
                             const float* __restrict__ bias, bf16* __restrict__ cline) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (blockIdx.x == 0 && threadIdx.x < 64) cline[threadIdx.x] = f2bf(bias[threadIdx.x]);     // the row of a position no hit reaches: bf16(0 + bias)
-    if (i >= nnz) return;
-    const int img = coords[i * 3], y = coords[i * 3 + 1], x = coords[i * 3 + 2];
-    if (img < 0 || img >= n_img || y < 0 || y >= H || x < 0 || x >= W) return;                 // k_scatter drops the same hits
+    int img, y, x;
+    if (i >= nnz || !hit_in_map(coords, i, n_img, H, W, img, y, x)) return;
     // output (oy, ox) reads input rows 2*oy - 3 .. 2*oy + 3: ceil((y - 3) / 2) <= oy <= floor((y + 3) / 2)
     const int oy0 = max(0, (y - 2) >> 1), oy1 = min(Hc - 1, (y + 3) >> 1);
     const int ox0 = max(0, (x - 2) >> 1), ox1 = min(Wc - 1, (x + 3) >> 1);
@@ -136,7 +140,7 @@ __global__ __launch_bounds__(256, 2) void k_stem_wgrad_sparse(const StemWgradArg
         const int y = __builtin_amdgcn_readfirstlane(c_y);
         const int x = __builtin_amdgcn_readfirstlane(c_x);
         if (hit + nw < a.nnz) { c_im = a.coords[(hit + nw) * 3]; c_y = a.coords[(hit + nw) * 3 + 1]; c_x = a.coords[(hit + nw) * 3 + 2]; }
-        if (im < 0 || im >= a.n_img || y < 0 || y >= a.H || x < 0 || x >= a.W) continue;
+        if (im < 0 || im >= a.n_img || y < 0 || y >= a.H || x < 0 || x >= a.W) continue;               // = !hit_in_map, on the prefetched coordinates
         const long pix = ((long)im * a.H + y) * a.W + x;
         const T* px = img + pix * a.Cpix;
         // a pixel listed k times must enter once: only the entry that owns it (scatter_pixels: the highest index) carries its value, the
@@ -169,7 +173,6 @@ __global__ __launch_bounds__(256, 2) void k_stem_wgrad_sparse(const StemWgradArg
 #pragma unroll
                 for (int ix = 0; ix < NX; ++ix) {
                     const float eff = okq[iy][ix] ? gq[iy][ix] + pn * xq[iy][ix] + qn : 0.f;
-                    constexpr int dummy = 0; (void)dummy;
                     const int t = (PY + 2 * iy) * 7 + (PX + 2 * ix);
 #pragma unroll
                     for (int c = 0; c < 3; ++c) acc[t][c] = fmaf(v[c], eff, acc[t][c]);
@@ -192,8 +195,6 @@ __global__ __launch_bounds__(256, 2) void k_stem_wgrad_sparse(const StemWgradArg
         out[i] = k < 49 * a.Cpix ? wacc[k][nn] : 0.f;
     }
 }
-
-
 
 // Tiled variant (64 channels): a workgroup owns 8 x 32 conv0-output pixels of one map.  The effective gradient of the 5 x 17
 // pooled pixels whose 3x3/2 windows touch the tile is computed ONCE into LDS (fp32); the per-pixel pass then sums its <= 4 windows
@@ -230,9 +231,7 @@ __global__ __launch_bounds__(256, 2) void k_pool0_bwd_tile(const Pool0BwdArgs a,
         v[0] = x0.x; v[1] = x0.y; v[2] = x0.z; v[3] = x0.w; v[4] = x1.x; v[5] = x1.y; v[6] = x1.z; v[7] = x1.w;
     };
     // a thread's running sums cover a few hundred values: fp32 here, fp64 across threads and workgroups
-    float s1[8], s2[8], s3[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { s1[j] = 0; s2[j] = 0; s3[j] = 0; }
+    float s1[8] = {}, s2[8] = {}, s3[8] = {};
     const long ntiles = (long)a.n_img * tiles_x * tiles_y;
     for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int tx = (int)(tile % tiles_x), ty = (int)((tile / tiles_x) % tiles_y);
@@ -313,22 +312,13 @@ __global__ __launch_bounds__(256, 2) void k_pool0_bwd_tile(const Pool0BwdArgs a,
             }
         }
     }
-    // threads with equal (tid & 7) hold the same channels: fold lanes 8, 16, 32 apart, then the four waves
-    const int lane = tid & 63, wave = tid >> 6;
+    double s[3][8], tot[3];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        double d1 = (double)s1[j], d2 = (double)s2[j], d3 = (double)s3[j];
-#pragma unroll
-        for (int o = 8; o < 64; o <<= 1) { d1 += __shfl_xor(d1, o); d2 += __shfl_xor(d2, o); d3 += __shfl_xor(d3, o); }
-        if (lane < 8) { red[wave][lane][j][0] = d1; red[wave][lane][j][1] = d2; red[wave][lane][j][2] = d3; }
-    }
-    __syncthreads();
+    for (int j = 0; j < 8; ++j) { s[0][j] = (double)s1[j]; s[1][j] = (double)s2[j]; s[2][j] = (double)s3[j]; }
+    channel_fold(s, &red[0][0][0][0], tid, tot);
     if (tid < 64) {
-        const int ch = tid >> 3, j = tid & 7;
-        double x = 0, y = 0, z = 0;
-        for (int w = 0; w < 4; ++w) { x += red[w][ch][j][0]; y += red[w][ch][j][1]; z += red[w][ch][j][2]; }
         double* o = a.part + ((long)blockIdx.x * a.C + tid) * 3;
-        o[0] = x; o[1] = y; o[2] = z;
+        o[0] = tot[0]; o[1] = tot[1]; o[2] = tot[2];
     }
 }
 

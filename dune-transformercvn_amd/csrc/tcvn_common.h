@@ -165,6 +165,38 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// Channel-group fold of a 256-thread workgroup over 64 channels: every thread carries NS running sums of the eight channels
+// (tid & 7) * 8 + j, so threads of equal (tid & 7) hold the same channels.  Folds the lanes 8 / 16 / 32 apart, then the four waves in the
+// order 0..3 through `red` (channel_fold_bytes(NS) of LDS that nobody else touches from the caller's last barrier on).  Thread c < 64
+// gets tot[k] = the workgroup's sum k of channel c; the other threads get nothing.  Holds one barrier: call it from uniform code.
+constexpr int channel_fold_bytes(int ns) { return 4 * 64 * ns * 8; }
+template <int NS>
+__device__ __forceinline__ void channel_fold(double (&s)[NS][8], double* red, int tid, double (&tot)[NS]) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+#pragma unroll
+        for (int k = 0; k < NS; ++k) {
+#pragma unroll
+            for (int o = 8; o < 64; o <<= 1) s[k][j] += __shfl_xor(s[k][j], o);
+            if ((tid & 63) < 8) red[(((tid >> 6) * 8 + (tid & 7)) * 8 + j) * NS + k] = s[k][j];      // [wave][tid & 7][j][NS]
+        }
+    __syncthreads();
+    if (tid < 64)
+#pragma unroll
+        for (int k = 0; k < NS; ++k) {
+            tot[k] = 0;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) tot[k] += red[(g * 64 + tid) * NS + k];
+        }
+}
+
+// COO hit lists: an entry outside the maps is dropped by everything that reads the list -- the scatter, the sparse-stem index and the
+// activity bitmap agree because they ask here (k_stem_wgrad_sparse spells the same test out on its prefetched coordinates)
+__device__ __forceinline__ bool hit_in_map(const int* __restrict__ coords, long i, int n_img, int H, int W, int& img, int& y, int& x) {
+    img = coords[i * 3]; y = coords[i * 3 + 1]; x = coords[i * 3 + 2];
+    return !(img < 0 || img >= n_img || y < 0 || y >= H || x < 0 || x >= W);
+}
+
 #define TCVN_CHECK(expr)                                                                   \
     do {                                                                                   \
         hipError_t e_ = (expr);                                                            \

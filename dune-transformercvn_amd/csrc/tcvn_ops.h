@@ -360,7 +360,7 @@ struct StemSparseArgs {
     const int* coords; const float* values; long nnz;       // COO list [nnz][3] (image, y, x), values [nnz][Cpix]
     int n_img, H, W, Cpix, value_mode; float noise_std; uint64_t seed;
     int *row_start, *row_fill; uint4* rec;                   // index (stem_sparse_carve): per (map, pixel row) prefix and cursors; 16-byte records
-                                                             // (y << 16 | x, v0 | v1 << 16 as bf16, v2 | flags, list index) bucketed by row
+                                                             // bucketed by row (format: HitRec in stem_sparse.hip)
     const void* Wk; int Kp; const float* bias;               // conv0 weights [64][Kp] bf16 (k = tap*Cpix + c), bias fp32
     int Hc, Wc, Ho, Wo;                                      // conv0 output map, pooled map
     const float *sc, *sh, *sl;                               // BatchNorm0 (scale, shift) table, PReLU0 slope
@@ -370,17 +370,19 @@ struct StemSparseArgs {
     const float *P0, *Q0;                                    // backward pass 1: BatchNorm0's (P, Q)
     float* slab; long slab_bytes; float* dWk;                // backward pass 1: per-workgroup partial weight gradients, result [64][Kp]
 };
+// The four passes and how each is cut into work: a band is `rows` output rows of a map, a unit one of `nsplit` ranges of a map's `nbands`
+// bands; `grid` workgroups share the `nunits` units and each writes one row of partials -- launchers and reducing callers both ask here.
+enum class StemPass { Stats, Pool, BwdSums, BwdWgrad };
+struct StemPassPlan { int rows, nbands, nsplit, nunits, grid; };
+StemPassPlan stem_sparse_plan(const StemSparseArgs& a, StemPass pass);
 long stem_sparse_hit_capacity(int n_img);
 long stem_sparse_index_bytes(int n_img, int H, int W);
 void stem_sparse_carve(StemSparseArgs& a, char* base);      // points the index arrays into a buffer of stem_sparse_index_bytes()
 bool stem_sparse_ok(int mode, int in_ch, int init_ch, int H, int W, int value_mode, long nnz, int n_img, long ldo);
-int stem_sparse_stats_grid(const StemSparseArgs& a);
-int stem_sparse_pool_grid(const StemSparseArgs& a);
-int stem_sparse_bwd_grid(const StemSparseArgs& a);
 int stem_sparse_index(const StemSparseArgs& a, hipStream_t st);
 int stem_sparse_stats(const StemSparseArgs& a, hipStream_t st);
 int stem_sparse_pool(const StemSparseArgs& a, hipStream_t st);
-int stem_sparse_bwd(const StemSparseArgs& a, int pass, hipStream_t st);      // pass 0: backward sums; pass 1: conv0 weight gradient
+int stem_sparse_bwd(const StemSparseArgs& a, StemPass pass, hipStream_t st);  // BwdSums: backward sums; BwdWgrad: conv0 weight gradient
 
 // kernel-layout fp32 weight gradients -> reference OIHW gradients (accumulate)
 struct UnpackDesc { const float* src; float* dst; int N, Cin, taps, Kp; int nfast; };   // nfast: src is [k][32]

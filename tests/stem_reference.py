@@ -41,7 +41,7 @@ def owners(coords, n, H, W, defect=None):
 
 
 def pixel_values(values, mode, rnd):
-    """Value arithmetic of k_scatter (elementwise.hip:100) = preprocess_value (stem_sparse.hip:41) without noise, for fp32 `values`:
+    """Value arithmetic of k_scatter (elementwise.hip:100) = preprocess_value (stem_sparse.hip:65) without noise, for fp32 `values`:
     mode 0: v / 255 (one correctly rounded division), mode 1: logf(v + 1) (v + 1 exact for the integer pixel values), mode 2: v itself.
     bf16 mode: the stored value is bf16(fp32 result).  The fp32 result lies within 1/2 ulp (division) or a few ulps (logf; its error is
     not bounded here) of the exact value, so wherever the exact value keeps TIE_MARGIN = 8 fp32 ulps from every bf16 rounding tie the
@@ -82,9 +82,9 @@ C_CONV0 = 1
 
 def conv0(img, w, b, rnd, defect=None):
     """7x7, stride 2, pad 3 over the map as the kernel holds it (the `img` tap: already bf16 values in bf16 mode), bf16 weights in bf16
-    mode.  One fp32 fma chain over the 147 products (the MFMA is one; the padded contraction slots of k_stem_fwd2_bf16, stem.hip:510,
-    multiply zero weights: exact) plus c = 1 further operation, the bias add (stem.hip:592; generic k_conv_fwd, conv_fwd.hip:104; the
-    sparse kernels start the chain AT the bias, stem_sparse.hip:201: no more roundings): delta = R(147 + 1) S, S = sum |a_k| |w_k| + |b|.
+    mode.  One fp32 fma chain over the 147 products (the MFMA is one; the padded contraction slots of k_stem_fwd2_bf16, stem.hip:500,
+    multiply zero weights: exact) plus c = 1 further operation, the bias add (stem.hip:582; generic k_conv_fwd, conv_fwd.hip:104; the
+    sparse kernels start the chain AT the bias, stem_sparse.hip:346: no more roundings): delta = R(147 + 1) S, S = sum |a_k| |w_k| + |b|.
     A position no hit reaches has S = |b| and ref = b: with the store rule it must be the stored-precision bias exactly (bias_exact).
     defects: "drop_tap" (tap (2, 5) of input channel 1 missing), "transpose" (ky and kx swapped).  -> ref [n, Hc, Wc, N], delta."""
     w = bf16(w) if rnd else w
@@ -100,9 +100,9 @@ def conv0(img, w, b, rnd, defect=None):
 
 
 def conv0_from_hits(coords, values, n, H, W, mode, w, b, rnd):
-    """The same map from the de-duplicated records, as the sparse kernels evaluate it (stem_sparse.hip:197-214 conv0_at): bias plus, per
+    """The same map from the de-duplicated records, as the sparse kernels evaluate it (stem_sparse.hip:344-348 conv0_at): bias plus, per
     owner hit (y, x) and tap (ky, kx) with y + 3 - ky and x + 3 - kx even, v . w[:, :, ky, kx] at position ((y + 3 - ky) / 2,
-    (x + 3 - kx) / 2).  Records hold bf16 values (stem_sparse.hip:101-104), so this is the bf16-mode map whatever `rnd` says about the
+    (x + 3 - kx) / 2).  Records hold bf16 values (HitRec::pack, stem_sparse.hip:46-49), so this is the bf16-mode map whatever `rnd` says about the
     weights.  Equal to conv0(image(...)) up to float64 summation order (test_stem_reference_cpu.py).  -> ref, delta."""
     idx, pix = owners(coords, n, H, W)
     val, _ = pixel_values(values[idx], mode, rnd)
@@ -140,8 +140,8 @@ def _pool3(t, defect=None):
 
 
 def sparse_pool(c0, d0, sc, sh, sl, defect=None):
-    """BN0 table + PReLU0 + AvgPool 3 / 2 of a conv0 map that stays fp32 on chip (k_stem_sparse_pool, stem_sparse.hip:403-411; the constant
-    vector of an all-empty window makes the same nine additions, :342-345): c0 = the float64 map, d0 its allowed error (conv0_from_hits).
+    """BN0 table + PReLU0 + AvgPool 3 / 2 of a conv0 map that stays fp32 on chip (k_stem_sparse_pool, stem_sparse.hip:438-446; the constant
+    vector of an all-empty window makes the same nine additions, :404-407): c0 = the float64 map, d0 its allowed error (conv0_from_hits).
     f = prelu(fma(c0, sc, sh)): PReLU is continuous with slopes 1 and sl, so the conv0 error passes through |sc| max(1, |sl|) and no
     element is excluded; one fma and the slope multiply add R(2) |f|; nine additions from 0 and * fl(1 / 9) (two roundings: the constant,
     the product): delta = (1 + R(11)) mean9(|sc| max(1, |sl|) d0) + R(2 + 9 + 2) mean9 |f|.  -> ref, delta (bf16 store on top)."""
@@ -151,7 +151,7 @@ def sparse_pool(c0, d0, sc, sh, sl, defect=None):
 
 
 def sparse_stats(c0, d0):
-    """raw:bstat0 of the sparse train pass (k_stem_sparse_stats, stem_sparse.hip:289-315): per channel the mean and E[x^2] = var + mean^2
+    """raw:bstat0 of the sparse train pass (k_stem_sparse_stats, stem_sparse.hip:352-386): per channel the mean and E[x^2] = var + mean^2
     (never the variance alone: cancellation) of the fp32 on-chip conv0 values, every value widened to double before it is added.  Gate of
     a double accumulator as test_batchnorm_stats_gpu.py derives it (1e-9 s on the mean, 1e-9 s^2 on E2, s = sqrt(E2)) plus the conv0
     error itself: mean d0 on the mean, mean (2 |x| d0 + d0^2) on E2.  -> (mean, gate), (E2, gate)."""
@@ -165,9 +165,9 @@ def sparse_stats(c0, d0):
 # ---------------------------------------------------------------------------------------------------------------------
 def pool_backward(G, X, P, Q, Hc, Wc, defect=None):
     """dz over the conv0 map from what reaches the pooled map: eff1 = G + P X + Q per pooled pixel (three fp32 roundings of a value no
-    larger than |G| + |P X| + |Q|: stem.hip:72, :263; stem_sparse.hip:493), dz[p] = fl(1 / 9) * sum of eff1 over the <= 4 windows (rows
-    2q .. 2q + 2) that hold p: at most three additions (stem.hip:303-304; four from 0 in the flat kernel, :72, and in the sparse one,
-    stem_sparse.hip:507) and two roundings for * fl(1 / 9) (:78, :305; stem_sparse.hip:510):
+    larger than |G| + |P X| + |Q|: stem.hip:76, :262; stem_sparse.hip:490), dz[p] = fl(1 / 9) * sum of eff1 over the <= 4 windows (rows
+    2q .. 2q + 2) that hold p: at most three additions (stem.hip:302-303; four from 0 in the flat kernel, :76, and in the sparse one,
+    stem_sparse.hip:505) and two roundings for * fl(1 / 9) (:82, :304; stem_sparse.hip:508):
         ddz = R(3 + 4 + 2) * 1/9 sum (|G| + |P X| + |Q|).
     A position no window covers -- the last row / column of an even extent -- has dz = 0 exactly and ddz = 0.
     G, X [n, Ho, Wo, C] (raw:grad1 / dense1, first C channels), P, Q [C].
@@ -202,8 +202,8 @@ def uncovered(Hc, Wc):
 
 def stem_sums(dz, ddz, x, dx, sc, sh, sl):
     """The three sums the pooling backward leaves for BatchNorm0 -- s1 = sum dU, t2 = sum dU x, s3 = sum dz min(u, 0), dU = prelu'(u) dz,
-    u = fma(x, sc, sh) -- over ALL conv0 positions (stem.hip:305-309; the sparse pass takes the hit-free positions in through the identity
-    sum_p dz = sum_q eff, in double, stem_sparse.hip:611-617).  x: the conv0 map the kernel read, dx its uncertainty (0: the stored map;
+    u = fma(x, sc, sh) -- over ALL conv0 positions (stem.hip:304-308; the sparse pass takes the hit-free positions in through the identity
+    sum_p dz = sum_q eff, in double, stem_sparse.hip:562-568).  x: the conv0 map the kernel read, dx its uncertainty (0: the stored map;
     the sparse kernels rebuild it on chip: conv0_from_hits' delta).
     dx = 0: densenet_layer_reference.bn_sums as it stands.  dx > 0, on top of it: u is off by |sc| dx more, so the kink set grows to
     |u| <= R(2) (|sc x| + |sh|) + |sc| dx and each of its new members adds the difference between the two branches to the gates; t2 takes
@@ -223,7 +223,7 @@ def stem_sums(dz, ddz, x, dx, sc, sh, sl):
 def conv0_wgrad(e, de, img, terms, c=516, defect_img=None, bias_terms=None):
     """dW0[n][c][ky][kx] = sum over positions of eff0[pos][n] img[2 oy - 3 + ky][2 ox - 3 + kx][c] and db0[n] = sum eff0[pos][n]:
     e, de [n, Hc, Wc, N] the eff0 rows as the kernel holds them and their uncertainty, img the dense map [n, H, W, Cpix] with each listed
-    pixel ONCE (image()).  The hit-list kernel (stem.hip:114-194) walks the owner entries -- fma chains per wave, at most one term per
+    pixel ONCE (image()).  The hit-list kernel (stem.hip:118-197) walks the owner entries -- fma chains per wave, at most one term per
     entry, then <= 3 LDS additions, the slab reduction over its 512 workgroups and the addition into the zeroed gradient -- and the
     generic kernel sums all positions with fp32 atomics; zero pixels contribute exact zeros, so a sum passes at most `terms` + c
     roundings, terms = the number of summands that can be nonzero (the caller's count), c = 3 + 512 + 1:
@@ -249,8 +249,8 @@ def stem_backward(G, X, P, Q, c0, dc0, tab, sl, gamma, stats, img, du0=None, pq0
       c0, dc0        the conv0 map the kernels read and its uncertainty (None: the stored map)
       tab, sl        BatchNorm0's (sc, sh) out of raw:tabs, PReLU0's slope              -> dU, the three sums (stem_sums)
       gamma, stats   norm0.weight, (mean, var) out of raw:bstat0                          -> dgamma0, dbeta0, dslope0, (P0, Q0) (bn_link)
-      DU0 = sc dU: one more rounding on top of the slope multiply (stem.hip:310; prelu_bn_backward's gate)
-      eff0 = DU0 + P0 c0 + Q0 (eff_rows; fma(sc, dU, fma(P0, x, Q0)) in the sparse pass, stem_sparse.hip:555: fewer roundings)
+      DU0 = sc dU: one more rounding on top of the slope multiply (stem.hip:309; prelu_bn_backward's gate)
+      eff0 = DU0 + P0 c0 + Q0 (eff_rows; fma(sc, dU, fma(P0, x, Q0)) in the sparse pass, stem_sparse.hip:596: fewer roundings)
       dW0, db0 (conv0_wgrad) from the STORED du0 [n, Hc, Wc, C] and pq0 [2 C] where they are given (NaN rows of du0 -- never stored, no
       hit reaches them -- multiply zero pixels only and are taken as 0), so that one kernel's error is not charged to the next; without them
       (sparse pass) from the chain, whose per-element error |sc| ddU + |P0| dc0 goes into F.  rnd_eff: the generic bf16 kernel rounds the

@@ -16,7 +16,7 @@ Gates (all from the arithmetic; u = 2^-24):
     at most (L - 1) u mean|x| on the mean and L u E2 on E2 for an fp32 chain of L values.  The other producers (_chains):
       - k_pool0 / k_pool0_vec64 (elementwise.hip:189, :449), k_rows_bn_fwd (rows.hip:69), the generic k_conv_fwd (StatAcc is double for
         both types, conv_tile.h:160-161) and k_conv3x3_fwd_f32 (conv3x3_f32.hip:279) widen every value to double first: L = 1, no term;
-      - k_stem_fwd2_bf16 adds one pixel per lane and 8 x 16 tile in fp32 (stem.hip:593-594): L = tiles per workgroup;
+      - k_stem_fwd2_bf16 adds one pixel per lane and 8 x 16 tile in fp32 (stem.hip:583-584): L = tiles per workgroup;
       - k_gemm_nt_bf16<fwd> (transition, unfused 1x1): 64-row instance (Kp <= 256) four rows per tile in fp32 running sums
         (gemm_nt.hip:88, :223), 128-row instance eight rows per tile, then double (gemm_nt.hip:250): L = 4 x tiles per workgroup, or 8;
       - k_conv1x1_fwd_f32 the 16 positions of one epilogue (conv1x1_f32.hip:390-401): L = 16, also taken where the generic kernel
@@ -164,7 +164,7 @@ def _chains(cfg, mode, fused, pair, n_img, hw0, n_blk):
     up32 = lambda c: -(-c // 32) * 32
     def gemm_nt(n, N, K):                                    # k_gemm_nt_bf16<EPI_FWD>; grid cap: gemm_nt_nblk (gemm_nt.hip:297-305)
         return 4 * _tiles_per_wg(-(-n // 64), max(64, 512 // -(-N // 128))) if up32(K) <= 256 else 8
-    stem2 = mode == BF16 and init == 64 and cfg.pixel_dim == 3                    # stem_fwd_ok; grid cap 512 (stem_fwd_nblk, stem.hip:689-692)
+    stem2 = mode == BF16 and init == 64 and cfg.pixel_dim == 3                    # stem_fwd_ok; grid cap 512 (stem_fwd_nblk, stem.hip:679-682)
     L0 = _tiles_per_wg(n_img * -(-hw0[0] // 8) * -(-hw0[1] // 16), 512) if stem2 else 1
     Lblock, Lmid, ch = [], [], init
     for b, layers in enumerate(cfg.densenet_structure):

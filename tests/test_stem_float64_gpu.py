@@ -11,9 +11,9 @@ Cases (stem_reference.case_hits; structure [1], one encoder layer, no dropout), 
               in no pooling window (dz exactly 0 there) -- corners, borders, an empty map, entries outside the maps, 40 pixels listed twice
   odd         45 x 37: stem_fwd_ok needs Hin == 2 H, so the product bf16 build takes the generic conv0; 23 x 19: every row is pooled
   dense-band  40 x 280 with a fully set 24 x 120 block: sparse bands of more than SS_HCAP = 2048 records read them from the index
-              (load_band's !in_lds path, stem_sparse.hip:143); the record counts per band are computed from the list and asserted
+              (load_band's !in_lds path, stem_sparse.hip:216); the record counts per band are computed from the list and asserted
   many        150 maps: 2100 backward tiles (grid cap 2048 in pool0_bwd_vec_grid), 3150 forward tiles (512 in stem_fwd_nblk)
-  many-tiny   12 x 16, 1030 maps: more sparse work units than the cap of 1024 in unit_grid
+  many-tiny   12 x 16, 1030 maps: more sparse work units than the cap of 1024 in stem_sparse_plan
   wide-limit  24 x 384: the sparse stem's largest W (eval only)
 Builds: product bf16 train, fp32, and the validation build with TCVN_DISABLE_TILE check img, conv0 (a position no hit reaches must be the
 stored-precision bias exactly), pool0 and the backward (raw:du0, raw:pq0, dgamma0, dbeta0, dslope0, dW0, dbias0); TCVN_NO_STEM_SKIP and
@@ -43,7 +43,7 @@ WEIGHT_SEED = 19
 N0 = "features.norm0"
 TRAIN_CASES = ["partial", "odd", "dense-band", "many", "many-tiny"]
 ALL_CASES = TRAIN_CASES + ["wide-limit"]
-ST_CR, PL_PR, SS_HCAP = 8, 4, 2048            # stem_sparse.hip: conv0 rows per band, pooled rows per band, records of a band kept in LDS
+SS_CROWS, SS_PROWS, SS_HCAP = 8, 4, 2048            # stem_sparse.hip: conv0 rows per band, pooled rows per band, records of a band kept in LDS
 
 
 def _cfg(case):
@@ -57,14 +57,14 @@ def _kink_free(sc, sh, b0):
 
 
 def _band_records(coords, n, H, W, Hc, Ho):
-    """Records (entries inside the maps, duplicates included: stem_sparse.hip:90-106) per band of every sparse pass -> the largest count of
+    """Records (entries inside the maps, duplicates included: stem_sparse.hip:113-124) per band of every sparse pass -> the largest count of
     the conv0-row bands (statistics, backward: 21 input rows) and of the pooled-row bands (23 input rows)."""
     c = coords.long()
     ok = (c[:, 0] >= 0) & (c[:, 0] < n) & (c[:, 1] >= 0) & (c[:, 1] < H) & (c[:, 2] >= 0) & (c[:, 2] < W)
     rows = torch.zeros(n, H, dtype=torch.int64)
     rows.index_put_((c[ok, 0], c[ok, 1]), torch.ones(int(ok.sum()), dtype=torch.int64), accumulate=True)
     best = []
-    for per, extent, lo, hi in ((ST_CR, Hc, lambda h0: 2 * h0 - 3, lambda h1: 2 * h1 + 3), (PL_PR, Ho, lambda q0: 4 * q0 - 3, lambda q1: 4 * q1 + 7)):
+    for per, extent, lo, hi in ((SS_CROWS, Hc, lambda h0: 2 * h0 - 3, lambda h1: 2 * h1 + 3), (SS_PROWS, Ho, lambda q0: 4 * q0 - 3, lambda q1: 4 * q1 + 7)):
         m = 0
         for r0 in range(0, extent, per):
             r1 = min(r0 + per, extent) - 1
@@ -235,7 +235,7 @@ def _assert_case(rep, case):
     if case == "many":
         assert n * cdiv(Hc, 8) * cdiv(Wc, 32) > 2048 and cdiv(n * Hc * Wc, 32) > 2048 and n * cdiv(Hc, 8) * cdiv(Wc, 16) > 512
     if case == "many-tiny":
-        assert n > 1024                       # one work unit per map at least (split_count)
+        assert n > 1024                       # one work unit per map at least (stem_sparse_plan)
     if case == "wide-limit":
         assert W == 384
     assert rep["info"]["hit_free"] > 0 and rep["d_out_rows"] >= 2
