@@ -30,19 +30,25 @@ extern "C" void tcvn_debug_pq_tap(int block, int layer, float* dst) { g_pq_tap =
 // (P, Q) rows; behind the last launch G[block] and (P, Q) again, DU, (PY, QY) and the layer's eff rows EY3 (where the layout has them).
 // Sections in that order, each starting at a multiple of 256 bytes (tcvn_debug_layer_snapshot_report gives the total); a buffer that is
 // too small is refused.  The report also says which 3x3 data-gradient kernel ran (Conv3x3Dgrad), whether the fused 1x1 backward ran and
-// whether the data-gradient kernel filled EY3.  The backward-overlap side stream must be off (the default).
-struct LayerSnap { int block, layer; char* dst; long cap, bytes; int dgrad_kernel, fused1, ey_valid; };
+// whether the data-gradient kernel filled EY3; tcvn_debug_layer_snapshot_grid gives the fused 1x1 backward's grid (row workgroups, 128-column
+// slices; 0 row workgroups where it did not run).  The backward-overlap side stream must be off (the default).
+struct LayerSnap { int block, layer; char* dst; long cap, bytes; int dgrad_kernel, fused1, ey_valid, nblk1, slices1; };
 static std::vector<LayerSnap> g_snaps;
-static struct { int dgrad_kernel, fused1, ey_valid; } g_snap_path = {0, 0, 0};
+static struct { int dgrad_kernel, fused1, ey_valid, nblk1, slices1; } g_snap_path = {0, 0, 0, 0, 0};
 extern "C" void tcvn_debug_layer_snapshot_clear(void) { g_snaps.clear(); }
 extern "C" int tcvn_debug_layer_snapshot(int block, int layer, void* dst, int64_t cap) {
     if (!dst || cap <= 0) return -1;
-    g_snaps.push_back(LayerSnap{block, layer, reinterpret_cast<char*>(dst), (long)cap, 0, 0, 0, 0});
+    g_snaps.push_back(LayerSnap{block, layer, reinterpret_cast<char*>(dst), (long)cap, 0, 0, 0, 0, 0, 0});
     return (int)g_snaps.size() - 1;
 }
 extern "C" int tcvn_debug_layer_snapshot_report(int i, int* dgrad_kernel, int* fused1, int* ey_valid, int64_t* bytes) {
     if (i < 0 || i >= (int)g_snaps.size()) return -1;
     *dgrad_kernel = g_snaps[i].dgrad_kernel; *fused1 = g_snaps[i].fused1; *ey_valid = g_snaps[i].ey_valid; *bytes = g_snaps[i].bytes;
+    return 0;
+}
+extern "C" int tcvn_debug_layer_snapshot_grid(int i, int* nblk, int* slices) {
+    if (i < 0 || i >= (int)g_snaps.size()) return -1;
+    *nblk = g_snaps[i].nblk1; *slices = g_snaps[i].slices1;
     return 0;
 }
 static int layer_snapshot(const DenseNetPlan& pl, const Step& s, int bi, int l, bool after) {
@@ -65,6 +71,7 @@ static int layer_snapshot(const DenseNetPlan& pl, const Step& s, int bi, int l, 
         TCVN_CHECK(hipMemcpyAsync(d + db, s.ws + s.L.pqY, (size_t)mid * 8, hipMemcpyDeviceToDevice, s.st));
         if (ey) TCVN_CHECK(hipMemcpyAsync(d + db + yb, s.ws + s.L.EY3[bi][l], (size_t)(M * 32 * pl.esz), hipMemcpyDeviceToDevice, s.st));
         sn.dgrad_kernel = g_snap_path.dgrad_kernel; sn.fused1 = g_snap_path.fused1; sn.ey_valid = g_snap_path.ey_valid;
+        sn.nblk1 = g_snap_path.nblk1; sn.slices1 = g_snap_path.slices1;
     }
     return 0;
 }
@@ -385,7 +392,7 @@ int DenseNetPlan::bwd_layer(Step& s, int bi, int l) const {
     Bwd1x1Args fa{};
     const bool fuse1 = bwd1x1_fill(bi, l, M, s.ws, L, fa);       // (the same function the forward asked before it dropped the activated copy)
 #ifdef TCVN_DEBUG_KNOBS
-    g_snap_path.fused1 = fuse1 ? 1 : 0;
+    g_snap_path.fused1 = fuse1 ? 1 : 0; g_snap_path.nblk1 = fuse1 ? fa.nblk : 0; g_snap_path.slices1 = cdiv(ls.cin, 128);
 #endif
     SlabJob w3jobs[2] = {};        // the 3x3 weight gradient's slab reductions, folded into the fused kernel's reduction launch (same stream only)
     bool w3_deferred = false;

@@ -441,3 +441,197 @@ def test_1x1_backward_and_link_gates_bite_and_hold():
         assert R.Check(q, "link", lk[q][0], lk[q][1], False).ratio(R.f32(missing[q][0]))[1] > 0, q
     no_mean = R.bn_link(sim_sums, gates, torch.zeros_like(mu), var, P[n1 + ".weight"], M)
     assert R.Check("Q", "link", lk["Q"][0], lk["Q"][1], False).ratio(R.f32(no_mean["Q"][0]))[1] > 0
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the fused 1x1 backward at the hook test's widths and trip counts
+# ---------------------------------------------------------------------------------------------------------------------
+def layer_case(name):
+    """The hook test's own cases (test_densenet_layers_float64_gpu.py, LAYER_CASES) -> cfg, coords, values, n_img.
+    mod4: one block, cin = 228 .. 388 (cin % 8 == 4: production block 4's widths, two to four 128-column slices), event map + two prong
+    maps of 13 x 9 pixels.  trips: one block, cin = 232 .. 392, 27 prong maps of 25 x 17 pixels: M = 11 475 = 179 full 64-pixel tiles + 19
+    rows, more than the fused 1x1 backward's grid cap at three slices (170 workgroups) and at four (128)."""
+    base = dict(pixel_noise_std=0.0, num_encoder_layers=2, dropout=0.0)
+    if name == "mod4":
+        cfg = O.tutorial_config(initial_pixel_dim=228, densenet_structure=[6], pixel_shape=(56, 40), **base)
+        b = O.synthetic_batch([2], 41, cfg, event_hits=(60, 200), prong_hits=(20, 120))
+        pc = b[5].clone()
+        pc[:, 0] += 1                                                     # image 0 = the event map
+        return cfg, torch.cat([b[2], pc]).contiguous(), torch.cat([b[3], b[6]]).contiguous(), 3
+    assert name == "trips"
+    cfg = O.tutorial_config(initial_pixel_dim=232, densenet_structure=[6], pixel_shape=(104, 72), **base)
+    b = O.synthetic_batch([14, 13], 43, cfg, prong_hits=(60, 400))
+    return cfg, b[5], b[6], 27
+
+
+def fused_grid(M, cin):
+    """(row workgroups, 128-column slices, 64-pixel tiles) of the fused 1x1 backward: bwd1x1_fused.hip, bwd1x1_fused_nblk."""
+    slices, tiles = -(-cin // 128), -(-M // 64)
+    return min(tiles, max(64, 512 // slices)), slices, tiles
+
+
+@pytest.mark.parametrize("case", ["mod4", "trips"])
+def test_new_layer_cases_stay_under_the_kink_cap(case):
+    """With the reference alone (the bf16-faithful forward, tables from its own maps): the PReLU kink sets of norm1 and norm2 of every
+    layer and of final_norm -- they depend on the forward maps only -- hold at most KINK_CAP of their tensor."""
+    cfg, coords, values, n_img = layer_case(case)
+    _, P = _params(cfg)
+    _, maps = R.run_forward(cfg, P, True, True, _conv0(cfg, P, coords, values, True))
+    x, g = maps["dense1"], cfg.densenet_growth_rate
+    assert x.shape[0] * x.shape[1] * x.shape[2] == {"mod4": 351, "trips": 11475}[case]
+
+    def share(t, norm):
+        sc, sh = (R.f32(v) for v in R.bn_table(t, P[norm + ".weight"], P[norm + ".bias"]))
+        kink = (t * sc + sh).abs() <= R.R(2) * ((t * sc).abs() + sh.abs())
+        return int(kink.sum()) / kink.numel()
+    worst = share(x, "features.final_norm")
+    for l in range(cfg.densenet_structure[0]):
+        p = f"features.dense1.layers.{l}"
+        cin = cfg.initial_pixel_dim + l * g
+        assert cin % 8 == 4 or case == "trips"
+        worst = max(worst, share(x[..., :cin], p + ".bottleneck_block.norm1"), share(maps[f"bottleneck1.{l}"], p + ".output_block.norm2"))
+    print(case, "largest share of a tensor at a PReLU kink:", worst)
+    assert worst <= R.KINK_CAP
+
+
+@functools.lru_cache(maxsize=None)
+def _fused_operands(M, cin):
+    """Synthetic operands of one fused 1x1 backward launch at the hook cases' own M and cin (bf16 maps, fp32 rows and tables), the block's
+    buffers 32 channels wider than cin (the layer's own 3x3 slice behind it), and the intact reference with its gates."""
+    gen = torch.Generator().manual_seed(1000 * cin + M)
+    rn = lambda *s: torch.randn(*s, generator=gen, dtype=torch.float64)
+    mid, ld = 128, cin + 32
+    o = dict(M=M, cin=cin, DU=R.bf16(rn(M, mid) * 1e-2), Y=R.bf16(rn(M, mid)), PY=R.f32(rn(mid) * 2e-3), QY=R.f32(rn(mid) * 2e-3),
+             X=R.bf16(rn(M, ld)), G=R.bf16(rn(M, ld) * 1e-2), gamma=1.0 + 0.1 * rn(cin), w1=rn(mid, cin) * 0.05, sl=R.f32(0.25 + 0.05 * rn(cin)))
+    xin = o["X"][:, :cin]
+    o["sc"], o["sh"] = (R.f32(t) for t in R.bn_table(xin, o["gamma"], 0.1 * rn(cin)))
+    _, _, a1, da1 = R.activation(xin, o["sc"], o["sh"], o["sl"], True)
+    out, sums, gates = R.conv1x1_backward(o["DU"], o["Y"], o["PY"], o["QY"], a1, da1, o["w1"], o["G"][:, :cin], xin, o["sc"], o["sh"], o["sl"], True)
+    o["mu"], o["var"] = xin.mean(0), ((xin - xin.mean(0)) ** 2).mean(0)
+    lk = R.bn_link(sums, gates, o["mu"], o["var"], o["gamma"], M)
+    checks = {"G": R.Check("G", "1x1 backward", out["G"][0], out["G"][1], True, out["G"][2]),
+              "dW1": R.Check("dW1", "1x1 backward", out["dW1"][0], out["dW1"][1], False),
+              "db1": R.Check("db1", "1x1 backward", out["db1"][0], out["db1"][1], False)}
+    for q in ("dgamma", "dbeta", "dslope", "P", "Q"):
+        checks[q] = R.Check(q, "norm1 link", lk[q][0], lk[q][1], False)
+    return o, gates, checks
+
+
+def _fused_kernel(o, defect=None):
+    """k_bwd1x1_fused_bf16 (bwd1x1_fused.hip) in fp32, in the kernel's order: workgroup b of nblk takes the 64-pixel tiles b, b + nblk, ...;
+    per tile EY = bf16(DU + PY Y + QY), dX = EY W1, the epilogue against x, G = bf16(G + sc dU); every thread keeps fp32 sums over its rows
+    (row % 16) of all its workgroup's tiles and widens them to double at the end; the weight-gradient tile and the bias column sums stay
+    in fp32 per workgroup over all its tiles and leave as one slab, added over the workgroups in fp32.
+    defect: "slice_table" columns 256..383 read the table rows of columns 128..255; "drop_last4" the last four channels of a width with
+    cin % 8 == 4 missing from G and dW1; "foreign_written" the four channels behind them stored with the chunk; "second_trip_missing"
+    every tile of a second trip missing from dW1, db1 and the sums; "second_trip_rows" the second trip's G rows stored at the first
+    trip's offsets; "reset_between_tiles" the weight-gradient accumulators zeroed in front of every tile; "one_tile_missing" tile 0
+    missing from the three sums.  -> {G (all ld columns), dW1, db1, sums}, the results as stored."""
+    M, cin = o["M"], o["cin"]
+    nblk, slices, tiles = fused_grid(M, cin)
+    trips = -(-tiles // nblk)
+    f = lambda t: t.float()
+    sc, sh, sl = f(o["sc"]).clone(), f(o["sh"]).clone(), f(o["sl"]).clone()
+    if defect == "slice_table":
+        k = min(384, cin) - 256
+        assert k > 0
+        for t in (sc, sh, sl):
+            t[256:256 + k] = t[128:128 + k].clone()
+    x = f(o["X"][:, :cin])
+    e = (f(o["DU"]) + f(o["PY"]) * f(o["Y"]) + f(o["QY"])).to(torch.bfloat16).float()
+    dX = e @ f(R.bf16(o["w1"]))
+    u = x * sc + sh
+    dU = torch.where(u > 0, dX, sl * dX)
+    G = o["G"].clone()
+    G[:, :cin] = (f(o["G"][:, :cin]) + sc * dU).to(torch.bfloat16).double()
+    a = torch.where(u > 0, u, sl * u).to(torch.bfloat16).float()
+    rows = trips * nblk * 64
+
+    def tiled(t):                                                           # [M, C] -> [trip, workgroup, 64, C], rows behind M zero
+        return torch.cat([t, t.new_zeros(rows - M, t.shape[1])]).reshape(trips, nblk, 64, t.shape[1])
+    live = torch.ones(trips, nblk)                                          # tiles that reach the sums and the slabs
+    if defect == "second_trip_missing":
+        live[1:] = 0
+    live_w = live.clone()
+    if defect == "reset_between_tiles":                                     # only a workgroup's last tile survives
+        last = torch.tensor([(tiles - 1 - b) // nblk for b in range(nblk)])
+        live_w = (torch.arange(trips)[:, None] == last[None, :]).float()
+    live_s = live.clone()
+    if defect == "one_tile_missing":
+        live_s[0, 0] = 0
+    if defect == "second_trip_rows":
+        assert trips == 2
+        new, Gb = tiled(G[:, :cin]), tiled(o["G"][:, :cin])
+        n2 = tiles - nblk                                                   # tiles of the second trip; the last one is partial
+        mixed = torch.cat([new[0], Gb[1]]).clone()                          # [tile, 64, cin]: trip 0 as stored, trip 1 never written ...
+        mixed[:n2 - 1] = new[1][:n2 - 1]                                    # ... its rows land on trip 0's tiles
+        mixed[n2 - 1][:M - (tiles - 1) * 64] = new[1][n2 - 1][:M - (tiles - 1) * 64]
+        G[:, :cin] = mixed.reshape(rows, cin)[:M]
+    if defect == "drop_last4":
+        assert cin % 8 == 4
+        G[:, cin - 4:cin] = o["G"][:, cin - 4:cin]
+        a = a.clone()
+        a[:, cin - 4:] = 0
+    if defect == "foreign_written":                                         # the 16-byte store of the last chunk, its foreign half with the
+        assert cin % 8 == 4                                                 # values of the channels in front of it
+        G[:, cin:cin + 4] = (f(o["G"][:, cin:cin + 4]) + sc[cin - 4:] * dU[:, cin - 4:]).to(torch.bfloat16).double()
+    et, at = tiled(e), tiled(a)
+    accW, accb = torch.zeros(nblk, 128, cin), torch.zeros(nblk, 16, 128)
+    st = [torch.zeros(nblk, 16, cin) for _ in range(3)]
+    terms = [tiled(t) for t in (dU, dU * x, torch.where(u > 0, torch.zeros_like(dX), dX) * u)]
+    for t in range(trips):
+        accW += live_w[t][:, None, None] * torch.bmm(et[t].transpose(1, 2), at[t])
+        for i in range(4):
+            accb += live[t][:, None, None] * et[t][:, 16 * i: 16 * i + 16]
+            for s, term in zip(st, terms):
+                s += live_s[t][:, None, None] * term[t][:, 16 * i: 16 * i + 16]
+    return dict(G=G, dW1=accW.sum(0).double(), db1=accb.sum(1).sum(0).double(), sums=tuple(s.double().sum((0, 1)) for s in st))
+
+
+def _outside(o, gates, checks, sim):
+    """Elements outside the gate per result of a simulated launch (the link from the launch's own sums)."""
+    lk = R.bn_link(sim["sums"], gates, o["mu"], o["var"], o["gamma"], o["M"])
+    got = dict(G=sim["G"][:, :o["cin"]], dW1=sim["dW1"], db1=sim["db1"], **{q: R.f32(lk[q][0]) for q in ("dgamma", "dbeta", "dslope", "P", "Q")})
+    return {k: (c.ratio(got[k])[1], round(c.ratio(got[k])[0], 3)) for k, c in checks.items()}
+
+
+FUSED_SIZES = [(351, 260), (11475, 260), (11475, 392)]                      # mod4's layer 1; trips' M at three and at four slices
+
+
+@pytest.mark.parametrize("M,cin", FUSED_SIZES)
+def test_fused_1x1_backward_gates_hold_and_bite_at_the_hook_cases_sizes(M, cin):
+    """The sum gates grow with M (R(M) of the sum of magnitudes), so what bites at 1 275 pixels need not bite at 11 475: at the hook
+    cases' own sizes a correct kernel summing tile by tile and slab by slab stays inside every gate, and each defect of a column slice,
+    of the half-foreign last chunk and of a workgroup's second tile leaves the gates it must.
+    Resolution of the sum checks at M = 11 475 (printed below): ONE missing 64-row tile still leaves the gates of dgamma1, dbeta1,
+    dslope1, P and Q -- on 154 .. 288 of the cin channels, worst |error| / gate 5.6 .. 8.7 on these operands."""
+    o, gates, checks = _fused_operands(M, cin)
+    nblk, slices, tiles = fused_grid(M, cin)
+    assert slices == -(-cin // 128) >= 3 and (tiles > nblk) == (M == 11475)
+    assert int(checks["G"].kink.sum()) <= R.KINK_CAP * checks["G"].kink.numel()
+    ok = _outside(o, gates, checks, _fused_kernel(o))
+    print(M, cin, "correct kernel, (elements outside, worst |error| / gate):", ok)
+    assert all(v[0] == 0 for v in ok.values()), ok
+    intact = _fused_kernel(o)
+    assert torch.equal(intact["G"][:, cin:], o["G"][:, cin:])
+
+    def bites(defect, *results):
+        out = _outside(o, gates, checks, _fused_kernel(o, defect))
+        print(M, cin, defect, out)
+        for r in results:
+            assert out[r][0] > 0, (defect, r, out)
+        return out
+    out = bites("slice_table", "G", "dbeta", "dgamma", "dslope")
+    assert all(ix[1] >= 256 for ix in checks["G"].ratio(_fused_kernel(o, "slice_table")["G"][:, :cin])[2])
+    if cin % 8 == 4:
+        bites("drop_last4", "G", "dW1")
+        wrong = _fused_kernel(o, "foreign_written")
+        assert not torch.equal(wrong["G"][:, cin:], o["G"][:, cin:]) and checks["G"].ratio(wrong["G"][:, :cin])[1] == 0
+    if tiles > nblk:
+        assert tiles - nblk == {3: 10, 4: 52}[slices] and M % 64 == 19       # the partial last tile lands in the second trip
+        bites("second_trip_missing", "dW1", "db1", "dbeta", "dgamma", "dslope", "P", "Q")
+        bites("second_trip_rows", "G")
+        bites("reset_between_tiles", "dW1")
+        one = _outside(o, gates, checks, _fused_kernel(o, "one_tile_missing"))
+        print(M, cin, "one 64-row tile missing from the sums (resolution of the sum checks at this size):", {q: one[q] for q in ("dgamma", "dbeta", "dslope", "P", "Q")})
+        assert all(one[q][0] > 0 for q in ("dgamma", "dbeta", "dslope", "P", "Q")), one

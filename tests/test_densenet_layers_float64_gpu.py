@@ -30,14 +30,29 @@ the weight gradient; the odd-width case, whose slices are not 16-byte aligned, s
 fp32.  With one image the output block's train-mode BatchNorm1d passes no gradient: every reference is exactly zero there, and so must
 the kernels' results be.
 The layers' transient state -- DU of any layer, (PY, QY), G[:, :cin] and (P, Q) in front of a layer's update -- is read through the snapshot
-hook of the validation build (tcvn_debug_layer_snapshot, densenet_bwd.hip), armed in one backward for the first and the last layer of
-every block and for its transition or the head (test_first_and_last_layer_backward_...): eff rows, DU, norm2's link (dgamma2, dbeta2,
+hook of the validation build (tcvn_debug_layer_snapshot, densenet_bwd.hip), armed in one backward for EVERY layer of
+every block and for its transition or the head (test_every_layer_backward_...; test_first_and_last_layer_backward_... keeps its name and
+assertions and reads the first and last layers' part of the same run, _first_and_last): eff rows, DU, norm2's link (dgamma2, dbeta2,
 dslope2, PY, QY), db1, dW1, the read-add-write of G[:, :cin], norm1's link (dgamma1, dbeta1, dslope1, P / Q[:cin] +=), everything else of
 G, P, Q bit-unchanged; for the block's first writer G and (P, Q) over all channels as the contribution alone, the transition's weight and
 bias gradient and its norm's parameter gradients.  Builds: validation library without knobs (the product kernel choice; also in fp32
 mode), TCVN_DGRAD3_ANY_SIZE, the unfused build (eff_materialize, TN and NT GEMMs on stored operands) and TCVN_DISABLE_TILE.  The hook's
 report (which 3x3 data-gradient kernel ran, whether the fused 1x1 backward ran, whether the eff rows were stored) and the launch labels
-are asserted per build."""
+are asserted per build.
+The hook test has two cases of its own (LAYER_CASES; defined in test_densenet_layer_reference_cpu.layer_case, which also shows on the CPU
+that the gates bite at these sizes), chosen along the three axes on which k_bwd1x1_fused_bf16 changes its behaviour:
+  * column slices (grid.y = cdiv(cin, 128): own table rows, own slab columns): with every layer armed `odd` gives two to five slices at
+    cin % 8 == 2, `mod4` and `trips` two to four;
+  * cin % 8: `mod4` has cin = 228 .. 388, all % 8 == 4 -- production block 4's widths, where the last 16-byte chunk of a row is half
+    foreign and the layer's 3x3 slice is 8-byte aligned only (the two-workgroup 3x3 data gradient, asserted);
+  * tiles per workgroup (grid.x = min(tiles, max(64, 512 // slices)) workgroups of 64 pixels; a workgroup that takes a second tile keeps
+    its weight-gradient accumulators, bias sums and statistics across tiles): `trips` has M = 11 475 pixels = 179 full tiles + 19 rows, so
+    at three slices (cap 170) ten workgroups and at four slices (cap 128) fifty-two take a second tile, the partial tile among them.  The
+    grid comes from tcvn_debug_layer_snapshot_grid and is asserted against the re-stated formula for every layer of every case: should
+    the cap change, the test fails instead of going back to one tile per workgroup.  Layer 0 of `trips` (two slices, cap 256) stays at one
+    tile: a second trip at one or two slices needs M > 16 384 and is left out to keep the float64 recomputation small.
+The same cases run the unfused build's k_gemm_tn_bf16<conv1> / k_gemm_nt_bf16<dgrad1x1> (same cap formula), the generic kernels and fp32
+mode (k_gemm_tn_f32 split-K, k_conv1x1_dgrad_f32) at these widths and trip counts."""
 import ctypes as C
 import functools
 
@@ -47,6 +62,7 @@ import torch
 import densenet_layer_reference as R
 from oracle import tcvn_oracle as O
 from test_densenet_gpu import _conv0_activity, _engine
+from test_densenet_layer_reference_cpu import fused_grid, layer_case
 
 pytestmark = pytest.mark.gpu
 
@@ -64,6 +80,8 @@ def _all_maps(batch):
 def _case(name):
     """-> cfg, coords, values, n_img"""
     base = dict(pixel_noise_std=0.0, num_encoder_layers=2)
+    if name in ("mod4", "trips"):             # cin % 8 == 4 at production block 4's widths; M = 11 475 pixels, past the fused 1x1 backward's grid caps
+        return layer_case(name)
     if name in ("wide", "wide-dropout"):      # block 1 as wide as production's: conv0 20 x 140, block 1 9 x 69 (odd in front of the transition), block 2 4 x 34
         cfg = O.tutorial_config(pixel_shape=(40, 280), densenet_structure=[3, 2], dropout=0.1 if name == "wide-dropout" else 0.0, **base)
         b = O.synthetic_batch([3], 47, cfg, prong_hits=(20, 400))
@@ -80,6 +98,8 @@ def _case(name):
 
 
 CASES = ["wide", "wide-dropout", "narrow", "narrow-one", "odd"]
+FWD_CASES = CASES + ["mod4"]                  # the forward test
+LAYER_CASES = CASES + ["mod4", "trips"]       # the snapshot-hook test
 
 
 def _geometry(cfg):
@@ -263,16 +283,19 @@ def _ru(v):
 
 
 def _run_layers_backward(case, mode):
-    """Validation build only: one backward with the snapshot hook (tcvn_debug_layer_snapshot, densenet_bwd.hip) armed for the first and the
-    last layer of every block; every kernel of those layers against float64 on the state the layer found: eff rows (where stored), DU,
+    """Validation build only: one backward with the snapshot hook (tcvn_debug_layer_snapshot, densenet_bwd.hip) armed for EVERY layer of
+    every block and its transition / the head; every kernel of those layers against float64 on the state the layer found: eff rows (where stored), DU,
     norm2's link (dgamma2, dbeta2, dslope2, PY, QY), db1, dW1, the read-add-write of G[:, :cin], norm1's link (dgamma1, dbeta1, dslope1,
-    P / Q[:cin] +=); the rest of G and (P, Q) must be bit-unchanged.  -> report."""
+    P / Q[:cin] +=); the rest of G and (P, Q) must be bit-unchanged.  The report carries the fused 1x1 backward's grid per layer
+    (tcvn_debug_layer_snapshot_grid).  -> report."""
     from transformercvn.hip import _lib
     lib = _lib.lib
     lib.tcvn_debug_layer_snapshot.restype = C.c_int
     lib.tcvn_debug_layer_snapshot.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int64]
     lib.tcvn_debug_layer_snapshot_clear.restype = None
     lib.tcvn_debug_layer_snapshot_report.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int64)]
+    lib.tcvn_debug_layer_snapshot_grid.restype = C.c_int
+    lib.tcvn_debug_layer_snapshot_grid.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     cfg, coords, values, n_img = _case(case)
     sd = O.fill_state(cfg, 19)
     eng, data, grads = _engine(cfg, sd, mode=mode, with_grad=True)
@@ -290,7 +313,7 @@ def _run_layers_backward(case, mode):
         H, W, _ = geo[b]
         M, ld = n_img * H * W, eng.tap(f"raw:pq{b + 1}").numel() // 2
         sizes = [_ru(M * ld * esz), _ru(ld * 8)] * 2 + [_ru(M * mid * esz), _ru(mid * 8)] + ([_ru(M * 32 * esz)] if has_ey else [])
-        for l in [-1] + sorted({0, layers - 1}):                         # -1: the block's transition, or the head
+        for l in [-1] + list(range(layers)):                             # -1: the block's transition, or the head
             buf = torch.zeros(sum(sizes), dtype=torch.uint8, device="cuda")
             idx = lib.tcvn_debug_layer_snapshot(b, l, buf.data_ptr(), buf.numel())
             armed.append((b, l, idx, buf, sizes, M, ld))
@@ -303,21 +326,25 @@ def _run_layers_backward(case, mode):
     labels = [r[0] for r in _lib.profile_records()]
     _lib.lib.tcvn_profile_reset()
     gr = {k: v.detach().double().cpu() for k, v in grads.items()}
-    figures, reports = [], []
+    figures, reports, owners = [], [], []                                # owners[i]: the armed (block, layer) figure i belongs to
 
     def compare(name, kernel, ref, delta, got, rnd_store, kink=None):
         c = R.Check(name, kernel, ref, delta, rnd_store, kink)
         worst, bad, where = c.ratio(got.reshape(ref.shape))
+        owners.append(owner)
         figures.append((name, kernel, worst, bad, ref.numel(), where, 0 if kink is None else int(kink.sum()), float(ref.abs().max())))
 
     for b, l, idx, buf, sizes, M, ld in armed:
+        owner = (b, l)
         kern, fused, eyv, nbytes = C.c_int(), C.c_int(), C.c_int(), C.c_int64()
         assert lib.tcvn_debug_layer_snapshot_report(idx, C.byref(kern), C.byref(fused), C.byref(eyv), C.byref(nbytes)) == 0
         assert nbytes.value == buf.numel() - (0 if l >= 0 or not has_ey else sizes[-1]), (nbytes.value, buf.numel())      # (no eff rows around a transition)
         H, W, c0 = geo[b]
         cin = c0 + l * g
         if l >= 0:
-            reports.append((b, l, cin, kern.value, fused.value, eyv.value))
+            nblk, slices = C.c_int(-1), C.c_int(-1)
+            assert lib.tcvn_debug_layer_snapshot_grid(idx, C.byref(nblk), C.byref(slices)) == 0
+            reports.append((b, l, cin, kern.value, fused.value, eyv.value, nblk.value, slices.value, M))
         offs = [sum(sizes[:i]) for i in range(len(sizes))]
         raw = buf.cpu()
         sec = lambda i, nbytes_, d: raw[offs[i]: offs[i] + nbytes_].view(d).double()
@@ -396,6 +423,7 @@ def _run_layers_backward(case, mode):
         Ct = X.shape[-1]                                               # (the columns behind Ctot are padding nobody initialises)
         same = bool(torch.equal(G1[..., cin:Ct], G0[..., cin:Ct])) and bool(torch.equal(pq1[:ld][cin:Ct], pq0[:ld][cin:Ct])) and \
             bool(torch.equal(pq1[ld:][cin:Ct], pq0[ld:][cin:Ct]))
+        owners.append(owner)
         figures.append((nm + ":rest of G, P, Q unchanged", "untouched", 0.0 if same else float("inf"), 0 if same else 1, 1, [], 0, 1.0))
         # ---- norm1's link
         bs = _tap(eng, f"raw:bstat{b + 1}").flatten()[:2 * ld].view(ld, 2)[:cin]
@@ -406,7 +434,15 @@ def _run_layers_backward(case, mode):
             inc, d_inc = lk[q]
             compare(nm + f":{q}[0:{cin}]", "norm1 link", pq0[i0: i0 + cin] + inc, d_inc + 0.5 * R.ulp(inc.abs() + d_inc, 24), pq1[i0: i0 + cin], False)
     lib.tcvn_debug_layer_snapshot_clear()
-    return dict(figures=figures, labels=labels, reports=reports)
+    return dict(figures=figures, labels=labels, reports=reports, owners=owners)
+
+
+def _first_and_last(rep, cfg):
+    """The part of an every-layer report that belongs to the first and the last layer of every block and to the blocks' first writers, in
+    the form the hook had before every layer was armed (reports without the grid): what test_first_and_last_layer_... reads."""
+    keep = {(b, l) for b, L in enumerate(cfg.densenet_structure) for l in (-1, 0, L - 1)}
+    return dict(figures=[f for f, o in zip(rep["figures"], rep["owners"]) if o in keep], labels=rep["labels"],
+                reports=[r[:6] for r in rep["reports"] if r[:2] in keep])
 
 
 BUILDS = {"validation": {}, "consec": dict(TCVN_DGRAD3_ANY_SIZE="1"), "unfused": dict(TCVN_NO_FWD1_FUSE="1", TCVN_NO_BWD1_FUSE="1", TCVN_NO_ACT_FUSE="1"), "generic": dict(TCVN_DISABLE_TILE="1")}
@@ -414,15 +450,17 @@ BUILDS = {"validation": {}, "consec": dict(TCVN_DGRAD3_ANY_SIZE="1"), "unfused":
 
 @functools.lru_cache(maxsize=None)
 def _child_reports(build):
-    """All cases of one validation-build knob set in ONE child process (knobs are read once per process)."""
+    """All cases of one validation-build knob set in ONE child process (knobs are read once per process) -> {case: (forward report,
+    backward report, {mode: first-and-last-layer view of the hook report}, {mode: hook report of every layer})}."""
     from variant_utils import run_on_debug_build
     fwd, bwd = build in ("unfused", "generic"), build in ("consec", "generic")
     modes = "(T.BF16, T.F32)" if build == "validation" else "(T.BF16,)"
-    return run_on_debug_build("import test_densenet_layers_float64_gpu as T\n"
-                              f"result = dict((c, (T._run(c, T.BF16, True) if {fwd} else None,\n"
-                              f"                       T._run_backward(c, T.BF16, {build == 'generic'}) if {bwd} else None,\n"
-                              f"                       dict((m, T._run_layers_backward(c, m)) for m in {modes}))) for c in T.CASES)\n",
-                              BUILDS[build])
+    out = run_on_debug_build("import test_densenet_layers_float64_gpu as T\n"
+                             f"result = dict((c, (T._run(c, T.BF16, True) if {fwd} and c in T.FWD_CASES else None,\n"
+                             f"                       T._run_backward(c, T.BF16, {build == 'generic'}) if {bwd} and c in T.CASES else None,\n"
+                             f"                       dict((m, T._run_layers_backward(c, m)) for m in {modes}))) for c in T.LAYER_CASES)\n",
+                             BUILDS[build])
+    return {c: (f, b, {m: _first_and_last(r, _case(c)[0]) for m, r in full.items()}, full) for c, (f, b, full) in out.items()}
 
 
 @functools.lru_cache(maxsize=None)
@@ -444,7 +482,7 @@ def _count(labels, what):
 
 
 @pytest.mark.parametrize("build", ["bf16", "bf16-eval", "fp32", "unfused", "generic"])
-@pytest.mark.parametrize("case", CASES)
+@pytest.mark.parametrize("case", FWD_CASES)
 def test_every_forward_kernel_matches_float64_on_its_own_stored_input(case, build):
     rep = _report(case, build)
     cfg, _, _, n_img = _case(case)
@@ -471,6 +509,8 @@ def test_every_forward_kernel_matches_float64_on_its_own_stored_input(case, buil
         assert geo[-1][:2] == (6, 4)
     if case == "odd":
         assert [p[2] % 8 for p in rep["paths"]] == [2] * 10 and rep["paths"][-1][2] > 512
+    if case == "mod4":                        # production block 4's widths: the last 16-byte chunk of a row is half foreign
+        assert [p[2] for p in rep["paths"]] == [228, 260, 292, 324, 356, 388] and all(p[2] % 8 == 4 for p in rep["paths"])
     # ---- every operation was compared
     n_ops = 2 * layers + len(cfg.densenet_structure) - 1 + 2 + int(rep["conv0"]) + sum(p[3] + (p[4] and p[5]) for p in rep["paths"])
     assert len(rep["figures"]) == n_ops, (len(rep["figures"]), n_ops)
@@ -572,6 +612,68 @@ def test_first_and_last_layer_backward_match_float64_on_the_state_they_found(cas
         else:
             assert kern == 0 and not eyv, rep["reports"]
         assert fused == int(build in ("validation", "consec")), rep["reports"]
+    if build == "unfused":
+        assert _count(labels, "k_gemm_tn_bf16<conv1>") == layers and _count(labels, "k_gemm_nt_bf16<dgrad1x1>") == layers, labels
+        assert not _count(labels, "k_bwd1x1_fused_bf16"), labels
+    if build in ("validation", "consec"):
+        assert _count(labels, "k_bwd1x1_fused_bf16") == layers, labels
+
+
+@pytest.mark.parametrize("build", ["validation", "validation-fp32", "consec", "unfused", "generic"])
+@pytest.mark.parametrize("case", LAYER_CASES)
+def test_every_layer_backward_matches_float64_on_the_state_it_found(case, build):
+    """The snapshot hook of the validation build, armed for every layer of every block (_run_layers_backward); the fused 1x1 backward's grid
+    is asserted per layer, so that a changed cap cannot quietly take `trips` back to one tile per workgroup."""
+    child, mode = ("validation", F32) if build == "validation-fp32" else (build, BF16)
+    rep = _child_reports(child)[case][3][mode]
+    cfg, _, _, n_img = _case(case)
+    worst = {}
+    for name, kernel, w, bad, numel, where, kinks, amax in rep["figures"]:
+        if not w <= worst.get(kernel, (-1.0, ""))[0]:
+            worst[kernel] = (w, name)
+    print(case, build, "worst |error| / gate per kernel:", {k: (round(v, 4), nm) for k, (v, nm) in sorted(worst.items())},
+          "elements at a PReLU kink (left out):", sum(f[6] for f in rep["figures"]),
+          "layers (block, layer, cin, dgrad kernel, fused 1x1, eff rows, fused grid, slices, M):", rep["reports"])
+    bad = [f for f in rep["figures"] if f[3] or not f[2] <= 1.0]
+    assert not bad, [f[:5] for f in bad[:12]]
+    layers = sum(cfg.densenet_structure)
+    geo, g = _geometry(cfg), cfg.densenet_growth_rate
+    assert len(rep["reports"]) == layers and [r[:3] for r in rep["reports"]] == \
+        [(b, l, geo[b][2] + l * g) for b, L in enumerate(cfg.densenet_structure) for l in range(L)], rep["reports"]
+    # every layer was compared: DU, norm2's link (5), db1, dW1, G[:, :cin], the rest unchanged, norm1's link (5) (+ the eff rows where stored);
+    # per first writer G, three parameter gradients, P, Q (+ dW, db of a transition)
+    n_first = 6 * len(cfg.densenet_structure) + 2 * (len(cfg.densenet_structure) - 1)
+    n_ey = len([f for f in rep["figures"] if f[1] == "eff rows"])
+    assert len(rep["figures"]) == 15 * layers + n_ey + n_first, (len(rep["figures"]), layers, n_ey, n_first)
+    for kind, n in (("dgrad3x3", 1), ("norm2 link", 5), ("norm1 link", 5), ("untouched", 1)):
+        assert len([f for f in rep["figures"] if f[1] == kind]) == n * layers, kind
+    labels = rep["labels"]
+    fused_build = build in ("validation", "consec")
+    aligned = cfg.initial_pixel_dim % 8 == 0
+    TWO_WG, PIPELINED, CONSEC = 1, 2, 3                                # Conv3x3Dgrad (tcvn_ops.h)
+    for b, l, cin, kern, fused, eyv, nblk, slices, M in rep["reports"]:
+        if build in ("validation", "unfused"):
+            assert kern == (PIPELINED if aligned else TWO_WG) and not eyv, rep["reports"]      # the product choice at these sizes
+        elif build == "consec":
+            assert kern == (CONSEC if aligned else TWO_WG) and eyv == int(aligned), rep["reports"]
+        else:
+            assert kern == 0 and not eyv, rep["reports"]
+        assert fused == int(fused_build), rep["reports"]
+        # ---- the fused kernel's grid: bwd1x1_fused_nblk re-stated (max(64, 512 // slices) workgroups of 64 pixels, at most one per tile)
+        assert M == n_img * geo[b][0] * geo[b][1] and slices == -(-cin // 128), rep["reports"]
+        assert nblk == (min(-(-M // 64), max(64, 512 // slices)) if fused_build else 0) and (not fused_build or (nblk, slices) == fused_grid(M, cin)[:2]), rep["reports"]
+        if case != "trips" and fused_build:
+            assert nblk == -(-M // 64), rep["reports"]                  # one tile per workgroup everywhere else
+    if case == "mod4":
+        assert [r[2] for r in rep["reports"]] == [228, 260, 292, 324, 356, 388] and all(r[2] % 8 == 4 for r in rep["reports"])
+        assert [r[7] for r in rep["reports"]] == [2, 3, 3, 3, 3, 4], rep["reports"]
+        assert not aligned and all(r[3] == (TWO_WG if mode == BF16 and build != "generic" else 0) for r in rep["reports"]), rep["reports"]
+    if case == "trips":
+        assert [r[7] for r in rep["reports"]] == [2, 3, 3, 3, 3, 4] and all(r[8] == 11475 for r in rep["reports"]), rep["reports"]
+        assert 11475 % 64 == 19 and -(-11475 // 64) == 180              # the partial last tile is tile 179: it lands in a second trip
+        if fused_build:
+            assert [r[6] for r in rep["reports"]] == [180, 170, 170, 170, 170, 128], rep["reports"]
+            assert all(-(-r[8] // 64) > r[6] for r in rep["reports"] if r[7] >= 3), rep["reports"]      # a second tile per workgroup
     if build == "unfused":
         assert _count(labels, "k_gemm_tn_bf16<conv1>") == layers and _count(labels, "k_gemm_nt_bf16<dgrad1x1>") == layers, labels
         assert not _count(labels, "k_bwd1x1_fused_bf16"), labels
