@@ -17,6 +17,7 @@
 // gradient, never in an atomic: weight AND bias gradients of the dense layers are the same from run to run.
 #include "tcvn_ops.h"
 #include "prof.h"
+#include <type_traits>
 
 namespace tcvn {
 
@@ -34,12 +35,19 @@ constexpr int SMEM_BYTES = OFF_TAB + 5 * 128 * 4;        // 69 120 B: two workgr
 
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 
-__device__ __forceinline__ bf16x8_t tr_frag(const char* smem_base, int off_lo, int off_hi) {
-    typedef __attribute__((address_space(3))) s16x4* lds_p;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(smem_base + off_lo));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(smem_base + off_hi));
+// Two ds_read_b64_tr_b16 = one transposed MFMA fragment, as inline assembly: before __builtin_amdgcn_ds_read_tr16_b64 (an LDS read that
+// carries no alias information; gemm_tn.hip uses it) the compiler waits vmcnt(0) for every LDS-DMA in flight -- here the next tile's Y.  The compiler does not count these reads: tr_wait() is
+// their lgkmcnt(0), tied to the fragments so that no MFMA moves in front of it.  (LDS returns in issue order, so reads the compiler does
+// count are only ever waited for longer.)
+__device__ __forceinline__ bf16x8_t tr_frag_asm(unsigned a_lo, unsigned a_hi, int off) {
+    s16x4 lo, hi;
+    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(lo) : "v"(a_lo), "i"(off) : "memory");
+    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(hi) : "v"(a_hi), "i"(off) : "memory");
     struct { s16x4 a, b; } pr = {lo, hi};
     return __builtin_bit_cast(bf16x8_t, pr);
+}
+__device__ __forceinline__ void tr_wait(bf16x8_t& a0, bf16x8_t& a1, bf16x8_t& b0, bf16x8_t& b1) {
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a0), "+v"(a1), "+v"(b0), "+v"(b1) :: "memory");
 }
 
 // [64 rows][128 columns] of a row-major bf16 matrix -> LDS, 16-B chunks XOR-swizzled by the row (slot s of row r holds source chunk s ^ swz16(r):
@@ -59,6 +67,39 @@ __device__ __forceinline__ void dma64(char* smem_base, int buf_off, const bf16* 
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Schedule of a trip (one 64-pixel tile t of a workgroup; t+ = its next tile).  The requests of t+ are split by when their target is free:
+//   [top]  wait, barrier | EY phase (reads DU, Y -> EY) | barrier | data-gradient MFMAs (read EY), C tile over the Y region |
+//   [epi]  wait, barrier | epilogue (reads C, x, G registers; S = 4 G stores; activated input over x) | barrier |
+//          R_Y(t+) R_G(t+) | weight-gradient MFMAs (read EY, activated input) | barrier | R_E(t+) R_X(t+) | next trip
+// so Y and the G rows of t+ travel under the weight-gradient phase and x of t+ under the next trip's EY and data-gradient phases; only
+// DU's latency is exposed.  R_Y, R_E, R_X are ROWS / 16 = 4 LDS-DMAs per wave each, R_G four 16-B register loads; every wave issues all of
+// them (a wave holds all sixteen chunk columns and chunk 0 of a slice lies inside cin, so no lane condition empties a wave; the G loads
+// are unconditional).  The prologue issues R_Y R_G R_E R_X of the first tile in the same order.
+//
+// Vector-memory queue of a wave (it retires in issue order, stores included; the scheme of k_fwd1x1_wide_bf16, fwd1x1_fused.hip):
+//   at [top] of trip t, before the wait:   [S(t-1)]  R_Y(t) R_G(t)  R_E(t) R_X(t)           S(t-1): the previous trip's G stores (four, or up
+//                                                                                            to 28 element stores at cin % 8 != 0; none in the first trip)
+//   [top] leaves R_X(t) in flight:         vmcnt(4) -- S, Y, G and DU are older and have retired with it; the same count in a workgroup's
+//                                          first trip (no S) and in its last (R_X(t) is still the youngest: nothing is requested before [top])
+//   at [epi], before the wait:             R_X(t)                                            nothing younger exists: R_Y(t+) is issued behind the epilogue
+//   [epi] waits for x:                     vmcnt(0) -- in every trip; it is also the wait for the G registers, which retired at [top]
+// The counts do not depend on the trip: a request is never issued before the wait that must not count it.  A partial tile's requests
+// (dma64: rows beyond M from the zero line) are four DMAs per wave and operand as well.
+// Between a request and its wait stand bare barriers only (s_waitcnt lgkmcnt(0) + s_barrier; a __syncthreads() drains the queue), and
+// the barrier that publishes DMA'd data follows the wave's own counted wait for them.  Region reuse: R_Y(t+) overwrites the C tile
+// behind the barrier that ends the epilogue (its only reader); R_E(t+) / R_X(t+) overwrite EY and the activated input behind the barrier
+// that ends the weight-gradient phase, whose fragment reads a wave has completed (lgkmcnt(0)) before it arrives there.
+// Compiler waits: LDS reads through f32x4 / u16x8 / bf16x8_t get none; float4 (a struct) and the ds_read_tr builtin get vmcnt(0) for
+// every LDS-DMA in flight (hence tr_frag_asm); the prologue's loads are retired with one __builtin_amdgcn_s_waitcnt before the first
+// request.  In the generated full-tile loop the only vmcnt waits are [top], [epi] and the compiler's own vmcnt(0) for the G registers
+// inside the epilogue (behind [epi]: nothing is in flight there); check with
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -S --cuda-device-only -Rpass-analysis=kernel-resource-usage bwd1x1_fused.hip
+// FULLC (cin % 8 == 0, chosen on the host): full tiles run a path without row guards, `live` selects and partial-chunk code, and the
+// partial tile -- the launch's last, so its workgroup's last trip -- runs the guarded path behind the loop.  !FULLC: the guarded path
+// for every tile.  <true>: 232 VGPRs, <false>: 242, no scratch, 2 waves per SIMD.
+// ---------------------------------------------------------------------------------------------------------------------------------
+template <bool FULLC>
 __global__ __launch_bounds__(256, 2) void k_bwd1x1_fused_bf16(const Bwd1x1Args g) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* Cs = reinterpret_cast<float*>(smem + OFF_C);
@@ -122,7 +163,9 @@ __global__ __launch_bounds__(256, 2) void k_bwd1x1_fused_bf16(const Bwd1x1Args g
     const bool xchunk_ok = n0 + (d_chunk << 3) < N;
     const unsigned voffA = (unsigned)(d_r0 * 256 + (d_chunk << 4));
     const unsigned voffX = (unsigned)(d_r0 * (int)g.ldx * 2 + (d_chunk << 4));
-    const unsigned voffG = (unsigned)(((tid >> 4) * (int)g.ldg + n0 + col_chunk * 8) * 2);
+    // (a lane whose chunk lies beyond cin reads the slice's chunk 0 instead and never uses it: the G loads are unconditional, a conditional
+    // load is a copy of the old registers behind a wait for everything in flight)
+    const unsigned voffG = (unsigned)(((tid >> 4) * (int)g.ldg + n0 + (col_ok ? col_chunk : 0) * 8) * 2);
     if (!xchunk_ok) {
 #pragma unroll
         for (int i = 0; i < ROWS / 16; ++i) *reinterpret_cast<u16x8*>(smem + OFF_X + ((tid >> 6) + 4 * i) * 1024 + (tid & 63) * 16) = z8;
@@ -130,60 +173,76 @@ __global__ __launch_bounds__(256, 2) void k_bwd1x1_fused_bf16(const Bwd1x1Args g
     u16x8 pgv[ROWS / 16];
 #pragma unroll
     for (int i = 0; i < ROWS / 16; ++i) pgv[i] = z8;
-    auto request = [&](long t) {          // the three operand tiles of row tile t, and this thread's G rows of it (for the epilogue)
+    // Staged requests (schedule and wait counts: the head of this kernel).  Every wave issues exactly four DMAs per operand: each wave holds
+    // all sixteen chunk columns, chunk 0 of a slice is always inside cin, so the lane conditions below never empty a wave.
+    auto request_yg = [&](long t) {       // Y of row tile t into the region the C tile has left, and this thread's G rows of it (for the epilogue)
         const long m0 = t * ROWS;
-        const int wave = tid >> 6, lane = tid & 63;
+        const int wave = tid >> 6;
         if (m0 + ROWS <= g.M) {
-            const char* bE = reinterpret_cast<const char*>(DU) + m0 * 256;
             const char* bY = reinterpret_cast<const char*>(Yp) + m0 * 256;
-            const char* bX = reinterpret_cast<const char*>(Xp) + (m0 * g.ldx + n0) * 2;
             const char* bG = reinterpret_cast<const char*>(Gp) + m0 * g.ldg * 2;
-#pragma unroll
-            for (int i = 0; i < ROWS / 16; ++i)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(bE + i * 4096 + voffA),
-                                                 (__attribute__((address_space(3))) void*)(smem + OFF_E + (wave + 4 * i) * 1024), 16, 0, 0);
 #pragma unroll
             for (int i = 0; i < ROWS / 16; ++i)
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(bY + i * 4096 + voffA),
                                                  (__attribute__((address_space(3))) void*)(smem + OFF_Y + (wave + 4 * i) * 1024), 16, 0, 0);
+#pragma unroll
+            for (int i = 0; i < ROWS / 16; ++i) pgv[i] = *reinterpret_cast<const u16x8*>(bG + (long)i * 32 * g.ldg + voffG);
+        } else {                           // the launch's last, partial tile: rows beyond M come from the zero line.  Per-lane 64-bit pointers
+            int t_p = tid;                 // with range selects: from an opaque copy of the thread index, or they become loop invariants
+            asm volatile("" : "+v"(t_p));
+            dma64(smem, OFF_Y, Yp, 128, 128, 0, m0, g.M, zeros, t_p >> 6, t_p & 63);
+#pragma unroll
+            for (int i = 0; i < ROWS / 16; ++i) {      // rows beyond M read row M - 1 (never used)
+                const long m = m0 + (t_p >> 4) + 16 * i;
+                pgv[i] = *reinterpret_cast<const u16x8*>(Gp + (m < g.M ? m : g.M - 1) * g.ldg + n0 + (col_ok ? t_p & 15 : 0) * 8);
+            }
+        }
+    };
+    auto request_ex = [&](long t) {       // DU and x of row tile t: DU first, so that a wait can leave the four x DMAs in flight
+        const long m0 = t * ROWS;
+        const int wave = tid >> 6;
+        if (m0 + ROWS <= g.M) {
+            const char* bE = reinterpret_cast<const char*>(DU) + m0 * 256;
+            const char* bX = reinterpret_cast<const char*>(Xp) + (m0 * g.ldx + n0) * 2;
+#pragma unroll
+            for (int i = 0; i < ROWS / 16; ++i)
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(bE + i * 4096 + voffA),
+                                                 (__attribute__((address_space(3))) void*)(smem + OFF_E + (wave + 4 * i) * 1024), 16, 0, 0);
             if (xchunk_ok) {
 #pragma unroll
                 for (int i = 0; i < ROWS / 16; ++i)
                     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(bX + (long)i * 32 * g.ldx + voffX),
                                                      (__attribute__((address_space(3))) void*)(smem + OFF_X + (wave + 4 * i) * 1024), 16, 0, 0);
             }
-            if (col_ok) {
-#pragma unroll
-                for (int i = 0; i < ROWS / 16; ++i) pgv[i] = *reinterpret_cast<const u16x8*>(bG + (long)i * 32 * g.ldg + voffG);
-            }
-        } else {                           // the launch's last, partial tile: rows beyond M come from the zero line
-            dma64(smem, OFF_E, DU, 128, 128, 0, m0, g.M, zeros, wave, lane);
-            dma64(smem, OFF_Y, Yp, 128, 128, 0, m0, g.M, zeros, wave, lane);
-            if (xchunk_ok) dma64(smem, OFF_X, Xp, g.ldx, N, n0, m0, g.M, zeros, wave, lane);
-            if (col_ok) {
-#pragma unroll
-                for (int i = 0; i < ROWS / 16; ++i) {
-                    const long m = m0 + (tid >> 4) + 16 * i;
-                    if (m < g.M) pgv[i] = *reinterpret_cast<const u16x8*>(Gp + m * g.ldg + n0 + col_chunk * 8);
-                }
-            }
+        } else {
+            int t_p = tid;
+            asm volatile("" : "+v"(t_p));
+            dma64(smem, OFF_E, DU, 128, 128, 0, m0, g.M, zeros, t_p >> 6, t_p & 63);
+            if (xchunk_ok) dma64(smem, OFF_X, Xp, g.ldx, N, n0, m0, g.M, zeros, t_p >> 6, t_p & 63);
         }
     };
 
-    long mt = blockIdx.x;
-    if (mt < mtiles) request(mt);
-    for (; mt < mtiles; mt += gridDim.x) {
+    // every load of the prologue (weight fragments, tables) has returned before the first request: told to the compiler with its own wait
+    // instruction (vmcnt(0)), or it waits for them inside the loop with a vmcnt(0) that drains the requests in flight
+    __builtin_amdgcn_s_waitcnt(0x0F70);
+    if ((long)blockIdx.x < mtiles) { request_yg(blockIdx.x); request_ex(blockIdx.x); }
+    // One trip = one row tile.  FT: a full tile (m0 + ROWS <= M, tile-uniform): no row guard, no `live` select; with FULLC (cin % 8 == 0,
+    // chosen on the host) no partial-chunk code either.  The partial tile (at most one per launch, a workgroup's last) and the cin % 8 != 0
+    // widths keep the guarded code, element for element what it was.
+    auto trip = [&](auto full_tile, long mt) {
+        constexpr bool FT = decltype(full_tile)::value;
         const long m0 = mt * ROWS;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
+        const bool more = mt + gridDim.x < mtiles;
+        asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");      // [top] DU, Y (and G) of this tile are here, x travels on
         // Index arithmetic of the phases below starts from an opaque copy of the thread index: left to loop-invariant code motion the
         // compiler keeps ~60 LDS addresses of all four phases alive across the whole loop, next to the accumulators, and spills.
         int t_o = tid;
         asm volatile("" : "+v"(t_o));
         const int c8 = t_o & 15, c_r0 = t_o >> 4;                          // element-wise roles: rows c_r0 + 16*i, channel chunk c8
         const int e_off = c_r0 * 256 + ((c8 ^ swz16(c_r0)) << 4);          // (c_r0 + 16*i) & 15 == c_r0 & 15: the row group adds i*4096
+        // f32x4, not float4: before an LDS read of the struct type the compiler waits for every LDS-DMA in flight (vmcnt(0)), see fwd1x1_fused.hip
         auto tab8 = [&](int which, float (&v)[8]) {
-            const float4 a = *reinterpret_cast<const float4*>(tab + which * 128 + c8 * 8), b = *reinterpret_cast<const float4*>(tab + which * 128 + c8 * 8 + 4);
+            const f32x4 a = *reinterpret_cast<const f32x4*>(tab + which * 128 + c8 * 8), b = *reinterpret_cast<const f32x4*>(tab + which * 128 + c8 * 8 + 4);
             v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
         };
         // ---- EY = bf16(DU + PY*Y + QY) in place of DU (rows beyond M: zero), column sums for the bias gradient
@@ -195,18 +254,24 @@ __global__ __launch_bounds__(256, 2) void k_bwd1x1_fused_bf16(const Bwd1x1Args g
                 const int off = e_off + i * 4096;
                 const u16x8 dv = *reinterpret_cast<const u16x8*>(smem + OFF_E + off);
                 const u16x8 yv = *reinterpret_cast<const u16x8*>(smem + OFF_Y + off);
-                const bool live = m0 + c_r0 + 16 * i < g.M;
+                const bool live = FT || m0 + c_r0 + 16 * i < g.M;
                 u16x8 o;
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     const float t = eff3(bf2f(dv[j]), pP[j], bf2f(yv[j]), pQ[j]);
-                    o[j] = live ? f2bf(t) : (bf16)0;
+                    if constexpr (FT) o[j] = f2bf(t);
+                    else o[j] = live ? f2bf(t) : (bf16)0;
                     cs[j] += bf2f(o[j]);
                 }
                 *reinterpret_cast<u16x8*>(smem + OFF_E + off) = o;
+                if constexpr (FT) {                                         // row group by row group: without the row guards' branches the four are one
+#pragma unroll                                                              // basic block, which the SLP vectoriser turns into 16-register tuples that
+                    for (int j = 0; j < 8; ++j) asm volatile("" : "+v"(cs[j]));      // push the weight fragments into scratch
+                    __builtin_amdgcn_sched_barrier(0);
+                }
             }
         }
-        __syncthreads();
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");    // bare: a __syncthreads() would drain x
         // ---- data gradient: C[64][128-column slice] = EY x W1 (K = 128)
         {
             const int lane = t_o & 63, wave = t_o >> 6;
@@ -241,7 +306,7 @@ __global__ __launch_bounds__(256, 2) void k_bwd1x1_fused_bf16(const Bwd1x1Args g
 #pragma unroll
                 for (int e = 0; e < 16; ++e) cw[(i * 32 + (e & 3) + 8 * (e >> 2)) * CLD] = acc[i][e];
         }
-        __syncthreads();
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");      // [epi] x has landed (nothing younger is in flight); the C tile is written
         // ---- epilogue: PReLU1 / norm1 backward against x (LDS), G += sc*dU (16-B lanes), activated input left in place of x
         if (col_ok) {
             float csc[8], csh[8], csl[8];
@@ -250,15 +315,17 @@ __global__ __launch_bounds__(256, 2) void k_bwd1x1_fused_bf16(const Bwd1x1Args g
             char* gbase = reinterpret_cast<char*>(Gp) + m0 * g.ldg * 2;
 #pragma unroll
             for (int i = 0; i < ROWS / 16; ++i) {
-                if (m0 + c_r0 + 16 * i < g.M) {
+                if (FT || m0 + c_r0 + 16 * i < g.M) {
                     const int xoff = OFF_X + e_off + i * 4096;
                     u16x8 xv = *reinterpret_cast<const u16x8*>(smem + xoff);
-                    if (col_rem < 8) {                                      // partial chunk (never in the tutorial widths): foreign x -> 0, so no
-#pragma unroll                                                              // non-finite foreign value can reach the sums or the activated operand
-                        for (int j = 0; j < 8; ++j) xv[j] = j < col_rem ? xv[j] : (bf16)0;
+                    if constexpr (!FULLC) {
+                        if (col_rem < 8) {                                  // partial chunk (cin % 8 != 0): foreign x -> 0, so no non-finite foreign
+#pragma unroll                                                              // value can reach the sums or the activated operand
+                            for (int j = 0; j < 8; ++j) xv[j] = j < col_rem ? xv[j] : (bf16)0;
+                        }
                     }
-                    const float4 ca = *reinterpret_cast<const float4*>(crow + i * 16 * CLD);
-                    const float4 cc = *reinterpret_cast<const float4*>(crow + i * 16 * CLD + 4);
+                    const f32x4 ca = *reinterpret_cast<const f32x4*>(crow + i * 16 * CLD);
+                    const f32x4 cc = *reinterpret_cast<const f32x4*>(crow + i * 16 * CLD + 4);
                     const float cv[8] = {ca.x, ca.y, ca.z, ca.w, cc.x, cc.y, cc.z, cc.w};
                     const u16x8 gv = pgv[i];
                     u16x8 o, xa;
@@ -272,7 +339,7 @@ __global__ __launch_bounds__(256, 2) void k_bwd1x1_fused_bf16(const Bwd1x1Args g
                         o[j] = f2bf(fmaf(csc[j], du, bf2f(gv[j])));
                         xa[j] = f2bf(prelu(u, csl[j]));
                     }
-                    if (col_rem >= 8) *reinterpret_cast<u16x8*>(gbase + (long)i * 32 * g.ldg + voffG) = o;
+                    if (FULLC || col_rem >= 8) *reinterpret_cast<u16x8*>(gbase + (long)i * 32 * g.ldg + voffG) = o;
                     else {                                                  // partial chunk: the layer's own channels only (the next ones belong to its 3x3
                         bf16* gp = reinterpret_cast<bf16*>(gbase + (long)i * 32 * g.ldg + voffG);     // output gradient, which other kernels may be reading)
 #pragma unroll
@@ -281,9 +348,15 @@ __global__ __launch_bounds__(256, 2) void k_bwd1x1_fused_bf16(const Bwd1x1Args g
                     }
                     *reinterpret_cast<u16x8*>(smem + xoff) = xa;
                 }
+                if constexpr (FT) {                                         // (as in the EY phase)
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) asm volatile("" : "+v"(st1[j]), "+v"(st2[j]), "+v"(st3[j]));
+                    __builtin_amdgcn_sched_barrier(0);
+                }
             }
         }
-        __syncthreads();
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");    // the C tile (= the Y region) and the G registers are free
+        if (more) request_yg(mt + gridDim.x);                              // ... Y and G of the next tile travel under the weight-gradient MFMAs
         // ---- weight gradient: accW += EY^T x prelu(bn1(x)) over the tile's 64 pixels
         if (wj_live) {
             const int lane = t_o & 63, wave = t_o >> 6;
@@ -292,7 +365,8 @@ __global__ __launch_bounds__(256, 2) void k_bwd1x1_fused_bf16(const Bwd1x1Args g
             const int khalf = gq >> 1, chalf = gq & 1;
             const int sub = (tp & 1) * 8;
             const int rl = 8 * khalf + tq;                                  // row inside a 16-row k-step (rows rl and rl + 4); k-step ks adds ks*4096
-            int a_lo[2], a_hi[2], b_lo[2], b_hi[2];
+            const unsigned lds0 = (unsigned)reinterpret_cast<size_t>((__attribute__((address_space(3))) char*)smem);
+            unsigned a_lo[2], a_hi[2], b_lo[2], b_hi[2];
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
                 const int ac = wi * 8 + t * 4 + 2 * chalf + (tp >> 1), bc = wj * 8 + t * 4 + 2 * chalf + (tp >> 1);
@@ -304,9 +378,10 @@ __global__ __launch_bounds__(256, 2) void k_bwd1x1_fused_bf16(const Bwd1x1Args g
                 bf16x8_t a[2], b[2];
 #pragma unroll
                 for (int t = 0; t < 2; ++t) {
-                    a[t] = tr_frag(smem, a_lo[t] + ks * 4096, a_hi[t] + ks * 4096);
-                    b[t] = tr_frag(smem, b_lo[t] + ks * 4096, b_hi[t] + ks * 4096);
+                    a[t] = tr_frag_asm(lds0 + a_lo[t], lds0 + a_hi[t], ks * 4096);
+                    b[t] = tr_frag_asm(lds0 + b_lo[t], lds0 + b_hi[t], ks * 4096);
                 }
+                tr_wait(a[0], a[1], b[0], b[1]);
 #pragma unroll
                 for (int ta = 0; ta < 2; ++ta)
 #pragma unroll
@@ -314,8 +389,16 @@ __global__ __launch_bounds__(256, 2) void k_bwd1x1_fused_bf16(const Bwd1x1Args g
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-        __syncthreads();                                                   // every LDS tile is free again
-        if (mt + gridDim.x < mtiles) request(mt + gridDim.x);
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");    // EY and the activated input are read: their regions are free
+        if (more) request_ex(mt + gridDim.x);
+    };
+    // the partial tile is the launch's last one, so it is the last trip of the workgroup that owns it: the loop holds the full-tile path alone
+    long mt = blockIdx.x;
+    if constexpr (FULLC) {
+        for (; mt * ROWS + ROWS <= g.M; mt += gridDim.x) trip(std::true_type{}, mt);
+        if (mt < mtiles) trip(std::false_type{}, mt);
+    } else {                               // cin % 8 != 0: the guarded body for every tile (its partial-chunk branches need the registers)
+        for (; mt < mtiles; mt += gridDim.x) trip(std::false_type{}, mt);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
@@ -387,12 +470,15 @@ int bwd1x1_fused_launch(const Bwd1x1Args& a, hipStream_t st) {
     if (a.nblk != bwd1x1_fused_nblk(a)) { fprintf(stderr, "tcvn: bwd1x1_fused nblk mismatch\n"); return -3; }
     static bool attr = false;
     if (!attr) {
-        TCVN_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bwd1x1_fused_bf16), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        TCVN_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bwd1x1_fused_bf16<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        TCVN_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bwd1x1_fused_bf16<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr = true;
     }
     // SURVEY 8(d) strict bytes: operands DU, Y, x read once, the G contribution written once (its read is traffic, not algorithm)
     ProfScope ps("k_bwd1x1_fused_bf16", 4.0 * a.M * 128.0 * a.cin, (double)a.M * (512.0 + 4.0 * a.cin), st);
-    hipLaunchKernelGGL(k_bwd1x1_fused_bf16, dim3(a.nblk, cdiv(a.cin, 128)), dim3(256), SMEM_BYTES, st, a);
+    // cin % 8 == 0 (every width of production blocks 1-3): the instantiation without partial-chunk code
+    if (a.cin % 8 == 0) hipLaunchKernelGGL(k_bwd1x1_fused_bf16<true>, dim3(a.nblk, cdiv(a.cin, 128)), dim3(256), SMEM_BYTES, st, a);
+    else hipLaunchKernelGGL(k_bwd1x1_fused_bf16<false>, dim3(a.nblk, cdiv(a.cin, 128)), dim3(256), SMEM_BYTES, st, a);
     TCVN_LAUNCH_CHECK();
     return 0;
 }

@@ -186,7 +186,7 @@ __global__ __launch_bounds__(256, 3) void k_fwd1x1_fused_bf16(const Fwd1x1Args g
                     cw[(i * 32 + (e & 3) + 8 * (e >> 2)) * CLD] = f2bf(v);
                 }
         }
-        __syncthreads();
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");     // bare: a __syncthreads() would drain the request just issued
         // ---- epilogue: statistics of the rounded values, 16-B stores (a tile of Y is 16 KB contiguous)
         {
             const bf16* crow = Cs + c_r0 * CLD + c8 * 8;
