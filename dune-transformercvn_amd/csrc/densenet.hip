@@ -439,13 +439,16 @@ LfLink DenseNetPlan::lf_link(const Step& s, const BnSlots& bn, const long long* 
 // in front of the first 3x3 convolution, and the eval layout gives the stem's channels of D[0], the packed weights (wk) and the BatchNorm
 // tables (tabs) regions that no later launch of an eval pass writes (link() returns at once, lf_link needs lf_on).
 int DenseNetPlan::forward(int n, const int32_t* coords, const float* values, long nnz, int log_pixels, float noise_std,
-                          float* out, long out_ld, char* ws, long ws_bytes, int train, uint64_t seed, hipStream_t st, bool draw, bool resume) {
+                          float* out, long out_ld, char* ws, long ws_bytes, int train, uint64_t seed, hipStream_t st, bool draw, bool resume,
+                          bool frozen) {
     if (!bound) return -11;
+    if (frozen && (train || draw || resume)) return -1;
+    if (frozen && log_pixels == 3) { fprintf(stderr, "tcvn: densenet forward_frozen: one-hot pixels are class indices and have no gradient\n"); return -22; }
     if (n <= 0) return 0;
     Layout L;
-    layout(n, train != 0, L);
+    layout(n, train != 0 || frozen, L);
     if (ws_bytes < L.total) { fprintf(stderr, "tcvn: densenet workspace too small (%ld < %ld)\n", ws_bytes, L.total); return -12; }
-    if (resume && !(last_ws == ws && last_eval && last_n == n && last_coords == coords && last_nnz == nnz && last_values == values &&
+    if (resume && !(last_ws == ws && last_eval && !last_frozen && last_n == n && last_coords == coords && last_nnz == nnz && last_values == values &&
                     last_value_mode == log_pixels)) {
         fprintf(stderr, "tcvn: densenet forward_mc cannot resume: the last call on this workspace was not an eval-mode forward of these inputs\n");
         return -18;
@@ -453,6 +456,7 @@ int DenseNetPlan::forward(int n, const int32_t* coords, const float* values, lon
     int rc;
     if (!resume) {
         last_ws = nullptr;       // until this call has come through
+        last_frozen = false;
         if ((rc = upload_descs(ws, L, st))) return rc;
         // weights -> kernel layout (fp32 -> T); eval: all BN tables from the running statistics in one launch
         if ((rc = pack_weights(reinterpret_cast<const PackDesc*>(d_desc), n_pack, cfg.mode, st))) return rc;
@@ -464,7 +468,7 @@ int DenseNetPlan::forward(int n, const int32_t* coords, const float* values, lon
     static const bool no_lf = TCVN_KNOB_SET("TCVN_NO_LF");
     const bool lf_on = train && !no_lf && cfg.mode == MODE_BF16 && L.isum_bytes > 0;
     TCVN_CHECK(hipMemsetAsync(ws + L.zeros, 0, 1024 + (lf_on ? L.isum_bytes : 0), st));
-    const Step s{ws, L, st, n, train != 0, seed, reinterpret_cast<double*>(ws + L.part), lf_on, false, 0, false, draw && !train};
+    const Step s{ws, L, st, n, train != 0, seed, reinterpret_cast<double*>(ws + L.part), lf_on, false, 0, false, draw && !train, frozen};
     FreshStats fr{};                  // statistics of the newest channels of the block being built (read by train-mode links only)
     if (!resume && (rc = fwd_stem(s, coords, values, nnz, log_pixels, noise_std, fr))) return rc;
     for (int bi = 0; bi < (int)blocks.size(); ++bi) {
@@ -473,7 +477,7 @@ int DenseNetPlan::forward(int n, const int32_t* coords, const float* values, lon
         if ((rc = fwd_transition(s, bi, fr))) return rc;
     }
     if ((rc = fwd_output(s, out, out_ld))) return rc;
-    last_seed = seed; last_n = n; last_coords = coords; last_nnz = nnz; last_ws = ws; last_eval = !train;
+    last_seed = seed; last_n = n; last_coords = coords; last_nnz = nnz; last_ws = ws; last_eval = !train; last_frozen = frozen;
     return 0;
 }
 
@@ -503,7 +507,10 @@ int DenseNetPlan::fwd_stem(const Step& s, const int32_t* coords, const float* va
     // below its streaming rate), the backward gained 10 %, the step did not move (19.65-19.76 against 19.74-19.86 ms).
     static const bool no_stem_skip = TCVN_KNOB_SET("TCVN_NO_STEM_SKIP") || TCVN_KNOB_SET("TCVN_POOL0_BWD_FLAT");   // (the flat backward kernel reads every row)
     stem_path = StemPath{};
-    stem_path.sparse = !dense_stem_knob && (!s.train || sparse_train_knob) && L.sidx >= 0 &&
+    // A frozen pass takes the dense stem: its backward needs the conv0 map behind the pooling backward (DU0), and the duplicate record.
+    // The activity bitmap stays off with it (act_skip asks for train), so the pooling backward stores EVERY row of DU0 -- a hit gathers from
+    // the <= 16 conv0 outputs whose window holds it, and all of them are stored rows whatever the other hits are.
+    stem_path.sparse = !s.frozen && !dense_stem_knob && (!s.train || sparse_train_knob) && L.sidx >= 0 &&
                        stem_sparse_ok(mode, cfg.in_ch, cfg.init_ch, cfg.H, cfg.W, log_pixels, nnz, n, b0.ld);
     last_values = values; last_value_mode = log_pixels; last_noise = noise;
     fr = FreshStats{0, b0.C0, 0, cfg.init_ch, false};
@@ -552,7 +559,7 @@ LayerPath DenseNetPlan::layer_path(const Step& s, int bi, int l, const ConvFwdAr
     // Eval mode (running statistics: no batch reduction between the 1x1 output and its BatchNorm): the 1x1 GEMM's epilogue
     // applies norm2 + PReLU and writes the activated map the 3x3 tile kernel stages -- the raw bottleneck output Y and the
     // k_act_bf16 pass over it (512 B per pixel and layer, one launch) do not exist.  Train mode needs Y for the statistics.
-    p.fuse_ya = !s.train && fast1 && k3 != CONV3X3_FWD_NONE;
+    p.fuse_ya = !s.train && !s.frozen && fast1 && k3 != CONV3X3_FWD_NONE;      // (a frozen pass keeps Y: its backward reads it)
     // Round 4: norm2 + PReLU are applied INSIDE the 3x3 kernel (and inside the layer's weight-gradient kernel): the raw
     // bottleneck map is staged by LDS-DMA and the wave that fetched a row activates it in LDS once -- the activated copy YA
     // (256 B written + 256 B read per pixel and layer) and the k_act_bf16 launch over Y do not exist.  Bit-identical images.
@@ -560,20 +567,21 @@ LayerPath DenseNetPlan::layer_path(const Step& s, int bi, int l, const ConvFwdAr
     // Train mode (round 4): the 1x1 runs on the RAW concat buffer, norm1 + PReLU1 applied to the landed LDS tiles (fwd1x1_fused.hip);
     // the fused 1x1 backward kernel rebuilds that activation from x, so the activated copy XA is neither written nor read.
     static const bool no_fuse1 = TCVN_KNOB_SET("TCVN_NO_FWD1_FUSE") || TCVN_KNOB_SET("TCVN_NO_BWD1_FUSE");
-    if ((s.train || p.fuse_ya) && fast1 && !no_fuse1 && cfg.bn_size * cfg.growth == 128 && bf16) {
+    const bool keep = s.train || s.frozen;      // a backward follows: the layer keeps what it needs
+    if ((keep || p.fuse_ya) && fast1 && !no_fuse1 && cfg.bn_size * cfg.growth == 128 && bf16) {
         const WkEntry& e = wk_find(ls.w1, 0, 1);
         const Tab t1 = tab(s.ws, L, ls.n1);
         f1 = Fwd1x1Args{};
         f1.Xin = s.ws + L.D[bi]; f1.ldx = bg.ld; f1.cin = ls.cin; f1.sc = t1.sc; f1.sh = t1.sh; f1.sl = data[ls.a1]; f1.M = M;
         f1.Wfrag = s.ws + L.wk + e.off; f1.Kp = e.Kp; f1.bias = data[ls.b1]; f1.Out = s.ws + L.Y[bi][l]; f1.zeros = s.ws + L.zeros;
         f1.part = s.train ? s.part : nullptr; f1.nblk = fwd1x1_fused_nblk(f1);
-        if (!s.train) {                // eval: norm2 + PReLU2 in the epilogue, the activated map is the only output (as k_gemm_nt_bf16<.., XF = 2>)
+        if (!keep) {                   // eval: norm2 + PReLU2 in the epilogue, the activated map is the only output (as k_gemm_nt_bf16<.., XF = 2>)
             f1.osc = c3.sc; f1.osh = c3.sh; f1.osl = c3.sl; f1.Out = s.ws + L.YA[bi][l];
         }
         // train mode: the activated copy XA is only dropped when the backward's fused 1x1 kernel will accept this layer (it rebuilds
         // the activation from x); otherwise the step would die in backward after the forward has already run
         Bwd1x1Args b1;
-        p.raw1x1 = fwd1x1_fused_ok(f1) && (!s.train || bwd1x1_fill(bi, l, M, s.ws, L, b1));
+        p.raw1x1 = fwd1x1_fused_ok(f1) && (!keep || bwd1x1_fill(bi, l, M, s.ws, L, b1));
     }
     const bool pair = k3 == CONV3X3_FWD_PAIR;            // the kernel that honours lf / isum_out and fills keep_out
     // norm2's consumer: the 3x3 pair kernel with the activation in LDS derives the table itself; anything else takes the link kernel
@@ -860,6 +868,15 @@ int tcvn_densenet_forward_mc(tcvn_densenet* p, int n_img, const int32_t* coords,
                              float* out, int64_t out_ld, void* ws, int64_t ws_bytes, uint64_t seed, int resume, void* stream) {
     return p->plan.forward(n_img, coords, values, nnz, log_pixels, 0.f, out, out_ld, reinterpret_cast<char*>(ws), ws_bytes, 0, seed,
                            reinterpret_cast<hipStream_t>(stream), true, resume != 0);
+}
+int tcvn_densenet_forward_frozen(tcvn_densenet* p, int n_img, const int32_t* coords, const float* values, int64_t nnz, int log_pixels,
+                                 float* out, int64_t out_ld, void* ws, int64_t ws_bytes, void* stream) {
+    return p->plan.forward(n_img, coords, values, nnz, log_pixels, 0.f, out, out_ld, reinterpret_cast<char*>(ws), ws_bytes, 0, 0,
+                           reinterpret_cast<hipStream_t>(stream), false, false, true);
+}
+int tcvn_densenet_input_gradient(tcvn_densenet* p, int n_img, const float* d_out, int64_t d_out_ld, float* d_values, void* ws,
+                                 int64_t ws_bytes, void* stream) {
+    return p->plan.input_gradient(n_img, d_out, d_out_ld, d_values, reinterpret_cast<char*>(ws), ws_bytes, reinterpret_cast<hipStream_t>(stream));
 }
 int tcvn_densenet_backward(tcvn_densenet* p, int n_img, const float* d_out, int64_t d_out_ld, void* ws, int64_t ws_bytes,
                            void* stream) {

@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include "densenet_plan.h"
 #include "tcvn_rows.h"
+#include "tcvn_input_grad.h"
 
 using namespace tcvn;
 
@@ -159,6 +160,7 @@ float* DenseNetPlan::gw_of(const Step& s, int slot) const {      // kernel-layou
 }
 
 int DenseNetPlan::bwd_link(const Step& s, const BnSlots& bn, int nblk, const double* bstat, long count, float* P, float* Q, int acc, int a_slot) const {
+    if (s.frozen) return 0;      // running statistics: the BatchNorm is a per-channel affine map, P = Q = 0 (zeroed by input_gradient) and no parameter gradient
     BnBwdLinkArgs a{s.part, nblk, bn.C, bstat, count, kEps, data[bn.w], grad[bn.w], grad[bn.b], grad[a_slot], P, Q, acc};
     return bn_bwd_link(a, s.st);
 }
@@ -183,6 +185,7 @@ int DenseNetPlan::backward(int n, const float* d_out, long d_out_ld, char* ws, l
     const bool first_part = bi_hi == (int)blocks.size() - 1, last_part = bi_lo == 0;
     if (n <= 0) return 0;
     if (n != last_n) { fprintf(stderr, "tcvn: densenet backward without matching forward\n"); return -13; }
+    if (last_frozen) { fprintf(stderr, "tcvn: densenet backward after a frozen forward: only tcvn_densenet_input_gradient is defined there\n"); return -20; }
     for (size_t i = 0; i < slots.size(); ++i)
         if (slots[i].kind == TCVN_SLOT_PARAM && grad[i] == nullptr) { fprintf(stderr, "tcvn: grad of %s unbound\n", slots[i].name.c_str()); return -14; }
     Layout L;
@@ -258,6 +261,52 @@ int DenseNetPlan::backward(int n, const float* d_out, long d_out_ld, char* ws, l
     return unpack_wgrads(reinterpret_cast<const UnpackDesc*>(d_undesc) + u0, u1 - u0, st);
 }
 
+// Data-only backward of the last frozen forward (hit gradients).  With running statistics every BatchNorm is a per-channel affine map, so
+// its data gradient dx = sc*dU + Px*x + Qx (bn_link.h) loses the two terms that come from batch statistics: the reverse schedule above runs
+// with P = Q = 0 everywhere, without a link (launched or riding), with dropout probability 0 in every EffSrc, and without any launch or
+// reduction that delivers a parameter gradient -- no 3x3 / 1x1 / stem weight gradient, no TN GEMM, no bias column sum, no k_unpack; the bound
+// grad pointers are neither read nor written and may be null.  Where the weight gradient is part of a data-gradient kernel (the fused 1x1
+// backward) it stays in that kernel's slabs.  The chain ends in DU0 = sc0 * prelu0'(u) * dz over the whole conv0 map (dense stem, no activity
+// bitmap), which k_hit_gradient (input_grad.hip) takes through conv0 at the hits.
+int DenseNetPlan::input_gradient(int n, const float* d_out, long d_out_ld, float* d_values, char* ws, long ws_bytes, hipStream_t st) {
+    if (!bound) return -11;
+    if (n <= 0) return 0;
+    if (!last_frozen || last_ws != ws || n != last_n) {
+        fprintf(stderr, "tcvn: densenet input_gradient: the last forward of this plan on this workspace was not a frozen forward of %d maps\n", n);
+        return -21;
+    }
+    if (stem_path.sparse || stem_path.act_skip || last_coords == nullptr) return -16;
+    Layout L;
+    layout(n, true, L);
+    if (ws_bytes < L.total) return -12;
+    int rc;
+    Step s{ws, L, st, n, true, last_seed, reinterpret_cast<double*>(ws + L.bpart), false, false, 0, false, false, true};
+    // (P, Q) of every block (not the kernel-layout weight gradients behind them: nothing is delivered), (PY, QY) and (P0, Q0) -- the links
+    // write the last two with acc = 0 in a training backward, so the per-backward memset does not cover them
+    TCVN_CHECK(hipMemsetAsync(ws + L.pqD[0], 0, (size_t)(L.gwk - L.pqD[0]), st));
+    TCVN_CHECK(hipMemsetAsync(ws + L.pqY, 0, (size_t)cfg.bn_size * cfg.growth * 8, st));
+    TCVN_CHECK(hipMemsetAsync(ws + L.pq0, 0, (size_t)cfg.init_ch * 8, st));
+    for (size_t bi = 0; bi + 1 < blocks.size(); ++bi) {      // G buffers whose first contribution accumulates: as backward()
+        const long bytes = (long)n * blocks[bi].H * blocks[bi].W * blocks[bi].ld * esz;
+        if (L.XP[bi] >= 0 && cfg.mode == MODE_BF16) {
+            if ((rc = zero_pool_remainder(ws + L.G[bi], blocks[bi].ld, n, blocks[bi].H, blocks[bi].W, blocks[bi + 1].H, blocks[bi + 1].W, st))) return rc;
+        } else TCVN_CHECK(hipMemsetAsync(ws + L.G[bi], 0, (size_t)bytes, st));
+    }
+    if ((rc = bwd_output(s, d_out, d_out_ld))) return rc;
+    for (int bi = (int)blocks.size() - 1; bi >= 0; --bi) {
+        if ((rc = bwd_transition(s, bi))) return rc;
+        for (int l = blocks[bi].L - 1; l >= 0; --l)
+            if ((rc = bwd_layer(s, bi, l))) return rc;
+    }
+    if ((rc = bwd_stem(s))) return rc;
+    HitGradArgs h{};
+    h.mode = cfg.mode; h.coords = last_coords; h.values = last_values; h.nnz = last_nnz; h.n_img = n; h.H = cfg.H; h.W = cfg.W; h.Cpix = cfg.in_ch;
+    h.value_mode = last_value_mode; h.E0 = ws + L.du0; h.lde = cfg.init_ch; h.Hc = Hc; h.Wc = Wc; h.N = cfg.init_ch; h.W0 = data[s_w0];
+    h.o = PixelOwners{reinterpret_cast<uint32_t*>(ws + L.own), (long)n * cfg.H * cfg.W};
+    h.d_values = d_values;
+    return hit_gradient(h, st);
+}
+
 // ---- output block backward: Dropout - PReLU - BatchNorm1d - Linear ----
 int DenseNetPlan::bwd_output(const Step& s, const float* d_out, long d_out_ld) const {
     const Layout& L = s.L;
@@ -267,6 +316,12 @@ int DenseNetPlan::bwd_output(const Step& s, const float* d_out, long d_out_ld) c
     float* dZ = reinterpret_cast<float*>(s.ws + L.dZ);
     float* hs = reinterpret_cast<float*>(s.ws + L.head_stat);
     int rc;
+    if (s.frozen) {
+        RowsBnFrozenBwdArgs f{Z, cfg.out_dim, d_out, d_out_ld, s.n, cfg.out_dim, data[nl.w], data[nl.b], data[s_al], data[nl.rm], data[nl.rv], kEps,
+                              dZ, cfg.out_dim, 0};
+        if ((rc = rows_bn_bwd_frozen(f, s.st))) return rc;
+        return linear_bwd_dx(dZ, cfg.out_dim, data[s_wl], dF, Cf, s.n, cfg.out_dim, Cf, 0, s.st);
+    }
     RowsBnBwdArgs r{};
     r.X = Z; r.ldx = cfg.out_dim; r.dY = d_out; r.lddy = d_out_ld; r.R = s.n; r.C = cfg.out_dim;
     r.gamma = data[nl.w]; r.beta = data[nl.b]; r.slope = data[s_al]; r.save_mean = hs; r.save_rstd = hs + cfg.out_dim;
@@ -309,11 +364,11 @@ int DenseNetPlan::bwd_transition(Step& s, int bi) const {
         // materialise the output gradient once (+ bias gradient), then dW = ET^T x XP on the TN GEMM
         const int Nt8 = (int)round_up(Nt, 8);
         SlabJob bias_job{};
-        EffMatArgs em{e, Mn, s.ws + L.ey, Nt8, grad[bg.tb], reinterpret_cast<float*>(s.ws + L.slab + kSlabGemmBytes), &bias_job};
+        EffMatArgs em{e, Mn, s.ws + L.ey, Nt8, s.frozen ? nullptr : grad[bg.tb], reinterpret_cast<float*>(s.ws + L.slab + kSlabGemmBytes), &bias_job};
         if ((rc = eff_materialize_bf16(em, s.st))) return rc;
         GemmTnArgs gt{s.ws + L.ey, Nt8, Nt8, s.ws + L.XP[bi], bg.ldp, bg.ldp, Mn, gw_of(s, bg.tw), ef.Kp, s.ws + L.zeros,
                       reinterpret_cast<float*>(s.ws + L.slab), kSlabGemmBytes, Nt, bias_job};
-        if ((rc = gemm_tn_bf16(gt, "k_gemm_tn_bf16<transition>", s.st))) return rc;
+        if (!s.frozen && (rc = gemm_tn_bf16(gt, "k_gemm_tn_bf16<transition>", s.st))) return rc;
         const WkEntry& etf = wk_find(bg.tw, 1, 1);
         GemmNtArgs ga{};
         ga.epi = EPI_DGRAD_POOL; ga.A = s.ws + L.ey; ga.lda = Nt8; ga.K = Nt8; ga.M = Mn; ga.N = bg.Ctot;
@@ -328,7 +383,7 @@ int DenseNetPlan::bwd_transition(Step& s, int bi) const {
     w.mode = mode; w.e = e; w.dWk = gw_of(s, bg.tw); w.dbias = grad[bg.tb];
     w.fa = trans_args(s, bi);               // fp32 with the pooled activation of the forward materialised: that is the weight gradient's operand
     if (L.XP[bi] >= 0) { w.slab = reinterpret_cast<float*>(s.ws + L.slab); w.slab_bytes = kSlabBytes; }      // split-K slabs of k_gemm_tn_f32 (the stream was drained above)
-    if ((rc = conv_wgrad(w, s.st))) return rc;
+    if (!s.frozen && (rc = conv_wgrad(w, s.st))) return rc;
     const WkEntry& et = wk_find(bg.tw, 1);
     ConvDgradArgs d{};
     d.mode = mode; d.dmode = DG_1X1_POOL; d.e = e; d.M = (int)Mn; d.N = bg.Ctot; d.Kp = et.Kp;
@@ -361,7 +416,7 @@ int DenseNetPlan::bwd_layer(Step& s, int bi, int l) const {
     ConvWgradArgs w3{};                    // conv2 (3x3) weight gradient; its operand arguments serve the data gradient's table too
     w3.fa = conv3_args(s, bi, l);
     // gradient of this layer's output slice D[:, cin:cin+g]
-    EffSrc e2{G, bg.ld, D, bg.ld, ls.cin, g, P + ls.cin, Q + ls.cin, cfg.dropout, s.seed, (uint32_t)(bi * 64 + l + 1)};
+    EffSrc e2{G, bg.ld, D, bg.ld, ls.cin, g, P + ls.cin, Q + ls.cin, s.frozen ? 0.f : cfg.dropout, s.seed, (uint32_t)(bi * 64 + l + 1)};
     if (p.keep_stored) e2.keep = reinterpret_cast<const uint32_t*>(s.ws + L.KM[bi][l]);      // keep words of this layer's forward (else: the hash)
     bool ey_valid = false;
     BnBwdLinkArgs link2{};                 // norm2 backward link (partials of the data gradient below -> PY / QY, which only the 1x1 backward reads)
@@ -396,7 +451,7 @@ int DenseNetPlan::bwd_layer(Step& s, int bi, int l) const {
 #endif
     SlabJob w3jobs[2] = {};        // the 3x3 weight gradient's slab reductions, folded into the fused kernel's reduction launch (same stream only)
     bool w3_deferred = false;
-    {   // conv2 (3x3) weight gradient: beside the rest of this layer's data-gradient chain
+    if (!s.frozen) {   // conv2 (3x3) weight gradient: beside the rest of this layer's data-gradient chain (frozen: neither it nor the norm2 link, PY = QY = 0)
         w3.mode = mode; w3.e = e2; w3.dWk = gw_of(s, ls.w2); w3.dbias = grad[ls.b2];
         if (ey_valid) w3.e.ey = s.ws + L.EY3[bi][l];
         if (fast3x3) {
@@ -428,6 +483,8 @@ int DenseNetPlan::bwd_layer(Step& s, int bi, int l) const {
         // The slab reductions stay on `st` behind the launch (on the side stream, with double-buffered slabs, the step was 0.25 ms LONGER);
         // one launch reduces this kernel's slabs and the 3x3 weight gradient's.
         if ((rc = bwd1x1_fused_launch(fa, st))) return rc;
+        // frozen: the kernel's weight-gradient tiles and bias column sums stay in its slabs (workspace scratch): no reduction into a gradient, no link
+        if (s.frozen) return 0;
         // Round 5: the norm1 link rides in the reduction launch (the workgroups behind the last job of k_slab_reduce_link's 1-D grid): both are ~5 us latency-floor
         // launches on the critical chain and independent of each other -- 60 launches fewer per step
         const BnSlots& s1 = ls.n1;
@@ -445,7 +502,7 @@ int DenseNetPlan::bwd_layer(Step& s, int bi, int l) const {
         w.mode = mode; w.e = e1; w.dWk = gw_of(s, ls.w1); w.dbias = grad[ls.b1];
         w.fa = conv1_args(s, bi, l);
         if (mode == MODE_F32) { w.slab = reinterpret_cast<float*>(s.ws + L.slab); w.slab_bytes = kSlabBytes; }     // k_gemm_tn_f32 (cin % 4 != 0); same stream as every other user
-        if ((rc = conv_wgrad(w, st))) return rc;
+        if (!s.frozen && (rc = conv_wgrad(w, st))) return rc;
         const WkEntry& et = wk_find(ls.w1, 1);
         ConvDgradArgs d{};
         d.mode = mode; d.dmode = DG_1X1; d.e = e1; d.M = (int)M; d.N = ls.cin; d.Kp = et.Kp; d.H = bg.H; d.W = bg.W;
@@ -460,7 +517,7 @@ int DenseNetPlan::bwd_layer(Step& s, int bi, int l) const {
     float* tail = reinterpret_cast<float*>(s.ws + L.slab + kSlabGemmBytes + (odd ? (kSlabBytes - kSlabGemmBytes) / 2 : 0));
     if (s.side_on && s.seq >= 2) TCVN_CHECK(hipStreamWaitEvent(st, ev_done[s.seq & 1], 0));   // that EY buffer / tail half is free again
     SlabJob bias_job{};     // bias column sums: reduced together with the weight-gradient slab below
-    EffMatArgs em{e1, M, EY, mid, grad[ls.b1], tail, &bias_job};
+    EffMatArgs em{e1, M, EY, mid, s.frozen ? nullptr : grad[ls.b1], tail, &bias_job};
     if ((rc = eff_materialize_bf16(em, st))) return rc;
     if (s.side_on) {
         TCVN_CHECK(hipEventRecord(ev_fork_b, st));
@@ -470,7 +527,7 @@ int DenseNetPlan::bwd_layer(Step& s, int bi, int l) const {
     const int cin8 = (int)round_up(ls.cin, 8);
     GemmTnArgs gt{EY, mid, mid, s.ws + L.XA[bi][l], cin8, cin8, M, gw_of(s, ls.w1), wk_find(ls.w1, 0).Kp, s.ws + L.zeros,
                   reinterpret_cast<float*>(s.ws + L.slab), kSlabGemmBytes, mid, bias_job};
-    if ((rc = gemm_tn_bf16(gt, "k_gemm_tn_bf16<conv1>", s.side_on ? side_st : st))) return rc;
+    if (!s.frozen && (rc = gemm_tn_bf16(gt, "k_gemm_tn_bf16<conv1>", s.side_on ? side_st : st))) return rc;
     if (s.side_on) TCVN_CHECK(hipEventRecord(ev_done[s.seq & 1], side_st));
     const WkEntry& etf = wk_find(ls.w1, 1, 1);
     GemmNtArgs ga{};
@@ -519,6 +576,7 @@ int DenseNetPlan::bwd_stem(const Step& s) const {
     else rc = pool0_bwd(a, s.st);
     if (rc) return rc;
     if ((rc = bwd_link(s, n0, a.nblk, bstat0, M0, P0, Q0, 0, s_a0))) return rc;
+    if (s.frozen) return 0;      // DU0 is the effective conv0-output gradient itself (P0 = Q0 = 0): input_gradient gathers it at the hits
     const EffSrc e0{s.ws + L.du0, cfg.init_ch, s.ws + L.c0, cfg.init_ch, 0, cfg.init_ch, P0, Q0, 0.f, 0, 0};
     if (conv3x3_tile_enabled() && cfg.in_ch <= 3 && cfg.init_ch <= 64 && last_coords != nullptr) {
         // conv0 weight gradient from the hit list (bias gradient is exactly zero in exact arithmetic: BN0 follows)

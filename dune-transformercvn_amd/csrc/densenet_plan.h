@@ -66,7 +66,11 @@ struct Step {                  // values shared by the pieces of one forward or 
     bool side_on; int seq; bool side_busy;      // backward: weight gradients on the side stream; parity of the EY buffer / tail half (reset by drain);
                                                 // work on the side stream that `st` has not waited for
     bool draw = false;         // forward, train == false: the dropout sites draw their masks (Monte-Carlo dropout); everything else is the eval pass
-    float drop_p(float cfg_p) const { return train || draw ? cfg_p : 0.f; }      // the effective dropout probability of this call
+    // Frozen pass (hit gradients): the eval pass -- running statistics, no dropout, no noise -- in a workspace laid out with backward and on
+    // the layer paths that keep what a backward needs (dense stem, raw bottleneck maps).  Its backward (input_gradient) is the data-gradient
+    // chain alone: no BatchNorm link (P = Q = 0), no weight gradient, dropout probability 0, nothing added to a bound grad pointer.
+    bool frozen = false;
+    float drop_p(float cfg_p) const { return (train || draw) && !frozen ? cfg_p : 0.f; }      // the effective dropout probability of this call
 };
 
 bool backward_overlap_enabled();
@@ -93,6 +97,8 @@ struct DenseNetPlan {
     const float* last_values = nullptr; int last_value_mode = 0; float last_noise = 0.f;
     const char* last_ws = nullptr; bool last_eval = false;       // workspace of the last forward, and whether it ran on running statistics: what a
                                                                  // Monte-Carlo dropout sample may resume from (null: nothing)
+    bool last_frozen = false;                                    // the last forward was a frozen one: input_gradient may follow, backward and a
+                                                                 // Monte-Carlo resume may not
     std::vector<std::vector<LayerPath>> path;    // [block][layer] of the last forward
     StemPath stem_path;
     bool sparse_stem_possible() const;   // plan-level condition (bf16, 3 -> 64 channels); the hit count decides per call
@@ -116,8 +122,11 @@ struct DenseNetPlan {
     int bind(void* const* d, void* const* g);
     int upload_descs(char* ws, const Layout& L, hipStream_t st);
     int forward(int n, const int32_t* coords, const float* values, long nnz, int log_pixels, float noise_std, float* out,
-                long out_ld, char* ws, long ws_bytes, int train, uint64_t seed, hipStream_t st, bool draw = false, bool resume = false);
+                long out_ld, char* ws, long ws_bytes, int train, uint64_t seed, hipStream_t st, bool draw = false, bool resume = false,
+                bool frozen = false);
     int backward(int n, const float* d_out, long d_out_ld, char* ws, long ws_bytes, hipStream_t st, int bi_hi = -1, int bi_lo = 0);
+    // data-only backward of the last frozen forward: d_out -> d_values [nnz][in_ch] at the hits of that forward's list
+    int input_gradient(int n, const float* d_out, long d_out_ld, float* d_values, char* ws, long ws_bytes, hipStream_t st);
     // the pieces of forward and of backward, each in launch order
     int fwd_stem(const Step& s, const int32_t* coords, const float* values, long nnz, int log_pixels, float noise_std, FreshStats& fr);
     int fwd_layer(const Step& s, int bi, int l, FreshStats& fr);

@@ -339,6 +339,7 @@ int add_ln_bwd(const AddLnBwdArgs& a, hipStream_t st) {
     if (a.D > 512) return -2;
     hipLaunchKernelGGL(k_add_ln_bwd, dim3(cdiv(a.T, 4)), dim3(256), 0, st, a);
     TCVN_LAUNCH_CHECK();
+    if (a.dgamma == nullptr && a.dbeta == nullptr) return 0;      // data gradient alone (frozen backward): no parameter gradient is formed
     hipLaunchKernelGGL(k_ln_param_grads, dim3(cdiv(a.D, 16)), dim3(256), 0, st, a.dY, a.XH, a.T, a.D, a.dgamma, a.dbeta);
     TCVN_LAUNCH_CHECK(); return 0;
 }

@@ -646,6 +646,7 @@ int encoder_fused_bwd(const EncFusedBwdArgs& a, const EncWgradArgs& w, hipStream
     if (a.H == 8) rc = nr == 3 ? launch_bwd<16, 3>(a, st) : nr == 5 ? launch_bwd<16, 5>(a, st) : nr == 8 ? launch_bwd<16, 8>(a, st) : launch_bwd<16, 11>(a, st);
     else rc = nr == 3 ? launch_bwd<32, 3>(a, st) : nr == 5 ? launch_bwd<32, 5>(a, st) : nr == 8 ? launch_bwd<32, 8>(a, st) : launch_bwd<32, 11>(a, st);
     if (rc) return rc;
+    if (w.n_jobs == 0) return 0;      // data gradient alone (frozen backward): the weight-gradient launch is left out
     const int ln_blocks = cdiv((long)a.L * 4 * D, 256);
     hipLaunchKernelGGL(k_encoder_wgrad, dim3(w.n_tiles + ln_blocks), dim3(256), 0, st, w);
     TCVN_LAUNCH_CHECK();

@@ -12,6 +12,7 @@
 #include "head_plan.h"
 #include "tcvn_rows.h"
 #include "tcvn_encoder.h"
+#include "tcvn_input_grad.h"
 
 using namespace tcvn;
 
@@ -141,7 +142,8 @@ void HeadPlan::layout(int B, int P, int nP, HLayout& L) const {
 }
 
 // ---- the step: what check() was, plus every size constant the drivers derive from (B, P, nP) ---------------------------------
-int HeadPlan::step(int B, int P, int nP, void* ws, long ws_bytes, int train, uint64_t seed, hipStream_t st, HeadStep& s, bool draw) const {
+int HeadPlan::step(int B, int P, int nP, void* ws, long ws_bytes, int train, uint64_t seed, hipStream_t st, HeadStep& s, bool draw, bool keep_note) const {
+    if (!keep_note) last_frozen_ws = nullptr;
     if (!bound) return -11;
     if (cfg.dec_out_in != dec_width) { fprintf(stderr, "tcvn: prong decoder width mismatch (reference would fail too)\n"); return -21; }
     if (B <= 0 || P < 0 || nP < 0 || 1 + P > 64) return -1;          // attention kernel: sequences up to 64 tokens
@@ -188,6 +190,15 @@ RowsBnBwdArgs HeadPlan::block_bwd(const HDec& d, const HeadStep& s, long X, long
     r.dX = s.F(dX); r.lddx = d.out;
     r.drop_p = d.drop ? s.dp : 0.f; r.seed = s.seed; r.stream_id = d.sid;
     return r;
+}
+// The block's backward: on batch statistics with its parameter gradients, or (frozen) the running-statistics form for the data alone
+int HeadPlan::block_bwd_run(const HDec& d, const HeadStep& s, long X, long dY, long stat, long dX, int rows) const {
+    if (!s.frozen) return rows_bn_bwd(block_bwd(d, s, X, dY, stat, dX, rows), s.st);
+    RowsBnFrozenBwdArgs r{};
+    r.X = s.F(X); r.ldx = d.out; r.dY = s.F(dY); r.lddy = d.out; r.R = rows; r.C = d.out; r.no_norm = cfg.no_linear_bn;
+    r.slope = d.a >= 0 ? data[d.a] : nullptr; r.eps = kEps; r.dX = s.F(dX); r.lddx = d.out;
+    if (!r.no_norm) { r.gamma = data[d.n.w]; r.beta = data[d.n.b]; r.running_mean = data[d.n.rm]; r.running_var = data[d.n.rv]; }
+    return rows_bn_bwd_frozen(r, s.st);
 }
 // The prong decoder chain: layer i (i == n_dec: the output layer) reads the prong tokens of HID (i == 0) or the block before it, and
 // its input gradient goes to the prong rows of dHID or to the scratch t0 that the block before reads as its dY.
@@ -297,6 +308,30 @@ int HeadPlan::forward(int B, int P, int nP, const float* rows, const int32_t* to
     return 0;
 }
 
+// Frozen pass (hit gradients).  The token path keeps its backward state in every forward (one layout, the fused encoder always saves), so
+// the frozen forward IS the eval forward -- running statistics, dropout 0 -- plus the note that input_gradient may follow on this workspace.
+int HeadPlan::forward_frozen(int B, int P, int nP, const float* rows, const int32_t* tok_row, float* ev_logits, float* pr_logits,
+                             void* ws, long ws_bytes, hipStream_t st) {
+    if (int rc = forward(B, P, nP, rows, tok_row, ev_logits, pr_logits, ws, ws_bytes, 0, 0, st)) return rc;
+    last_frozen_ws = ws; last_frozen_shape[0] = B; last_frozen_shape[1] = P; last_frozen_shape[2] = nP;
+    return 0;
+}
+
+// Data-only backward of the last frozen forward: the reverse schedule of backward() with dropout probability 0 at every site (not the replay
+// of cfg.dropout), the running-statistics rows backward in every LinearBlock, and no parameter gradient -- every dW / db / LayerNorm
+// gradient launch is left out (gp() gives null), the bound grad pointers are not read and may be null.
+int HeadPlan::input_gradient(int B, int P, int nP, const float* rows, const int32_t* tok_row, const float* dEv, const float* dPr,
+                             float* d_rows, void* ws, long ws_bytes, hipStream_t st) {
+    if (bound && (last_frozen_ws == nullptr || last_frozen_ws != ws || last_frozen_shape[0] != B || last_frozen_shape[1] != P || last_frozen_shape[2] != nP)) {
+        fprintf(stderr, "tcvn: head input_gradient: the last forward of this plan on this workspace was not a frozen forward of this batch\n");
+        return -21;
+    }
+    HeadStep s;
+    if (int rc = step(B, P, nP, ws, ws_bytes, 0, 0, st, s, false, true)) return rc;      // (the note stays: other seeds may follow on the same forward)
+    s.frozen = true;
+    return backward_chain(s, rows, tok_row, dEv, dPr, d_rows);
+}
+
 int HeadPlan::loss(int B, int P, const float* ev_logits, const float* pr_logits, const int64_t* et, const int8_t* pt, float* losses,
                    float* accs, float* dEv, float* dPr, hipStream_t st) {
     float* lb = accs + 2;                       // accs has room for 2 + 4 floats (scratch behind the two accuracies)
@@ -315,11 +350,15 @@ int HeadPlan::backward(int B, int P, int nP, const float* rows, const int32_t* t
             if (slots[i].kind == TCVN_SLOT_PARAM && grad[i] == nullptr) return -14;
     // train = 1 always: backward replays the masks of cfg.dropout whatever the forward's train flag was (the backward of an
     // eval-mode forward is not supported; callers run it after train-mode forwards only)
+    if (bound && last_frozen_ws == ws) { fprintf(stderr, "tcvn: head backward after a frozen forward: only tcvn_head_input_gradient is defined there\n"); return -20; }
     HeadStep s;
     if (int rc = step(B, P, nP, ws, ws_bytes, 1, last_seed, st, s)) return rc;
+    return backward_chain(s, rows, tok_row, dEv, dPr, d_rows);
+}
+int HeadPlan::backward_chain(const HeadStep& s, const float* rows, const int32_t* tok_row, const float* dEv, const float* dPr, float* d_rows) const {
     if (int rc = decoders_bwd(s, dEv, dPr)) return rc;
     float* dX = s.F(s.L.t2);
-    if (int rc = mask_rows(s.F(s.L.dHID), tok_row, dX, B, s.S, cfg.hidden_dim, st)) return rc;
+    if (int rc = mask_rows(s.F(s.L.dHID), tok_row, dX, s.B, s.S, cfg.hidden_dim, s.st)) return rc;
     int rc = 0;
     switch (enc_path(s.S)) {
     case EncPath::FUSED: rc = encoder_bwd_fused(s, dX, s.F(s.L.t3)); dX = s.F(s.L.t3); break;
@@ -335,17 +374,17 @@ int HeadPlan::decoders_bwd(const HeadStep& s, const float* dEv, const float* dPr
     const int D = cfg.hidden_dim, TP = s.TP, Ce = cfg.event_classes, Cp = cfg.prong_classes, n_dec = (int)dec.size();
     if (int rc = permute_rows(dPr, s.F(L.dLG), s.B, s.P, Cp, 0, s.st)) return rc;
     const DecIn last = dec_in(s, n_dec);
-    if (int rc = linear_bwd_dw(s.F(L.dLG), Cp, last.x, last.w, grad[ow], grad[ob], TP, Cp, last.w, s.st)) return rc;
+    if (int rc = linear_bwd_dw(s.F(L.dLG), Cp, last.x, last.w, gp(s, ow), gp(s, ob), TP, Cp, last.w, s.st)) return rc;
     if (int rc = linear_bwd_dx(s.F(L.dLG), Cp, data[ow], last.dx, last.w, TP, Cp, last.w, 0, s.st)) return rc;
     float* dZ = s.F(L.t1);
     for (int i = n_dec - 1; i >= 0; --i) {
         const HDec& d = dec[i];
         const DecIn in = dec_in(s, i);
-        if (int rc = rows_bn_bwd(block_bwd(d, s, L.Zd[i], L.t0, L.dstat[i], L.t1, TP), s.st)) return rc;       // dY: what layer i + 1 left in t0
-        if (int rc = linear_bwd_dw(dZ, d.out, in.x, in.w, grad[d.w], grad[d.b], TP, d.out, d.in, s.st)) return rc;
+        if (int rc = block_bwd_run(d, s, L.Zd[i], L.t0, L.dstat[i], L.t1, TP)) return rc;       // dY: what layer i + 1 left in t0
+        if (int rc = linear_bwd_dw(dZ, d.out, in.x, in.w, gp(s, d.w), gp(s, d.b), TP, d.out, d.in, s.st)) return rc;
         if (int rc = linear_bwd_dx(dZ, d.out, data[d.w], in.dx, in.w, TP, d.out, d.in, 0, s.st)) return rc;
     }
-    if (int rc = linear_bwd_dw(dEv, Ce, s.F(L.HID), D, grad[ew], grad[eb], s.B, Ce, D, s.st)) return rc;
+    if (int rc = linear_bwd_dw(dEv, Ce, s.F(L.HID), D, gp(s, ew), gp(s, eb), s.B, Ce, D, s.st)) return rc;
     return linear_bwd_dx(dEv, Ce, data[ew], s.F(L.dHID), D, s.B, Ce, D, 0, s.st);
 }
 
@@ -364,14 +403,15 @@ int HeadPlan::encoder_bwd_fused(const HeadStep& s, const float* dY, float* dX) c
         const HLayBuf& q = L.lay[l];
         a.w[l] = enc_w(l); a.buf[l] = enc_buf(s, l);
         a.g[l] = EncLayerGrad{s.F(q.g_dqkv), s.F(q.g_dao), s.F(q.g_dhp), s.F(q.g_df)};
-        w.job[nj++] = EncWgradJob{s.F(q.g_dqkv), 3 * D, s.F(L.X[l]), grad[W.win], grad[W.bin], 3 * D / 32};
-        w.job[nj++] = EncWgradJob{s.F(q.g_dao), D, s.F(q.ctx), grad[W.wo], grad[W.bo], D / 32};
-        w.job[nj++] = EncWgradJob{s.F(q.g_dhp), D, s.F(q.x1), grad[W.w1], grad[W.b1], D / 32};
-        w.job[nj++] = EncWgradJob{s.F(q.g_df), D, s.F(q.hact), grad[W.w2], grad[W.b2], D / 32};
+        w.job[nj++] = EncWgradJob{s.F(q.g_dqkv), 3 * D, s.F(L.X[l]), gp(s, W.win), gp(s, W.bin), 3 * D / 32};
+        w.job[nj++] = EncWgradJob{s.F(q.g_dao), D, s.F(q.ctx), gp(s, W.wo), gp(s, W.bo), D / 32};
+        w.job[nj++] = EncWgradJob{s.F(q.g_dhp), D, s.F(q.x1), gp(s, W.w1), gp(s, W.b1), D / 32};
+        w.job[nj++] = EncWgradJob{s.F(q.g_df), D, s.F(q.hact), gp(s, W.w2), gp(s, W.b2), D / 32};
         nt += 3 * D / 32 + 3 * (D / 32);
-        w.ln_dst[l][0] = grad[W.g1]; w.ln_dst[l][1] = grad[W.be1]; w.ln_dst[l][2] = grad[W.g2]; w.ln_dst[l][3] = grad[W.be2];
+        w.ln_dst[l][0] = gp(s, W.g1); w.ln_dst[l][1] = gp(s, W.be1); w.ln_dst[l][2] = gp(s, W.g2); w.ln_dst[l][3] = gp(s, W.be2);
     }
     w.n_jobs = nj; w.n_tiles = nt;
+    if (s.frozen) { w.n_jobs = 0; w.n_tiles = 0; }      // the chain kernel alone: its weight-gradient operands and LayerNorm sums stay in the workspace
     return encoder_fused_bwd(a, w, s.st);
 }
 
@@ -383,20 +423,20 @@ int HeadPlan::encoder_bwd_post(const HeadStep& s, float* dX) const {
     for (int l = cfg.n_layers - 1; l >= 0; --l) {
         const HLayer& W = layers[l];
         const HLayBuf& q = L.lay[l];
-        AddLnBwdArgs n2{dX, s.F(q.xh2), s.F(q.rstd2), data[W.g2], d1, dR, grad[W.g2], grad[W.be2], T, D, s.dp, s.seed, sid_enc(l, 3)};
+        AddLnBwdArgs n2{dX, s.F(q.xh2), s.F(q.rstd2), data[W.g2], d1, dR, gp(s, W.g2), gp(s, W.be2), T, D, s.dp, s.seed, sid_enc(l, 3)};
         if (int rc = add_ln_bwd(n2, s.st)) return rc;                                   // d1 = d(x1) residual, dR = d(f)
-        if (int rc = linear_bwd_dw(dR, D, s.F(q.hact), D, grad[W.w2], grad[W.b2], T, D, D, s.st)) return rc;
+        if (int rc = linear_bwd_dw(dR, D, s.F(q.hact), D, gp(s, W.w2), gp(s, W.b2), T, D, D, s.st)) return rc;
         if (int rc = linear_bwd_dx(dR, D, data[W.w2], dT, D, T, D, D, 0, s.st)) return rc;      // dT = d(hact)
         if (int rc = act_bwd(s.F(q.hpre), dT, dR, (long)T * D, cfg.gelu, s.dp, s.seed, sid_enc(l, 2), s.st)) return rc;   // dR = d(hpre)
-        if (int rc = linear_bwd_dw(dR, D, s.F(q.x1), D, grad[W.w1], grad[W.b1], T, D, D, s.st)) return rc;
+        if (int rc = linear_bwd_dw(dR, D, s.F(q.x1), D, gp(s, W.w1), gp(s, W.b1), T, D, D, s.st)) return rc;
         if (int rc = linear_bwd_dx(dR, D, data[W.w1], d1, D, T, D, D, 1, s.st)) return rc;      // d1 += through FFN
-        AddLnBwdArgs n1{d1, s.F(q.xh1), s.F(q.rstd1), data[W.g1], dX, dR, grad[W.g1], grad[W.be1], T, D, s.dp, s.seed, sid_enc(l, 1)};
+        AddLnBwdArgs n1{d1, s.F(q.xh1), s.F(q.rstd1), data[W.g1], dX, dR, gp(s, W.g1), gp(s, W.be1), T, D, s.dp, s.seed, sid_enc(l, 1)};
         if (int rc = add_ln_bwd(n1, s.st)) return rc;                                   // dX = d(x_l) residual, dR = d(ao)
-        if (int rc = linear_bwd_dw(dR, D, s.F(q.ctx), D, grad[W.wo], grad[W.bo], T, D, D, s.st)) return rc;
+        if (int rc = linear_bwd_dw(dR, D, s.F(q.ctx), D, gp(s, W.wo), gp(s, W.bo), T, D, D, s.st)) return rc;
         if (int rc = linear_bwd_dx(dR, D, data[W.wo], dT, D, T, D, D, 0, s.st)) return rc;      // dT = d(ctx)
         AttnBwdArgs ab{s.F(q.qkv), s.F(q.probs), dT, dR, s.B, s.S, H, hd, s.dp, s.seed, sid_enc(l, 0)};       // dR = d(qkv) [T, 3D]
         if (int rc = attn_bwd(ab, s.st)) return rc;
-        if (int rc = linear_bwd_dw(dR, 3 * D, s.F(L.X[l]), D, grad[W.win], grad[W.bin], T, 3 * D, D, s.st)) return rc;
+        if (int rc = linear_bwd_dw(dR, 3 * D, s.F(L.X[l]), D, gp(s, W.win), gp(s, W.bin), T, 3 * D, D, s.st)) return rc;
         if (int rc = linear_bwd_dx(dR, 3 * D, data[W.win], dX, D, T, 3 * D, D, 1, s.st)) return rc;
     }
     return 0;
@@ -414,22 +454,22 @@ int HeadPlan::encoder_bwd_pre(const HeadStep& s, float* dX) const {
         const HLayer& W = layers[l];
         const HLayBuf& q = L.lay[l];
         if (int rc = mul_drop(dX, dR, n, s.dp, s.seed, sid_enc(l, 3), s.st)) return rc;                         // dR = d f
-        if (int rc = linear_bwd_dw(dR, D, s.F(q.hact), D, grad[W.w2], grad[W.b2], T, D, D, s.st)) return rc;
+        if (int rc = linear_bwd_dw(dR, D, s.F(q.hact), D, gp(s, W.w2), gp(s, W.b2), T, D, D, s.st)) return rc;
         if (int rc = linear_bwd_dx(dR, D, data[W.w2], dT, D, T, D, D, 0, s.st)) return rc;                  // dT = d hact
         if (int rc = act_bwd(s.F(q.hpre), dT, dR, n, cfg.gelu, s.dp, s.seed, sid_enc(l, 2), s.st)) return rc;   // dR = d hpre
-        if (int rc = linear_bwd_dw(dR, D, s.F(q.h2), D, grad[W.w1], grad[W.b1], T, D, D, s.st)) return rc;
+        if (int rc = linear_bwd_dw(dR, D, s.F(q.h2), D, gp(s, W.w1), gp(s, W.b1), T, D, D, s.st)) return rc;
         if (int rc = linear_bwd_dx(dR, D, data[W.w1], dT, D, T, D, D, 0, s.st)) return rc;                  // dT = d h2
-        AddLnBwdArgs n2{dT, s.F(q.xh2), s.F(q.rstd2), data[W.g2], dS, d1, grad[W.g2], grad[W.be2], T, D, 0.f, s.seed, sid_enc(l, 3)};
+        AddLnBwdArgs n2{dT, s.F(q.xh2), s.F(q.rstd2), data[W.g2], dS, d1, gp(s, W.g2), gp(s, W.be2), T, D, 0.f, s.seed, sid_enc(l, 3)};
         if (int rc = add_ln_bwd(n2, s.st)) return rc;                                                       // dS = LN2 input gradient
         if (int rc = add_inplace(dX, dS, n, s.st)) return rc;                                               // dX = d x1
         if (int rc = mul_drop(dX, dR, n, s.dp, s.seed, sid_enc(l, 1), s.st)) return rc;                         // dR = d ao
-        if (int rc = linear_bwd_dw(dR, D, s.F(q.ctx), D, grad[W.wo], grad[W.bo], T, D, D, s.st)) return rc;
+        if (int rc = linear_bwd_dw(dR, D, s.F(q.ctx), D, gp(s, W.wo), gp(s, W.bo), T, D, D, s.st)) return rc;
         if (int rc = linear_bwd_dx(dR, D, data[W.wo], dT, D, T, D, D, 0, s.st)) return rc;                  // dT = d ctx
         AttnBwdArgs ab{s.F(q.qkv), s.F(q.probs), dT, dR, s.B, s.S, H, hd, s.dp, s.seed, sid_enc(l, 0)};     // dR = d qkv [T, 3D]
         if (int rc = attn_bwd(ab, s.st)) return rc;
-        if (int rc = linear_bwd_dw(dR, 3 * D, s.F(q.h1), D, grad[W.win], grad[W.bin], T, 3 * D, D, s.st)) return rc;
+        if (int rc = linear_bwd_dw(dR, 3 * D, s.F(q.h1), D, gp(s, W.win), gp(s, W.bin), T, 3 * D, D, s.st)) return rc;
         if (int rc = linear_bwd_dx(dR, 3 * D, data[W.win], dT, D, T, 3 * D, D, 0, s.st)) return rc;         // dT = d h1
-        AddLnBwdArgs n1{dT, s.F(q.xh1), s.F(q.rstd1), data[W.g1], dS, d1, grad[W.g1], grad[W.be1], T, D, 0.f, s.seed, sid_enc(l, 1)};
+        AddLnBwdArgs n1{dT, s.F(q.xh1), s.F(q.rstd1), data[W.g1], dS, d1, gp(s, W.g1), gp(s, W.be1), T, D, 0.f, s.seed, sid_enc(l, 1)};
         if (int rc = add_ln_bwd(n1, s.st)) return rc;
         if (int rc = add_inplace(dX, dS, n, s.st)) return rc;                                               // dX = d x_l
     }
@@ -441,8 +481,8 @@ int HeadPlan::embed_bwd(const HeadStep& s, const float* dX0, const float* rows, 
     const HLayout& L = s.L;
     const int D = cfg.hidden_dim;
     if (int rc = scatter_tokens_bwd(dX0, tok_row, s.F(L.dC), s.B, s.S, D, s.st)) return rc;
-    if (int rc = rows_bn_bwd(block_bwd(comb, s, L.Zc, L.dC, L.cstat, L.dZc, s.R), s.st)) return rc;
-    if (int rc = linear_bwd_dw(s.F(L.dZc), D, rows, cfg.in_dim, grad[comb.w], comb.b >= 0 ? grad[comb.b] : nullptr, s.R, D, cfg.in_dim, s.st)) return rc;
+    if (int rc = block_bwd_run(comb, s, L.Zc, L.dC, L.cstat, L.dZc, s.R)) return rc;
+    if (int rc = linear_bwd_dw(s.F(L.dZc), D, rows, cfg.in_dim, gp(s, comb.w), gp(s, comb.b), s.R, D, cfg.in_dim, s.st)) return rc;
     return linear_bwd_dx(s.F(L.dZc), D, data[comb.w], d_rows, cfg.in_dim, s.R, D, cfg.in_dim, 0, s.st);
 }
 
@@ -515,6 +555,18 @@ int tcvn_head_loss(tcvn_head* p, int batch, int max_prongs, const float* event_l
                    float* d_prong_logits, void* stream) {
     return p->plan.loss(batch, max_prongs, event_logits, prong_logits, event_targets, prong_targets, losses, accs, d_event_logits,
                         d_prong_logits, reinterpret_cast<hipStream_t>(stream));
+}
+int tcvn_head_forward_frozen(tcvn_head* p, int batch, int max_prongs, int n_prongs, const float* rows, const int32_t* tok_row,
+                             float* event_logits, float* prong_logits, void* ws, int64_t ws_bytes, void* stream) {
+    p->last_np = n_prongs; p->last_b = batch; p->last_p = max_prongs;
+    return p->plan.forward_frozen(batch, max_prongs, n_prongs, rows, tok_row, event_logits, prong_logits, ws, ws_bytes,
+                                  reinterpret_cast<hipStream_t>(stream));
+}
+int tcvn_head_input_gradient(tcvn_head* p, int batch, int max_prongs, int n_prongs, const float* rows, const int32_t* tok_row,
+                             const float* d_event_logits, const float* d_prong_logits, float* d_rows, void* ws, int64_t ws_bytes,
+                             void* stream) {
+    return p->plan.input_gradient(batch, max_prongs, n_prongs, rows, tok_row, d_event_logits, d_prong_logits, d_rows, ws, ws_bytes,
+                                  reinterpret_cast<hipStream_t>(stream));
 }
 int tcvn_head_backward(tcvn_head* p, int batch, int max_prongs, int n_prongs, const float* rows, const int32_t* tok_row,
                        const float* d_event_logits, const float* d_prong_logits, float* d_rows, void* ws, int64_t ws_bytes,

@@ -29,6 +29,7 @@ struct HeadStep {
     char* ws; HLayout L;
     int train; uint64_t seed; float dp; hipStream_t st;      // dp: the effective dropout probability (0 in eval mode, unless the call draws)
     bool draw = false;               // train == 0: the dropout sites draw their masks (Monte-Carlo dropout); everything else is the eval pass
+    bool frozen = false;             // backward of a frozen forward (hit gradients): dp = 0, running-statistics LinearBlock backward, no parameter gradient
     float* F(long off) const { return reinterpret_cast<float*>(ws + off); }
 };
 enum class EncPath { FUSED, POST_NORM, PRE_NORM };
@@ -51,18 +52,24 @@ struct HeadPlan {
     bool bound = false;
     bool fused_encoder = true;     // encoder_fused.hip when the shape allows (tcvn_head_set_fused_encoder(p, 0): unfused kernels, for A/B tests)
     uint64_t last_seed = 0;
+    // workspace and (B, P, nP) of the last forward when it was a frozen one, else null: step() drops the note before anything writes a
+    // workspace (a forward that fails midway, a stage entry, a scan), forward_frozen sets it when it has come through
+    mutable const void* last_frozen_ws = nullptr; int last_frozen_shape[3] = {0, 0, 0};
 
     explicit HeadPlan(const tcvn_head_cfg& c);
     int add_slot(const std::string& name, long numel, int kind);
     HBn add_bn(const std::string& p, int c);
     int bind(void* const* d, void* const* g);
     void layout(int B, int P, int nP, HLayout& L) const;
-    int step(int B, int P, int nP, void* ws, long ws_bytes, int train, uint64_t seed, hipStream_t st, HeadStep& s, bool draw = false) const;
+    int step(int B, int P, int nP, void* ws, long ws_bytes, int train, uint64_t seed, hipStream_t st, HeadStep& s, bool draw = false,
+             bool keep_note = false) const;
     EncPath enc_path(int S) const;
     // launch arguments that forward and backward must agree on
     EncLayerW enc_w(int l) const;  EncLayerBuf enc_buf(const HeadStep& s, int l) const;
     RowsBnArgs block_fwd(const HDec& d, const HeadStep& s, long X, long Y, long stat, int rows) const;
     RowsBnBwdArgs block_bwd(const HDec& d, const HeadStep& s, long X, long dY, long stat, long dX, int rows) const;
+    int block_bwd_run(const HDec& d, const HeadStep& s, long X, long dY, long stat, long dX, int rows) const;
+    float* gp(const HeadStep& s, int slot) const { return s.frozen || slot < 0 ? nullptr : grad[slot]; }      // where a parameter gradient goes (frozen: nowhere)
     DecIn dec_in(const HeadStep& s, int i) const;
     int embed(const HeadStep& s, const float* rows, const int32_t* tok_row) const;
     int encode(const HeadStep& s, const int32_t* tok_row) const, encode_post(const HeadStep& s, const int32_t* tok_row) const,
@@ -74,6 +81,11 @@ struct HeadPlan {
              float* accs, float* dEv, float* dPr, hipStream_t st);
     int backward(int B, int P, int nP, const float* rows, const int32_t* tok_row, const float* dEv, const float* dPr, float* d_rows,
                  void* ws, long ws_bytes, hipStream_t st);
+    int forward_frozen(int B, int P, int nP, const float* rows, const int32_t* tok_row, float* ev_logits, float* pr_logits, void* ws,
+                       long ws_bytes, hipStream_t st);
+    int input_gradient(int B, int P, int nP, const float* rows, const int32_t* tok_row, const float* dEv, const float* dPr, float* d_rows,
+                       void* ws, long ws_bytes, hipStream_t st);
+    int backward_chain(const HeadStep& s, const float* rows, const int32_t* tok_row, const float* dEv, const float* dPr, float* d_rows) const;
     int decoders_bwd(const HeadStep& s, const float* dEv, const float* dPr) const;
     int encoder_bwd_fused(const HeadStep& s, const float* dY, float* dX) const;      // d HID (masked) -> d X[0]
     int encoder_bwd_post(const HeadStep& s, float* dX) const, encoder_bwd_pre(const HeadStep& s, float* dX) const;      // in place

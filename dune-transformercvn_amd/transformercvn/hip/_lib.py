@@ -155,6 +155,16 @@ def _load():
     sig("tcvn_head_forward_mc", i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, i64, u64, vp)
     sig("tcvn_rows_bn_prelu_forward_mc", i32, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, i64, f32, u64, C.c_uint32, vp)
     sig("tcvn_mc_dropout_stats", i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp)
+    sig("tcvn_densenet_forward_frozen", i32, vp, i32, vp, vp, i64, i32, vp, i64, vp, i64, vp)
+    sig("tcvn_densenet_input_gradient", i32, vp, i32, vp, i64, vp, vp, i64, vp)
+    sig("tcvn_head_forward_frozen", i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, i64, vp)
+    sig("tcvn_head_input_gradient", i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp)
+    sig("tcvn_hit_gradient_workspace_bytes", i64, i32, i32, i32, i32)
+    sig("tcvn_hit_gradient_gather", i32, i32, vp, vp, i64, i32, i32, i32, i32, i32, vp, i64, i32, vp, vp, vp, i64, vp)
+    sig("tcvn_hit_gradient_seed", i32, vp, vp, i32, i32, i32, vp, vp)
+    sig("tcvn_ig_scale", i32, vp, f32, vp, i64, vp)
+    sig("tcvn_ig_accumulate", i32, vp, vp, C.c_double, i64, vp)
+    sig("tcvn_ig_finish", i32, vp, vp, vp, i64, vp)
     sig("tcvn_linear_backward", i32, vp, i64, vp, i64, vp, vp, i64, vp, vp, i32, i32, i32, vp)
     sig("tcvn_rows_bn_prelu_backward", i32, vp, i64, vp, i64, i32, i32, vp, vp, vp, vp, vp, i64, vp, vp, vp, f32, u64, C.c_uint32, vp)
     sig("tcvn_focal_loss", i32, vp, vp, i32, i32, f32, f32, vp, vp, vp)
@@ -199,6 +209,9 @@ EXPORTS = [
     "tcvn_head_shapley_workspace_bytes", "tcvn_head_shapley_count", "tcvn_head_shapley",
     "tcvn_densenet_forward_mc", "tcvn_head_forward_mc", "tcvn_rows_bn_prelu_forward_mc", "tcvn_mc_dropout_stats",
     "tcvn_detector_workspace_bytes", "tcvn_detector_variants", "tcvn_detector_build_pass", "tcvn_detector_response",
+    "tcvn_densenet_forward_frozen", "tcvn_densenet_input_gradient", "tcvn_head_forward_frozen", "tcvn_head_input_gradient",
+    "tcvn_hit_gradient_workspace_bytes", "tcvn_hit_gradient_gather", "tcvn_hit_gradient_seed",
+    "tcvn_ig_scale", "tcvn_ig_accumulate", "tcvn_ig_finish",
 ]
 
 lib = _load()

@@ -295,6 +295,30 @@ class DenseNetEngine(_EmbedderEngine):
         self._n = n_img
         self._inputs = (coords, values)
 
+    # ---- hit gradients: the eval pass with its state kept, and the data-only backward down to the hit values -------------------------
+    def forward_frozen(self, coords: torch.Tensor, values: torch.Tensor, n_img: int, out: torch.Tensor, log_pixels=False):
+        """tcvn_densenet_forward_frozen: the eval forward (running statistics, no dropout, no noise) in the step workspace laid out with
+        backward, on the layer paths that keep what input_gradient() reads.  coords / values must stay as they are until then."""
+        assert coords.dtype == torch.int32 and coords.is_contiguous() and values.dtype == torch.float32 and values.is_contiguous()
+        assert values.shape[0] == coords.shape[0]
+        self._check_out(out, n_img)
+        ws = self.workspace(self.workspace_bytes(n_img, True), coords.device)
+        check(lib.tcvn_densenet_forward_frozen(self.handle, n_img, _ptr(coords), _ptr(values), coords.shape[0], int(log_pixels), _ptr(out),
+                                               out.stride(0), _ptr(ws), ws.numel(), _stream_ptr()), "densenet_forward_frozen")
+        self._n = n_img
+        self._inputs = (coords, values)
+
+    def input_gradient(self, d_out: torch.Tensor) -> torch.Tensor:
+        """tcvn_densenet_input_gradient: d_out [n_img, out_dim] -> d <d_out, out> / d values [nnz, C] of the last forward_frozen()'s hit
+        list (raw values, in front of the v/255 / log(v+1) transform).  No parameter gradient is formed."""
+        self._check_out(d_out, self._n)
+        coords, values = self._inputs
+        d_values = torch.empty_like(values)
+        ws = self._ws
+        check(lib.tcvn_densenet_input_gradient(self.handle, self._n, _ptr(d_out), d_out.stride(0), _ptr(d_values), _ptr(ws), ws.numel(),
+                                               _stream_ptr()), "densenet_input_gradient")
+        return d_values
+
 
 class SdxlEngine(_EmbedderEngine):
     """SDXL-style embedder plan (tcvn_sdxl_* in include/tcvn_hip.h; parity unpinned, see oracle/sdxl_oracle.py)."""
@@ -560,6 +584,32 @@ class HeadEngine(_Plan):
         ws = self._ws
         check(lib.tcvn_head_backward(self.handle, batch, max_prongs, n_prongs, _ptr(rows), _ptr(tok_row), _ptr(d_ev), _ptr(d_pr),
                                      _ptr(d_rows), _ptr(ws), ws.numel(), _stream_ptr()), "head_backward")
+        return d_rows
+
+    def forward_frozen(self, rows: torch.Tensor, tok_row: torch.Tensor, batch: int, max_prongs: int, n_prongs: int
+                       ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """tcvn_head_forward_frozen: forward(train=False) in the step workspace, noted as the forward input_gradient() may follow."""
+        self._check_rows(rows, batch + n_prongs)
+        self._check_tok_row(tok_row, batch, 1 + max_prongs)
+        ws = self._stage_ws(batch, max_prongs, n_prongs, rows.device)
+        ev = torch.empty(batch, self.cfg.event_classes, device=rows.device)
+        pr = torch.empty(batch, max_prongs, self.cfg.prong_classes, device=rows.device)
+        self._shape = (batch, max_prongs, n_prongs)
+        self._last = (batch, max_prongs)
+        check(lib.tcvn_head_forward_frozen(self.handle, batch, max_prongs, n_prongs, _ptr(rows), _ptr(tok_row), _ptr(ev), _ptr(pr),
+                                           _ptr(ws), ws.numel(), _stream_ptr()), "head_forward_frozen")
+        return ev, pr
+
+    def input_gradient(self, rows: torch.Tensor, tok_row: torch.Tensor, d_ev: torch.Tensor, d_pr: torch.Tensor) -> torch.Tensor:
+        """tcvn_head_input_gradient: the logit seeds of the last forward_frozen() -> d_rows [batch + n_prongs, in_dim], as backward()
+        returns it; running statistics, dropout 0, no parameter gradient."""
+        batch, max_prongs, n_prongs = self._shape
+        assert d_ev.is_contiguous() and d_pr.is_contiguous() and d_ev.dtype == torch.float32 and d_pr.dtype == torch.float32
+        assert d_ev.shape == (batch, self.cfg.event_classes) and d_pr.shape == (batch, max_prongs, self.cfg.prong_classes)
+        d_rows = torch.empty_like(rows)
+        ws = self._ws
+        check(lib.tcvn_head_input_gradient(self.handle, batch, max_prongs, n_prongs, _ptr(rows), _ptr(tok_row), _ptr(d_ev), _ptr(d_pr),
+                                           _ptr(d_rows), _ptr(ws), ws.numel(), _stream_ptr()), "head_input_gradient")
         return d_rows
 
 

@@ -14,7 +14,7 @@ from typing import Dict, List, NamedTuple, Optional, Tuple
 import torch
 from torch import Tensor, nn
 
-from . import _lib, attention, detector, occlusion, uncertainty
+from . import _lib, attention, detector, gradients, occlusion, uncertainty
 from .engine import DenseNetEngine, HeadEngine, mc_stats
 from .native import gpu_only
 from .pixels import SparsePixels, VALUE_ONE_HOT
@@ -488,6 +488,79 @@ class HipRuntime:
             valid = last.tok_row[:, 1:].contiguous().view(-1)
             prong = uncertainty.McStats.from_rows(mc_stats(sample_pr.view(samples, B * P, pr.shape[2]), valid), (B, P))
             return uncertainty.McDropout(ev, pr, sample_ev, sample_pr, seeds.to(dev), event, prong)
+
+    # ---------------------------------------------------------------------------------------------------------------
+    # hit gradients: the eval-mode model differentiated with respect to the raw hit values (hip/gradients.py)
+    # ---------------------------------------------------------------------------------------------------------------
+    def _frozen_pass(self, last: LastForward, event_px: SparsePixels, prong_px: SparsePixels, ev_values: Tensor, pr_values: Tensor,
+                     target: "gradients.Target") -> Tuple[Tensor, Tensor]:
+        """One frozen forward of the whole model on the hit values given (the coordinates are event_px / prong_px's) plus its data-only
+        backward from the target's seeds -> (d target / d ev_values, d target / d pr_values).  The feature and position columns of the
+        input rows are those of `last`: the smart-feature MLP does not see the pixels."""
+        pe = self.network.prong_embedding
+        feat, pix = pe.feature_embedding_dim, pe.pixel_embedding_dim
+        B, P, n_prongs = last.B, last.P, last.n_prongs
+        rows = last.rows.clone()
+        has_ev, has_pr = event_px.coords.shape[0] > 0, n_prongs > 0 and prong_px.coords.shape[0] > 0
+        if has_ev:
+            self.ev_engine.forward_frozen(event_px.coords, ev_values, B, rows[:B, :feat + pix], event_px.value_mode)
+        if has_pr:
+            self.pr_engine.forward_frozen(prong_px.coords, pr_values, n_prongs, rows[B:, feat:feat + pix], prong_px.value_mode)
+        ev, pr = self.head.forward_frozen(rows, last.tok_row, B, P, n_prongs)
+        d_ev, d_pr = target.seeds(ev, pr)
+        d_rows = self.head.input_gradient(rows, last.tok_row, d_ev, d_pr)
+        g_ev = self.ev_engine.input_gradient(d_rows[:B, :feat + pix]) if has_ev else torch.zeros_like(ev_values)
+        g_pr = self.pr_engine.input_gradient(d_rows[B:, feat:feat + pix]) if has_pr else torch.zeros_like(pr_values)
+        return g_ev, g_pr
+
+    def forward_hit_gradients(self, features: Tensor, extra: Tensor, event_px: SparsePixels, event_mask: Tensor, prong_px: SparsePixels,
+                              prong_mask: Tensor, counts: Optional[Tuple[int, int]] = None, target="event", value: str = "prob",
+                              method: str = "gradient", steps: int = 32) -> "gradients.HitGradients":
+        """Eval-mode forward() plus the gradient of a class score with respect to the raw values of every hit -> gradients.HitGradients.
+        "gradient": one frozen forward and one data-only backward; "integrated": `steps` of them along alpha * values (midpoint rule,
+        baseline "no hits"), accumulated in double, and one more forward() (the baseline) for the completeness figure.  Nothing of the model is touched:
+        no parameter gradient is formed, no running statistic or counter moves, and the step counter is put back."""
+        one_hot = VALUE_ONE_HOT in (event_px.value_mode, prong_px.value_mode)
+        target, kind, method, steps = gradients.check_args(target, value, method, steps, one_hot)
+        if self.network.training:
+            raise RuntimeError("hit_gradients explains an eval-mode prediction: call network.eval() first")
+        for eng in (self.ev_engine, self.pr_engine):
+            if not hasattr(eng, "forward_frozen"):
+                raise NotImplementedError("hit_gradients: the SDXL embedder has no frozen forward and no data-only backward; only the "
+                                          "DenseNet network can be differentiated with respect to its hits")
+        self.ensure_bound()
+        step0, seeds0 = self.step, getattr(self, "last_seeds", None)
+        inputs = (features, extra, event_px, event_mask, prong_px, prong_mask, counts)
+        try:
+            with torch.no_grad():
+                ev, pr = self.forward(*inputs)
+                last = self._last_forward
+                tgt = gradients.Target(target, kind, ev, pr, prong_mask)
+                dev = ev.device
+                b_idx, _ = prong_mask.to(dev).nonzero(as_tuple=True)
+                common = (event_px.coords, prong_px.coords, prong_mask.to(dev), self.pixel_shape, method)
+                if method == "gradient":
+                    g_ev, g_pr = self._frozen_pass(last, event_px, prong_px, event_px.values, prong_px.values, tgt)
+                    return gradients.HitGradients(ev, pr, g_ev, g_pr, g_ev * event_px.values, g_pr * prong_px.values, *common)
+                acc_ev = torch.zeros(event_px.values.shape, dtype=torch.float64, device=dev)
+                acc_pr = torch.zeros(prong_px.values.shape, dtype=torch.float64, device=dev)
+                for alpha, w in gradients.ig_alphas(steps):
+                    v_ev, v_pr = gradients.ig_scale(event_px.values, alpha), gradients.ig_scale(prong_px.values, alpha)
+                    g_ev, g_pr = self._frozen_pass(last, event_px, prong_px, v_ev, v_pr, tgt)
+                    gradients.ig_accumulate(acc_ev, g_ev, w)
+                    gradients.ig_accumulate(acc_pr, g_pr, w)
+                a_ev, a_pr = gradients.ig_finish(acc_ev, event_px.values), gradients.ig_finish(acc_pr, prong_px.values)
+                val = tgt.value(ev, pr)
+                zero_ev = SparsePixels(event_px.coords, torch.zeros_like(event_px.values), event_px.shape, event_px.value_mode, 0.0, event_px.count)
+                zero_pr = SparsePixels(prong_px.coords, torch.zeros_like(prong_px.values), prong_px.shape, prong_px.value_mode, 0.0, prong_px.count)
+                base = tgt.value(*self.forward(features, extra, zero_ev, event_mask, zero_pr, prong_mask, counts))
+                pr_event = b_idx[prong_px.coords[:, 0].long()] if prong_px.coords.shape[0] else b_idx[:0]
+                gap = gradients.completeness_gap(a_ev, a_pr, event_px.coords[:, 0], pr_event, val, base)
+                return gradients.HitGradients(ev, pr, acc_ev.float(), acc_pr.float(), a_ev, a_pr, *common, val, base, gap)
+        finally:
+            self.step = step0
+            if seeds0 is not None:
+                self.last_seeds = seeds0
 
     def _backward(self, st: dict, d_ev: Tensor, d_pr: Tensor):
         """Backward of the fused step in the order the gradient segments become final -- token path, event embedder (side

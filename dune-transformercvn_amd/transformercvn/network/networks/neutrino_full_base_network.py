@@ -274,3 +274,28 @@ class NeutrinoBaseNetwork(nn.Module):
         event_pixels, prong_pixels = _as_sparse(event_pixels), _as_sparse(prong_pixels)
         return self.hip_runtime().forward_mc_dropout(features, extra, event_pixels, event_mask, prong_pixels, prong_mask, counts,
                                                      samples, seed, reuse_stem)
+
+    # ---- which hits a prediction rests on (eager only; the eval-mode model differentiated by the native plans, no autograd graph) -----
+    @torch.jit.unused
+    def hit_gradients(self, features: Tensor, extra: Tensor, event_pixels: Tensor, event_mask: Tensor, prong_pixels: Tensor,
+                      prong_mask: Tensor, counts: Optional[Tuple[int, int]] = None, target="event", value: str = "prob",
+                      method: str = "gradient", steps: int = 32):
+        """Eval mode only -> transformercvn.hip.gradients.HitGradients: the gradient of a class score with respect to the raw value of
+        every hit, per hit and per detector view -- one backward pass instead of one forward pass per occluded tile.  target: "event"
+        (each event's predicted event class), an int (that event class everywhere) or a [B] integer tensor of event classes, "prong" (the predicted class of every valid prong,
+        summed per event) or a pair (d_event_logits [B, Ce], d_prong_logits [B, P, Cp]) handed to the backward as it is (padded slots
+        contribute nothing).  value: "prob" (class probability) or "logit".  method "gradient": saliency (result.event_grad) and
+        gradient x value (result.event_attr); "integrated": integrated gradients from the baseline "no hits" along alpha * values,
+        midpoint rule over `steps` points, with result.completeness_gap.  result.heatmap(tile) -> [B, 1+P, Ht, Wt], the shape
+        occlusion_curves(relevance=...) takes.  BatchNorm runs on its running statistics and nothing draws dropout; parameters,
+        gradients, buffers, counters and the step counter are not touched.  One-hot pixels have no gradient (ValueError); the SDXL
+        embedder has no data-only backward: NotImplementedError."""
+        from transformercvn.hip import gradients
+        from transformercvn.hip.pixels import VALUE_ONE_HOT
+        one_hot = any(isinstance(px, SparsePixels) and px.value_mode == VALUE_ONE_HOT for px in (event_pixels, prong_pixels))
+        gradients.check_args(target, value, method, steps, one_hot)
+        if self.training:
+            raise RuntimeError("hit_gradients explains an eval-mode prediction: call .eval() first")
+        event_pixels, prong_pixels = _as_sparse(event_pixels), _as_sparse(prong_pixels)
+        return self.hip_runtime().forward_hit_gradients(features, extra, event_pixels, event_mask, prong_pixels, prong_mask, counts,
+                                                        target, value, method, steps)

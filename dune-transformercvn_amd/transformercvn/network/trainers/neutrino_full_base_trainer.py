@@ -255,6 +255,19 @@ class NeutrinoFullBaseTrainer(NeutrinoBase, ABC):
         return self.network.mc_dropout(*self._network_inputs(features, extra, event_coords, event_values, event_mask, prong_coords,
                                                              prong_values, prong_mask), None, samples, seed, reuse_stem)
 
+    def hit_gradients(self, features: Tensor, extra: Tensor, event_coords: Tensor, event_values: Tensor, event_mask: Tensor,
+                      prong_coords: Tensor, prong_values: Tensor, prong_mask: Tensor, target="event", value: str = "prob",
+                      method: str = "gradient", steps: int = 32):
+        """Eval mode only -> HitGradients (transformercvn.hip.gradients): the gradient of a class score with respect to the raw value of
+        every hit (saliency, gradient x value, integrated gradients); see NeutrinoBaseNetwork.hit_gradients.  Bad keywords raise
+        ValueError and train mode RuntimeError before any device work."""
+        from transformercvn.hip import gradients
+        gradients.check_args(target, value, method, steps, bool(getattr(self.options, "one_hot_pixels", False)))
+        if self.training:
+            raise RuntimeError("hit_gradients explains an eval-mode prediction: call .eval() first")
+        return self.network.hit_gradients(*self._network_inputs(features, extra, event_coords, event_values, event_mask, prong_coords,
+                                                                prong_values, prong_mask), None, target, value, method, steps)
+
     def shared_step(self, batch):
         (features, extra, ev_c, ev_v, ev_m, pr_c, pr_v, pr_m, ev_t, pr_t) = batch[:10]
         counts = batch[10] if len(batch) > 10 else None               # optional host-side (max_prongs, n_prongs): avoids syncs

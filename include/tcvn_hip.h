@@ -510,6 +510,59 @@ int tcvn_rows_bn_prelu_forward_mc(const float* x, int64_t ldx, int rows, int cha
 int tcvn_mc_dropout_stats(const float* sample_logits, const int32_t* valid, int n_samples, int rows, int classes, float* mean_prob,
                           float* std_prob, float* entropy, float* expected_entropy, float* mutual_info, float* votes, void* stream);
 
+/* Hit gradients: the gradient of an embedder output with respect to the raw values of the hits, through the eval-mode model.
+ * With running statistics a BatchNorm is a per-channel affine map, so its data gradient dx = sc*dU + P*x + Q loses the batch terms
+ * (P = Q = 0) and the backward of the eval pass is the training backward's data-gradient chain with the links left out.
+ *   densenet_forward_frozen   the eval forward (running statistics, no dropout whatever cfg.dropout is, no pixel noise, no running-stat
+ *               update, nothing added to num_batches_tracked) in a workspace of tcvn_densenet_workspace_bytes(p, n_img, 1), on the
+ *               dense stem and the layer paths that keep what a backward reads.  Same `out` as tcvn_densenet_forward with train = 0
+ *               up to the kernel choice (bit-identical in fp32 mode).  log_pixels = 3 (one-hot: class indices have no gradient) is
+ *               refused.  `coords` and `values` must stay valid and unchanged until input_gradient has run.
+ *   densenet_input_gradient   d_out [n_img, out_dim] -> d_values [nnz, in_ch] fp32 = d <d_out, out> / d values of that forward's list.
+ *               Every entry is written exactly once, without atomics: an entry outside the maps and an entry that does not own its
+ *               pixel (duplicate coordinates: the highest list index owns it) get exactly 0; two calls agree bit for bit.  No
+ *               parameter gradient is formed or delivered: the bound grad pointers are not touched and may be NULL.  Accepted only
+ *               if the plan's last forward was a frozen one of n_img maps on this workspace; tcvn_densenet_backward and a
+ *               tcvn_densenet_forward_mc resume are refused after a frozen forward.  Refusals: one "tcvn:" line, non-zero, no launch.
+ *   head_forward_frozen   tcvn_head_forward with train = 0 (the token path keeps its backward state in every forward), noted as the
+ *               forward that head_input_gradient may follow on this workspace.
+ *   head_input_gradient   the logit seeds -> d_rows [batch + n_prongs, in_dim], as tcvn_head_backward returns it, through the reverse
+ *               schedule with dropout probability 0 at every site, the running-statistics form of every LinearBlock's BatchNorm1d and no
+ *               parameter gradient (no dW / db / LayerNorm-gradient launch; grad pointers may be NULL), on whichever encoder path the
+ *               forward took.  Accepted only while the plan's last call that writes a workspace was a head_forward_frozen of the same
+ *               shape on this workspace that came through (any forward, stage entry or scan of the plan drops the note before its first
+ *               launch; further head_input_gradient calls with other seeds keep it); tcvn_head_backward on that workspace is refused
+ *               until then.
+ *   hit_gradient_gather   the last stage alone: e0 [n_img, Hc, Wc, init_ch] (mode: TCVN_MODE_F32 / _BF16 elements, row pitch lde), the
+ *               gradient with respect to the conv0 output (7x7, stride 2, pad 3; Hc = (height - 1) / 2 + 1), and conv0_weight
+ *               [init_ch, in_ch, 7, 7] fp32 ->
+ *                 d_values[h, c] = pre'(v[h, c]) * sum over the <= 16 outputs (oy, ox) whose window holds the hit, and over co, of
+ *                                  e0[img, oy, ox, co] * conv0_weight[co, c, y + 3 - 2 oy, x + 3 - 2 ox],
+ *               pre' = 1/255 (value_mode 0), 1/(v + 1) (1), 1 (2); sums in double, rounded to fp32 once.  in_ch <= 4.  The workspace
+ *               (hit_gradient_workspace_bytes) holds the duplicate record, built as a forward builds it.
+ *   ig_scale / ig_accumulate / ig_finish   integrated gradients along alpha * v: out = alpha * v; acc (double) += weight * grad;
+ *               attr = (float)(acc * v).  Element-wise over `count` values. */
+int tcvn_densenet_forward_frozen(tcvn_densenet* p, int n_img, const int32_t* coords, const float* values, int64_t nnz, int log_pixels,
+                                 float* out, int64_t out_ld, void* workspace, int64_t workspace_bytes, void* stream);
+int tcvn_densenet_input_gradient(tcvn_densenet* p, int n_img, const float* d_out, int64_t d_out_ld, float* d_values, void* workspace,
+                                 int64_t workspace_bytes, void* stream);
+int tcvn_head_forward_frozen(tcvn_head* p, int batch, int max_prongs, int n_prongs, const float* rows, const int32_t* tok_row,
+                             float* event_logits, float* prong_logits, void* workspace, int64_t workspace_bytes, void* stream);
+int tcvn_head_input_gradient(tcvn_head* p, int batch, int max_prongs, int n_prongs, const float* rows, const int32_t* tok_row,
+                             const float* d_event_logits, const float* d_prong_logits, float* d_rows, void* workspace,
+                             int64_t workspace_bytes, void* stream);
+int64_t tcvn_hit_gradient_workspace_bytes(int n_img, int height, int width, int in_ch);
+int tcvn_hit_gradient_gather(int mode, const int32_t* coords, const float* values, int64_t nnz, int n_img, int height, int width,
+                             int in_ch, int value_mode, const void* e0, int64_t lde, int init_ch, const float* conv0_weight,
+                             float* d_values, void* workspace, int64_t workspace_bytes, void* stream);
+/* seed [rows, n_classes] = d score / d logits for the score of class classes[r] of every row: value_kind 1 (TCVN_SHAP_VALUE_LOGIT) the logit
+ * (a one-hot row), 0 (TCVN_SHAP_VALUE_PROB) its softmax probability (the Jacobian row p_t (delta_ct - p_c), formed in double precision,
+ * max-subtracted).  classes[r] < 0, a padded slot, gives a zero row. */
+int tcvn_hit_gradient_seed(const float* logits, const int32_t* classes, int rows, int n_classes, int value_kind, float* seed, void* stream);
+int tcvn_ig_scale(const float* values, float alpha, float* out, int64_t count, void* stream);
+int tcvn_ig_accumulate(double* acc, const float* grad, double weight, int64_t count, void* stream);
+int tcvn_ig_finish(const double* acc, const float* values, float* attr, int64_t count, void* stream);
+
 /* Row operators behind the holder modules' own forward() (forward only, fp32):
  *   y = x W^T + b (torch.nn.Linear layout; bias may be NULL)                      -- layers/prong_decoder.py:15-16
  *   y = dropout(prelu(batchnorm1d(x)))  with batch statistics + running-stat update when train != 0, running statistics

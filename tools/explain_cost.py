@@ -10,8 +10,10 @@ mc_dropout() is timed at samples = 8 and 32, with and without reuse_stem: the wh
 from it and the forward() line, what one sample costs beside one forward().
 detector_scan() is timed with 8 effects in both scopes: the whole call (forward() included) and, from it and the forward() line, what one
 variant -- one whole-event setting, or one map under one effect -- costs beside one forward().
+hit_gradients() is timed with method "gradient" and with "integrated", steps=16: the whole call (forward() included), what one frozen
+forward + data-only backward costs beside one forward(), and the call beside the 16x16 occlusion scan of the same batch.
 
-    python tools/explain_cost.py [--batch 32 --reps 15 --occ-reps 3 --shap-reps 5 --mc-reps 3 --det-reps 3 --precision bf16 --keep 0.25]
+    python tools/explain_cost.py [--batch 32 --reps 15 --occ-reps 3 --shap-reps 5 --mc-reps 3 --det-reps 3 --grad-reps 3 --precision bf16 --keep 0.25]
 """
 import argparse
 import json
@@ -37,6 +39,7 @@ def main():
     ap.add_argument("--shap-reps", type=int, default=5, help="repetitions of each prong_shapley line (0: skip them)")
     ap.add_argument("--mc-reps", type=int, default=3, help="repetitions of each mc_dropout line (0: skip them)")
     ap.add_argument("--det-reps", type=int, default=3, help="repetitions of each detector_scan line (0: skip them)")
+    ap.add_argument("--grad-reps", type=int, default=3, help="repetitions of each hit_gradients line (0: skip them)")
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--keep", type=float, nargs="*", default=[0.25], help="keep of each occlusion_refine line (none: skip them)")
     args = ap.parse_args()
@@ -146,6 +149,17 @@ def main():
                           "variant_over_forward": round(per / fwd, 5),
                           "us_per_perturbed_map": round(1e3 * (statistics.median(ts) - fwd) / max(1, maps), 2)}
         out["detector_scan_effects8"] = row
+    for name, kw in (("hit_gradients_gradient", dict(method="gradient")),
+                     ("hit_gradients_integrated_steps16", dict(method="integrated", steps=16))) if args.grad_reps > 0 else ():
+        res, ts = timed(lambda: model.hit_gradients(*inputs[:8], **kw), args.grad_reps)
+        passes = 1 if kw["method"] == "gradient" else kw["steps"]
+        extra = 1 if kw["method"] == "gradient" else 2                          # forward() calls of the whole call
+        per = (statistics.median(ts) - extra * fwd) / passes
+        row = {"hits": int(res.event_grad.shape[0] + res.prong_grad.shape[0]), "passes": passes, "reps": args.grad_reps, "ms": ms(ts),
+               "ms_per_pass": round(per, 3), "pass_over_forward": round(per / fwd, 3)}
+        if "occlusion_maps_16x16" in out:
+            row["over_occlusion_16x16"] = round(statistics.median(ts) / out["occlusion_maps_16x16"]["ms"]["median"], 4)
+        out[name] = row
     cfg = rt.head.cfg
     out["weights_bytes"] = cfg.n_layers * args.batch * cfg.heads * (1 + width) ** 2 * 4
     print(json.dumps(out))
