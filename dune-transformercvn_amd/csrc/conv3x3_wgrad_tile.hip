@@ -25,15 +25,6 @@ __device__ unsigned long long g_wg_ph[16];                   // phase counters (
 // wave reads the eff fragment once and nine shifted Yact fragments, and owns the 9 x (32 c x 32 n) accumulators of its
 // 32-channel slice for the whole launch (144 accumulator registers); one atomic pass at the end.
 // ---------------------------------------------------------------------------------------------------------------------
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-__device__ __forceinline__ bf16x8_t tr_frag(const char* smem_base, int off_lo, int off_hi) {
-    typedef __attribute__((address_space(3))) s16x4* lds_p;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(smem_base + off_lo));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(smem_base + off_hi));
-    struct { s16x4 a, b; } pr = {lo, hi};
-    return __builtin_bit_cast(bf16x8_t, pr);
-}
-
 constexpr int WG_RING = 512, WG_TBL = 1024;
 // Round 5: the ring carries WG_MIRROR extra rows behind its end that MIRROR its first rows (whoever writes ring row r < WG_MIRROR also writes
 // row WG_RING + r).  A transposed read takes the 16 consecutive rows of a k-step starting anywhere in the ring: with the mirror it never

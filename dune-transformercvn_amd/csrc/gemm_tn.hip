@@ -13,15 +13,6 @@ namespace tcvn {
 namespace {
 
 constexpr int ROWS = 64;                       // pixels per stage; 64 KB of LDS per workgroup -> two workgroups per CU
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-
-__device__ __forceinline__ bf16x8_t tr_frag(const char* smem_base, int off_lo, int off_hi) {
-    typedef __attribute__((address_space(3))) s16x4* lds_p;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(smem_base + off_lo));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(smem_base + off_hi));
-    struct { s16x4 a, b; } pr = {lo, hi};
-    return __builtin_bit_cast(bf16x8_t, pr);
-}
 
 // DMA one [ROWS][128-column] operand tile: source rows m0.., columns col0.. (zeros beyond `ncols` / `m_end`)
 __device__ __forceinline__ void dma_tile(char* smem_base, int buf_off, const bf16* __restrict__ X, long ld, int ncols, int col0,

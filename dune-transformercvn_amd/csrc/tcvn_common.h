@@ -65,6 +65,21 @@ __device__ __forceinline__ float eff3(float g, float P, float x, float Q) { retu
 // (rocprofv3 round 4: LDS_BANK_CONFLICT = 2.6 x the LDS-active cycles of the 3x3 weight-gradient kernel).  Here row & 3 picks the quad.
 __device__ __forceinline__ int swz16(int r) { return ((r & 3) << 2) | ((r >> 2) & 3); }
 
+// One bf16 MFMA operand fragment read transposed (ds_read_b64_tr_b16) from an LDS image whose ROW index is the contraction index: the two
+// 8-byte halves of the lane's 8 elements come from byte offsets off_lo / off_hi of smem_base (lane roles: tools/micro/tr_read_test.hip).
+typedef __attribute__((ext_vector_type(4))) short s16x4;
+__device__ __forceinline__ bf16x8_t tr_frag(const char* smem_base, int off_lo, int off_hi) {
+    typedef __attribute__((address_space(3))) s16x4* lds_p;
+    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(smem_base + off_lo));
+    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(smem_base + off_hi));
+    struct { s16x4 a, b; } pr = {lo, hi};
+    return __builtin_bit_cast(bf16x8_t, pr);
+}
+
+// Bare s_barrier + lgkmcnt(0) for the barriers inside a pipeline: a __syncthreads() would drain the DMA, the prefetched loads and every
+// outstanding global store (its fence waits for vmcnt(0)).
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
 // load 8 consecutive elements as float (vector path requires 16B/32B alignment)
 template <typename T> __device__ __forceinline__ void load8(const T* p, float v[8]);
 template <> __device__ __forceinline__ void load8<float>(const float* p, float v[8]) {

@@ -123,10 +123,6 @@ __device__ __forceinline__ void act_tab_fill(float* __restrict__ xtab, const flo
     for (int i = tid; i < 128; i += nthreads) { xtab[i] = sc[i]; xtab[128 + i] = sh[i]; xtab[256 + i] = sl[i]; }
 }
 
-// Bare s_barrier + lgkmcnt(0) for the barriers inside a pipeline: a __syncthreads() would drain the DMA and the prefetched loads
-// (its fence waits for vmcnt(0)).
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 // Phase counters of the role-split kernels (validation build only): wave-cycles per phase into the kernel's local `ph[16]`, which every
 // 16th workgroup adds to the kernel's global counters (tcvn_debug_pair_phases / tcvn_debug_wgrad_phases read them)
 #ifdef TCVN_DEBUG_KNOBS

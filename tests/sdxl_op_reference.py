@@ -11,10 +11,11 @@ Gates (u = 2^-24, R(n) = (1 + u)^n - 1 the compound of n fp32 roundings; line nu
   * Weight packs (elementwise.hip:383-412 k_pack): wk[n][tap Cin + c] = wkt[c][tap Cout + n] = bf16(w[n][c][tap]) (f2bf, :360) or w itself
     in fp32 mode (:363); every column from taps * inner up to Kp is written 0 (:351-352).  Bit for bit, no gate.
   * Convolution forward.  Operands are stored values, bf16 x bf16 products are exact in fp32, and every kernel is one fp32 accumulation
-    chain over the K = ks ks Cin products of an output element (the MFMA is one, whatever its internal order: sdxl_conv3x3.hip:145-154
-    C64, :287-302 G over its channel chunks without a break, :422-435 S2, sdxl_stem.hip:75-82 IN, sdxl_kernels.hip:109-119 generic), then
-    c epilogue additions: the bias (sdxl_conv3x3.hip:170, :313, :440, sdxl_stem.hip:86-87, sdxl_kernels.hip:131) and, with a residual,
-    one more (sdxl_conv3x3.hip:185, :328, sdxl_kernels.hip:132): c = 1 or 2.
+    chain over the K = ks ks Cin products of an output element (the MFMA is one, whatever its internal order: sdxl_conv3x3.hip:122-132
+    tap_step, called over the nine taps at :258-259 C64 and :147-160 ring_taps -- G over its channel chunks without a break, :335, and
+    S2, :405 --, sdxl_stem.hip:75-82 IN, sdxl_kernels.hip:109-119 generic), then
+    c epilogue additions: the bias (sdxl_conv3x3.hip:171 acc_to_cs, sdxl_stem.hip:86-87, sdxl_kernels.hip:131) and, with a residual,
+    one more (sdxl_conv3x3.hip:180 cs_store8, sdxl_kernels.hip:132): c = 1 or 2.
         delta = R(K + c) S,   S = sum |a| |w| + |bias| + |res|
     fp32 mode (generic kernel only): the fp32 MFMA may round a product before it adds it, one more rounding per term: R(K + c + 1).
     Store: bf16 (from_f / f2bf) or fp32 for the final convolution (sdxl_kernels.hip:133) and in fp32 mode: densenet's store_gate.
@@ -24,9 +25,10 @@ Gates (u = 2^-24, R(n) = (1 + u)^n - 1 the compound of n fp32 roundings; line nu
     fp32 first and widens to double per tile / per 8 values; a value passes at most D fp32 additions on that way, a square one
     multiplication more (its product f * f is rounded):  gate_sum = R(D) sum |x|,  gate_sq = R(D + 1) sum x^2,  plus 2^-48 of the same
     sums for the double atomics (fewer than 2^4 of them per value chain would already be generous).
-        fused epilogue, C64 / G (512 threads): 2 passes x 2 rows x 8 values per thread (sdxl_conv3x3.hip:164-192, :307-336), six
-            wave_sum steps and one LDS float atomic per wave of eight (:58-61), then double (:62-64):           D = 32 + 6 + 8 = 46
-        fused epilogue, S2 (256 threads): 2 x 8 values (:444-454), wave_sum, four waves:                          D = 16 + 6 + 4 = 26
+        fused epilogue, C64 / G (512 threads): 2 passes x 2 rows x 8 values per thread (sdxl_conv3x3.hip:202-215 tile8x32_out, the
+            sums at :187 cs_store8), six wave_sum steps and one LDS float atomic per wave of eight (:74-77), then double (:78-81):
+                                                                                                                  D = 32 + 6 + 8 = 46
+        fused epilogue, S2 (256 threads): 2 x 8 values (:410-416, :187), wave_sum, four waves:                    D = 16 + 6 + 4 = 26
         fused epilogue, IN (256 threads): 8 x 8 values (sdxl_stem.hip:93-103), wave_sum, four waves (:108-109):   D = 64 + 6 + 4 = 74
         stand-alone k_gn_stats after a generic or packed-G launch (sdxl_kernels.hip:817-820): groups of 8 values in fp32, then double
             (:387-390) when C % 8 == 0, else double throughout (:393-396):                                        D = 8 or 0
@@ -57,7 +59,7 @@ OP_CONV, OP_GN = 0, 1
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# TileMap (sdxl_conv3x3.hip:206-214 make_map, :580 packed) restated
+# TileMap (sdxl_conv3x3.hip:274-282 make_map, :507 packed) restated
 # ---------------------------------------------------------------------------------------------------------------------
 def tile_map(H, W):
     """-> (px, py): images side by side / stacked in one 8 x 32 tile of SCONV_G."""
@@ -322,21 +324,21 @@ def pack_checks(ops, names, P, rnd, pack_shapes):
 # validation build's stop point tcvn_debug_sdxl_backward_stop makes readable):
 #   * Data gradient  dIn[y][x][c] = sum_{ky,kx,n} dO[(y + pad - ky) / s][(x + pad - kx) / s][n] w[n][c][ky][kx], exact divisions only
 #     (sdxl_ops.h:35).  One fp32 chain over at most K = ks ks Cout products (C64 / G on the transposed pack with flipped taps,
-#     sdxl_conv3x3.hip:102, :249, :896-897; S2 per parity class with 1, 2 or 4 of the 9 taps, :531-549; generic sdxl_kernels.hip:213-223),
+#     sdxl_conv3x3.hip:111 ring_load, :801-802; S2 per parity class with 1, 2 or 4 of the 9 taps, :477-490; generic sdxl_kernels.hip:213-223),
 #     no bias (launch_c64 / launch_g get bias = nullptr: acc + 0.f is exact), and with `accumulate` one addition of the earlier gradient
-#     (the residual operand of C64 / G, sdxl_conv3x3.hip:894; :562-566 S2; sdxl_kernels.hip:235 generic):
+#     (the residual operand of C64 / G, sdxl_conv3x3.hip:799; :458, :498 S2, both through cs_store8 :177-181; sdxl_kernels.hip:235 generic):
 #         delta = R(K + acc) S,  S = sum |dO| |w| + |earlier|;  bf16 / fp32 store.
 #   * Weight and bias gradient  dW[n][c][tap] = sum_m dO[m][n] a[m + shift(tap)][c],  db[n] = sum_m dO[m][n] over the M = n Ho Wo output
-#     pixels: fp32 sums in some order (per-workgroup MFMA chains and slab partials, k_sub_reduce / slab_reduce, sdxl_conv3x3.hip:909-936;
+#     pixels: fp32 sums in some order (per-workgroup MFMA chains and slab partials, k_sub_reduce / slab_reduce, sdxl_conv3x3.hip:807-833;
 #     fp32 atomics of the generic split-K kernel, sdxl_kernels.hip:332, :346-350; one wave per hit in sdxl_stem.hip) -- padding positions
 #     and empty partials add exact zeros, so any order passes at most M roundings -- then the addition into the zeroed kernel-layout
 #     gradient and the one of unpack_wgrads into the (zeroed) bound gradient (elementwise_bwd.hip:254):
 #         delta = R(M + 2) sum |dO| |a|;  fp32 store.
 #     Where the launch geometry is read off the launcher, the longest chain a product passes is far shorter than M and replaces it for the
-#     weight (wgrad_depth): a tile-family workgroup keeps its accumulators over its tiles t = lb, lb + gx, ... (sdxl_conv3x3.hip:691-702;
+#     weight (wgrad_depth): a tile-family workgroup keeps its accumulators over its tiles t = lb, lb + gx, ... (sdxl_conv3x3.hip:629-638;
 #     256 positions per 8 x 32 tile, 64 per 2 x 32 stride-2 tile) and writes one slab; gx slabs are summed (k_slab_reduce / k_sub_reduce):
-#         D = positions per tile * ceil(ntiles / gx) + gx,  gx = min(ntiles, 256) below 512 tiles else 512 for C64 (:909),
-#         gx = max(1, min(512 / nsub, ntiles)) with nsub = Cin / 64 * Cout / 64 for G and S2 (:917-920), ntiles as wgrad_args counts (:871-875);
+#         D = positions per tile * ceil(ntiles / gx) + gx,  gx = min(ntiles, 256) below 512 tiles else 512 for C64 (:813),
+#         gx = max(1, min(512 / nsub, ntiles)) with nsub = Cin / 64 * Cout / 64 for G and S2 (:819-822), ntiles as wgrad_args counts (:776-780);
 #     the generic kernel sums `rows` pixels per z-workgroup and adds `split` partials by atomics (sdxl_kernels.hip:717-727): D = rows + split.
 #     The bias gradient and SCONV_IN's hit-list weight gradient keep M.
 #   * GroupNorm backward (sdxl_kernels.hip:465-469, :493-499, :583-587, :632-636): xh = (x - mean) rstd (two roundings), u = xh gamma + beta
