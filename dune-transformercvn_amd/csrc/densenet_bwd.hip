@@ -294,9 +294,22 @@ int DenseNetPlan::input_gradient(int n, const float* d_out, long d_out_ld, float
     }
     if ((rc = bwd_output(s, d_out, d_out_ld))) return rc;
     for (int bi = (int)blocks.size() - 1; bi >= 0; --bi) {
+#ifdef TCVN_DEBUG_KNOBS
+        if ((rc = layer_snapshot(*this, s, bi, -1, false))) return rc;
+#endif
         if ((rc = bwd_transition(s, bi))) return rc;
-        for (int l = blocks[bi].L - 1; l >= 0; --l)
+#ifdef TCVN_DEBUG_KNOBS
+        if ((rc = layer_snapshot(*this, s, bi, -1, true))) return rc;
+#endif
+        for (int l = blocks[bi].L - 1; l >= 0; --l) {
+#ifdef TCVN_DEBUG_KNOBS
+            if ((rc = layer_snapshot(*this, s, bi, l, false))) return rc;
+#endif
             if ((rc = bwd_layer(s, bi, l))) return rc;
+#ifdef TCVN_DEBUG_KNOBS
+            if ((rc = layer_snapshot(*this, s, bi, l, true))) return rc;
+#endif
+        }
     }
     if ((rc = bwd_stem(s))) return rc;
     HitGradArgs h{};

@@ -136,14 +136,23 @@ __global__ void k_ig_finish(const double* acc, const float* v, float* attr, long
 int hit_gradient(const HitGradArgs& a, hipStream_t st) {
     if (a.value_mode == 3) { fprintf(stderr, "tcvn: hit gradient: one-hot pixels are class indices and have no gradient\n"); return -22; }
     if (a.value_mode < 0 || a.value_mode > 2 || (a.mode != MODE_F32 && a.mode != MODE_BF16)) return -1;
+    // the transposed conv0 weight in LDS: 37 KB at the product's 3 x 64 channels; wider stems (up to 160 KB: 3 x 278 channels) raise the 64 KB default
     const long lds = (long)a.Cpix * 49 * a.N * 4;
-    if (a.Cpix < 1 || a.Cpix > HG_MAXC || a.N < 1 || lds > 64 * 1024 || a.lde < a.N) {
+    if (a.Cpix < 1 || a.Cpix > HG_MAXC || a.N < 1 || lds > 160 * 1024 || a.lde < a.N) {
         fprintf(stderr, "tcvn: hit gradient: %d pixel channels x %d conv0 channels not supported\n", a.Cpix, a.N);
         return -2;
     }
     if (a.nnz <= 0) return 0;
     if (a.nnz > 0x7fffffffL) return -2;                      // the owner words hold 32-bit list indices
     const int nb = (int)std::min<long>(cdiv(a.nnz, 32), 1024);      // >= 8 hits per wave where the list allows: a workgroup loads the weights (37 KB) once
+    if (lds > 64 * 1024) {
+        static bool wide = false;
+        if (!wide) {
+            TCVN_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_hit_gradient<float>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            TCVN_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_hit_gradient<bf16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            wide = true;
+        }
+    }
     ProfScope ps("k_hit_gradient", 2.0 * a.nnz * 12.25 * a.Cpix * a.N, 0.0, st);
     if (a.mode == MODE_F32) hipLaunchKernelGGL(k_hit_gradient<float>, dim3(nb), dim3(256), (size_t)lds, st, a);
     else hipLaunchKernelGGL(k_hit_gradient<bf16>, dim3(nb), dim3(256), (size_t)lds, st, a);

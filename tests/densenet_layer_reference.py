@@ -29,6 +29,9 @@ Gates (derived, u = 2^-24, R(n) = (1 + u)^n - 1 the compound of n fp32 roundings
     head_backward below carry their derivations; the elements
     at a PReLU kink (|u| within the fp32 evaluation error of 0, where prelu' may take either branch) are the only ones ever left out of
     a comparison, at most KINK_CAP of a tensor.
+  * Frozen backward (hit gradients: running statistics, P = Q = PY = QY = 0, no dropout): output_block_backward_frozen
+    (k_rows_bn_bwd_frozen + the Linear's data gradient), frozen_block_slices (the final accumulator of a block as the end of its chain
+    of read-add-writes), hit_gradient_check (k_hit_gradient from the stored DU0) and the unrounded chain run_backward_frozen carry theirs.
 No other element is excluded and no gate carries a fitted factor."""
 import torch
 import torch.nn.functional as F
@@ -515,6 +518,165 @@ def run_backward(cfg, P, maps, d_cond, keeps=None):
     c0 = widths[0]
     x = maps["dense1"]
     return grads, G[0][..., :c0] + Pq[0][:c0] * x[..., :c0] + Qq[0][:c0]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the frozen backward (hit gradients): running statistics, P = Q = PY = QY = 0, no dropout, data gradients alone
+# ---------------------------------------------------------------------------------------------------------------------
+def output_block_backward_frozen(dOut, Z, gamma, beta, rm, rv, slope, W):
+    """Output block backward on running statistics -> the gradient of `condense` (raw:dcondense), its delta, the kink ROWS.
+    k_rows_bn_bwd_frozen (input_grad.hip:92-97), all fp32:
+        rstd = 1 / sqrtf(rv + eps)                 add, sqrt, divide: 3 roundings;
+        u    = (z - rm) * rstd * gamma + beta      subtract, two multiplies, add: 4 roundings on top of rstd's 3, each of a value no
+                                                   larger than |(z - rm) rstd gamma| + |beta|: tau_u = R(7) (|(z - rm) rstd gamma| + |beta|);
+        dZ   = (u > 0 ? dOut : slope dOut) * gamma * rstd     the slope multiply, two multiplies, rstd's 3: |error| <= R(6) |dZ|.
+    linear_bwd_dx (tcvn_rows.h:23-27 -> k_sgemm, rows.hip:36-43): dF[n][k] = sum_c dZ[n][c] W[c][k], one fma chain over the N = out_dim
+    products and alpha * acc + 0: delta = R(N + 1) (S + F) + F, S = |dZ| |W|, F = R(6) |dZ| |W|.
+    An element (n, c) with |u| <= tau_u may take either branch of prelu', and the Linear spreads it over the whole row n of the result:
+    the kink set is those ROWS.  dOut, Z [n, N]; gamma, beta, rm, rv, slope [N]; W [N, K] the bound Linear weight."""
+    rstd = 1.0 / torch.sqrt(rv + EPS)
+    lin = (Z - rm) * rstd * gamma
+    u = lin + beta
+    kink = (u.abs() <= R(7) * (lin.abs() + beta.abs())).any(1)
+    dZ = torch.where(u > 0, dOut, slope * dOut) * gamma * rstd
+    N = Z.shape[1]
+    S, Fm = dZ.abs() @ W.abs(), (R(6) * dZ.abs()) @ W.abs()
+    return dZ @ W, R(N + 1) * (S + Fm) + Fm, kink[:, None].expand(-1, W.shape[1])
+
+
+def running_tables(cfg, P, rnd=False):
+    """{norm prefix: (sc, sh)} of every BatchNorm2d from the bound RUNNING statistics (rounded to fp32 when rnd: what raw:tabs holds)."""
+    out = {}
+    for name, _, C in bn_names(cfg):
+        sc, sh = bn_table(None, P[name + ".weight"], P[name + ".bias"], (P[name + ".running_mean"], P[name + ".running_var"]))
+        out[name] = (f32(sc), f32(sh)) if rnd else (sc, sh)
+    return out
+
+
+def run_backward_frozen(cfg, P, maps, tables, d_out, defects=None):
+    """The whole frozen chain in float64 without rounding, composed from the functions above: output block on running statistics, head
+    pooling backward, per layer eff rows with P = Q = 0 and keep = None, the 3x3 data gradient, DU = sc2 dA prelu'(u2), the 1x1 backward
+    with PY = QY = 0, the transitions, down to DU0 over the conv0 map.  maps: what run_forward returned in eval mode with rnd off (they
+    hold conv0 and output_linear); tables: {norm prefix: (sc, sh)} (running_tables); d_out [n, out_dim].
+    defects (the gate tests): {"pq": {block: (P, Q)}} rows left in place instead of zero, {"keep": {(block, layer): keep}} a dropout keep
+    applied in the eff rows.  -> DU0 [n, Hc, Wc, C0], {name: tensor} of the intermediate state (dcondense, G<b> after each writer, du<b>.<l>)."""
+    import stem_reference as S
+    g, mid, nb = cfg.densenet_growth_rate, cfg.densenet_batch_norm_size * cfg.densenet_growth_rate, len(cfg.densenet_structure)
+    defects = defects or {}
+    zero = lambda t: torch.zeros_like(t)
+    widths, ch = [], cfg.initial_pixel_dim
+    for layers in cfg.densenet_structure:
+        widths.append(ch)
+        ch = (ch + layers * g) // 2
+    o = "output_block.norm"
+    d_cond, _, _ = output_block_backward_frozen(d_out, maps["output_linear"], P[o + ".weight"], P[o + ".bias"], P[o + ".running_mean"],
+                                                P[o + ".running_var"], P["output_block.relu.weight"], P["output_block.linear.weight"])
+    state = {"dcondense": d_cond}
+    G = {}
+    for b in reversed(range(nb)):
+        x = maps[f"dense{b + 1}"]
+        C = x.shape[-1]
+        Pb, Qb = defects.get("pq", {}).get(b, (torch.zeros(C, dtype=torch.float64), torch.zeros(C, dtype=torch.float64)))
+        if b == nb - 1:
+            sc, sh = tables["features.final_norm"]
+            (G[b], _, _), _, _ = head_backward(d_cond, x, sc, sh, P["features.final_relu.weight"])
+        else:
+            t = f"features.transition{b + 1}"
+            sc, sh = tables[t + ".norm"]
+            Cn = maps[f"dense{b + 2}"].shape[-1]
+            Pn, Qn = defects.get("pq", {}).get(b + 1, (torch.zeros(Cn, dtype=torch.float64), torch.zeros(Cn, dtype=torch.float64)))
+            out, _, _ = transition_backward(G[b + 1], maps[f"dense{b + 2}"], Pn, Qn, x, sc, sh, P[t + ".relu.weight"],
+                                            P[t + ".conv.weight"].reshape(C // 2, C), False)
+            G[b] = out["G"][0]
+        state[f"G{b + 1}:first"] = G[b]
+        for l in reversed(range(cfg.densenet_structure[b])):
+            p = f"features.dense{b + 1}.layers.{l}"
+            cin = widths[b] + l * g
+            cs = slice(cin, cin + g)
+            y = maps[f"bottleneck{b + 1}.{l}"]
+            sc2, sh2 = tables[p + ".output_block.norm2"]
+            _, _, e2, _ = eff_rows(G[b][..., cs], x[..., cs], Pb[cs], Qb[cs], defects.get("keep", {}).get((b, l)), False)
+            dA2, _ = conv3x3_dgrad(e2, zero(e2), P[p + ".output_block.conv2.weight"], False)
+            DU, _, _ = prelu_bn_backward(dA2, zero(dA2), y, sc2, sh2, P[p + ".output_block.relu2.weight"])
+            state[f"du{b + 1}.{l}"] = DU
+            xin = x[..., :cin]
+            sc1, sh1 = tables[p + ".bottleneck_block.norm1"]
+            sl1 = P[p + ".bottleneck_block.relu1.weight"]
+            _, _, a1, _ = activation(xin, sc1, sh1, sl1, False)
+            zy = torch.zeros(mid, dtype=torch.float64)
+            out, _, _ = conv1x1_backward(DU, y, zy, zy, a1, zero(a1), P[p + ".bottleneck_block.conv1.weight"].reshape(mid, cin),
+                                         G[b][..., :cin], xin, sc1, sh1, sl1, False)
+            G[b] = torch.cat([out["G"][0], G[b][..., cin:]], -1)
+        state[f"G{b + 1}"] = G[b]
+    c0 = maps["conv0"]
+    C0 = widths[0]
+    P0, Q0 = defects.get("pq", {}).get(0, (torch.zeros(C0, dtype=torch.float64),) * 2)
+    sc, sh = tables["features.norm0"]
+    dz, ddz = S.pool_backward(G[0][..., :C0], maps["dense1"][..., :C0], P0[:C0], Q0[:C0], c0.shape[1], c0.shape[2])
+    dU, _, _, _, _ = bn_sums(dz, zero(dz), c0, sc, sh, P["features.relu0.weight"])
+    return sc * dU, state
+
+
+def frozen_block_slices(name, first, G_final, x, ys, tabs1, tabs2, sl1s, sl2s, w1s, w2s, c0, g, rnd):
+    """The FINAL accumulator of one block after a frozen backward (raw:grad<b>), every layer's slice and the block's first channels,
+    without a hook: what stays readable is the end of a chain of read-add-writes, G[:, :cin_l] = store(G + sc1 dU1) for l = L - 1 .. 0,
+    behind the first writer.  The chain is walked with a running reference A and the |error| dpre a correct schedule may have in front
+    of a store (the buffer then holds a value within store_gate(A, dpre)):
+      * the first writer's (ref, delta, kink) as head_backward / transition_backward give them: A = ref, dpre = delta;
+      * layer l: its slice [cin, cin + g) is final -- Check(A, dpre) against the stored slice.  The STORED slice then feeds the layer's own
+        3x3 data gradient (eff rows with P = Q = 0: fma(0, x, g) + 0 = g exactly), so no error is carried from one layer's check into the
+        next through this path: DU = prelu_bn_backward(conv3x3_dgrad(...)) with its gate.  DU itself is gone (every layer overwrites it), so
+        the 1x1 backward's operand is the reference DU with the uncertainty of its store, de = store_gate(DU, dDU); with PY = QY = 0 the
+        eff row is DU itself (fma(0, y, du) + 0, already of the stored format).  dX = DU W1: one chain of mid products,
+        ddX = R(mid) (S + F) + F, F = de |W1|; bn_sums gives dU1 and its error; the read-add-write (gemm_nt.hip:242, conv1x1_backward):
+        A[:cin] += sc1 dU1,  dpre[:cin] = store_gate(A, dpre) + |sc1| ddU1 + R(2) (|A| + |sc1 dU1|);
+      * an element whose history holds a PReLU kink is left out: the first writer's kink set, norm1's per element, and for a kink of norm2
+        at one pixel the pixel's whole row of G[:, :cin] (the 1x1 spreads it); Check holds the set to KINK_CAP.
+    first = (ref, delta, kink) over all Ct channels; G_final, x [n, H, W, Ct]; ys, tabs*, sl*, w* per layer (w1 [mid, cin], w2 [g, mid, 3, 3]).
+    -> [Check] for every layer's slice (last layer first) and the first c0 channels, the stored counterparts."""
+    A, dpre, skip = first[0].clone(), first[1].clone(), first[2].clone()
+    L = len(ys)
+    checks, got = [], []
+    for l in reversed(range(L)):
+        cin = c0 + l * g
+        cs = slice(cin, cin + g)
+        checks.append(Check(f"{name}:grad[{cin}:{cin + g}]", "final G slice", A[..., cs].clone(), dpre[..., cs].clone(), rnd, skip[..., cs].clone()))
+        got.append(G_final[..., cs])
+        zero = torch.zeros(g, dtype=torch.float64)
+        _, _, e, de = eff_rows(G_final[..., cs], x[..., cs], zero, zero, None, rnd)
+        dA2, ddA2 = conv3x3_dgrad(e, de, w2s[l], rnd)
+        DU, dDU, kink2 = prelu_bn_backward(dA2, ddA2, ys[l], tabs2[l][0], tabs2[l][1], sl2s[l])
+        de1 = store_gate(DU, dDU, rnd)
+        w = _weights(w1s[l], rnd)
+        dX = DU @ w
+        Fx = de1 @ w.abs()
+        ddX = R(DU.shape[-1]) * (DU.abs() @ w.abs() + Fx) + Fx
+        xin = x[..., :cin]
+        sc1, sh1 = tabs1[l]
+        dU1, ddU1, kink1, _, _ = bn_sums(dX, ddX, xin, sc1, sh1, sl1s[l])
+        c = sc1 * dU1
+        Ain, din = A[..., :cin], dpre[..., :cin]
+        dnew = store_gate(Ain, din, rnd) + sc1.abs() * ddU1 + R(2) * (Ain.abs() + c.abs())
+        A = torch.cat([Ain + c, A[..., cin:]], -1)
+        dpre = torch.cat([dnew, dpre[..., cin:]], -1)
+        skip = torch.cat([skip[..., :cin] | kink1 | kink2.any(-1, keepdim=True), skip[..., cin:]], -1)
+    checks.append(Check(f"{name}:grad[0:{c0}]", "final G slice", A[..., :c0], dpre[..., :c0], rnd, skip[..., :c0]))
+    got.append(G_final[..., :c0])
+    return checks, got
+
+
+def hit_gradient_check(du0, w0, coords, values, shape, value_mode, name="d_values"):
+    """k_hit_gradient (input_grad.hip:45-75) from the STORED DU0 (raw:du0: bf16 or fp32 values, exact in double) and the bound fp32 conv0
+    weight: per hit and pixel channel at most 16 taps x N output channels of double fma (:60), 6 double additions of the xor-shuffle sum
+    (:68), the value-mode factor formed in double (:74: at most an addition and a division) and its multiply, ONE rounding to fp32 (:75):
+        delta = Rd(16 N + 6 + 3) S,  S = the same gather over |DU0| |W0| |factor|,  Rd(n) = (1 + 2^-53)^n - 1,
+    then the fp32 store rule.  Entries that do not own their pixel (and entries outside the maps) are exactly 0: gate 0.
+    The reference is hit_gradients_reference.gather.  -> Check."""
+    import hit_gradients_reference as H
+    ref = H.gather(du0, w0, coords, values, shape, value_mode)
+    S = H.gather(du0.abs(), w0.abs(), coords, values, shape, value_mode).abs()
+    n = 16 * du0.shape[-1] + 9
+    return Check(name, "k_hit_gradient", ref, ((1.0 + 2.0 ** -53) ** n - 1.0) * S, False)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

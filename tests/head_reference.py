@@ -35,10 +35,12 @@ def head_shapes(cfg, in_dim):
 
 
 def head_reference(params, cfg, rows, counts, P, event_targets=None, prong_targets=None, dtype=torch.float64, train=True,
-                   mask_provider=None):
+                   mask_provider=None, seeds=None):
     """One head step in `dtype`.  params: {slot name: tensor} (any shape with the slot's element count); rows [B + nP, in_dim];
     counts: prongs per event; P: prong slots per event.  Dropout is applied only through mask_provider (cfg.dropout still decides
     the prong decoder's Sequential indices).  train: batch statistics, the loss and every gradient; else running statistics and logits.
+    seeds = (d_ev [B, Ce], d_pr [B, P, Cp]) with train = False: the frozen backward -- d_rows is the gradient of
+    sum d_ev * ev + sum over the valid prong slots of d_pr * pr on running statistics, no dropout, by torch autograd.
     -> namespace(event_logits [B, Ce], prong_logits [B, P, Cp], losses {total, event, prong}, d_rows, grads {slot name: tensor},
     new_running {slot name: tensor})."""
     B = len(counts)
@@ -51,9 +53,10 @@ def head_reference(params, cfg, rows, counts, P, event_targets=None, prong_targe
         if train and not name.endswith(STAT_LEAVES):
             leaves[name] = t.requires_grad_(True)
         sd["network." + name] = t
-    x = rows.detach().cpu().to(dtype).clone().requires_grad_(train)
+    assert seeds is None or not train
+    x = rows.detach().cpu().to(dtype).clone().requires_grad_(train or seeds is not None)
     ctx = O._Ctx(train, cfg.dropout if mask_provider is not None else 0.0, mask_provider)
-    with torch.set_grad_enabled(train):
+    with torch.set_grad_enabled(train or seeds is not None):
         comb = O.linear_block(sd, COMBINED, cfg, x, ctx)
         prong_mask = torch.arange(P).view(1, P) < torch.tensor(counts).view(B, 1)
         I1, I2 = O.pack_indices(prong_mask)
@@ -64,6 +67,9 @@ def head_reference(params, cfg, rows, counts, P, event_targets=None, prong_targe
         hidden = O.encoder_forward(sd, cfg, tokens, mask, ctx)
         ev, pr = O.decoders_forward(sd, cfg, hidden, ctx)
         out = SimpleNamespace(event_logits=ev.detach(), prong_logits=pr.detach(), losses=None, d_rows=None, grads={}, new_running={})
+        if seeds is not None:
+            d_ev, d_pr = (t.detach().cpu().to(dtype) for t in seeds)
+            out.d_rows = torch.autograd.grad((d_ev * ev).sum() + (d_pr * pr)[prong_mask].sum(), x)[0]
         if not train:
             return out
         total, el, pl = O.training_loss(cfg, ev, pr, event_targets.cpu(), prong_targets.cpu())

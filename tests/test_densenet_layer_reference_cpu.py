@@ -6,7 +6,13 @@ on every map the oracle exposes, in train and eval mode, without and with dropou
 
 Rounding on: a "defective kernel" -- the reference with one deliberate defect, reading the same bf16-faithful stored inputs -- must leave
 the gates of the intact reference on at least one element of the operation it sits in (and nowhere else); a simulated correct kernel
-(operands rounded after a perturbation by +-tau, fp32 accumulation, one bf16 store) must stay inside them everywhere."""
+(operands rounded after a perturbation by +-tau, fp32 accumulation, one bf16 store) must stay inside them everywhere.
+
+The frozen backward (hit gradients; run_backward_frozen): rounding off it is float64 autograd through the oracle's eval forward down to
+the conv0 map and, behind the gather, the hit values, on the GPU test's cases narrow, wide and odd; each defect a schedule threaded
+through the training one can have -- stale (P, Q), a dropout keep in the eff rows, batch-statistics tables, a non-zero odd edge behind
+a transition, a 128-column slice of G[:, :cin] not accumulated, the gather reading DU0 at the fp32 stride in bf16 mode -- leaves the
+gate of the check it affects at those sizes; and every GPU case stays under KINK_CAP on running-statistics tables."""
 import functools
 
 import pytest
@@ -635,3 +641,196 @@ def test_fused_1x1_backward_gates_hold_and_bite_at_the_hook_cases_sizes(M, cin):
         one = _outside(o, gates, checks, _fused_kernel(o, "one_tile_missing"))
         print(M, cin, "one 64-row tile missing from the sums (resolution of the sum checks at this size):", {q: one[q] for q in ("dgamma", "dbeta", "dslope", "P", "Q")})
         assert all(one[q][0] > 0 for q in ("dgamma", "dbeta", "dslope", "P", "Q")), one
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the frozen backward (hit gradients): running statistics, P = Q = PY = QY = 0, no dropout
+# ---------------------------------------------------------------------------------------------------------------------
+def frozen_case(name):
+    """The GPU test's cases (test_densenet_layers_float64_gpu._case) -> cfg, coords, values, n_img.  The frozen leg runs on running
+    statistics, so its kink sets differ from the train leg's; FROZEN_WEIGHT_SEED gives a case another weight seed for the frozen leg
+    should its share of kink elements exceed KINK_CAP (test_frozen_cases_stay_under_the_kink_cap; none does at seed 19)."""
+    from test_densenet_layers_float64_gpu import _case
+    return _case(name)
+
+
+FROZEN_WEIGHT_SEED = {}      # case -> weight seed of the frozen leg where it is not 19
+
+
+def frozen_seed(case):
+    return FROZEN_WEIGHT_SEED.get(case, 19)
+
+
+@functools.lru_cache(maxsize=None)
+def _frozen_maps(case, rnd):
+    """Eval-mode forward of the reference alone (running-statistics tables) -> cfg, P, maps, tables, n_img, coords, values."""
+    cfg, coords, values, n_img = frozen_case(case)
+    _, P = _params(cfg, frozen_seed(case))
+    _, maps = R.run_forward(cfg, P, rnd, False, _conv0(cfg, P, coords, values, rnd))
+    return cfg, P, maps, R.running_tables(cfg, P, rnd), n_img, coords, values
+
+
+@pytest.mark.parametrize("case", ["narrow", "wide", "odd"])
+def test_frozen_chain_without_rounding_is_the_oracle_autograd(case):
+    """run_backward_frozen with rnd off against float64 autograd through O.densenet_forward in eval mode (running statistics, no dropout):
+    the gradient reaching the conv0 map (DU0), every block's accumulator where the oracle exposes the concat buffer, and the hit-value
+    gradient behind the gather -- to the 1e-9 relative of the train-mode pin."""
+    import hit_gradients_reference as H
+    cfg, P, maps, tables, n_img, coords, values = _frozen_maps(case, False)
+    sd = O.fill_state(cfg, frozen_seed(case))
+    sd64 = {k: (v.double() if v.is_floating_point() else v) for k, v in sd.items()}
+    v = values.double().clone().requires_grad_(True)
+    ctx = O._Ctx(False, 0.0, None)
+    out = O.densenet_forward(sd64, PFX, cfg, O.preprocess_pixels(cfg, coords, v, False), ctx)
+    ctx.taps[PFX + ":conv0"].retain_grad()
+    d_out = torch.randn(out.shape, generator=torch.Generator().manual_seed(5), dtype=torch.float64)
+    (out * d_out).sum().backward()
+    du0, state = R.run_backward_frozen(cfg, P, maps, tables, d_out)
+    o = "output_block.norm"
+    sc, sh = R.bn_table(None, P[o + ".weight"], P[o + ".bias"], (P[o + ".running_mean"], P[o + ".running_var"]))
+    figures = {"out": _rel(R._prelu(maps["output_linear"] * sc + sh, P["output_block.relu.weight"]), out.detach()),
+               "du0": _rel(du0.permute(0, 3, 1, 2), ctx.taps[PFX + ":conv0"].grad)}
+    got = H.gather(du0, P["features.conv0.weight"], coords, values, tuple(cfg.pixel_shape), 0)
+    own = torch.tensor(H.owners(coords, n_img, *cfg.pixel_shape))
+    # the oracle scatters a list with duplicates by index_put: the gradient lands on the entry that owns the pixel there too, or on all
+    # of them; compare the owners only, the rest must be exactly zero on the library's side
+    figures["d_values"] = _rel(got[own], v.grad[own])
+    assert bool((got[~own] == 0).all())
+    print(case, figures, "max |du0|", float(du0.abs().max()))
+    assert float(du0.abs().max()) > 0 and max(figures.values()) < 1e-9, figures
+
+
+@pytest.mark.parametrize("case", ["wide", "wide-dropout", "narrow", "narrow-one", "odd", "mod4", "trips"])
+def test_frozen_cases_stay_under_the_kink_cap(case):
+    """Under running-statistics tables, from the reference alone (the bf16-faithful eval forward): the share of elements at a PReLU kink of
+    norm0, of every layer's norm1 and norm2, of every transition norm and of final_norm stays <= KINK_CAP; no row of the output block's
+    BatchNorm1d sits at a kink."""
+    cfg, P, maps, tables, n_img, _, _ = _frozen_maps(case, True)
+    g = cfg.densenet_growth_rate
+
+    def share(t, norm):
+        sc, sh = tables[norm]
+        kink = (t * sc + sh).abs() <= R.R(2) * ((t * sc).abs() + sh.abs())
+        return int(kink.sum()) / kink.numel()
+    worst = {"norm0": share(maps["conv0"], "features.norm0")}
+    ch = cfg.initial_pixel_dim
+    for b, layers in enumerate(cfg.densenet_structure):
+        x = maps[f"dense{b + 1}"]
+        for l in range(layers):
+            p = f"features.dense{b + 1}.layers.{l}"
+            worst[f"norm1 {b + 1}.{l}"] = share(x[..., :ch + l * g], p + ".bottleneck_block.norm1")
+            worst[f"norm2 {b + 1}.{l}"] = share(maps[f"bottleneck{b + 1}.{l}"], p + ".output_block.norm2")
+        ch += layers * g
+        if b + 1 < len(cfg.densenet_structure):
+            worst[f"transition{b + 1}"] = share(x, f"features.transition{b + 1}.norm")
+            ch //= 2
+        else:
+            worst["final_norm"] = share(x, "features.final_norm")
+    o = "output_block.norm"
+    d_out = torch.randn(n_img, maps["output_linear"].shape[1], generator=torch.Generator().manual_seed(5), dtype=torch.float64)
+    _, _, krows = R.output_block_backward_frozen(d_out, maps["output_linear"], P[o + ".weight"], P[o + ".bias"], P[o + ".running_mean"],
+                                                 P[o + ".running_var"], P["output_block.relu.weight"], P["output_block.linear.weight"])
+    top = max(worst, key=worst.get)
+    print(case, "largest share of a tensor at a PReLU kink under running statistics:", worst[top], top, "output-block kink rows", int(krows[:, 0].sum()))
+    assert worst[top] <= R.KINK_CAP, (top, worst[top])
+    assert not krows.any()
+
+
+@functools.lru_cache(maxsize=None)
+def _frozen_layer_state(case):
+    """The bf16-faithful frozen forward of a case and the state its LAST layer of block 1 finds in the frozen backward: G of the block as
+    its first writer left it (the unrounded frozen chain's, rounded to bf16), zero rows."""
+    cfg, P, maps, tables, n_img, coords, values = _frozen_maps(case, True)
+    d_out = torch.randn(n_img, maps["output_linear"].shape[1], generator=torch.Generator().manual_seed(5), dtype=torch.float64)
+    du0, state = R.run_backward_frozen(cfg, P, maps, tables, d_out)
+    return cfg, P, maps, tables, n_img, coords, values, d_out, du0, state
+
+
+def _stale_rows(x, G_first, d_cond, P, norm, relu, tables_batch):
+    """(P, Q) of a block as the head's link of a TRAINING backward leaves them (bn_link on batch statistics of the same maps)."""
+    sc, sh = tables_batch
+    _, sums, gates = R.head_backward(d_cond, x, sc, sh, P[relu + ".weight"])
+    xf = x.reshape(-1, x.shape[-1])
+    mu, var = xf.mean(0), ((xf - xf.mean(0)) ** 2).mean(0)
+    lk = R.bn_link(sums, gates, mu, var, P[norm + ".weight"], xf.shape[0])
+    return R.f32(lk["P"][0]), R.f32(lk["Q"][0])
+
+
+FROZEN_DEFECTS = ["stale_pq", "keep", "batch_tables", "odd_edge", "slice_not_accumulated", "gather_stride"]
+
+
+@pytest.mark.parametrize("defect", FROZEN_DEFECTS)
+def test_a_defective_frozen_schedule_leaves_the_gates(defect):
+    """Each defect a frozen schedule threaded through the training one can have, at the GPU cases' own sizes (`odd`: one block, cin up to
+    538, five 128-column slices; `wide`: the odd 9 x 69 map in front of the transition): the worst |error| / gate of the check it
+    affects exceeds 1, and the intact result stays inside."""
+    case = "wide" if defect == "odd_edge" else "odd"
+    cfg, P, maps, tables, n_img, coords, values, d_out, du0, state = _frozen_layer_state(case)
+    g, mid = cfg.densenet_growth_rate, cfg.densenet_batch_norm_size * cfg.densenet_growth_rate
+    L = cfg.densenet_structure[0]
+    l = L - 1
+    cin = cfg.initial_pixel_dim + l * g
+    p = f"features.dense1.layers.{l}"
+    x, y = maps["dense1"], maps[f"bottleneck1.{l}"]
+    Ct = x.shape[-1]
+    zero = torch.zeros(Ct, dtype=torch.float64)
+    G = R.bf16(state["G1:first"])
+    sc2, sh2 = tables[p + ".output_block.norm2"]
+    sl2, w2 = P[p + ".output_block.relu2.weight"], P[p + ".output_block.conv2.weight"]
+    dgrad = lambda **kw: R.dgrad3_layer("l", **dict(dict(G=G, X=x, P=zero, Q=zero, keep=None, y=y, sc2=sc2, sh2=sh2, sl2=sl2, w2=w2, rnd=True,
+                                                         c_off=cin), **kw))[0]
+    if defect in ("stale_pq", "keep", "batch_tables"):
+        intact = dgrad()
+        if defect == "stale_pq":
+            assert len(cfg.densenet_structure) == 1
+            nf = "features.final_norm"
+            Ps, Qs = _stale_rows(x, G, state["dcondense"], P, nf, "features.final_relu", R.bn_table(x, P[nf + ".weight"], P[nf + ".bias"]))
+            assert float(Ps.abs().max()) > 0
+            wrong = dgrad(P=Ps, Q=Qs)
+        elif defect == "keep":
+            ks = float(torch.tensor(1.0, dtype=torch.float32) / (torch.tensor(1.0, dtype=torch.float32) - torch.tensor(0.1, dtype=torch.float32)))
+            keep = (torch.rand(G.shape[:3] + (g,), generator=torch.Generator().manual_seed(7)) >= 0.1).double() * ks
+            wrong = dgrad(keep=keep)
+        else:
+            n2 = p + ".output_block.norm2"
+            scb, shb = (R.f32(t) for t in R.bn_table(y, P[n2 + ".weight"], P[n2 + ".bias"]))
+            wrong = dgrad(sc2=scb, sh2=shb)
+        got = R.bf16(wrong.ref)
+    elif defect == "odd_edge":
+        assert x.shape[1:3] == (9, 69)
+        t = "features.transition1"
+        xn = maps["dense2"]
+        zn = torch.zeros(xn.shape[-1], dtype=torch.float64)
+        args = (R.bf16(state["G2"]), xn, zn, zn, x, *tables[t + ".norm"], P[t + ".relu.weight"], P[t + ".conv.weight"].reshape(Ct // 2, Ct), True, Ct - g)
+        DU, d, kink = R.transition_dgrad(*args)
+        intact = R.Check("t", "transition dgrad", DU, d, True, kink)
+        got = R.bf16(R.transition_dgrad(*args, defect="spill")[0])
+        assert float(intact.gate[:, 8].max()) == 0 and float(intact.gate[:, :, 68].max()) == 0      # exactly zero where no window covers
+    elif defect == "slice_not_accumulated":
+        DU = R.bf16(state[f"du1.{l}"])
+        xin = x[..., :cin]
+        sc1, sh1 = tables[p + ".bottleneck_block.norm1"]
+        sl1 = P[p + ".bottleneck_block.relu1.weight"]
+        _, _, a1, da1 = R.activation(xin, sc1, sh1, sl1, True)
+        zy = torch.zeros(mid, dtype=torch.float64)
+        out, _, _ = R.conv1x1_backward(DU, y, zy, zy, a1, da1, P[p + ".bottleneck_block.conv1.weight"].reshape(mid, cin), G[..., :cin], xin,
+                                       sc1, sh1, sl1, True)
+        intact = R.Check("G", "1x1 backward", out["G"][0], out["G"][1], True, out["G"][2])
+        assert cin > 256
+        got = R.bf16(out["G"][0]).clone()
+        got[..., 128:256] = G[..., 128:256]
+    else:
+        N = du0.shape[-1]
+        stored = R.bf16(du0)
+        w0 = P["features.conv0.weight"]
+        intact = R.hit_gradient_check(stored, w0, coords, values, tuple(cfg.pixel_shape), 0)
+        flat = torch.cat([stored.reshape(-1), torch.zeros(stored.numel(), dtype=torch.float64)])
+        rows = torch.arange(stored.numel() // N)
+        strided = flat[(2 * rows[:, None] * N + torch.arange(N)[None, :]).reshape(-1)].reshape(stored.shape)      # row r read at byte offset r * N * 4
+        import hit_gradients_reference as H
+        got = R.f32(H.gather(strided, w0, coords, values, tuple(cfg.pixel_shape), 0))
+    worst, bad, where = intact.ratio(got)
+    ok = intact.ratio((R.f32 if defect == "gather_stride" else R.bf16)(intact.ref))
+    print(defect, case, "elements outside:", bad, "worst |error| / gate", worst, "intact:", ok[:2], "max |ref|", float(intact.ref.abs().max()))
+    assert float(intact.ref.abs().max()) > 0 and ok[1] == 0 and ok[0] <= 1.0
+    assert bad > 0 and worst > 1.0

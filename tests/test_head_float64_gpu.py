@@ -10,9 +10,16 @@ Measured on an MI355X, largest err / e32 over the tensors whose err is above the
     row kernels, post-norm (train)         1.51   S9_layers8 with the fused encoder off, a prong decoder weight gradient (2.7e-6 / 1.8e-6)
     row kernels, pre-norm (train)          1.84   dropout_pre_norm_S9, event loss (2.5e-6 / 1.3e-6)
     eval logits, every path                none above the floor (largest err 8.0e-7)
+    frozen d_rows, every path              none above the floor (largest err 8.5e-7, S9_layers8 with the fused encoder off; largest err / e32
+                                           1.08, S23; frozen logits: largest err 5.3e-7, bit-equal to the eval forward's)
 Largest err of any tensor: 4.4e-6 (d_rows, 8 layers); every 2-layer case stays under 1e-6 but for pre-norm with dropout.  The kernels'
 summation orders, MFMA 16x16x4 f32 products and erff / expf sit as close to float64 as torch's float32 does.
 K = 4: twice the largest ratio (1.84), rounded up to a power of two.
+The frozen leg (test_head_frozen_backward_...: forward_frozen + input_gradient behind a train step on the same engine and workspace, all
+17 cases, random logit seeds with the padded slots zeroed) holds d_rows to the same bound with the same K; it also asserts that the
+frozen logits are the eval forward's bit for bit, that on the fused path switching the fused encoder off changes some bit, that the
+bound gradient tensors (filled with a NaN pattern) and the running statistics keep their bits, and that the dropout cases give the
+d_rows of an engine configured with dropout 0.
 
 Two traps (both asserted):
   * the gradient of a Linear bias that feeds a train-mode BatchNorm1d is analytically zero (1e-17 in float64, 1e-8 in float32): such
@@ -181,6 +188,72 @@ def test_head_step_matches_the_float64_reference(case):
         out_rows = head_train_step(eng, grads, rows, tok_row, et, pt, nP, SEED)
         diff = [k for k in out if not torch.equal(out[k].view(torch.int32), out_rows[k].view(torch.int32))]
         assert not diff, f"{case}: fused encoder on / off differ in {diff[:3]}: the fused kernels ran where the row kernels must"
+    rep.done()
+
+
+ARENA_PATTERN = 0x7FA5C3E1   # bits of a NaN: the bound gradient tensors hold them while a frozen backward runs
+
+
+def _frozen(eng, rows, tok_row, B, P, nP, d_ev, d_pr):
+    ev, pr = eng.forward_frozen(rows, tok_row, B, P, nP)
+    d_rows = eng.input_gradient(rows, tok_row, d_ev, d_pr)
+    torch.cuda.synchronize()
+    return ev, pr, d_rows
+
+
+@pytest.mark.parametrize("case", list(CASES))
+def test_head_frozen_backward_matches_the_float64_reference(case):
+    """forward_frozen + input_gradient (the data-only backward of hit gradients: running statistics, dropout 0, no parameter gradient) on
+    every case of the train test, behind one train step on the same engine and workspace."""
+    from transformercvn.hip import _lib
+    cfg, eng, p0, data, grads, counts, path = _build(case)
+    P = max(counts)
+    rows, tok_row, et, pt, nP = head_batch(6, counts, P, IN_DIM, cfg.num_event_classes, cfg.num_prong_classes)
+    B = len(counts)
+    valid = (pt >= 0)
+    buffers = {n for n, _, kind in eng.slots() if kind == _lib.SLOT_BUFFER}
+    head_train_step(eng, grads, rows, tok_row, et, pt, nP, SEED)             # the workspace now holds a train step's state
+    for k in buffers:
+        data[k].copy_(p0[k])                                                # running statistics back to what was bound
+    g = torch.Generator().manual_seed(31)
+    d_ev = torch.randn(B, cfg.num_event_classes, generator=g).cuda()
+    d_pr = (torch.randn(B, P, cfg.num_prong_classes, generator=g).cuda() * valid.unsqueeze(2)).contiguous()      # padded slots zeroed, as the runtime does
+    for t in grads.values():
+        t.view(torch.int32).fill_(ARENA_PATTERN)
+    ev, pr, d_rows = _frozen(eng, rows, tok_row, B, P, nP, d_ev, d_pr)
+    assert all(bool((t.view(torch.int32) == ARENA_PATTERN).all()) for t in grads.values()), "a frozen backward wrote a parameter gradient"
+    assert all(torch.equal(data[k].cpu(), p0[k]) for k in buffers), "running statistics moved"
+    ev_e, pr_e = eng.forward(rows, tok_row, B, P, nP, False, 0)
+    torch.cuda.synchronize()
+    assert torch.equal(ev, ev_e) and torch.equal(pr, pr_e), "the frozen forward is the eval forward"
+    r64 = head_reference(p0, cfg, rows, counts, P, dtype=torch.float64, train=False, seeds=(d_ev, d_pr))
+    r32 = head_reference(p0, cfg, rows, counts, P, dtype=torch.float32, train=False, seeds=(d_ev, d_pr))
+    rep = _Report(case)
+    assert r64.d_rows.abs().max() > 0
+    rep.check("frozen:event_logits", ev, r64.event_logits, r32.event_logits)
+    rep.check("frozen:d_rows", d_rows, r64.d_rows, r32.d_rows)
+    if path == "fused":
+        _fused(eng, False)
+        ev_r, pr_r, d_rows_r = _frozen(eng, rows, tok_row, B, P, nP, d_ev, d_pr)
+        rep.check("frozen(rows):d_rows", d_rows_r, r64.d_rows, r32.d_rows)
+        same = torch.equal(d_rows.view(torch.int32), d_rows_r.view(torch.int32)) and torch.equal(ev.view(torch.int32), ev_r.view(torch.int32))
+        assert not same, f"{case}: the fused encoder was to run here, yet switching it off changes no bit"
+        _fused(eng, True)
+    if cfg.dropout > 0:
+        # the frozen pass ignores dropout: an engine with dropout 0 and the same parameters gives the same bits
+        o = dict(CASES[case], dropout=0.0)
+        for k in ("counts", "path", "fused"):
+            o.pop(k, None)
+        dec_layers = o.pop("dec_layers", 2)
+        cfg0 = head_config(dec_layers=dec_layers, **o)
+        dims, final = O.prong_decoder_dims(cfg0)
+        eng0, data0, _ = head_engine(5, in_dim=IN_DIM, dec_dims=[w for _, w in dims], dec_out_in=final, fill=scaled_fill(cfg0, IN_DIM), **o)
+        assert [v.numel() for v in data0.values()] == [v.numel() for v in data.values()]
+        for v0, v in zip(data0.values(), data.values()):
+            v0.copy_(v)
+        _, _, d_rows0 = _frozen(eng0, rows, tok_row, B, P, nP, d_ev, d_pr)
+        assert torch.equal(d_rows0, d_rows), f"{case}: dropout {cfg.dropout} configured changes the frozen d_rows"
+    assert all(bool((t.view(torch.int32) == ARENA_PATTERN).all()) for t in grads.values())
     rep.done()
 
 

@@ -4,7 +4,7 @@
      frozen pass ignores dropout) and on all three encoder paths; case B (280-wide maps): target "prong" and raw seeds;
   2. bf16 mode against the oracle under torch.autocast (no more than 2x its relative L2, cosine no lower than 2 cos_autocast - 1);
   3. the stages: token path alone, one embedder alone;
-  4. the gather kernel alone through its C entry (corners, a full row, duplicates, every value mode);
+  4. the gather kernel alone through its C entry (corners, a full row, duplicates, every value mode, fp32 and bf16 rows);
   5. integrated gradients against the oracle's own midpoint rule, completeness;
   6. finite differences of the library's own eval forward at full size;
   7. nothing else moves, refusals.
@@ -236,17 +236,30 @@ def gather_case():
 
 @pytest.mark.parametrize("value_mode", [0, 1, 2])
 def test_gather_kernel_alone(value_mode):
+    """Both instances of k_hit_gradient through the C entry.  bf16: E0 is rounded to bf16 before either side sees it (the kernel reads
+    2-byte elements at a row stride of N of them); the gate is the same."""
     from transformercvn.hip import gradients
-    shape, coords, values, e0, w0 = gather_case()
-    ref = R.gather(e0, w0, coords, values, shape, value_mode)
-    got = gradients.gather(e0.cuda(), w0.cuda(), coords.cuda(), values.cuda(), shape, value_mode).cpu()
+    from transformercvn.hip._lib import lib, check, MODE_F32, MODE_BF16
+    from transformercvn.hip.native import ptr, stream_ptr
+    shape, coords, values, e0_f32, w0 = gather_case()
     own = torch.tensor(R.owners(coords, 2, *shape))
     assert (~own).sum() == 4
-    assert torch.isfinite(got).all()                                        # every hit written (the output starts as NaN below)
-    assert (got[~own] == 0).all() and (ref[own] != 0).all()
-    rel = ((got.double() - ref).abs() / ref.abs())[own]
-    print(f"hit_gradients[gather mode {value_mode}] worst relative error per element {float(rel.max()):.3e}")
-    assert float(rel.max()) <= 1e-5
+    c, v, w = coords.cuda(), values.cuda(), w0.cuda()
+    ws = torch.empty(lib.tcvn_hit_gradient_workspace_bytes(2, *shape, 3), dtype=torch.uint8, device="cuda")
+    for mode, e0 in ((MODE_F32, e0_f32), (MODE_BF16, e0_f32.to(torch.bfloat16))):
+        ref = R.gather(e0, w0, coords, values, shape, value_mode)
+        e = e0.cuda().contiguous()
+        out = torch.full_like(v, float("nan"))
+        check(lib.tcvn_hit_gradient_gather(mode, ptr(c), ptr(v), c.shape[0], 2, *shape, 3, value_mode, ptr(e), 64, 64, ptr(w), ptr(out), ptr(ws),
+                                           ws.numel(), stream_ptr()), "hit_gradient_gather")
+        torch.cuda.synchronize()
+        got = out.cpu()
+        assert torch.equal(got, gradients.gather(e, w, c, v, shape, value_mode).cpu())      # the Python wrapper is this entry
+        assert torch.isfinite(got).all()                                    # every hit written (the output starts as NaN)
+        assert (got[~own] == 0).all() and (ref[own] != 0).all()
+        rel = ((got.double() - ref).abs() / ref.abs())[own]
+        print(f"hit_gradients[gather {'bf16' if mode == MODE_BF16 else 'fp32'} mode {value_mode}] worst relative error per element {float(rel.max()):.3e}")
+        assert float(rel.max()) <= 1e-5
 
 
 def test_gather_kernel_writes_every_hit_and_refuses_one_hot():
