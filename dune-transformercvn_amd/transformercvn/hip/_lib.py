@@ -32,6 +32,7 @@ OCC_GROUP_EVENT, OCC_GROUP_MAP = 0, 1          # TCVN_OCC_GROUP_*: whose largest
 OCC_MAX_LEVELS = 16                 # TCVN_OCC_MAX_LEVELS: levels of one coarse-to-fine occlusion scan
 CURVE_MAX_STEPS, CURVE_MAX_TILES = 64, 4096    # TCVN_CURVE_MAX_*: steps of a deletion / insertion curve, tiles per map it can rank
 CURVE_DELETION, CURVE_INSERTION = 0, 1         # TCVN_CURVE_*: which hits a curve variant keeps
+TSHAP_MAX_TILES, TSHAP_MAX_SAMPLES, TSHAP_MAX_EXACT = 1024, 256, 10    # TCVN_TSHAP_MAX_*: limits of the tile Shapley scan
 DET_MAX_EFFECTS = 64                # TCVN_DET_MAX_EFFECTS: settings of one detector-effect scan
 DET_SCOPE_EVENT, DET_SCOPE_MAP = 0, 1          # TCVN_DET_SCOPE_*: an effect hits every map of an event, or one map at a time
 MC_MAX_CLASSES = 256                # TCVN_MC_MAX_CLASSES: the widest logit row tcvn_mc_dropout_stats takes
@@ -145,6 +146,13 @@ def _load():
     sig("tcvn_occlusion_curve_build_pass", i32, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, i64, i32, i32, vp, vp, i64,
         vp)
     sig("tcvn_occlusion_curve", i32, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp)
+    sig("tcvn_occlusion_shapley_workspace_bytes", i64, i32, i32, i32, i32, i32, i32, i32, i32)
+    sig("tcvn_occlusion_shapley_variants", i32, vp, i64, i32, i32, i32, i32, i32, vp, i32, i32, i32, i32, u64, vp, vp, vp, i32, vp, vp, vp,
+        i64, P(i64), i64, vp)
+    sig("tcvn_occlusion_shapley_build", i32, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, i64, i32, i32, vp, vp, i64,
+        vp)
+    sig("tcvn_occlusion_shapley_values", i32, vp, vp, vp, vp, vp, i64, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp,
+        vp, vp, vp, i64, vp)
     sig("tcvn_detector_workspace_bytes", i64, i32, i32, i32)
     sig("tcvn_detector_variants", i32, vp, i64, i32, i32, i32, i32, vp, vp, P(DetectorEffectC), i32, i32, vp, vp, vp, i64, P(i64), i64, vp)
     sig("tcvn_detector_build_pass", i32, vp, vp, i64, i32, i32, i32, i32, vp, i32, i32, vp, vp, i64, i32, i32, vp, vp, i64, vp)
@@ -206,6 +214,8 @@ EXPORTS = [
     "tcvn_head_occlusion", "tcvn_occlusion_heatmap",
     "tcvn_occlusion_select", "tcvn_occlusion_refine_variants", "tcvn_occlusion_mark", "tcvn_occlusion_occupancy", "tcvn_occlusion_paint",
     "tcvn_occlusion_curve_workspace_bytes", "tcvn_occlusion_curve_variants", "tcvn_occlusion_curve_build_pass", "tcvn_occlusion_curve",
+    "tcvn_occlusion_shapley_workspace_bytes", "tcvn_occlusion_shapley_variants", "tcvn_occlusion_shapley_build",
+    "tcvn_occlusion_shapley_values",
     "tcvn_head_shapley_workspace_bytes", "tcvn_head_shapley_count", "tcvn_head_shapley",
     "tcvn_densenet_forward_mc", "tcvn_head_forward_mc", "tcvn_rows_bn_prelu_forward_mc", "tcvn_mc_dropout_stats",
     "tcvn_detector_workspace_bytes", "tcvn_detector_variants", "tcvn_detector_build_pass", "tcvn_detector_response",

@@ -150,6 +150,28 @@ class _EmbedderEngine(_Plan):
                                     "occlusion_curve_variants", coords, n_img, shape, tile, img_bs, max_pass, need, n_img * (steps + 1),
                                     (steps, mode))
 
+    def occlusion_shapley_variants(self, coords: torch.Tensor, n_img: int, shape: Tuple[int, int], tile: Tuple[int, int],
+                                   img_bs: torch.Tensor, max_pass: int, samples: int, max_exact: int, seed: int,
+                                   permutations: torch.Tensor, n_tiles: torch.Tensor, exact: torch.Tensor) -> Tuple[VariantPlan, bool, bool]:
+        """tcvn_occlusion_shapley_variants: the coalitions of every map of this list that holds a hit -- all 2^n - 1 but the full one for
+        1 <= n <= max_exact occupied tiles, else the empty map and the prefixes 1 .. n - 1 of `samples` permutations drawn under `seed`.
+        The maps' rows of permutations int32 [B, 1 + P, samples, Ht * Wt], n_tiles and exact int32 [B, 1 + P] are written.  Same
+        results as occlusion_variants(), with index [V, 4] = (b, s, m, k); the plan serves occlusion_shapley_build.
+        Memory: vimg, index and the workspace are sized for the worst case before V is known -- n_img * max(2^max_exact - 1,
+        1 + samples * (Ht * Wt - 1)) candidate rows of 32 bytes, plus 6 bytes per (map, permutation, tile) of rank and prefix tables:
+        about 40 bytes * n_img * samples * Ht * Wt with the caller's permutations.  A max_variants of the caller does not bound it."""
+        Ht, Wt = -(-shape[0] // tile[0]), -(-shape[1] // tile[1])
+        for t in (permutations, n_tiles, exact):
+            assert t.dtype == torch.int32 and t.is_contiguous() and t.device == coords.device
+        B, S = n_tiles.shape
+        assert exact.shape == (B, S) and permutations.shape == (B, S, samples, Ht * Wt)
+        need = lib.tcvn_occlusion_shapley_workspace_bytes(n_img, *shape, *tile, samples, max_exact, max_pass)
+        rows = n_img * max((1 << max_exact) - 1, 1 + samples * (Ht * Wt - 1))
+        return self._occlusion_list(lib.tcvn_occlusion_shapley_variants,
+                                    (B, S - 1, samples, max_exact, C.c_uint64(seed), _ptr(permutations), _ptr(n_tiles), _ptr(exact)),
+                                    "occlusion_shapley_variants", coords, n_img, shape, tile, img_bs, max_pass, need, rows,
+                                    (samples, max_exact))
+
     def _occlusion_list(self, fn, extra: tuple, what: str, coords: torch.Tensor, n_img: int, shape: Tuple[int, int], tile: Tuple[int, int],
                         img_bs: torch.Tensor, max_pass: int, need: Optional[int] = None, rows: Optional[int] = None, geometry: tuple = ()):
         """One variant-list call.  need / rows: the workspace bytes and the largest number of variants (default: those of the tile
@@ -185,6 +207,12 @@ class _EmbedderEngine(_Plan):
         """tcvn_occlusion_curve_build_pass: the same for a plan of occlusion_curve_variants()."""
         self._occlusion_build(lib.tcvn_occlusion_curve_build_pass, "occlusion_curve_build_pass", plan, coords, values, first, count,
                               out_coords, out_values)
+
+    def occlusion_shapley_build(self, plan: VariantPlan, coords: torch.Tensor, values: torch.Tensor, first: int, count: int,
+                                out_coords: torch.Tensor, out_values: torch.Tensor):
+        """tcvn_occlusion_shapley_build: the same for a plan of occlusion_shapley_variants()."""
+        self._occlusion_build(lib.tcvn_occlusion_shapley_build, "occlusion_shapley_build", plan, coords, values, first, count, out_coords,
+                              out_values)
 
     def _occlusion_build(self, fn, what: str, plan: VariantPlan, coords: torch.Tensor, values: torch.Tensor, first: int, count: int,
                          out_coords: torch.Tensor, out_values: torch.Tensor):

@@ -13,6 +13,10 @@ fine.  Level 0 is the flat scan at ``tile``; every later level halves the tiles 
 ``trainer.occlusion_curves(...)`` / ``network.occlusion_curves(...)`` return an :class:`OcclusionCurves`: how faithful a relevance map
 ``[B, 1 + P, Ht, Wt]`` is.  Per map, the tiles that hold a hit are ranked by relevance and removed (deletion) or added back (insertion)
 in ``steps`` steps; ``curve()`` is the class probability at every step and ``auc()`` the area under it.
+
+``trainer.occlusion_shapley(...)`` / ``network.occlusion_shapley(...)`` return a :class:`TileShapley`: the Shapley value of every tile
+that holds a hit, the players of a map being its occupied tiles and a coalition the map with only their hits.  Maps with few occupied
+tiles run all their coalitions, wider ones the prefixes of random permutations; ``values()`` sums to ``full - empty`` per map.
 """
 from __future__ import annotations
 
@@ -334,6 +338,93 @@ def curve_and_auc(result: OcclusionCurves, target: Union[str, int, Tensor] = "ev
     return curve, auc
 
 
+# ---- tile Shapley values ------------------------------------------------------------------------------------------------------------------
+SHAPLEY_VALUES = {"prob": _lib.SHAP_VALUE_PROB, "logit": _lib.SHAP_VALUE_LOGIT}
+
+
+def check_shapley_args(tile, max_exact, samples, seed, maps, max_maps_per_pass, max_variants, pixel_shape: Tuple[int, int]):
+    """Validates the arguments of occlusion_shapley on the host (ValueError) before any device work -> (tile, max_exact, samples, seed,
+    maps, max_maps_per_pass, max_variants)."""
+    who = "occlusion_shapley"
+    tile, maps, max_maps_per_pass = check_args(tile, maps, max_maps_per_pass)
+    grid = (-(-pixel_shape[0] // tile[0]), -(-pixel_shape[1] // tile[1]))
+    if grid[0] * grid[1] > _lib.TSHAP_MAX_TILES:
+        raise ValueError(f"{who}: tiles of {tile} give {grid[0]} x {grid[1]} tiles per map, more than {_lib.TSHAP_MAX_TILES}")
+    if not (whole(max_exact) and 0 <= max_exact <= _lib.TSHAP_MAX_EXACT):
+        raise ValueError(f"{who}: max_exact must be an integer in 0..{_lib.TSHAP_MAX_EXACT}, got {max_exact!r}")
+    if not (whole(samples) and 1 <= samples <= _lib.TSHAP_MAX_SAMPLES):
+        raise ValueError(f"{who}: samples must be an integer in 1..{_lib.TSHAP_MAX_SAMPLES}, got {samples!r}")
+    if not (whole(seed) and 0 <= seed < 1 << 64):
+        raise ValueError(f"{who}: seed must be an integer in 0..2**64 - 1, got {seed!r}")
+    if max_variants is not None and not (whole(max_variants) and max_variants >= 1):
+        raise ValueError(f"{who}: max_variants must be None or a positive integer, got {max_variants!r}")
+    return tile, int(max_exact), int(samples), int(seed), maps, max_maps_per_pass, max_variants
+
+
+class TileShapley:
+    """The class score of every scanned map shared among its tiles that hold a hit.  Plain tensors, no autograd graph.
+
+    event_logits [B, Ce], prong_logits [B, P, Cp]      the prediction being explained (what forward() returns for the same input)
+    index int32 [V, 4]                                  (b, s, m, k) of every variant, ascending: map s of event b with only the hits of
+                                                        a coalition of its tiles.  Exact maps: m = 0 and k = 0 .. 2^n - 2 the coalition
+                                                        number (bit i: the i-th occupied tile in ascending ty * Wt + tx).  Sampled maps:
+                                                        (0, 0) the map without hits, (m, k >= 1) the first k tiles of permutation m
+    coalition_event_logits [V, Ce], coalition_prong_logits [V, P, Cp]   the prediction of event b under variant v
+    permutations int32 [B, 1 + P, samples, Ht * Wt]     the n occupied tiles of the map in the order of permutation m, then -1 (drawn
+                                                        for every map that holds a hit; the exact mode does not use them)
+    exact bool [B, 1 + P]                               which reading of (m, k) applies: 1 <= n <= max_exact
+    n_tiles int32 [B, 1 + P]                            n; -1 at padded slots and at maps not scanned
+    tile = (th, tw), grid = (Ht, Wt), samples, max_exact, seed"""
+
+    def __init__(self, event_logits: Tensor, prong_logits: Tensor, index: Tensor, coalition_event_logits: Tensor,
+                 coalition_prong_logits: Tensor, permutations: Tensor, exact: Tensor, n_tiles: Tensor, tile: Tuple[int, int],
+                 grid: Tuple[int, int], samples: int, max_exact: int, seed: int):
+        self.event_logits, self.prong_logits, self.index = event_logits, prong_logits, index
+        self.coalition_event_logits, self.coalition_prong_logits = coalition_event_logits, coalition_prong_logits
+        self.permutations, self.exact, self.n_tiles = permutations, exact, n_tiles
+        self.tile, self.grid, self.samples, self.max_exact, self.seed = tuple(tile), tuple(grid), int(samples), int(max_exact), int(seed)
+
+    @property
+    def num_variants(self) -> int:
+        return int(self.index.shape[0])
+
+    def values(self, target: Union[str, int, Tensor] = "event", value: str = "prob") -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+        """-> (phi, stderr float32 [B, 1 + P, Ht, Wt], full, empty float64 [B, 1 + P]) of the softmax probability ("prob") or the raw
+        logit ("logit") of the target class (as in heatmap).  phi: the Shapley value of every tile, exact or the mean over the
+        permutations; stderr: 0 (exact) or the standard error of that mean; full / empty: the value of the map as it is (from
+        event_logits / prong_logits) and without hits.  sum(phi) = full - empty per map.  phi and stderr are 0 at tiles without hits;
+        everything is NaN at padded slots, at maps not scanned and, with target "prong", in row s = 0."""
+        return shapley_values(self, target, value)
+
+    def heatmap(self, target: Union[str, int, Tensor] = "event") -> Tensor:
+        """phi of values(target, "prob") with 0 in its NaN rows: float32 [B, 1 + P, Ht, Wt], the shape occlusion_curves(relevance=...)
+        takes (at the same tile)."""
+        return torch.nan_to_num(shapley_values(self, target, "prob")[0], nan=0.0)
+
+
+def shapley_values(result: TileShapley, target: Union[str, int, Tensor] = "event", value: str = "prob"):
+    """tcvn_occlusion_shapley_values, see TileShapley.values."""
+    if value not in SHAPLEY_VALUES:
+        raise ValueError(f"occlusion_shapley: value must be one of {sorted(SHAPLEY_VALUES)}, got {value!r}")
+    rows = (result.event_logits, result.prong_logits, result.coalition_event_logits, result.coalition_prong_logits, result.index)
+    B, P, Ce, Cp, V, mode, classes = _compared_rows(*rows, target, "the tile Shapley values")
+    dev, (Ht, Wt), M = rows[0].device, result.grid, result.samples
+    n_tiles, perms = result.n_tiles, result.permutations
+    exact = result.exact.to(torch.int32).contiguous()
+    assert n_tiles.dtype == torch.int32 and n_tiles.is_contiguous() and n_tiles.shape == (B, 1 + P) and n_tiles.device == dev
+    assert perms.dtype == torch.int32 and perms.is_contiguous() and perms.shape == (B, 1 + P, M, Ht * Wt) and perms.device == dev
+    assert exact.shape == (B, 1 + P) and exact.device == dev
+    phi, se = torch.empty(B, 1 + P, Ht, Wt, device=dev), torch.empty(B, 1 + P, Ht, Wt, device=dev)
+    full, empty = (torch.empty(B, 1 + P, dtype=torch.float64, device=dev) for _ in range(2))
+    scratch = torch.empty(B * (1 + P) + V, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib.tcvn_occlusion_shapley_values(*map(_vp, rows), V, ptr(exact), ptr(n_tiles), ptr(perms), B, P, Ce, Cp, Ht, Wt, M,
+                                                          mode, _vp(classes), SHAPLEY_VALUES[value], ptr(phi), ptr(se), ptr(full),
+                                                          ptr(empty), ptr(scratch), scratch.numel() * 8, _stream()),
+                   "occlusion_shapley_values")
+    return phi, se, full, empty
+
+
 # ---- the scan driver ------------------------------------------------------------------------------------------------------------------------
 @dataclass(frozen=True)
 class HitList:
@@ -362,15 +453,18 @@ class VariantPlan:
 
 def plan_variants(lst: HitList, shape: Tuple[int, int], tile: Optional[Tuple[int, int]], max_pass: int,
                   keep_map: Optional[Tensor] = None, curve: Optional[tuple] = None,
-                  detector: Optional[tuple] = None) -> Tuple[HitList, VariantPlan]:
+                  detector: Optional[tuple] = None, shapley: Optional[tuple] = None) -> Tuple[HitList, VariantPlan]:
     """The variant list of one hit list (one host read-back): every tile that holds a hit, or (keep_map) the children of the selected
     tiles of the level above, or (curve = (relevance, steps, mode, rank), see the engine's occlusion_curve_variants) the steps of a
     deletion / insertion curve, or (detector = (effects,), see the engine's detector_variants; no tile) the maps under detector
-    effects.  -> (the list the plan is for, the plan): `lst` itself, or a cleaned copy if the engine found it unsorted or with hits
-    outside the maps -- the caller keeps that one for the later levels."""
+    effects, or (shapley = (samples, max_exact, seed, permutations, n_tiles, exact), see the engine's occlusion_shapley_variants) the
+    coalitions of the occupied tiles.  -> (the list the plan is for, the plan): `lst` itself, or a cleaned copy if the engine found it
+    unsorted or with hits outside the maps -- the caller keeps that one for the later levels."""
     def variants(hits):
         if detector is not None:
             return hits.engine.detector_variants(hits.coords, hits.values, hits.n_img, shape, hits.img_bs, max_pass, *detector)
+        if shapley is not None:
+            return hits.engine.occlusion_shapley_variants(hits.coords, hits.n_img, shape, tile, hits.img_bs, max_pass, *shapley)
         if curve is not None:
             return hits.engine.occlusion_curve_variants(hits.coords, hits.n_img, shape, tile, hits.img_bs, max_pass, *curve)
         if keep_map is None:
@@ -499,6 +593,27 @@ class Scan:
         parts = [self._passes(lst, plan, max_pass, lst.engine.occlusion_curve_build) for lst, plan in planned]
         index, step_ev, step_pr = self._merged(parts, (steps + 1, MAX_TILES + 1))
         return OcclusionCurves(self.ev, self.pr, index, step_ev, step_pr, rank, steps, mode, tile, grid)
+
+    def shapley(self, tile: Tuple[int, int], max_exact: int, samples: int, seed: int, max_pass: int,
+                max_variants: Optional[int]) -> "TileShapley":
+        """The coalitions of the occupied tiles of every scanned map (all of them up to max_exact tiles, else the prefixes of `samples`
+        permutations drawn on the device) through the same passes as a level's.  The lists come first: ValueError, before any variant
+        is run, if they hold more than max_variants variants together."""
+        dev, B, P = self.last.rows.device, self.last.B, self.last.P
+        grid = (-(-self.shape[0] // tile[0]), -(-self.shape[1] // tile[1]))
+        T = grid[0] * grid[1]
+        perms = torch.full((B, 1 + P, samples, T), -1, dtype=torch.int32, device=dev)
+        n_tiles = torch.full((B, 1 + P), -1, dtype=torch.int32, device=dev)
+        exact = torch.zeros(B, 1 + P, dtype=torch.int32, device=dev)
+        players = (samples, max_exact, seed, perms, n_tiles, exact)
+        planned = [plan_variants(lst, self.shape, tile, max_pass, shapley=players) for lst in self.lists]
+        self.lists = [lst for lst, _ in planned]
+        V = sum(plan.V for _, plan in planned)
+        if max_variants is not None and V > max_variants:
+            raise ValueError(f"occlusion_shapley: the scan needs V = {V} variants, more than max_variants = {max_variants}")
+        parts = [self._passes(lst, plan, max_pass, lst.engine.occlusion_shapley_build) for lst, plan in planned]
+        index, co_ev, co_pr = self._merged(parts, (samples, max(1 << max_exact, T + 1)))
+        return TileShapley(self.ev, self.pr, index, co_ev, co_pr, perms, exact.bool(), n_tiles, tile, grid, samples, max_exact, seed)
 
     def refine(self, tile: Tuple[int, int], levels: int, keep: float, target, max_pass: int,
                max_variants: Optional[int]) -> RefinedOcclusion:

@@ -426,6 +426,20 @@ class HipRuntime:
             scan = self._scan(maps, features, extra, event_px, event_mask, prong_px, prong_mask, counts)
             return scan.curves(relevance, tile, steps, mode, max_pass)
 
+    def forward_occlusion_shapley(self, features: Tensor, extra: Tensor, event_px: SparsePixels, event_mask: Tensor,
+                                  prong_px: SparsePixels, prong_mask: Tensor, counts: Optional[Tuple[int, int]] = None,
+                                  tile: Tuple[int, int] = (32, 32), max_exact: int = 6, samples: int = 16, seed: int = 0,
+                                  maps: str = "all", max_maps_per_pass: int = 256, max_variants: Optional[int] = None):
+        """Eval-mode forward() plus the tile Shapley scan over its pixel maps (occlusion.Scan.shapley: per map, the coalitions of the
+        tiles that hold a hit, all of them or the prefixes of `samples` permutations) -> occlusion.TileShapley."""
+        tile, max_exact, samples, seed, maps, max_pass, max_variants = occlusion.check_shapley_args(
+            tile, max_exact, samples, seed, maps, max_maps_per_pass, max_variants, self.pixel_shape)
+        if self.network.training:
+            raise RuntimeError("occlusion_shapley explains an eval-mode prediction: call network.eval() first")
+        with torch.no_grad():
+            scan = self._scan(maps, features, extra, event_px, event_mask, prong_px, prong_mask, counts)
+            return scan.shapley(tile, max_exact, samples, seed, max_pass, max_variants)
+
     def forward_detector_scan(self, features: Tensor, extra: Tensor, event_px: SparsePixels, event_mask: Tensor,
                               prong_px: SparsePixels, prong_mask: Tensor, counts: Optional[Tuple[int, int]] = None, effects=None,
                               scope: str = "event", maps: str = "all", max_maps_per_pass: int = 256):

@@ -234,6 +234,26 @@ class NeutrinoBaseNetwork(nn.Module):
         return self.hip_runtime().forward_occlusion_curves(features, extra, event_pixels, event_mask, prong_pixels, prong_mask, counts,
                                                            relevance, tile, steps, mode, maps, max_maps_per_pass)
 
+    @torch.jit.unused
+    def occlusion_shapley(self, features: Tensor, extra: Tensor, event_pixels: Tensor, event_mask: Tensor, prong_pixels: Tensor,
+                          prong_mask: Tensor, counts: Optional[Tuple[int, int]] = None, tile: Tuple[int, int] = (32, 32),
+                          max_exact: int = 6, samples: int = 16, seed: int = 0, maps: str = "all", max_maps_per_pass: int = 256,
+                          max_variants: Optional[int] = None):
+        """Eval mode only -> transformercvn.hip.occlusion.TileShapley: the Shapley value of every tile that holds a hit, the one tile
+        attribution whose scores sum to value(map as it is) - value(map without hits).  The players of a scanned map are its n
+        occupied tiles, a coalition is the map with only their hits (occlusion_maps' replacement).  Maps with 1 <= n <= max_exact
+        (0..10) run all 2^n - 1 coalitions but the full one; wider maps run the empty map and the prefixes of `samples` (1..256)
+        permutations drawn on the device from `seed`, and get a standard error.  max_variants: ValueError, before any variant runs, if
+        the scan needs more (it bounds the work, not the lists' memory: about 42 bytes x maps x samples x tiles per map are allocated
+        before the count is known).  result.values(target, value) -> (phi, stderr, full, empty); result.heatmap(target) -> phi."""
+        from transformercvn.hip import occlusion
+        occlusion.check_shapley_args(tile, max_exact, samples, seed, maps, max_maps_per_pass, max_variants, self.pixel_shape)
+        if self.training:
+            raise RuntimeError("occlusion_shapley explains an eval-mode prediction: call .eval() first")
+        event_pixels, prong_pixels = _as_sparse(event_pixels), _as_sparse(prong_pixels)
+        return self.hip_runtime().forward_occlusion_shapley(features, extra, event_pixels, event_mask, prong_pixels, prong_mask, counts,
+                                                            tile, max_exact, samples, seed, maps, max_maps_per_pass, max_variants)
+
     # ---- how far a prediction moves under detector effects (eager only; forward only, no autograd graph) -----------------------------
     @torch.jit.unused
     def detector_scan(self, features: Tensor, extra: Tensor, event_pixels: Tensor, event_mask: Tensor, prong_pixels: Tensor,

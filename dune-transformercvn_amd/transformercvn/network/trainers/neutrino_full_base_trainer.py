@@ -227,6 +227,22 @@ class NeutrinoFullBaseTrainer(NeutrinoBase, ABC):
                                                                    prong_coords, prong_values, prong_mask), None, relevance, tile,
                                              steps, mode, maps, max_maps_per_pass)
 
+    def occlusion_shapley(self, features: Tensor, extra: Tensor, event_coords: Tensor, event_values: Tensor, event_mask: Tensor,
+                          prong_coords: Tensor, prong_values: Tensor, prong_mask: Tensor, tile: Tuple[int, int] = (32, 32),
+                          max_exact: int = 6, samples: int = 16, seed: int = 0, maps: str = "all", max_maps_per_pass: int = 256,
+                          max_variants=None):
+        """Eval mode only -> TileShapley (transformercvn.hip.occlusion): a map's class score shared among its tiles that hold a hit;
+        see NeutrinoBaseNetwork.occlusion_shapley.  Bad arguments raise ValueError and train mode RuntimeError before any device
+        work."""
+        from transformercvn.hip import occlusion
+        occlusion.check_shapley_args(tile, max_exact, samples, seed, maps, max_maps_per_pass, max_variants,
+                                     self.training_dataset.pixel_shape)
+        if self.training:
+            raise RuntimeError("occlusion_shapley explains an eval-mode prediction: call .eval() first")
+        return self.network.occlusion_shapley(*self._network_inputs(features, extra, event_coords, event_values, event_mask,
+                                                                    prong_coords, prong_values, prong_mask), None, tile, max_exact,
+                                              samples, seed, maps, max_maps_per_pass, max_variants)
+
     def detector_scan(self, features: Tensor, extra: Tensor, event_coords: Tensor, event_values: Tensor, event_mask: Tensor,
                       prong_coords: Tensor, prong_values: Tensor, prong_mask: Tensor, effects, scope: str = "event", maps: str = "all",
                       max_maps_per_pass: int = 256):

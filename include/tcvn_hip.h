@@ -417,6 +417,63 @@ int tcvn_occlusion_curve(const float* event_logits, const float* prong_logits, c
                          int event_classes, int prong_classes, int steps, int target, const int32_t* classes, float* curve, float* auc,
                          void* stream);
 
+/* Tile Shapley values (forward only, eval arithmetic): the class score of a pixel map shared among its tiles.  For a scanned map (b, s)
+ * the players are its n tiles that hold at least one hit inside the map, tile index t = ty * grid_w + tx.  A coalition C is the map with
+ * only the hits of the tiles in C (all other hits removed, the survivors keep their order); every other token of event b stays as in the
+ * forward being explained, the replacement tcvn_occlusion_build_pass makes.  v(C) is the softmax probability (TCVN_SHAP_VALUE_PROB, double
+ * precision) or the raw logit (TCVN_SHAP_VALUE_LOGIT) of the target class under that variant; v(all) is taken from the logits of the
+ * forward itself, v(empty) is one variant per map.
+ *   exact    1 <= n <= max_exact (0..TCVN_TSHAP_MAX_EXACT): all coalitions but the full one are variants, numbered k = 0 .. 2^n - 2, bit i
+ *            of k being the i-th occupied tile in ascending tile index.  phi[t] = sum over C without t of |C|! (n-|C|-1)! / n! *
+ *            (v(C + t) - v(C)), stderr = 0.
+ *   sampled  n > max_exact: `samples` (1..TCVN_TSHAP_MAX_SAMPLES) permutations.  Permutation m of map (b, s) is its occupied tiles sorted
+ *            by (key, t), key = word 0 of the Philox-4x32-10 of the dropout masks at counter (t, m, b * (1 + max_prongs) + s, 0x54534850)
+ *            under (seed & 0xffffffff, seed >> 32).  Variants: the empty map, then for every m the prefixes of length 1 .. n - 1.
+ *            phi[t] = mean over m of v(prefix up to and including t) - v(prefix before t); stderr[t] = the sample standard deviation of
+ *            those contributions / sqrt(samples), 0 for samples = 1.
+ * A map contributes 2^n - 1 (exact) or 1 + samples * (n - 1) (sampled) variants, a map without hits none.  In both modes sum_t phi[t] =
+ * v(all) - v(empty): it telescopes per permutation.
+ *   shapley_variants  the hit list of tcvn_occlusion_variants -> the V variants ordered by (image, m, k): vimg [V] the image, index [V, 4] =
+ *            (img_bs[image][0], img_bs[image][1], m, k): exact maps m = 0 and k the coalition number; sampled maps (0, 0) the empty map and
+ *            (m, k), k >= 1, prefix k of permutation m.  Both need room for n_img * max(2^max_exact - 1, 1 + samples * (grid_h * grid_w - 1))
+ *            rows; host_out has 4 + ceil(that / max_pass) + 1 words with the meaning, the two flags and the one synchronisation of
+ *            tcvn_occlusion_variants.  At (b, s) = img_bs[image] the call writes permutations [batch, 1 + max_prongs, samples, grid_h *
+ *            grid_w] (the n tiles of permutation m in front, -1 behind; drawn for every map that holds a hit, whichever its mode), n_tiles
+ *            [batch, 1 + max_prongs] = n and exact [batch, 1 + max_prongs] = (1 <= n <= max_exact).  The caller fills them with -1, -1 and
+ *            0 first and may call once per hit list.  One workgroup per (map, m) sorts the 64-bit words (key << 32 | t) in LDS: grid_h *
+ *            grid_w <= TCVN_TSHAP_MAX_TILES.  The workspace holds the rank of every tile in every permutation (n_img x samples x tiles
+ *            16-bit words) and the hit counts of every prefix.
+ *   shapley_build  tcvn_occlusion_build_pass for these variants: a hit survives iff its tile's bit is set in k (exact) or its tile stands
+ *            in front of position k of permutation m (sampled).  The result goes through the embedder and tcvn_head_occlusion unchanged.
+ *   shapley_values  the base logits, the variants' logits coalition_event_logits [V, Ce] / coalition_prong_logits [V, max_prongs, Cp], index
+ *            (ordered by map; the lists of several calls merged), exact, n_tiles and permutations -> phi and std_err float32 [batch, 1 +
+ *            max_prongs, grid_h, grid_w], full = v(all) and empty = v(empty) float64 [batch, 1 + max_prongs].  target and classes as in
+ *            tcvn_occlusion_heatmap.  phi and std_err are 0 at tiles without hits of scanned maps (a map with n = 0 is all 0, and its empty
+ *            = full); all four are NaN where n_tiles < 0 (padded slots, maps not scanned) and in row s = 0 with TCVN_OCC_TARGET_PRONG.
+ *            The exact weights are an fp64 table, every sum is taken in double in a fixed order and rounded to float32 once; there is no
+ *            floating-point atomic.  scratch: 8 * (batch * (1 + max_prongs) + n_variants) bytes.
+ * Argument errors (NULL, tile < 1, samples, max_exact or the tiles per map out of range, max_pass outside 1..TCVN_OCC_MAX_PASS, workspace
+ * or scratch too small) return non-zero before any device call and print one "tcvn:" line. */
+#define TCVN_TSHAP_MAX_TILES 1024
+#define TCVN_TSHAP_MAX_SAMPLES 256
+#define TCVN_TSHAP_MAX_EXACT 10
+int64_t tcvn_occlusion_shapley_workspace_bytes(int n_img, int height, int width, int tile_h, int tile_w, int samples, int max_exact,
+                                               int max_pass);
+int tcvn_occlusion_shapley_variants(const int32_t* coords, int64_t nnz, int n_img, int height, int width, int tile_h, int tile_w,
+                                    const int32_t* img_bs, int batch, int max_prongs, int samples, int max_exact, uint64_t seed,
+                                    int32_t* permutations, int32_t* n_tiles, int32_t* exact, int max_pass, int32_t* vimg, int32_t* index,
+                                    void* workspace, int64_t workspace_bytes, int64_t* host_out, int64_t host_cap, void* stream);
+int tcvn_occlusion_shapley_build(const int32_t* coords, const float* values, int64_t nnz, int channels, int n_img, int height, int width,
+                                 int tile_h, int tile_w, int samples, int max_exact, int max_pass, const int32_t* vimg,
+                                 const void* workspace, int64_t workspace_bytes, int first, int count, int32_t* out_coords,
+                                 float* out_values, int64_t out_rows, void* stream);
+int tcvn_occlusion_shapley_values(const float* event_logits, const float* prong_logits, const float* coalition_event_logits,
+                                  const float* coalition_prong_logits, const int32_t* index, int64_t n_variants, const int32_t* exact,
+                                  const int32_t* n_tiles, const int32_t* permutations, int batch, int max_prongs, int event_classes,
+                                  int prong_classes, int grid_h, int grid_w, int samples, int target, const int32_t* classes, int value,
+                                  float* phi, float* std_err, double* full, double* empty, void* scratch, int64_t scratch_bytes,
+                                  void* stream);
+
 /* Detector-effect scans (forward only, eval arithmetic): how a prediction moves when the hits are not those of the detector the training
  * sample assumed.  A variant is a map whose hits went through one effect; unlike the occlusion variants it transforms coordinates and
  * values.  One effect acts on every hit (y, x, v[0..channels)) of the map (b, s) = img_bs[image] in this order -- the detector acts, then

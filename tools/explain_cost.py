@@ -4,6 +4,7 @@ interleaved, and prints one JSON line with the medians.  occlusion_maps() is tim
 its number of variants V and of embedder passes (a scan is thousands of maps: it gets --occ-reps repetitions of its own), and beside
 them occlusion_refine(tile=(64, 64), levels=4) -- the same 8x8 grid, coarse to fine -- for every --keep, with V per level.
 occlusion_curves(steps=10) on the 16x16 heat map is timed with its V = 11 x maps (the 16x16 scan that gives the heat map is not in it).
+occlusion_shapley(tile=(32, 32)) with its default keywords is timed with its V, beside the flat 32x32 scan of the same run.
 prong_shapley() is timed with its default keywords and with max_exact=12, beside leave_one_prong_out: the whole call (forward() included)
 and the coalition scan alone on the same tokens, with the number of coalitions and of encoder passes.
 mc_dropout() is timed at samples = 8 and 32, with and without reuse_stem: the whole call (forward() and the statistics included) and,
@@ -109,6 +110,14 @@ def main():
         out["occlusion_curves_16x16_steps10"] = {
             "variants": res.num_variants, "maps": res.num_variants // 11, "reps": args.occ_reps, "ms": ms(ts),
             "us_per_variant": round(1e3 * statistics.median(ts) / max(1, res.num_variants), 2)}
+        res, ts = timed(lambda: model.occlusion_shapley(*inputs[:8], tile=(32, 32)))
+        flat = out["occlusion_maps_32x32"]
+        out["occlusion_shapley_32x32"] = {
+            "variants": res.num_variants, "maps": int((res.n_tiles > 0).sum()), "exact_maps": int(res.exact.sum()),
+            "max_exact": res.max_exact, "samples": res.samples, "reps": args.occ_reps, "ms": ms(ts),
+            "us_per_variant": round(1e3 * statistics.median(ts) / max(1, res.num_variants), 2),
+            "flat_scan_32x32_variants": flat["variants"], "flat_scan_32x32_ms": flat["ms"]["median"],
+            "over_flat_scan_32x32": round(statistics.median(ts) / flat["ms"]["median"], 2)}
     for keep in args.keep if args.occ_reps > 0 else ():
         res, ts = timed(lambda: model.occlusion_refine(*inputs[:8], tile=(64, 64), levels=4, keep=keep))
         out[f"occlusion_refine_64x64_levels4_keep{keep:g}"] = {
