@@ -315,12 +315,12 @@ __device__ __forceinline__ void for_each_band(const StemSparseArgs& a, const Ban
     }
 }
 
-// conv0 weights -> LDS [147][64] bf16 (k = (ky*7 + kx)*3 + c), bias
+// conv0 weights -> LDS [147][64] bf16 (k = (ky*7 + kx)*3 + c; packed as k = (ky*7 + kx)*Cpix + c: zero for c >= Cpix), bias
 __device__ __forceinline__ void load_weights(const StemSparseArgs& a, const BandLds& L, int tid) {
     const bf16* Wk = reinterpret_cast<const bf16*>(a.Wk);
     for (int i = tid; i < SS_K * SS_N; i += 256) {
-        const int k = i >> 6, n = i & 63;
-        L.wl[i] = Wk[(long)n * a.Kp + k];
+        const int k = i >> 6, n = i & 63, tap = k / 3, c = k - tap * 3;
+        L.wl[i] = c < a.Cpix ? Wk[(long)n * a.Kp + tap * a.Cpix + c] : (bf16)0;
     }
     if (tid < SS_N) L.bias[tid] = a.bias[tid];
 }
@@ -617,10 +617,10 @@ __global__ __launch_bounds__(256, 2) void k_stem_sparse_bwd_wgrad(const StemSpar
         }
     });
     __syncthreads();
-    float* out = a.slab + (long)blockIdx.x * SS_N * a.Kp;                  // slab[block][n][Kp], k = (ky*7 + kx)*3 + c
+    float* out = a.slab + (long)blockIdx.x * SS_N * a.Kp;                  // slab[block][n][Kp], k = (ky*7 + kx)*Cpix + c
     for (int i = tid; i < SS_N * a.Kp; i += 256) {
-        const int nn = i / a.Kp, k = i - nn * a.Kp;
-        out[i] = k < SS_K ? wsum[k * SS_N + nn] : 0.f;
+        const int nn = i / a.Kp, k = i - nn * a.Kp, tap = k / a.Cpix, c = k - tap * a.Cpix;
+        out[i] = tap < 49 ? wsum[(tap * 3 + c) * SS_N + nn] : 0.f;
     }
 }
 
@@ -698,7 +698,7 @@ int stem_sparse_bwd(const StemSparseArgs& a, StemPass pass, hipStream_t st) {
     if (pass == StemPass::BwdSums) return launch_pass(k_stem_sparse_bwd_sums, pass, "k_stem_sparse_bwd<sums>", 2.0 * a.nnz * 12.25 * a.Cpix * SS_N, bytes, a, st);
     if (pass != StemPass::BwdWgrad) return -1;
     const int nb = stem_sparse_plan(a, pass).grid;
-    if (a.slab == nullptr || (long)nb * SS_N * a.Kp * 4 > a.slab_bytes || a.Kp < SS_K) return -3;
+    if (a.slab == nullptr || (long)nb * SS_N * a.Kp * 4 > a.slab_bytes || a.Kp < 49 * a.Cpix) return -3;
     int rc;
     if ((rc = launch_pass(k_stem_sparse_bwd_wgrad, pass, "k_stem_sparse_bwd<wgrad>", 4.0 * a.nnz * 12.25 * a.Cpix * SS_N, bytes, a, st))) return rc;
     return slab_reduce(a.slab, nb, (long)SS_N * a.Kp, a.dWk, st);

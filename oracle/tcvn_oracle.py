@@ -309,7 +309,7 @@ def synthetic_batch(prongs_per_event: List[int], seed: int, cfg=None, max_prongs
             flat.sort()
             y, x = flat // W, flat % W
             coords.append(np.stack([np.full(nnz, i), y, x], 1))
-            vals.append(rng.integers(1, 256, size=(nnz, 3)).astype(np.float32))
+            vals.append(rng.integers(1, 256, size=(nnz, cfg.pixel_dim)).astype(np.float32))
         return (torch.from_numpy(np.concatenate(coords).astype(np.int32)),
                 torch.from_numpy(np.concatenate(vals)))
 

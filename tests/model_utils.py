@@ -13,6 +13,16 @@ def build_trainer(cfg, state=None, precision="fp32", device="cuda", train_file="
     o.hip_precision = precision
     o.batch_size = 2
     o.num_dataloader_workers = 0
+    pixel_features = getattr(cfg, "pixel_dim", 3)
+    if pixel_features != 3:                  # the network takes its channel count from the dataset: give the synthetic one cfg's
+
+        class NeutrinoFullDenseTrainer(NeutrinoFullDenseTrainer):
+            def create_datasets(self):
+                sets = super().create_datasets()
+                for ds in sets:
+                    if ds is not None:
+                        ds.pixel_features = pixel_features
+                return sets
     m = NeutrinoFullDenseTrainer(o)
     if state is not None:
         res = m.load_state_dict(state, strict=True)

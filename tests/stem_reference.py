@@ -82,13 +82,17 @@ C_CONV0 = 1
 
 def conv0(img, w, b, rnd, defect=None):
     """7x7, stride 2, pad 3 over the map as the kernel holds it (the `img` tap: already bf16 values in bf16 mode), bf16 weights in bf16
-    mode.  One fp32 fma chain over the 147 products (the MFMA is one; the padded contraction slots of k_stem_fwd2_bf16, stem.hip:500,
+    mode.  One fp32 fma chain over the K = 49 Cpix products (147 at three channels; the MFMA is one; the padded contraction slots of
+    k_stem_fwd2_bf16, stem.hip:500, and the sparse kernels' slots of the channels a map does not have, stem_sparse.hip load_weights,
     multiply zero weights: exact) plus c = 1 further operation, the bias add (stem.hip:582; generic k_conv_fwd, conv_fwd.hip:104; the
-    sparse kernels start the chain AT the bias, stem_sparse.hip:346: no more roundings): delta = R(147 + 1) S, S = sum |a_k| |w_k| + |b|.
+    sparse kernels start the chain AT the bias, stem_sparse.hip:346: no more roundings): delta = R(K + 1) S, S = sum |a_k| |w_k| + |b|.
     A position no hit reaches has S = |b| and ref = b: with the store rule it must be the stored-precision bias exactly (bias_exact).
-    defects: "drop_tap" (tap (2, 5) of input channel 1 missing), "transpose" (ky and kx swapped).  -> ref [n, Hc, Wc, N], delta."""
+    defects: "drop_tap" (tap (2, 5) of input channel 1 missing), "transpose" (ky and kx swapped), "tap3" (the weights read with a tap
+    stride of 3 out of the packed rows, whatever Cpix is: tap3_weights).  -> ref [n, Hc, Wc, N], delta."""
     w = bf16(w) if rnd else w
     wk = w
+    if defect == "tap3":
+        wk = tap3_weights(w)
     if defect == "drop_tap":
         wk = w.clone(); wk[:, 1, 2, 5] = 0
     if defect == "transpose":
@@ -96,7 +100,38 @@ def conv0(img, w, b, rnd, defect=None):
     x = img.permute(0, 3, 1, 2)
     ref = F.conv2d(x, wk, b, stride=2, padding=3).permute(0, 2, 3, 1).contiguous()
     S = F.conv2d(x.abs(), w.abs(), b.abs(), stride=2, padding=3).permute(0, 2, 3, 1).contiguous()
-    return ref, R(147 + C_CONV0) * S
+    return ref, R(49 * w.shape[1] + C_CONV0) * S
+
+
+def packed_rows(w):
+    """conv0 weight [N, Cpix, 7, 7] as k_pack lays it out (elementwise.hip:383-414): one row per output channel, k = tap * Cpix + c, padded
+    with zeros to Kp = round_up(49 Cpix, 32).  -> [N, Kp]."""
+    N, C = w.shape[:2]
+    Kp = -(-49 * C // 32) * 32
+    rows = torch.zeros(N, Kp, dtype=w.dtype)
+    rows[:, :49 * C] = w.permute(0, 2, 3, 1).reshape(N, 49 * C)
+    return rows
+
+
+def tap3_weights(w):
+    """The weights a kernel contracts with when it reads the packed rows as k = tap * 3 + c: w'[n][c][tap] = flat[n Kp + tap * 3 + c].  At
+    Cpix = 3 the weights themselves; below, every tap but the first takes another tap's weights and the last taps run on into the row's
+    padding and the next row (zero past the last row).  -> [N, Cpix, 7, 7]."""
+    N, C = w.shape[:2]
+    rows = packed_rows(w)
+    flat = torch.cat([rows.flatten(), torch.zeros(147, dtype=w.dtype)])
+    idx = (torch.arange(N)[:, None, None] * rows.shape[1] + torch.arange(49)[None, None, :] * 3 + torch.arange(C)[None, :, None])
+    return flat[idx].reshape(N, C, 7, 7)
+
+
+def tap3_wgrad(dW):
+    """The weight gradient a kernel leaves when it stores its [tap * 3 + c] table into the packed row as it stands (slot k of the row takes
+    table entry k): read back as k = tap * Cpix + c, dW'[n][c][tap] = dW[n][k % 3][k // 3] where k % 3 < Cpix, else 0.  At Cpix = 3 dW itself."""
+    N, C = dW.shape[:2]
+    k = torch.arange(49)[None, :] * C + torch.arange(C)[:, None]                        # [C, 49]
+    tab = torch.zeros(N, 3, 49, dtype=dW.dtype)
+    tab[:, :min(C, 3)] = dW.reshape(N, C, 49)[:, :3]
+    return tab[:, k % 3, k // 3].reshape(N, C, 7, 7)
 
 
 def conv0_from_hits(coords, values, n, H, W, mode, w, b, rnd):
@@ -119,7 +154,7 @@ def conv0_from_hits(coords, values, n, H, W, mode, w, b, rnd):
             pos = ((im * Hc + ty // 2) * Wc + tx // 2)[ok]
             ref.index_add_(0, pos, val[ok] @ w[:, :, ky, kx].T)
             S.index_add_(0, pos, val[ok].abs() @ w[:, :, ky, kx].abs().T)
-    return ref.reshape(n, Hc, Wc, N), (R(147 + C_CONV0) * S).reshape(n, Hc, Wc, N)
+    return ref.reshape(n, Hc, Wc, N), (R(49 * w.shape[1] + C_CONV0) * S).reshape(n, Hc, Wc, N)
 
 
 def bias_exact(c0_stored, act, b, rnd):
@@ -286,8 +321,8 @@ CASE_SHAPES = {"partial": ((104, 72), 3), "odd": ((45, 37), 3), "dense-band": ((
                "many-tiny": ((12, 16), 1030), "wide-limit": ((24, 384), 2)}
 
 
-def case_hits(name, seed=7):
-    """-> coords int32 [nnz, 3], values fp32 [nnz, 3] (integers 1 .. 255), n_img, (H, W).
+def case_hits(name, seed=7, cpix=3):
+    """-> coords int32 [nnz, 3], values fp32 [nnz, cpix] (integers 1 .. 255; the coordinates do not depend on cpix), n_img, (H, W).
     partial: all four corners, both borders, one EMPTY map, entries outside the maps (image -1, image n, y == H, x == W) and 40 pixels
     listed twice with different values, everything shuffled.  dense-band: every pixel of rows 8 .. 31, columns 100 .. 219 of map 0.
     many / many-tiny: 5 .. 40 / 1 .. 6 hits per map.  wide-limit: the sparse stem's widest map, hits in the first and last column."""
@@ -315,5 +350,5 @@ def case_hits(name, seed=7):
         outside = np.array([(-1, 5, 5), (n, 0, 0), (0, H, 3), (2, 4, W), (0, -1, 2), (2, 7, -1)])
         coords = np.concatenate([coords, coords[dup], outside])
         coords = coords[rng.permutation(len(coords))]
-    values = rng.integers(1, 256, size=(len(coords), 3)).astype(np.float32)
+    values = rng.integers(1, 256, size=(len(coords), cpix)).astype(np.float32)
     return torch.from_numpy(coords.astype(np.int32)), torch.from_numpy(values), n, (H, W)

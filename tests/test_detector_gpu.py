@@ -52,10 +52,11 @@ def list_effects():
             E(scale=0.5, threshold=40.0, dead_rows=(3, 6), dead_cols=(10, 14), drop=0.3, shift=(2, -3), seed=7)]
 
 
-def synthetic_list():
+def synthetic_list(channels=CHANNELS):
     """Five maps of 40 x 28 with 0, 1, 255, 256 and 700 hits, sorted by map, uint8-like values; hit 40 of the 255-hit map repeats the
-    pixel of hit 7, and 700 hits on 1 120 pixels collide on their own."""
-    if "list" not in _cache:
+    pixel of hit 7, and 700 hits on 1 120 pixels collide on their own.  (The same hits at every channel count.)"""
+    key = "list" if channels == CHANNELS else f"list {channels}"
+    if key not in _cache:
         g = torch.Generator().manual_seed(21)
         rows = []
         for img, n in enumerate(COUNTS):
@@ -65,11 +66,11 @@ def synthetic_list():
                 c[40, 1:] = c[7, 1:]
             rows.append(c)
         coords = torch.cat(rows).int()
-        values = torch.randint(0, 256, (coords.shape[0], CHANNELS), generator=g).float()
+        values = torch.randint(0, 256, (coords.shape[0], channels), generator=g).float()
         big = coords[coords[:, 0] == 4]
         assert len({(y, x) for _, y, x in big.tolist()}) < 700 and coords.shape[0] == sum(COUNTS)
-        _cache["list"] = (coords, values)
-    return _cache["list"]
+        _cache[key] = (coords, values)
+    return _cache[key]
 
 
 def device_variants(coords, values, effects, max_pass, n_img=5, img_bs=MAPS5):
@@ -88,7 +89,7 @@ def device_variants(coords, values, effects, max_pass, n_img=5, img_bs=MAPS5):
     words = 4 + -(-rows // max_pass) + 1
     host = (C.c_int64 * words)(*([-7] * words))
     table = detector.effect_table(effects)
-    rc = lib.tcvn_detector_variants(ptr(d_coords), coords.shape[0], n_img, *SHAPE, CHANNELS, ptr(d_values), ptr(d_bs), table, K, max_pass,
+    rc = lib.tcvn_detector_variants(ptr(d_coords), coords.shape[0], n_img, *SHAPE, values.shape[1], ptr(d_values), ptr(d_bs), table, K, max_pass,
                                     ptr(vimg), ptr(index), ptr(ws), ws.numel(), host, words, stream_ptr())
     for k in range(K):                       # the caller's array is not read after the call: overwrite it before any build pass
         table[k].scale, table[k].drop, table[k].shift_x = 123.0, 1.0, 9
@@ -100,17 +101,18 @@ def check_passes(ref, vimg, index, ws, on_device, K, max_pass, n_img=5):
     from transformercvn.hip._lib import lib
     from transformercvn.hip.native import ptr, stream_ptr
     d_coords, d_values, d_bs = on_device
+    channels = d_values.shape[1]
     V, bounds = ref["header"][0], ref["bounds"]
     for k in range(-(-V // max_pass)):
         first, count, n = k * max_pass, min(max_pass, V - k * max_pass), bounds[k + 1] - bounds[k]
         if n == 0:
             continue
         out_coords = torch.full((n + GUARD, 3), -7, dtype=torch.int32, device=d_coords.device)
-        out_values = torch.full((n + GUARD, CHANNELS), -7.0, device=d_coords.device)
-        assert lib.tcvn_detector_build_pass(ptr(d_coords), ptr(d_values), d_coords.shape[0], CHANNELS, n_img, *SHAPE, ptr(d_bs), K, max_pass,
+        out_values = torch.full((n + GUARD, channels), -7.0, device=d_coords.device)
+        assert lib.tcvn_detector_build_pass(ptr(d_coords), ptr(d_values), d_coords.shape[0], channels, n_img, *SHAPE, ptr(d_bs), K, max_pass,
                                             ptr(vimg), ptr(ws), ws.numel(), first, count, ptr(out_coords), ptr(out_values), n + GUARD,
                                             stream_ptr()) == 0
-        want_coords, want_values = DR.pass_reference(ref, first, count, CHANNELS)
+        want_coords, want_values = DR.pass_reference(ref, first, count, channels)
         assert want_coords.shape[0] == n
         assert torch.equal(out_coords[:n].cpu(), want_coords), f"pass {k}: coords"
         assert torch.equal(out_values[:n].cpu(), want_values), f"pass {k}: values"
@@ -150,6 +152,25 @@ def test_variant_list_and_hit_lists_are_exact(max_pass):
     assert torch.equal(vimg[:V].cpu(), ref["vimg"]) and bool((vimg[V:] == -7).all())
     assert torch.equal(index[:V].cpu(), ref["index"]) and bool((index[V:] == -7).all())
     assert ref["index"][ref["index"][:, 2] == 3][:, 3].tolist() == [0, 0, 0, 0], "dead rows over the whole map: empty variants"
+    check_passes(ref, vimg, index, ws, on_device, K, max_pass)
+
+
+@pytest.mark.parametrize("channels", [1, 4])
+def test_variant_list_and_hit_lists_are_exact_at_other_channel_counts(channels):
+    """The same lists with one and four value channels per hit: the threshold's "any channel left" rule and the build pass's value rows
+    (hit * channels + c) against the reference, exactly as at three."""
+    coords, values = synthetic_list(channels)
+    assert values.shape[1] == channels and torch.equal(coords, synthetic_list()[0])
+    effects, max_pass = list_effects(), 3
+    K = len(effects)
+    ref = DR.list_reference(coords, values, 5, SHAPE, MAPS5, effects, max_pass)
+    at, _, v = DR.apply_effect(coords, values, MAPS5, effects[2], SHAPE)
+    assert {int(n) for n in (v != 0).sum(1).tolist()} == set(range(1, channels + 1)) and 0 < at.numel() < coords.shape[0]
+    host, vimg, index, ws, on_device = device_variants(coords, values, effects, max_pass)
+    V = ref["header"][0]
+    assert V == 4 * K and host[:4] == ref["header"] and host[4:] == ref["bounds"]
+    assert torch.equal(vimg[:V].cpu(), ref["vimg"]) and bool((vimg[V:] == -7).all())
+    assert torch.equal(index[:V].cpu(), ref["index"]) and bool((index[V:] == -7).all())
     check_passes(ref, vimg, index, ws, on_device, K, max_pass)
 
 

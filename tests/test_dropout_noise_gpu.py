@@ -184,3 +184,35 @@ def test_token_path_dropout_sites_bf16_step_matches_statistics():
         for j in range(i + 1, len(masks)):
             agree = (masks[i] == masks[j]).float().mean().item()
             assert abs(agree - 0.82) < 0.02, (sites[i], sites[j], agree)
+
+
+@pytest.mark.parametrize("cpix", [1, 2])
+def test_pixel_noise_at_other_channel_counts(cpix):
+    """One fp32 train forward of a prong embedder alone with 1 and 2 value channels per hit (k_scatter draws at hit * Cpix + c): the
+    factors recovered from the map are N(0,1) * std -- mean within 4 / sqrt(n), standard deviation within 4 / sqrt(2 n) -- and
+    consecutive draws, and the two channels of a hit, are drawn apart (sample correlation within 4 / sqrt(pairs))."""
+    from test_densenet_gpu import _engine
+    std = 0.001
+    cfg = O.tutorial_config(pixel_dim=cpix, pixel_shape=(104, 72), densenet_structure=[1], initial_pixel_dim=16, num_encoder_layers=1,
+                            dropout=0.0, pixel_noise_std=std)
+    batch = O.synthetic_batch([4], 23, cfg, event_hits=(100, 200), prong_hits=(1000, 1500))
+    coords, values = batch[5], batch[6]
+    assert values.shape[1] == cpix and coords.shape[0] >= 4000
+    eng, _, _ = _engine(cfg, O.fill_state(cfg, 7), mode=0)
+    out = torch.empty(4, eng.out_dim, device="cuda")
+    eng.forward(coords.cuda(), values.cuda(), 4, out, train=True, seed=29, noise_std=std)
+    torch.cuda.synchronize()
+    assert tuple(eng.tap("img").shape) == (4, 104, 72, cpix)
+    z = _noise_from_map(eng, coords, values, std).double()
+    n = z.numel()
+    print(f"pixel noise draws at Cpix {cpix}: n {n} mean {z.mean():.4f} std {z.std():.4f} |max| {z.abs().max():.2f}")
+    assert abs(z.mean()) < 4 / n ** 0.5 and abs(z.std() - 1) < 4 / (2 * n) ** 0.5 and z.abs().max() < 6
+    corr = lambda a, b: float(((a - a.mean()) * (b - b.mean())).sum() / ((a - a.mean()).norm() * (b - b.mean()).norm()))
+    flat = z.flatten()                                        # consecutive draws (list order, channel fastest) are drawn apart
+    lag = corr(flat[:-1], flat[1:])
+    print(f"    correlation of consecutive draws {lag:.4f}")
+    assert abs(lag) < 4 / n ** 0.5
+    if cpix == 2:                                             # ... and so are the two channels of a hit
+        both = corr(z[:, 0], z[:, 1])
+        print(f"    correlation of the two channels' draws {both:.4f}")
+        assert abs(both) < 4 / z.shape[0] ** 0.5

@@ -220,8 +220,8 @@ def test_one_embedder_alone(precision):
 
 
 # ---- 4. the gather kernel alone --------------------------------------------------------------------------------------------------------
-def gather_case():
-    H, W, N, C = 20, 12, 64, 3
+def gather_case(C=3):
+    H, W, N = 20, 12, 64
     g = torch.Generator().manual_seed(4)
     hits = [(0, 0, 0), (0, 0, W - 1), (0, H - 1, 0), (0, H - 1, W - 1), (1, 0, 0), (1, H - 1, W - 1)]
     hits += [(0, 7, x) for x in range(W)]                                   # a full row
@@ -234,23 +234,21 @@ def gather_case():
     return (H, W), coords, values, e0, w0
 
 
-@pytest.mark.parametrize("value_mode", [0, 1, 2])
-def test_gather_kernel_alone(value_mode):
-    """Both instances of k_hit_gradient through the C entry.  bf16: E0 is rounded to bf16 before either side sees it (the kernel reads
-    2-byte elements at a row stride of N of them); the gate is the same."""
+def _gather_kernel_alone(value_mode, cpix):
     from transformercvn.hip import gradients
     from transformercvn.hip._lib import lib, check, MODE_F32, MODE_BF16
     from transformercvn.hip.native import ptr, stream_ptr
-    shape, coords, values, e0_f32, w0 = gather_case()
+    shape, coords, values, e0_f32, w0 = gather_case(cpix)
+    assert values.shape[1] == cpix and w0.shape[1] == cpix
     own = torch.tensor(R.owners(coords, 2, *shape))
     assert (~own).sum() == 4
     c, v, w = coords.cuda(), values.cuda(), w0.cuda()
-    ws = torch.empty(lib.tcvn_hit_gradient_workspace_bytes(2, *shape, 3), dtype=torch.uint8, device="cuda")
+    ws = torch.empty(lib.tcvn_hit_gradient_workspace_bytes(2, *shape, cpix), dtype=torch.uint8, device="cuda")
     for mode, e0 in ((MODE_F32, e0_f32), (MODE_BF16, e0_f32.to(torch.bfloat16))):
         ref = R.gather(e0, w0, coords, values, shape, value_mode)
         e = e0.cuda().contiguous()
         out = torch.full_like(v, float("nan"))
-        check(lib.tcvn_hit_gradient_gather(mode, ptr(c), ptr(v), c.shape[0], 2, *shape, 3, value_mode, ptr(e), 64, 64, ptr(w), ptr(out), ptr(ws),
+        check(lib.tcvn_hit_gradient_gather(mode, ptr(c), ptr(v), c.shape[0], 2, *shape, cpix, value_mode, ptr(e), 64, 64, ptr(w), ptr(out), ptr(ws),
                                            ws.numel(), stream_ptr()), "hit_gradient_gather")
         torch.cuda.synchronize()
         got = out.cpu()
@@ -258,8 +256,34 @@ def test_gather_kernel_alone(value_mode):
         assert torch.isfinite(got).all()                                    # every hit written (the output starts as NaN)
         assert (got[~own] == 0).all() and (ref[own] != 0).all()
         rel = ((got.double() - ref).abs() / ref.abs())[own]
-        print(f"hit_gradients[gather {'bf16' if mode == MODE_BF16 else 'fp32'} mode {value_mode}] worst relative error per element {float(rel.max()):.3e}")
+        print(f"hit_gradients[gather {'bf16' if mode == MODE_BF16 else 'fp32'} mode {value_mode} Cpix {cpix}] worst relative error per element {float(rel.max()):.3e}")
         assert float(rel.max()) <= 1e-5
+
+
+@pytest.mark.parametrize("value_mode", [0, 1, 2])
+def test_gather_kernel_alone(value_mode):
+    """Both instances of k_hit_gradient through the C entry.  bf16: E0 is rounded to bf16 before either side sees it (the kernel reads
+    2-byte elements at a row stride of N of them); the gate is the same."""
+    _gather_kernel_alone(value_mode, 3)
+
+
+@pytest.mark.parametrize("value_mode", [0, 1, 2])
+@pytest.mark.parametrize("cpix", [1, 2, 4])
+def test_gather_kernel_alone_at_other_channel_counts(cpix, value_mode):
+    """The same list with 1, 2 and 4 value channels per hit (HG_MAXC = 4): the kernel indexes hit * Cpix + lane and c * 49 * N + co."""
+    _gather_kernel_alone(value_mode, cpix)
+
+
+def test_gather_kernel_refuses_five_channels():
+    from transformercvn.hip._lib import lib, MODE_F32
+    from transformercvn.hip.native import ptr, stream_ptr
+    (H, W), coords, values, e0, w0 = gather_case(5)
+    c, v, e, w = coords.cuda(), values.cuda(), e0.cuda(), w0.cuda()
+    ws = torch.empty(lib.tcvn_hit_gradient_workspace_bytes(2, H, W, 5), dtype=torch.uint8, device="cuda")
+    out = torch.full_like(v, float("nan"))
+    rc = lib.tcvn_hit_gradient_gather(MODE_F32, ptr(c), ptr(v), c.shape[0], 2, H, W, 5, 0, ptr(e), 64, 64, ptr(w), ptr(out), ptr(ws), ws.numel(), stream_ptr())
+    torch.cuda.synchronize()
+    assert rc == -2 and torch.isnan(out).all()                              # refused in front of the gather's launch: nothing written
 
 
 def test_gather_kernel_writes_every_hit_and_refuses_one_hot():

@@ -110,8 +110,8 @@ def check_list(coords, values, n_img, shape, tile, img_bs, max_pass, keep_map=No
         if n == 0:
             continue
         out_coords = torch.full((n + GUARD, 3), -7, dtype=torch.int32, device=d_coords.device)
-        out_values = torch.full((n + GUARD, 3), -7.0, device=d_coords.device)
-        assert fn(ptr(d_coords), ptr(d_values), coords.shape[0], 3, *geometry, ptr(vimg), ptr(ws), ws.numel(), first, count,
+        out_values = torch.full((n + GUARD, values.shape[1]), -7.0, device=d_coords.device)
+        assert fn(ptr(d_coords), ptr(d_values), coords.shape[0], values.shape[1], *geometry, ptr(vimg), ptr(ws), ws.numel(), first, count,
                   ptr(out_coords), ptr(out_values), n + GUARD, stream_ptr()) == 0
         want_coords, want_values = R.pass_reference(ref, coords, values, first, count)
         assert want_coords.shape[0] == n
@@ -151,6 +151,17 @@ def test_many_maps(tile):
     ref = check_list(coords, distinct_values(coords.shape[0]), 1100, (2, 2), tile, img_bs, 256)
     assert ref["header"][0] >= 1100 - 1100 // 3 and (tile == (1, 1)) == (ref["header"][3] > 0)
     assert (ref["header"][0] == 1100 - 1100 // 3) == (tile == (2, 2))
+
+
+@pytest.mark.parametrize("channels", [1, 4])
+def test_build_pass_at_other_channel_counts(channels):
+    """The detector tests' lists (40 x 28 maps of 0, 1, 255, 256 and 700 hits, pixels listed twice) with one and four value channels per
+    hit: the build pass copies hit * channels + c."""
+    from test_detector_gpu import SHAPE, synthetic_list
+    coords, values = synthetic_list(channels)
+    assert values.shape[1] == channels
+    ref = check_list(coords, values, 5, SHAPE, (8, 7), MAPS5, 3)
+    assert ref["header"][0] > 3 and ref["header"][3] > 0
 
 
 def test_empty_list():

@@ -1,6 +1,10 @@
 """The option branches both shipped option files leave off: smart prong features
 (layers/prong_feature_embedding.py:36-78), transformer_norm_first (layers/prong_custom_bert_encoder.py:45-52) and one_hot_pixels
-(trainers/neutrino_full_dense_trainer.py:47-52), each as a full fp32 train step against the CPU oracle."""
+(trainers/neutrino_full_dense_trainer.py:47-52), each as a full fp32 train step against the CPU oracle; and the dataset-derived channel
+count of the pixel maps (pixel_features: 1 and 2 instead of the tutorial's 3), as an fp32 train step and as bf16 eval logits, sparse stem
+against dense stem."""
+import functools
+
 import pytest
 import torch
 
@@ -140,3 +144,65 @@ def test_log_pixels_train_step_and_scattered_map():
     got = img[c[:, 0], c[:, 1], c[:, 2]]
     assert torch.allclose(got, torch.log(v + 1), rtol=2e-6, atol=0)
     assert int((img != 0).sum()) == int((v != 0).sum())
+
+
+# ---- pixel maps with one and two value channels per hit ----------------------------------------------------------------------------------
+PIX64 = dict(SMALL, initial_pixel_dim=64)            # 64 conv0 channels: the stem's fast paths (sparse stem, hit-list weight gradient) are eligible
+
+
+def _pixel_dim_batch(cfg):
+    """The default hit counts (events 500 .. 4000, prongs 20 .. 800 hits), as in the norm_first case above.  The gate of _step_vs_oracle
+    compares two fp32 runs, so the batch has to leave the fp32 oracle itself well inside it: against the same oracle run in float64 (CPU)
+    its worst gradient tensor is off by 4.3e-5 (one channel) and 2.6e-4 (two channels) relative L2 on this batch.  A batch of five nearly
+    empty maps ([2, 3], 200 .. 400 / 20 .. 100 hits) puts the fp32 oracle ALONE 7.8e-3 from float64 at one channel (dense1.layers.1 relu1.weight:
+    BatchNorm over maps that are almost constant), beyond the 6e-3 gate before any kernel runs: not a usable reference."""
+    return O.synthetic_batch([2, 4, 1], 33, cfg)
+
+
+@pytest.mark.parametrize("pixel_dim", [1, 2])
+def test_pixel_dim_train_step(pixel_dim):
+    cfg = O.tutorial_config(**dict(PIX64, pixel_dim=pixel_dim))
+    batch = _pixel_dim_batch(cfg)
+    assert batch[3].shape[1] == pixel_dim and batch[6].shape[1] == pixel_dim
+    worst, seen, grads, named = _step_vs_oracle(cfg, batch)
+    k = "network.prong_embedding.prong_pixel_embedding.features.conv0.weight"
+    assert tuple(named[k].shape) == (64, pixel_dim, 7, 7) and grads[k].abs().max() > 1e-6
+    print(f"pixel_dim {pixel_dim}: worst rel L2 gradient error {worst:.2e} over {seen} tensors")
+
+
+def bf16_eval_logits(pixel_dim):
+    """bf16 eval logits of the PIX64 model (real prongs only) and, per embedder, whether the sparse stem ran (no conv0 map exists)."""
+    cfg = O.tutorial_config(**dict(PIX64, pixel_dim=pixel_dim))
+    batch = _pixel_dim_batch(cfg)
+    model = build_trainer(cfg, O.fill_state(cfg, 21), precision="bf16")
+    model.eval()
+    with torch.no_grad():
+        _, _, ev, pr = model.shared_step(to_device(batch))
+    torch.cuda.synchronize()
+    rt = model.network.hip_runtime()
+    sparse = []
+    for eng in (rt.ev_engine, rt.pr_engine):
+        try:
+            eng.tap("conv0")
+            sparse.append(False)
+        except RuntimeError:
+            sparse.append(True)
+    return ev.float().cpu(), pr.float().cpu()[batch[7]], sparse
+
+
+@functools.lru_cache(maxsize=None)
+def _dense_stem_logits():
+    from variant_utils import run_on_debug_build
+    return run_on_debug_build("import test_options_gpu as T\nresult = {c: T.bf16_eval_logits(c) for c in (1, 2)}\n", dict(TCVN_DENSE_STEM="1"))
+
+
+@pytest.mark.parametrize("pixel_dim", [1, 2])
+def test_pixel_dim_bf16_eval_sparse_stem_against_dense_stem(pixel_dim):
+    """Inference at one and two channels takes the sparse stem; its logits against the dense stem kernels (TCVN_DENSE_STEM on the validation
+    build, separate process) within the sparse-versus-dense bound of test_stem_sparse_gpu.py, 4e-3 relative L2."""
+    ev, pr, sparse = bf16_eval_logits(pixel_dim)
+    r_ev, r_pr, r_sparse = _dense_stem_logits()[pixel_dim]
+    assert sparse == [True, True] and r_sparse == [False, False]
+    e_ev, e_pr = ((ev - r_ev).norm() / r_ev.norm()).item(), ((pr - r_pr).norm() / r_pr.norm()).item()
+    print(f"pixel_dim {pixel_dim} bf16 eval, sparse vs dense stem: event logits {e_ev:.2e}, prong logits {e_pr:.2e} (relative L2)")
+    assert torch.isfinite(ev).all() and torch.isfinite(pr).all() and e_ev < 4e-3 and e_pr < 4e-3

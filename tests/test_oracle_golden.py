@@ -30,6 +30,28 @@ def test_state_layout_matches_reference_counts():
     assert sum(int(np.prod(s)) if len(s) else 1 for s in lay.values()) == 5779136
 
 
+def test_synthetic_batch_at_three_channels_is_the_golden_batch_bit_for_bit():
+    """synthetic_batch draws cfg.pixel_dim value channels per hit; at the default 3 its Philox stream -- and with it every golden and every
+    seeded case of the suite -- is unchanged: the committed small_b3 batch comes back bit for bit."""
+    cfg, over, batch, g = load_case("small_b3")
+    assert cfg.pixel_dim == 3
+    again = O.synthetic_batch([int(n) for n in g["prongs"]], int(g["batch_seed"]), cfg)
+    assert len(again) == len(batch) == 10
+    for i, (a, b) in enumerate(zip(again, batch)):
+        assert a.dtype == b.dtype and torch.equal(a, b), i
+
+
+@pytest.mark.parametrize("pixel_dim", [1, 2, 4])
+def test_synthetic_batch_draws_the_configured_channel_count(pixel_dim):
+    cfg = O.tutorial_config(pixel_dim=pixel_dim, pixel_shape=(45, 37))
+    batch = O.synthetic_batch([2, 1], 9, cfg, event_hits=(20, 40), prong_hits=(5, 20))
+    for coords, values in ((batch[2], batch[3]), (batch[5], batch[6])):
+        assert values.shape == (coords.shape[0], pixel_dim) and values.dtype == torch.float32
+        assert float(values.min()) >= 1 and float(values.max()) <= 255 and bool((values == values.round()).all())
+    if pixel_dim > 1:                                          # the channels are drawn independently
+        assert not torch.equal(batch[6][:, 0], batch[6][:, 1])
+
+
 @pytest.mark.parametrize("name", CASES)
 def test_eval_logits(name):
     cfg, over, batch, g = load_case(name)

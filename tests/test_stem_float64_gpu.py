@@ -22,6 +22,10 @@ TCVN_SPARSE_STEM_TRAIN raw:bstat0, the pooled map and, after backward, raw:pq0, 
 validation-build variant runs all cases.  Every run asserts from the launch labels and the taps that it went through the kernel it is
 meant to cover; nothing is skipped when a path is not taken.
 
+Channel counts: every case above has the tutorial's three value channels per hit.  `partial` and `odd` run again with Cpix = 1, 2 and 4
+(EXPECTED_PATH: which kernels each build takes there): the sparse stem keeps a three-channel weight table in LDS and must fill it from
+the packed rows' k = tap * Cpix + c; four channels are past the hit-list weight gradient and the sparse stem, and take the generic kernels.
+
 raw:du0 starts as NaN: with the activity bitmap on, rows no hit reaches are never stored and must still be NaN afterwards (they are
 compared nowhere: nothing reads them); without it every row must have been written."""
 import functools
@@ -46,8 +50,8 @@ ALL_CASES = TRAIN_CASES + ["wide-limit"]
 SS_CROWS, SS_PROWS, SS_HCAP = 8, 4, 2048            # stem_sparse.hip: conv0 rows per band, pooled rows per band, records of a band kept in LDS
 
 
-def _cfg(case):
-    return O.tutorial_config(pixel_shape=S.CASE_SHAPES[case][0], densenet_structure=[1], num_encoder_layers=1, dropout=0.0, pixel_noise_std=0.0)
+def _cfg(case, cpix=3):
+    return O.tutorial_config(pixel_dim=cpix, pixel_shape=S.CASE_SHAPES[case][0], densenet_structure=[1], num_encoder_layers=1, dropout=0.0, pixel_noise_std=0.0)
 
 
 def _kink_free(sc, sh, b0):
@@ -82,12 +86,12 @@ def _figure(figures, name, kernel, ref, delta, got, rnd_store, kink=None, mask=N
     figures.append((name, kernel, worst, bad, ref.numel(), where, 0 if kink is None else int(kink.sum()), float(ref.abs().max()) if ref.numel() else 0.0))
 
 
-def _run(case, mode, train, value_mode=0, backward=True):
+def _run(case, mode, train, value_mode=0, backward=True, cpix=3):
     """One forward (and, in train mode, one backward) of the case on a fresh engine; the float64 recomputation of every stem operation
     from its own stored inputs -> report (plain data: it also travels from a child process)."""
     from transformercvn.hip import _lib
-    cfg = _cfg(case)
-    coords, values, n, (H, W) = S.case_hits(case)
+    cfg = _cfg(case, cpix)
+    coords, values, n, (H, W) = S.case_hits(case, cpix=cpix)
     sd = O.fill_state(cfg, WEIGHT_SEED)
     eng, data, grads = _engine(cfg, sd, mode=mode, with_grad=train)
     P = {k: v.detach().double().cpu() for k, v in data.items()}
@@ -119,7 +123,7 @@ def _run(case, mode, train, value_mode=0, backward=True):
     bstat0 = _tap(eng, "raw:bstat0").flatten().view(C0, 2) if train else None
     info = dict(sparse=sparse, bias_rows_wrong=0, img_wrong=0, hit_free=int((~act).sum()), bands=_band_records(coords, n, H, W, Hc, Ho))
     if not sparse:
-        assert tuple(img.shape) == (n, H, W, 3) and tuple(c0.shape) == (n, Hc, Wc, C0)
+        assert tuple(img.shape) == (n, H, W, cpix) and tuple(c0.shape) == (n, Hc, Wc, C0)
         ref, d = S.image(coords, values, n, H, W, value_mode, rnd)
         if rnd:                               # bit for bit: the stored value is bf16(exact) (stem_reference.pixel_values)
             info["img_wrong"] = int((img != ref).sum())
@@ -194,21 +198,53 @@ def _run(case, mode, train, value_mode=0, backward=True):
 
 
 BUILDS = {"generic": dict(TCVN_DISABLE_TILE="1"), "sparse-train": dict(TCVN_SPARSE_STEM_TRAIN="1"), "no-skip": dict(TCVN_NO_STEM_SKIP="1"),
-          "flat": dict(TCVN_POOL0_BWD_FLAT="1")}
+          "flat": dict(TCVN_POOL0_BWD_FLAT="1"), "dense-stem": dict(TCVN_DENSE_STEM="1")}
+EVAL_BUILDS = ("bf16-eval", "dense-stem")           # one eval forward; every other build runs a train forward and a backward
+
+# ---- the stem at 1, 2 and 4 value channels per hit -------------------------------------------------------------------
+CPIX = [1, 2, 4]
+CPIX_CASES = ["partial", "odd"]                     # the two smallest cases
+CPIX_CHILD_BUILDS = ["generic", "sparse-train", "no-skip", "dense-stem"]
+# The kernels each build must be SEEN on, per channel count: (forward, conv0 weight gradient).
+#   forward          "sparse"   k_stem_sparse_pool (+ k_stem_sparse_stats in a train pass): stem_sparse_ok, 1 <= Cpix <= 3, eval passes and
+#                               the TCVN_SPARSE_STEM_TRAIN child;  "generic" k_conv_fwd<bf16,3,64>;  "generic f32" k_conv_fwd<float,3,64>.
+#                               k_stem_fwd2_bf16 takes three channels only (stem_fwd_ok), so it -- and with it the activity bitmap --
+#                               appears nowhere in this table.
+#   weight gradient  "hit list" k_stem_wgrad_sparse (Cpix <= 3, in fp32 too);  "generic" k_conv_wgrad<bf16,3,64> / "generic f32"
+#                               k_conv_wgrad<float,3,64>: Cpix = 4, and TCVN_DISABLE_TILE;  "sparse" k_stem_sparse_bwd<sums>, <wgrad>.
+EXPECTED_PATH = {
+    # build           Cpix = 1                   Cpix = 2                   Cpix = 4
+    "bf16":         {1: ("generic", "hit list"), 2: ("generic", "hit list"), 4: ("generic", "generic")},
+    "no-skip":      {1: ("generic", "hit list"), 2: ("generic", "hit list"), 4: ("generic", "generic")},
+    "fp32":         {1: ("generic f32", "hit list"), 2: ("generic f32", "hit list"), 4: ("generic f32", "generic f32")},
+    "generic":      {1: ("generic", "generic"), 2: ("generic", "generic"), 4: ("generic", "generic")},
+    "sparse-train": {1: ("sparse", "sparse"), 2: ("sparse", "sparse"), 4: ("generic", "generic")},
+    "bf16-eval":    {1: ("sparse", None), 2: ("sparse", None), 4: ("generic", None)},
+    "dense-stem":   {1: ("generic", None), 2: ("generic", None), 4: ("generic", None)},
+}
+
+
+def _child_runs(build):
+    """What one validation-build child computes: the three-channel train cases (not for the eval-only knob), then the channel-count cases."""
+    train = build not in EVAL_BUILDS
+    out = dict((c, _run(c, BF16, True)) for c in TRAIN_CASES) if train else {}
+    if build in CPIX_CHILD_BUILDS:
+        out.update(((c, cpix), _run(c, BF16, train, cpix=cpix)) for cpix in CPIX for c in CPIX_CASES)
+    return out
 
 
 @functools.lru_cache(maxsize=None)
 def _child_reports(build):
-    """All train cases of one validation-build knob set in ONE child process (knobs are read once per process)."""
+    """All cases of one validation-build knob set in ONE child process (knobs are read once per process)."""
     from variant_utils import run_on_debug_build
-    return run_on_debug_build("import test_stem_float64_gpu as T\nresult = dict((c, T._run(c, T.BF16, True)) for c in T.TRAIN_CASES)\n", BUILDS[build])
+    return run_on_debug_build(f"import test_stem_float64_gpu as T\nresult = T._child_runs({build!r})\n", BUILDS[build])
 
 
 @functools.lru_cache(maxsize=None)
-def _report(case, build):
+def _report(case, build, cpix=3):
     if build in BUILDS:
-        return _child_reports(build)[case]
-    return _run(case, F32 if build == "fp32" else BF16, build != "bf16-eval")
+        return _child_reports(build)[case if cpix == 3 else (case, cpix)]
+    return _run(case, F32 if build == "fp32" else BF16, build not in EVAL_BUILDS, cpix=cpix)
 
 
 def _assert_figures(rep, case, build, kernels):
@@ -309,3 +345,67 @@ def test_value_modes_of_the_scatter_match_float64(mode, value_mode):
     assert not rep["info"]["sparse"]
     _assert_figures(rep, "partial", f"mode {mode} values {value_mode}", ["scatter", "conv0", "pool0"])
     assert rep["info"]["img_wrong"] == 0 and rep["info"]["bias_rows_wrong"] == 0
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 1, 2 and 4 value channels per hit
+# ---------------------------------------------------------------------------------------------------------------------
+def _assert_forward_path(labels, path, train):
+    sparse = path == "sparse"
+    assert _count(labels, "k_stem_sparse_pool") == int(sparse) and _count(labels, "k_stem_sparse_stats") == int(sparse and train), labels
+    assert _count(labels, "k_conv_fwd<bf16,3") == int(path == "generic") and _count(labels, "k_conv_fwd<float,3") == int(path == "generic f32"), labels
+    assert not _count(labels, "k_stem_fwd_bf16"), labels                # three channels only (stem_fwd_ok)
+
+
+@pytest.mark.parametrize("build", ["bf16", "fp32", "bf16-eval", "generic", "dense-stem", "no-skip", "sparse-train"])
+@pytest.mark.parametrize("case", CPIX_CASES)
+@pytest.mark.parametrize("cpix", CPIX)
+def test_stem_forward_matches_float64_at_other_channel_counts(cpix, case, build):
+    rep = _report(case, build, cpix)
+    _assert_case(rep, case)
+    path = EXPECTED_PATH[build][cpix][0]
+    train = build not in EVAL_BUILDS
+    assert rep["info"]["sparse"] == (path == "sparse"), (path, rep["fwd_labels"])      # sparse: neither img nor conv0 exists
+    _assert_forward_path(rep["fwd_labels"], path, train)
+    if path == "sparse":
+        _assert_figures(rep, case, f"{build} Cpix {cpix}", ["sparse pool"] + (["sparse stats"] if train else []))
+    else:
+        _assert_figures(rep, case, f"{build} Cpix {cpix}", ["scatter", "conv0", "pool0"])
+        assert rep["info"]["img_wrong"] == 0 and rep["info"]["bias_rows_wrong"] == 0, rep["info"]
+
+
+@pytest.mark.parametrize("build", ["bf16", "fp32", "generic", "no-skip", "sparse-train"])
+@pytest.mark.parametrize("case", CPIX_CASES)
+@pytest.mark.parametrize("cpix", CPIX)
+def test_stem_backward_matches_float64_at_other_channel_counts(cpix, case, build):
+    rep = _report(case, build, cpix)
+    fwd, wgrad = EXPECTED_PATH[build][cpix]
+    labels = rep["bwd_labels"]
+    assert _count(labels, "k_stem_wgrad_sparse") == int(wgrad == "hit list") and _count(labels, "k_conv_wgrad<bf16,3") == int(wgrad == "generic") and \
+        _count(labels, "k_conv_wgrad<float,3") == int(wgrad == "generic f32"), labels
+    assert _count(labels, "k_stem_sparse_bwd<sums>") == int(wgrad == "sparse") and _count(labels, "k_stem_sparse_bwd<wgrad>") == int(wgrad == "sparse"), labels
+    assert rep["info"]["sparse"] == (fwd == "sparse")
+    if wgrad == "sparse":
+        _assert_figures(rep, case, f"{build} Cpix {cpix}", ["sparse backward sums", "sparse wgrad"])
+        assert len([f for f in rep["figures"] if f[1] == "sparse backward sums"]) == 5
+        return
+    wg = "conv0 wgrad (hit list)" if wgrad == "hit list" else "conv0 wgrad (generic)"
+    _assert_figures(rep, case, f"{build} Cpix {cpix}", ["pool0 backward", "pool0 backward link", wg])
+    assert len([f for f in rep["figures"] if f[1] == wg]) == 2 and len([f for f in rep["figures"] if f[1] == "pool0 backward link"]) == 5
+    # no activity bitmap without the three-channel stem kernel: every row of raw:du0 has been written
+    assert rep["du0_nan_active"] == 0 and rep["du0_nan_rows"] == 0, (rep["du0_nan_rows"], rep["info"])
+
+
+@pytest.mark.parametrize("value_mode", [1, 2])
+@pytest.mark.parametrize("cpix", CPIX)
+def test_value_modes_of_the_eval_pass_match_float64_at_other_channel_counts(cpix, value_mode):
+    """log(v + 1) and pre-scaled values through the product bf16 eval pass on the `partial` list (v / 255: the bf16-eval build above)."""
+    rep = _run("partial", BF16, False, value_mode, cpix=cpix)
+    path = EXPECTED_PATH["bf16-eval"][cpix][0]
+    assert rep["info"]["sparse"] == (path == "sparse")
+    _assert_forward_path(rep["fwd_labels"], path, False)
+    if path == "sparse":
+        _assert_figures(rep, "partial", f"eval Cpix {cpix} values {value_mode}", ["sparse pool"])
+    else:
+        _assert_figures(rep, "partial", f"eval Cpix {cpix} values {value_mode}", ["scatter", "conv0", "pool0"])
+        assert rep["info"]["img_wrong"] == 0 and rep["info"]["bias_rows_wrong"] == 0

@@ -6,7 +6,9 @@ conv0_from_hits (what the sparse kernels evaluate) equals conv0(image(...)).
 
 Rounding on: a "defective kernel" -- the reference with one deliberate defect, on the `partial` hit list (corners, borders, an empty map,
 entries outside the maps, 40 pixels listed twice) -- must leave the gates of the intact reference on at least one element; the intact
-reference's own values, rounded as the kernel stores them, stay inside everywhere."""
+reference's own values, rounded as the kernel stores them, stay inside everywhere.  The same list with 1, 2 and 4 value channels per hit: the
+intact reference stays inside at every channel count, and a kernel that reads the packed conv0 weights -- or stores their gradient -- with
+the tap stride 3 of the three-channel layout leaves the gates at 1 and 2 channels (at 3 it is the intact kernel)."""
 import functools
 
 import pytest
@@ -20,13 +22,13 @@ N = 64
 
 
 @functools.lru_cache(maxsize=None)
-def _setup(rnd):
+def _setup(rnd, cpix=3):
     """The `partial` case with random parameters; in bf16 mode every stored input is rounded as the engine would store it."""
-    coords, values, n, (H, W) = S.case_hits("partial")
+    coords, values, n, (H, W) = S.case_hits("partial", cpix=cpix)
     g = torch.Generator().manual_seed(3)
     rn = lambda *s: torch.randn(*s, generator=g, dtype=torch.float64)
     st = (lambda t: L.bf16(t)) if rnd else (lambda t: t)
-    p = dict(w=L.f32(0.1 * rn(N, 3, 7, 7)), b=L.f32(0.2 * rn(N)), gamma=L.f32(1 + 0.2 * rn(N)), beta=L.f32(0.3 * rn(N)), sl=L.f32(0.25 + 0.1 * rn(N)))
+    p = dict(w=L.f32(0.1 * rn(N, cpix, 7, 7)), b=L.f32(0.2 * rn(N)), gamma=L.f32(1 + 0.2 * rn(N)), beta=L.f32(0.3 * rn(N)), sl=L.f32(0.25 + 0.1 * rn(N)))
     img, _ = S.image(coords, values, n, H, W, 0, rnd)
     c0, d0 = S.conv0(img, p["w"], p["b"], rnd)
     c0s = st(c0)
@@ -158,3 +160,47 @@ def test_duplicate_counted_twice_leaves_the_weight_gradient_gate():
     f, tau, e, de = L.eff_rows(du0, s["c0s"], pq0[:N], pq0[N:], None, False)
     (bad, _), _ = S.conv0_wgrad(e, de, s["img"], e.numel() // N, defect_img=twice)
     assert _outside(c, L.f32(bad)) > 0
+
+
+@pytest.mark.parametrize("cpix", [1, 2, 3, 4])
+def test_conv0_gate_at_every_channel_count_and_weights_read_with_tap_stride_3(cpix):
+    s = _setup(True, cpix)
+    p = s["p"]
+    assert s["values"].shape[1] == cpix and s["img"].shape[-1] == cpix
+    assert torch.equal(s["coords"], _setup(True)["coords"])                               # the same hits at every channel count
+    c = L.Check("conv0", "conv0", s["c0"], s["d0"], True)
+    assert _outside(c, s["c0s"]) == 0
+    hits, dh = S.conv0_from_hits(s["coords"], s["values"], s["n"], s["H"], s["W"], 0, p["w"], p["b"], True)
+    assert _outside(c, L.bf16(hits)) == 0 and _rel(s["d0"], dh) < 1e-12
+    ref, d = S.sparse_pool(s["c0"], s["d0"], s["tab"][0], s["tab"][1], p["sl"])
+    cp = L.Check("pooled", "sparse pool", ref, d, True)
+    assert _outside(cp, L.bf16(ref)) == 0
+    if cpix == 4:
+        return                                                                            # (no kernel with a three-channel table admits 4)
+    bad, _ = S.conv0(s["img"], p["w"], p["b"], True, "tap3")
+    pooled_bad, _ = S.sparse_pool(bad, s["d0"], s["tab"][0], s["tab"][1], p["sl"])
+    if cpix == 3:                                                                         # stride 3 IS the layout at three channels
+        assert torch.equal(S.tap3_weights(L.bf16(p["w"])), L.bf16(p["w"])) and torch.equal(bad, s["c0"])
+    else:
+        assert _outside(c, L.bf16(bad)) > 0 and _outside(cp, L.bf16(pooled_bad)) > 0
+
+
+@pytest.mark.parametrize("cpix", [1, 2, 3, 4])
+def test_weight_gradient_gate_at_every_channel_count_and_gradient_stored_with_tap_stride_3(cpix):
+    s = _setup(True, cpix)
+    ref = _backward(s, True)
+    c = L.Check("du0", "pool0 backward", *ref["du0"][:2], True, ref["du0"][2])
+    assert _outside(c, L.bf16(ref["du0"][0])) == 0
+    assert int(ref["du0"][2].sum()) <= L.KINK_CAP * ref["du0"][2].numel()
+    du0, pq0 = L.bf16(ref["du0"][0]), torch.cat([L.f32(ref["P0"][0]), L.f32(ref["Q0"][0])])
+    ok = _backward(s, True, du0=du0, pq0=pq0)
+    assert tuple(ok["dW0"][0].shape) == (N, cpix, 7, 7)
+    c = L.Check("dW0", "conv0 wgrad", *ok["dW0"], False)
+    assert _outside(c, L.f32(ok["dW0"][0])) == 0
+    if cpix == 4:
+        return
+    bad = S.tap3_wgrad(ok["dW0"][0])
+    if cpix == 3:
+        assert torch.equal(bad, ok["dW0"][0])
+    else:
+        assert _outside(c, L.f32(bad)) > 0
