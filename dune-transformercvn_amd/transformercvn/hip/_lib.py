@@ -173,6 +173,11 @@ def _load():
     sig("tcvn_ig_scale", i32, vp, f32, vp, i64, vp)
     sig("tcvn_ig_accumulate", i32, vp, vp, C.c_double, i64, vp)
     sig("tcvn_ig_finish", i32, vp, vp, vp, i64, vp)
+    sig("tcvn_noise_workspace_bytes", i64, i32)
+    sig("tcvn_noise_sigma", i32, vp, vp, i64, i32, i32, i32, i32, vp, i32, i32, C.c_double, vp, vp, i64, vp)
+    sig("tcvn_noise_replicate", i32, vp, vp, i64, i32, i32, i32, i32, vp, i32, i32, vp, u64, i32, i32, vp, vp, vp)
+    sig("tcvn_noise_accumulate", i32, vp, vp, vp, i64, i32, i32, vp)
+    sig("tcvn_noise_finish", i32, vp, i64, i32, vp, vp)
     sig("tcvn_linear_backward", i32, vp, i64, vp, i64, vp, vp, i64, vp, vp, i32, i32, i32, vp)
     sig("tcvn_rows_bn_prelu_backward", i32, vp, i64, vp, i64, i32, i32, vp, vp, vp, vp, vp, i64, vp, vp, vp, f32, u64, C.c_uint32, vp)
     sig("tcvn_focal_loss", i32, vp, vp, i32, i32, f32, f32, vp, vp, vp)
@@ -222,6 +227,7 @@ EXPORTS = [
     "tcvn_densenet_forward_frozen", "tcvn_densenet_input_gradient", "tcvn_head_forward_frozen", "tcvn_head_input_gradient",
     "tcvn_hit_gradient_workspace_bytes", "tcvn_hit_gradient_gather", "tcvn_hit_gradient_seed",
     "tcvn_ig_scale", "tcvn_ig_accumulate", "tcvn_ig_finish",
+    "tcvn_noise_workspace_bytes", "tcvn_noise_sigma", "tcvn_noise_replicate", "tcvn_noise_accumulate", "tcvn_noise_finish",
 ]
 
 lib = _load()

@@ -4,6 +4,10 @@ The eval-mode model is differentiated by the native plans themselves (include/tc
 statistics, no dropout, state kept -- then the data-only backward of the token path and of both embedders, ending in the conv0 gather
 at the hits.  One backward gives every event of the batch its own gradient: on running statistics no operator mixes events.  This
 module holds the host side: argument checks, the seeds of the backward, the integrated-gradients loop and the result.
+
+Noise-averaged gradients (SmoothGrad, SmoothGrad^2, VarGrad; include/tcvn_hip.h, "Noise-averaged hit gradients") sit on top: the noise
+scale of every map, the noisy copies of a hit list laid end to end so that several samples share one frozen pass, Welford accumulators
+in double, and SmoothHitGradients.
 """
 from __future__ import annotations
 
@@ -14,6 +18,7 @@ from torch import Tensor
 
 from . import _lib
 from .native import gpu_only, ptr, stream_ptr
+from .occlusion import MAX_MAPS_PER_PASS
 from .pixels import VALUE_ONE_HOT
 
 METHODS = ("gradient", "integrated")
@@ -49,6 +54,31 @@ def check_args(target, value, method, steps, one_hot: bool = False):
     if one_hot:
         raise ValueError("hit_gradients: one-hot pixels are class indices, a class score has no gradient with respect to them")
     return target, VALUES.index(value), method, int(steps)
+
+
+KINDS = ("smoothgrad", "smoothgrad_sq", "vargrad")      # which statistic of the per-sample gradients SmoothHitGradients.event_grad holds
+MAX_SAMPLES = 4096
+MAX_SEED = (1 << 63) - 1
+
+
+def check_smooth_args(target, value, kind, samples, noise, seed, max_maps_per_pass, one_hot: bool = False):
+    """Validates smooth_hit_gradients' keywords on the host (ValueError) before any device work -> (target, value kind, kind, samples,
+    noise, seed, max_maps_per_pass)."""
+    who = "smooth_hit_gradients"
+    if kind not in KINDS:
+        raise ValueError(f"{who}: kind must be one of {KINDS}, got {kind!r}")
+    if not (_whole(samples) and 1 <= samples <= MAX_SAMPLES):
+        raise ValueError(f"{who}: samples must be an integer in 1..{MAX_SAMPLES}, got {samples!r}")
+    if kind == "vargrad" and samples < 2:
+        raise ValueError(f"{who}: kind 'vargrad' is a variance over the samples and needs samples >= 2")
+    if isinstance(noise, bool) or not isinstance(noise, (int, float)) or not (0.0 <= float(noise) < float("inf")):
+        raise ValueError(f"{who}: noise must be a finite number >= 0 (sigma as a fraction of a map's value range), got {noise!r}")
+    if not (_whole(seed) and 0 <= seed <= MAX_SEED):
+        raise ValueError(f"{who}: seed must be an integer in 0..2^63-1, got {seed!r}")
+    if not (_whole(max_maps_per_pass) and 1 <= max_maps_per_pass <= MAX_MAPS_PER_PASS):
+        raise ValueError(f"{who}: max_maps_per_pass must be an integer in 1..{MAX_MAPS_PER_PASS}, got {max_maps_per_pass!r}")
+    target, vkind, _, _ = check_args(target, value, "gradient", 1, one_hot)
+    return target, vkind, kind, int(samples), float(noise), int(seed), int(max_maps_per_pass)
 
 
 def ig_alphas(steps: int) -> List[Tuple[float, float]]:
@@ -111,6 +141,45 @@ class HitGradients:
             raise ValueError(f"heatmap: reduce must be one of {REDUCE}, got {reduce!r}")
         return heatmap(self.event_attr, self.prong_attr, self.event_coords, self.prong_coords, self.prong_mask, self.pixel_shape,
                        (int(tile[0]), int(tile[1])), reduce)
+
+
+class NoiseStats:
+    """mean, var (unbiased; NaN at one sample) and mean_sq [nnz, C] fp32 of one per-sample quantity, from the double accumulators."""
+
+    def __init__(self, mean: Tensor, var: Tensor, mean_sq: Tensor):
+        self.mean, self.var, self.mean_sq = mean, var, mean_sq
+
+    def pick(self, kind: str) -> Tensor:
+        return {"smoothgrad": self.mean, "smoothgrad_sq": self.mean_sq, "vargrad": self.var}[kind]
+
+
+class SmoothHitGradients(HitGradients):
+    """HitGradients averaged over `samples` noisy copies of the input (SmoothGrad and its siblings).  Plain tensors, no autograd graph.
+
+    event_logits, prong_logits                         the plain prediction: forward() on the unperturbed input
+    event_grad, prong_grad, event_attr, prong_attr     the statistic `kind` names of the per-sample gradient g_t = d target / d v' at the
+                                                       perturbed values v' and of the per-sample attribution g_t * v': "smoothgrad" the
+                                                       mean over the samples, "smoothgrad_sq" the mean square, "vargrad" the unbiased variance
+    {event,prong}_{grad,attr}_{mean,var}               mean and unbiased variance of both, whatever `kind` (the variance is NaN at one sample)
+    sigma [B, 1 + P]                                   the noise scale of every map, noise * (max(0, max v) - min(0, min v)); NaN at padded slots
+    samples, noise, seed, kind                         the call's keywords
+    sample_{event,prong}_{values,grad} [T, nnz, C]     keep_samples=True only (else None): every sample's perturbed values and gradient
+    method is "gradient"; value, baseline_value and completeness_gap are None."""
+
+    def __init__(self, event_logits: Tensor, prong_logits: Tensor, event: Tuple[NoiseStats, NoiseStats], prong: Tuple[NoiseStats, NoiseStats],
+                 event_coords: Tensor, prong_coords: Tensor, prong_mask: Tensor, pixel_shape: Tuple[int, int], sigma: Tensor, samples: int,
+                 noise: float, seed: int, kind: str, kept: Optional[Tuple[Tensor, Tensor, Tensor, Tensor]] = None):
+        (eg, ea), (pg, pa) = event, prong
+        super().__init__(event_logits, prong_logits, eg.pick(kind), pg.pick(kind), ea.pick(kind), pa.pick(kind), event_coords, prong_coords,
+                         prong_mask, pixel_shape, "gradient")
+        self.event_grad_mean, self.event_grad_var, self.event_attr_mean, self.event_attr_var = eg.mean, eg.var, ea.mean, ea.var
+        self.prong_grad_mean, self.prong_grad_var, self.prong_attr_mean, self.prong_attr_var = pg.mean, pg.var, pa.mean, pa.var
+        self.sigma, self.samples, self.noise, self.seed, self.kind = sigma, samples, noise, seed, kind
+        self.sample_event_values, self.sample_event_grad, self.sample_prong_values, self.sample_prong_grad = kept or (None,) * 4
+
+    def stderr(self) -> Tuple[Tensor, Tensor]:
+        """(event [nnzE, C], prong [nnzP, C]): the standard error sqrt(var / samples) of the mean gradient -- was `samples` enough?"""
+        return (self.event_grad_var / self.samples).sqrt(), (self.prong_grad_var / self.samples).sqrt()
 
 
 def heatmap(event_attr: Tensor, prong_attr: Tensor, event_coords: Tensor, prong_coords: Tensor, prong_mask: Tensor,
@@ -180,6 +249,66 @@ def gather(e0: Tensor, conv0_weight: Tensor, coords: Tensor, values: Tensor, sha
     return out
 
 
+# ---- noise-averaged gradients: element-wise launches of noise_tunnel.hip ------------------------------------------------------------------
+def noise_sigma(coords: Tensor, values: Tensor, n_img: int, shape: Tuple[int, int], img_bs: Tensor, noise: float, sigma: Tensor):
+    """tcvn_noise_sigma: writes sigma [B, 1 + P] (fp32, the caller's) at the maps img_bs [n_img, 2] = (b, s) names."""
+    gpu_only(values, "the noise scale")
+    assert coords.dtype == torch.int32 and coords.is_contiguous() and values.dtype == torch.float32 and values.is_contiguous()
+    assert img_bs.dtype == torch.int32 and img_bs.is_contiguous() and img_bs.shape == (n_img, 2) and values.shape[0] == coords.shape[0]
+    assert sigma.dtype == torch.float32 and sigma.is_contiguous() and sigma.dim() == 2 and sigma.device == values.device
+    if n_img < 1:
+        return
+    ws = torch.empty(_lib.lib.tcvn_noise_workspace_bytes(n_img), dtype=torch.uint8, device=values.device)
+    with torch.cuda.device(values.device):
+        _lib.check(_lib.lib.tcvn_noise_sigma(ptr(coords), ptr(values), coords.shape[0], values.shape[1], n_img, shape[0], shape[1], ptr(img_bs),
+                                             sigma.shape[0], sigma.shape[1] - 1, float(noise), ptr(sigma), ptr(ws), ws.numel(),
+                                             stream_ptr(values.device)), "noise_sigma")
+
+
+def noise_replicate(coords: Tensor, values: Tensor, n_img: int, shape: Tuple[int, int], img_bs: Tensor, sigma: Tensor, seed: int, t0: int,
+                    reps: int) -> Tuple[Tensor, Tensor]:
+    """tcvn_noise_replicate: samples t0 .. t0 + reps - 1 of a hit list as one list over reps * n_img images -> (coords [reps * nnz, 3],
+    perturbed values [reps * nnz, C])."""
+    gpu_only(values, "the noisy copies of a hit list")
+    assert coords.dtype == torch.int32 and coords.is_contiguous() and values.dtype == torch.float32 and values.is_contiguous()
+    assert img_bs.dtype == torch.int32 and img_bs.is_contiguous() and img_bs.shape == (n_img, 2) and values.shape[0] == coords.shape[0]
+    assert sigma.dtype == torch.float32 and sigma.is_contiguous() and sigma.dim() == 2
+    nnz, C = values.shape
+    out_c = torch.empty(reps * nnz, 3, dtype=torch.int32, device=values.device)
+    out_v = torch.empty(reps * nnz, C, dtype=torch.float32, device=values.device)
+    if n_img < 1 or nnz == 0:
+        return out_c, out_v
+    with torch.cuda.device(values.device):
+        _lib.check(_lib.lib.tcvn_noise_replicate(ptr(coords), ptr(values), nnz, C, n_img, shape[0], shape[1], ptr(img_bs), sigma.shape[0],
+                                                 sigma.shape[1] - 1, ptr(sigma), int(seed), int(t0), int(reps), ptr(out_c), ptr(out_v),
+                                                 stream_ptr(values.device)), "noise_replicate")
+    return out_c, out_v
+
+
+def noise_accumulate(acc: Tensor, grads: Tensor, values: Tensor, t0: int):
+    """tcvn_noise_accumulate: acc [4, nnz, C] double += samples t0 .. t0 + R - 1, grads / values [R, nnz, C] fp32."""
+    assert acc.dtype == torch.float64 and acc.is_contiguous() and acc.shape == (4, *grads.shape[1:])
+    assert grads.dtype == torch.float32 and grads.is_contiguous() and values.dtype == torch.float32 and values.is_contiguous()
+    assert grads.shape == values.shape and grads.dim() == 3
+    count = grads.shape[1] * grads.shape[2]
+    if count == 0:
+        return
+    with torch.cuda.device(acc.device):
+        _lib.check(_lib.lib.tcvn_noise_accumulate(ptr(acc), ptr(grads), ptr(values), count, int(t0), grads.shape[0], stream_ptr(acc.device)),
+                   "noise_accumulate")
+
+
+def noise_finish(acc: Tensor, samples: int) -> Tuple[NoiseStats, NoiseStats]:
+    """tcvn_noise_finish: acc [4, nnz, C] after `samples` samples -> the statistics of (gradient, attribution)."""
+    assert acc.dtype == torch.float64 and acc.is_contiguous() and acc.dim() == 3 and acc.shape[0] == 4
+    stats = torch.empty(6, *acc.shape[1:], dtype=torch.float32, device=acc.device)
+    count = acc.shape[1] * acc.shape[2]
+    if count:
+        with torch.cuda.device(acc.device):
+            _lib.check(_lib.lib.tcvn_noise_finish(ptr(acc), count, int(samples), ptr(stats), stream_ptr(acc.device)), "noise_finish")
+    return NoiseStats(stats[0], stats[1], stats[2]), NoiseStats(stats[3], stats[4], stats[5])
+
+
 # ---- the seeds and the value of a target ------------------------------------------------------------------------------------------------
 class Target:
     """What is differentiated: event classes [B] and / or prong classes [B, P] (-1: not part of the score), or raw logit seeds."""
@@ -210,6 +339,16 @@ class Target:
             if d_ev.shape != (B, Ce) or d_pr.shape != (B, P, Cp):
                 raise ValueError(f"hit_gradients: raw seeds must be [{B}, {Ce}] and [{B}, {P}, {Cp}], got {tuple(d_ev.shape)} and {tuple(d_pr.shape)}")
             self.raw = (d_ev, (d_pr * self.mask.unsqueeze(2)).contiguous())      # a padded slot contributes nothing, whatever its seed
+
+    def repeat(self, reps: int) -> "Target":
+        """The same target for `reps` copies of the batch laid end to end ([reps * B] events): classes and raw seeds repeated."""
+        if reps == 1:
+            return self
+        out = object.__new__(Target)
+        out.kind, out.mask = self.kind, self.mask.repeat(reps, 1)
+        out.ev_cls, out.pr_cls = self.ev_cls.repeat(reps).contiguous(), self.pr_cls.repeat(reps, 1).contiguous()
+        out.raw = None if self.raw is None else (self.raw[0].repeat(reps, 1).contiguous(), self.raw[1].repeat(reps, 1, 1).contiguous())
+        return out
 
     def seeds(self, ev: Tensor, pr: Tensor) -> Tuple[Tensor, Tensor]:
         """d value / d logits at these logits (the raw seeds as they are)."""

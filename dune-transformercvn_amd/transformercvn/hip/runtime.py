@@ -576,6 +576,66 @@ class HipRuntime:
             if seeds0 is not None:
                 self.last_seeds = seeds0
 
+    def forward_smooth_hit_gradients(self, features: Tensor, extra: Tensor, event_px: SparsePixels, event_mask: Tensor,
+                                     prong_px: SparsePixels, prong_mask: Tensor, counts: Optional[Tuple[int, int]] = None, target="event",
+                                     value: str = "prob", kind: str = "smoothgrad", samples: int = 16, noise: float = 0.15, seed: int = 0,
+                                     max_maps_per_pass: int = 256, keep_samples: bool = False) -> "gradients.SmoothHitGradients":
+        """Eval-mode forward() plus the hit gradients of `samples` noisy copies of the input and their statistics (SmoothGrad, SmoothGrad^2,
+        VarGrad) -> gradients.SmoothHitGradients.  The classes are fixed once, by forward() on the unperturbed input.  R = max(1,
+        max_maps_per_pass // (B + n_prongs)) samples travel together: their hit lists are laid end to end as one list over R * B event maps
+        and R * n_prongs prong maps (tcvn_noise_replicate), the input rows and the target are repeated, and ONE frozen pass -- both embedders,
+        the token path, the seeds and the three data-only backwards -- gives all R gradients, folded into double accumulators in ascending
+        sample order.  Nothing of the model is touched, as in forward_hit_gradients."""
+        one_hot = VALUE_ONE_HOT in (event_px.value_mode, prong_px.value_mode)
+        target, vkind, kind, samples, noise, seed, max_pass = gradients.check_smooth_args(target, value, kind, samples, noise, seed,
+                                                                                         max_maps_per_pass, one_hot)
+        if self.network.training:
+            raise RuntimeError("smooth_hit_gradients explains an eval-mode prediction: call network.eval() first")
+        for eng in (self.ev_engine, self.pr_engine):
+            if not hasattr(eng, "forward_frozen"):
+                raise NotImplementedError("smooth_hit_gradients: the SDXL embedder has no frozen forward and no data-only backward; only the "
+                                          "DenseNet network can be differentiated with respect to its hits")
+        self.ensure_bound()
+        step0, seeds0 = self.step, getattr(self, "last_seeds", None)
+        try:
+            with torch.no_grad():
+                ev, pr = self.forward(features, extra, event_px, event_mask, prong_px, prong_mask, counts)
+                last = self._last_forward
+                B, P, n_prongs = last.B, last.P, last.n_prongs
+                dev = ev.device
+                mask = prong_mask.to(dev)
+                tgt = gradients.Target(target, vkind, ev, pr, prong_mask)
+                b_idx, p_idx = mask.nonzero(as_tuple=True)
+                ev_bs = torch.stack((torch.arange(B, device=dev), torch.zeros(B, dtype=torch.long, device=dev)), 1).to(torch.int32).contiguous()
+                pr_bs = torch.stack((b_idx, p_idx + 1), 1).to(torch.int32).contiguous()
+                lists = ((event_px, B, ev_bs), (prong_px, n_prongs, pr_bs))
+                sigma = torch.full((B, 1 + P), float("nan"), device=dev)
+                for px, n, bs in lists:
+                    gradients.noise_sigma(px.coords, px.values, n, self.pixel_shape, bs, noise, sigma)
+                acc = [torch.zeros(4, *px.values.shape, dtype=torch.float64, device=dev) for px, _, _ in lists]
+                kept = [torch.empty(samples, *px.values.shape, device=dev) for px, _, _ in lists for _ in range(2)] if keep_samples else None
+                R = max(1, max_pass // (B + n_prongs))
+                for t0 in range(0, samples, R):
+                    r = min(R, samples - t0)
+                    rep = [gradients.noise_replicate(px.coords, px.values, n, self.pixel_shape, bs, sigma, seed, t0, r) for px, n, bs in lists]
+                    rep_px = [SparsePixels(c, v, px.shape, px.value_mode, 0.0, r * n) for (c, v), (px, n, _) in zip(rep, lists)]
+                    rows = torch.cat((last.rows[:B].repeat(r, 1), last.rows[B:].repeat(r, 1)))
+                    last_r = LastForward(rows, token_rows(mask.repeat(r, 1), r * B), r * B, P, r * n_prongs)
+                    grads = self._frozen_pass(last_r, rep_px[0], rep_px[1], rep[0][1], rep[1][1], tgt.repeat(r))
+                    for k, ((px, _, _), g, (_, v)) in enumerate(zip(lists, grads, rep)):
+                        g, v = g.view(r, *px.values.shape), v.view(r, *px.values.shape)
+                        gradients.noise_accumulate(acc[k], g, v, t0)
+                        if kept is not None:
+                            kept[2 * k][t0:t0 + r] = v
+                            kept[2 * k + 1][t0:t0 + r] = g
+                stats = [gradients.noise_finish(a, samples) for a in acc]
+                return gradients.SmoothHitGradients(ev, pr, stats[0], stats[1], event_px.coords, prong_px.coords, mask, self.pixel_shape, sigma,
+                                                    samples, noise, seed, kind, None if kept is None else tuple(kept))
+        finally:
+            self.step = step0
+            if seeds0 is not None:
+                self.last_seeds = seeds0
+
     def _backward(self, st: dict, d_ev: Tensor, d_pr: Tensor):
         """Backward of the fused step in the order the gradient segments become final -- token path, event embedder (side
         stream), prong embedder -- reporting each to ``grad_ready_hook`` so that its all-reduce overlaps with what is left."""

@@ -319,3 +319,28 @@ class NeutrinoBaseNetwork(nn.Module):
         event_pixels, prong_pixels = _as_sparse(event_pixels), _as_sparse(prong_pixels)
         return self.hip_runtime().forward_hit_gradients(features, extra, event_pixels, event_mask, prong_pixels, prong_mask, counts,
                                                         target, value, method, steps)
+
+    # ---- the same, averaged over noisy copies of the input (eager only; no autograd graph) ---------------------------------------------
+    @torch.jit.unused
+    def smooth_hit_gradients(self, features: Tensor, extra: Tensor, event_pixels: Tensor, event_mask: Tensor, prong_pixels: Tensor,
+                             prong_mask: Tensor, counts: Optional[Tuple[int, int]] = None, target="event", value: str = "prob",
+                             kind: str = "smoothgrad", samples: int = 16, noise: float = 0.15, seed: int = 0,
+                             max_maps_per_pass: int = 256, keep_samples: bool = False):
+        """Eval mode only -> transformercvn.hip.gradients.SmoothHitGradients: hit_gradients(method="gradient") averaged over `samples`
+        (1..4096) noisy copies of the input.  Only listed hits are perturbed: v' = max(v + sigma z, 0), z standard normal drawn from
+        `seed` (0..2^63-1) per (sample, pixel, map, channel), sigma = noise * (a map's value range including 0).  target and value as in
+        hit_gradients; the classes are those of the unperturbed prediction.  kind "smoothgrad": the mean gradient (result.event_grad) and
+        mean gradient x perturbed value (result.event_attr); "smoothgrad_sq": their mean squares; "vargrad": their unbiased variances
+        (samples >= 2).  Mean and variance of both are always returned, result.stderr() is the standard error of the mean gradient,
+        result.heatmap(tile) feeds occlusion_curves(relevance=...).  Samples travel through the model max_maps_per_pass (1..256) maps at
+        a time: max_maps_per_pass // (B + prongs) of them share one frozen pass.  keep_samples=True also returns every sample's values
+        and gradient.  Nothing of the model is touched; refusals as in hit_gradients."""
+        from transformercvn.hip import gradients
+        from transformercvn.hip.pixels import VALUE_ONE_HOT
+        one_hot = any(isinstance(px, SparsePixels) and px.value_mode == VALUE_ONE_HOT for px in (event_pixels, prong_pixels))
+        gradients.check_smooth_args(target, value, kind, samples, noise, seed, max_maps_per_pass, one_hot)
+        if self.training:
+            raise RuntimeError("smooth_hit_gradients explains an eval-mode prediction: call .eval() first")
+        event_pixels, prong_pixels = _as_sparse(event_pixels), _as_sparse(prong_pixels)
+        return self.hip_runtime().forward_smooth_hit_gradients(features, extra, event_pixels, event_mask, prong_pixels, prong_mask, counts,
+                                                               target, value, kind, samples, noise, seed, max_maps_per_pass, keep_samples)

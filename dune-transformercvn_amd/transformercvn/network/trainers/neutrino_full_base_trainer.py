@@ -284,6 +284,22 @@ class NeutrinoFullBaseTrainer(NeutrinoBase, ABC):
         return self.network.hit_gradients(*self._network_inputs(features, extra, event_coords, event_values, event_mask, prong_coords,
                                                                 prong_values, prong_mask), None, target, value, method, steps)
 
+    def smooth_hit_gradients(self, features: Tensor, extra: Tensor, event_coords: Tensor, event_values: Tensor, event_mask: Tensor,
+                             prong_coords: Tensor, prong_values: Tensor, prong_mask: Tensor, target="event", value: str = "prob",
+                             kind: str = "smoothgrad", samples: int = 16, noise: float = 0.15, seed: int = 0,
+                             max_maps_per_pass: int = 256, keep_samples: bool = False):
+        """Eval mode only -> SmoothHitGradients (transformercvn.hip.gradients): the hit gradients averaged over noisy copies of the input
+        (SmoothGrad, SmoothGrad^2, VarGrad); see NeutrinoBaseNetwork.smooth_hit_gradients.  Bad keywords raise ValueError and train mode
+        RuntimeError before any device work."""
+        from transformercvn.hip import gradients
+        gradients.check_smooth_args(target, value, kind, samples, noise, seed, max_maps_per_pass,
+                                    bool(getattr(self.options, "one_hot_pixels", False)))
+        if self.training:
+            raise RuntimeError("smooth_hit_gradients explains an eval-mode prediction: call .eval() first")
+        return self.network.smooth_hit_gradients(*self._network_inputs(features, extra, event_coords, event_values, event_mask,
+                                                                       prong_coords, prong_values, prong_mask), None, target, value, kind,
+                                                 samples, noise, seed, max_maps_per_pass, keep_samples)
+
     def shared_step(self, batch):
         (features, extra, ev_c, ev_v, ev_m, pr_c, pr_v, pr_m, ev_t, pr_t) = batch[:10]
         counts = batch[10] if len(batch) > 10 else None               # optional host-side (max_prongs, n_prongs): avoids syncs

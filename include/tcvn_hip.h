@@ -619,6 +619,38 @@ int tcvn_hit_gradient_seed(const float* logits, const int32_t* classes, int rows
 int tcvn_ig_scale(const float* values, float alpha, float* out, int64_t count, void* stream);
 int tcvn_ig_accumulate(double* acc, const float* grad, double weight, int64_t count, void* stream);
 int tcvn_ig_finish(const double* acc, const float* values, float* attr, int64_t count, void* stream);
+/* Noise-averaged hit gradients (SmoothGrad, SmoothGrad^2, VarGrad; csrc/noise_tunnel.hip): T noisy copies of a hit list, R of them per
+ * frozen pass as one list over R * n_img images, and the running statistics of their gradients.  img_bs [n_img, 2] int32 = (event b, token
+ * slot s) of every image of the list, s = 0 the event's own map and 1 + p prong slot p; an image whose pair lies outside
+ * [batch, 1 + max_prongs] is left alone.  Entries outside the maps (tcvn hit rule: image, y or x out of range) are ignored by noise_sigma and
+ * copied unperturbed by noise_replicate.
+ *   noise_sigma      sigma[b * (1 + max_prongs) + s] = (float)(noise * ((double)max(0, max v) + (double)max(0, -min v))), max and min over
+ *               every value channel of every entry inside that map (a NaN value moves neither); a map without hits gets 0.  Slots that no
+ *               image names are not written: the caller pre-fills them.  Integer atomics on the sign-split values: exact and deterministic.
+ *               The workspace (noise_workspace_bytes) holds the two bounds per image.
+ *   noise_replicate  samples t0 .. t0 + reps - 1: coords_out[r * nnz + i] = (img + r * n_img, y, x) -- an image index outside 0 .. n_img - 1
+ *               is written as -1, so that it stays outside in every sample -- and values_out[r * nnz + i][c] =
+ *               (float)max((double)v + (double)sigma * z, 0) with z the draw of (sample t0 + r, pixel q = y * width + x, map m =
+ *               b * (1 + max_prongs) + s, channel c): Philox-4x32-10 with counters (q, m, t, 0x4e54554e + (c >> 2)) and key (seed lo, seed hi)
+ *               yields w0..w3; channel pair (c & 3) >> 1 takes (wa, wb) = (w0, w1) or (w2, w3); u1 = (wa + 1) 2^-32, u2 = wb 2^-32;
+ *               z = sqrt(-2 ln u1) cos(2 pi u2) for even c, sin for odd c, all in double.  Where sigma is 0 (noise 0, an empty range) or the
+ *               entry lies outside the maps the values are copied bit for bit, negative ones included.  The draw depends on nothing but
+ *               (t, q, m, c, seed): duplicates share it and every split into calls gives the same bits.  in_ch <= 16.
+ *   noise_accumulate folds grads [reps, count] and the matching perturbed values [reps, count] (count = nnz * in_ch) of samples
+ *               t0 .. t0 + reps - 1 into acc [4, count] doubles = (gradient mean, gradient M2, attribution mean, attribution M2), the
+ *               attribution being gradient x value (exact in double), by Welford's update in ascending t; t0 = 0 starts from zero whatever
+ *               acc holds.  One thread per element, no atomics; a call split at any t0 gives the bits of one call.
+ *   noise_finish     acc after `samples` samples -> stats [6, count] fp32 = (mean, unbiased variance M2 / (samples - 1), mean square
+ *               mean^2 + M2 / samples) of the gradient, then of the attribution; the variance is NaN at samples = 1. */
+int64_t tcvn_noise_workspace_bytes(int n_img);
+int tcvn_noise_sigma(const int32_t* coords, const float* values, int64_t nnz, int in_ch, int n_img, int height, int width,
+                     const int32_t* img_bs, int batch, int max_prongs, double noise, float* sigma, void* workspace,
+                     int64_t workspace_bytes, void* stream);
+int tcvn_noise_replicate(const int32_t* coords, const float* values, int64_t nnz, int in_ch, int n_img, int height, int width,
+                         const int32_t* img_bs, int batch, int max_prongs, const float* sigma, uint64_t seed, int t0, int reps,
+                         int32_t* coords_out, float* values_out, void* stream);
+int tcvn_noise_accumulate(double* acc, const float* grads, const float* values, int64_t count, int t0, int reps, void* stream);
+int tcvn_noise_finish(const double* acc, int64_t count, int samples, float* stats, void* stream);
 
 /* Row operators behind the holder modules' own forward() (forward only, fp32):
  *   y = x W^T + b (torch.nn.Linear layout; bias may be NULL)                      -- layers/prong_decoder.py:15-16

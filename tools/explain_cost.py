@@ -13,8 +13,12 @@ detector_scan() is timed with 8 effects in both scopes: the whole call (forward(
 variant -- one whole-event setting, or one map under one effect -- costs beside one forward().
 hit_gradients() is timed with method "gradient" and with "integrated", steps=16: the whole call (forward() included), what one frozen
 forward + data-only backward costs beside one forward(), and the call beside the 16x16 occlusion scan of the same batch.
+smooth_hit_gradients(samples=16) is timed at the batch and at a one-event batch, each with the default max_maps_per_pass (as many samples
+per frozen pass as fit 256 maps) and with max_maps_per_pass=1 (one sample per pass), beside forward() and hit_gradients() of that batch,
+with the mean deletion AUC (occlusion_curves, 16x16 tiles, 10 steps) of the raw and of the smooth heat map.
 
-    python tools/explain_cost.py [--batch 32 --reps 15 --occ-reps 3 --shap-reps 5 --mc-reps 3 --det-reps 3 --grad-reps 3 --precision bf16 --keep 0.25]
+    python tools/explain_cost.py [--batch 32 --reps 15 --occ-reps 3 --shap-reps 5 --mc-reps 3 --det-reps 3 --grad-reps 3 --smooth-reps 3
+                                  --precision bf16 --keep 0.25]
 """
 import argparse
 import json
@@ -41,6 +45,7 @@ def main():
     ap.add_argument("--mc-reps", type=int, default=3, help="repetitions of each mc_dropout line (0: skip them)")
     ap.add_argument("--det-reps", type=int, default=3, help="repetitions of each detector_scan line (0: skip them)")
     ap.add_argument("--grad-reps", type=int, default=3, help="repetitions of each hit_gradients line (0: skip them)")
+    ap.add_argument("--smooth-reps", type=int, default=3, help="repetitions of each smooth_hit_gradients line (0: skip them)")
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--keep", type=float, nargs="*", default=[0.25], help="keep of each occlusion_refine line (none: skip them)")
     args = ap.parse_args()
@@ -169,6 +174,26 @@ def main():
         if "occlusion_maps_16x16" in out:
             row["over_occlusion_16x16"] = round(statistics.median(ts) / out["occlusion_maps_16x16"]["ms"]["median"], 4)
         out[name] = row
+    if args.smooth_reps > 0:
+        one = bench.make_batch(1, (1, 16), 1234, dev)
+        w1, n1 = one[10]
+        one_inputs = (one[0][:, :w1].contiguous(), *one[1:7], one[7][:, :w1].contiguous(), (1, n1))
+        for tag, inp, maps in (("", inputs, args.batch + n_prongs), ("_one_event", one_inputs, 1 + n1)):
+            _, t_fwd = timed(lambda: model.forward(*inp), args.reps)
+            _, t_plain = timed(lambda: model.hit_gradients(*inp[:8]), args.smooth_reps)
+            row = {"samples": 16, "maps_per_sample": maps, "reps": args.smooth_reps, "forward_ms": ms(t_fwd), "hit_gradients_ms": ms(t_plain)}
+            for name, max_pass in (("batched", 256), ("one_sample_per_pass", 1)):
+                res, ts = timed(lambda: model.smooth_hit_gradients(*inp[:8], samples=16, max_maps_per_pass=max_pass), args.smooth_reps)
+                per_pass = max(1, max_pass // maps)
+                row[name] = {"max_maps_per_pass": max_pass, "passes": -(-16 // per_pass), "ms": ms(ts),
+                             "over_hit_gradients": round(statistics.median(ts) / statistics.median(t_plain), 2)}
+            row["batched_over_one_sample_per_pass"] = round(row["batched"]["ms"]["median"] / row["one_sample_per_pass"]["ms"]["median"], 3)
+            auc = {}                            # recorded, not judged: the model has random weights
+            for name, r in (("hit_gradients", model.hit_gradients(*inp[:8])), ("smooth_hit_gradients", res)):
+                curves = model.occlusion_curves(*inp[:8], torch.nan_to_num(r.heatmap((16, 16))), tile=(16, 16), steps=10)
+                auc[name] = round(float(torch.nanmean(curves.auc("event"))), 5)
+            row["deletion_auc_16x16_steps10"] = auc
+            out["smooth_hit_gradients_samples16" + tag] = row
     cfg = rt.head.cfg
     out["weights_bytes"] = cfg.n_layers * args.batch * cfg.heads * (1 + width) ** 2 * 4
     print(json.dumps(out))
